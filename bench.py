@@ -18,6 +18,12 @@ reverse-diffusion step (12-layer GNN forward + categorical posterior + Bernoulli
 rank's whole batch; inputs are resident in HBM when the timed region starts.  Synthetic data:
 uniform random points, k-NN graph incl. self, random-init weights of the reference architecture with
 per_layer_out re-randomised.  One JSON line on stdout (rank 0).
+
+A plain run measures the headline only: set-up, `--warmup` steps, ONE loop of exactly `--steps` timed steps between two
+fences, the result line.  `--full` adds everything else this file measures or checks, as one run: three repetitions of the
+timed loop, the in-library HIP-event brackets (roofline, kernels), live power / throttler sampling, the exact-fp32 sub-record,
+the CPU-oracle baseline with its parity check, the other workloads (`workloads`) and the full record in bench_full.json.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import ctypes
@@ -332,6 +338,24 @@ def cpu_baseline(wl, steps, params, gpu_model, device, warm=True):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32.  An array larger than its share of DUMP_LIMIT_BYTES is
+    replaced by a fixed sample of its flattened elements: sorted indices drawn without replacement by
+    numpy.random.default_rng(0), i.e. the same elements in every run of the same command."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        cap = share // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {out_dir}: {', '.join(sorted(arrays))}")
+
+
 def _r(v, nd=4):
     """Round floats for the compact line (significant digits, not decimals)."""
     if isinstance(v, float):
@@ -445,9 +469,13 @@ def main():
     ap.add_argument("--nodes", type=int, default=None, help="override the workload's node count (TSP)")
     ap.add_argument("--knn", type=int, default=None, help="override the workload's neighbour count (TSP)")
     ap.add_argument("--graphs-per-gpu", type=int, default=None, help="override the workload's graphs per GPU")
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-oracle steps (0 = skip cpu_baseline)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the in-library HIP-event brackets")
-    ap.add_argument("--profile-all", action="store_true", help="bracket every kernel launch (full per-kernel table in the JSON; "
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure (see the "
+                    "module docstring); the options marked [--full] below shape those parts and do nothing without it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step "
+                    "returned to its caller (rank 0) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--cpu-steps", type=int, default=3, help="[--full] timed CPU-oracle steps (0 = skip cpu_baseline)")
+    ap.add_argument("--no-profile", action="store_true", help="[--full] skip the in-library HIP-event brackets")
+    ap.add_argument("--profile-all", action="store_true", help="[--full] bracket every kernel launch (full per-kernel table in the JSON; "
                     "costs ~2.7 %% of a step) instead of the dominant kernel only")
     ap.add_argument("--no-fusion", action="store_true", help="unfused kernel sequence (A/B against the fused layer kernel)")
     ap.add_argument("--no-l0-fold", action="store_true", help="A/B: write the first layer's edge input to HBM as a separate "
@@ -469,21 +497,21 @@ def main():
     ap.add_argument("--prof-lib", action="store_true", help="load libdifusco_hip_prof.so (profiling build) instead of the "
                     "production library")
     ap.add_argument("--no-node-reorder", action="store_true", help="A/B: keep the caller's node numbering (no Morton order)")
-    ap.add_argument("--no-exact-fp32", action="store_true", help="skip the exact-fp32 (v_mfma_f32_32x32x2_f32) sub-record")
+    ap.add_argument("--no-exact-fp32", action="store_true", help="[--full] skip the exact-fp32 (v_mfma_f32_32x32x2_f32) sub-record")
     ap.add_argument("--precision", default="fp16x3", choices=["fp32", "bf16x3", "bf16x6", "fp16x3"],
                     help="arithmetic of the E-row linears: exact fp32 MFMA, or fp32 split into 2/3 bf16 planes "
                          "(bf16x6 keeps all 24 significand bits: fp32-class accuracy)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the `workloads` sub-record (the other north_star sizes: "
+    ap.add_argument("--no-workloads", action="store_true", help="[--full] skip the `workloads` sub-record (the other north_star sizes: "
                     "tsp500, tsp10000, mis - a few timed steps each with their own roofline, cpu_baseline and parity_linf)")
-    ap.add_argument("--repeats", type=int, default=3, help="repetitions of the timed K-step loop (each between its own fences); the "
-                    "headline is the median repetition, all of them are listed under `repeats`")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the timed K-step loop (each between its own fences; "
+                    "default 1, with --full 3); the headline is the median repetition, all of them are listed under `repeats`")
     ap.add_argument("--backend", default=None, choices=["ctypes", "torch"], help="host binding of the C ABI: the PyTorch custom ops "
                     "torch.ops.difusco.* (csrc/torch_ops.cpp; the default) or ctypes (the default with the profiling library)")
     ap.add_argument("--aggregation", default="sum", choices=["sum", "mean", "max"], help="A/B: the reference's --aggregation "
                     "(train.py:52); every published run - and the metric - uses sum")
     ap.add_argument("--no-prepare", action="store_true", help="A/B: recompute the step-invariant part of a TSP step (node "
                     "embedding, layer-0 node linear, time-bias rows) in every step instead of once per (graph, schedule)")
-    ap.add_argument("--no-power", action="store_true", help="do not sample socket power / engine clock during the timed loops")
+    ap.add_argument("--no-power", action="store_true", help="[--full] do not sample socket power / engine clock during the timed loops")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): every rank steps `graphs_per_gpu` graphs, the global batch grows with N; strong: the "
                          "BASELINE config's literal global batch (64 x TSP-1000, --global-batch to override) is split over the N ranks")
@@ -494,8 +522,12 @@ def main():
                          "chain on (|x_t| < ~5).  free: feed every step its predecessor's output; with the random-init weights of this bench "
                          "the predicted noise is uncorrelated with x_t, so the DDIM update multiplies x_t by sqrt(abar'/abar) per step and "
                          "|x_t| runs to ~100 within a schedule - off the generated-input table (|x| < 8), onto the contraction path")
-    ap.add_argument("--sub-steps", type=int, default=10, help="timed steps of each `workloads` entry (4 warm-up steps; three repetitions)")
+    ap.add_argument("--sub-steps", type=int, default=10, help="[--full] timed steps of each `workloads` entry (4 warm-up steps; three repetitions)")
     args = ap.parse_args()
+    if not args.full:      # a plain run: the headline figure only
+        args.cpu_steps, args.no_exact_fp32, args.no_workloads, args.no_profile, args.no_power = 0, True, True, True, True
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.aggregation != "sum":      # an A/B of the kernels only: the oracle legs and the sub-records are written for the metric (sum)
         args.cpu_steps, args.no_exact_fp32, args.no_workloads = 0, True, True
 
@@ -554,7 +586,7 @@ def main():
         k_, v_ = kv.split("=")
         _lib.check(_lib.lib().difusco_debug_set(int(k_), int(v_)))
     out = measure(args, args.workload, args.steps, args.warmup, args.cpu_steps, not args.no_exact_fp32, rank, world, device, dry,
-                  step_flags, dist, overrides=True)
+                  step_flags, dist, overrides=True, dump_dir=args.dump_outputs)
     if rank == 0:
         # the other sizes north_star names, on the same GPU in the same run: a few timed steps each, their own roofline
         # (live HIP events), one oracle step on one graph with the parity of that step.  Headline fields stay TSP-1000.
@@ -569,12 +601,13 @@ def main():
                         keep[k] = sub[k]
                 keep["wall_s"] = time.perf_counter() - t0
                 out["workloads"][name] = keep
-        # The FULL record (every sub-record, the prose fields, per-level traffic) goes to a file and to stderr; the LAST - and
-        # only - stdout line is a compact record (< 4 KB) with the contract's fields, so that a log tail always holds all of it.
-        full_path = os.environ.get("BENCH_FULL_JSON", os.path.join(ROOT, "bench_full.json"))      # (git-ignored, never tracked)
+        # The FULL record (every sub-record, the prose fields, per-level traffic) goes to stderr and, with --full, to a file; the
+        # LAST - and only - stdout line is a compact record (< 4 KB) with the contract's fields, so that a log tail always holds all of it.
+        full_path = os.environ.get("BENCH_FULL_JSON", os.path.join(ROOT, "bench_full.json")) if args.full else None   # (git-ignored)
         try:
-            with open(full_path, "w") as fh:
-                json.dump(out, fh)
+            if full_path:
+                with open(full_path, "w") as fh:
+                    json.dump(out, fh)
         except OSError as exc:
             log(f"[bench] could not write {full_path}: {exc}")
             full_path = None
@@ -600,9 +633,10 @@ def main():
         dist.destroy_process_group()
 
 
-def measure(args, workload, steps, warmup, cpu_steps, exact_fp32, rank, world, device, dry, step_flags, dist, overrides):
+def measure(args, workload, steps, warmup, cpu_steps, exact_fp32, rank, world, device, dry, step_flags, dist, overrides, dump_dir=None):
     """One workload on this rank's GPU: `warmup` untimed + `steps` timed denoise steps between fences; returns the JSON
-    record (rank 0; other ranks return None after taking part in the fences / collectives)."""
+    record (rank 0; other ranks return None after taking part in the fences / collectives).  dump_dir: rank 0 writes the
+    output of the last timed step there (dump_outputs)."""
     from difusco_amd import _lib
     wl = dict(WORKLOADS[workload])
     if overrides:
@@ -818,6 +852,8 @@ def measure(args, workload, steps, warmup, cpu_steps, exact_fp32, rank, world, d
         rank_ms = [float(v[1].item()) for v in allr]
     if ranks_seen != world:      # (never print a line for fewer ranks than the command names)
         raise SystemExit(f"bench.py: the collective gathered {ranks_seen} distinct ranks, the job has {world}")
+    if dump_dir and rank == 0:      # (after the last fence: outside the timed region) the next x_t the last step returned
+        dump_outputs(dump_dir, {"xt": xt if groups is None else torch.cat([gk["xt"].reshape(-1) for gk in groups])})
 
     prof = None
     if not args.no_profile:      # the brackets of the REPORTED (median) repetition: every per-launch figure below belongs to it

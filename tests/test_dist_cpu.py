@@ -97,7 +97,7 @@ def test_bench_py_multi_rank_plumbing_dry_run(gn_stats):
     env = dict(os.environ, BENCH_PLUMBING_DRY_RUN="1", MASTER_ADDR="127.0.0.1", BENCH_FULL_JSON=os.devnull)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--nodes", "40", "--knn", "6", "--graphs-per-gpu", "3", "--gn-stats", gn_stats]
+           "--nodes", "40", "--knn", "6", "--graphs-per-gpu", "3", "--gn-stats", gn_stats, "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -167,6 +167,31 @@ def test_bench_py_refuses_a_rank_count_that_differs_from_the_command():
     # outside the dry run a --gpus larger than the visible device count is refused before anything is launched
     res = _run_bench(["--gpus", "2"], env_extra={"BENCH_PLUMBING_DRY_RUN": "0"})
     assert res.returncode != 0 and not res.stdout.strip()
+
+
+def test_bench_py_plain_run_times_steps_once_and_dumps_the_last_output(tmp_path):
+    """A plain run is the headline only: ONE loop of exactly --steps timed steps, no sub-records, no full-record file;
+    --full brings back the three repetitions.  --dump-outputs writes what the last timed step returned (the plumbing stand-in
+    hands x_t back: the seeded binary x_t of the 2 x 40 x 6 edges), identically in two runs of the same command."""
+    import json
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--nodes", "40", "--knn", "6", "--graphs-per-gpu", "2"]
+    dumps = []
+    for k in range(2):
+        res = _run_bench(argv + ["--dump-outputs", str(tmp_path / f"run{k}")])
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["dry_run"] is True and out["steps"] == 3 and out["warmup"] == 1 and out["repeats"]["n"] == 1
+        assert out["ms_per_step"] == out["repeats"]["median_ms_per_step"] and out["full_record"] == "stderr"
+        assert not {"roofline", "cpu_baseline", "workloads", "exact_fp32", "power"} & set(out)
+        assert abs(out["value"] - 2 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
+        assert sorted(os.listdir(tmp_path / f"run{k}")) == ["xt.npy"]
+        dumps.append(np.load(tmp_path / f"run{k}" / "xt.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2 * 40 * 6,) and set(np.unique(dumps[0])) <= {0.0, 1.0}
+    assert np.array_equal(dumps[0], dumps[1])
+    res = _run_bench(argv + ["--full"])
+    assert res.returncode == 0, res.stderr[-3000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3 and out["repeats"]["n"] == 3
 
 
 def test_bench_py_strong_scaling_splits_the_literal_global_batch():

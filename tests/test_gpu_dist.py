@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +75,7 @@ def test_rccl_world_size_one_broadcast_allreduce_two_phase_step():
 
 def test_bench_gpus_1_under_torchrun_prints_the_plain_run_keys():
     common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-steps", "0", "--no-exact-fp32", "--graphs-per-gpu", "2",
-              "--nodes", "200", "--knn", "20"]
+              "--nodes", "200", "--knn", "20", "--full"]
     plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, capture_output=True, text=True, timeout=600,
                            cwd=ROOT)
     assert plain.returncode == 0, plain.stderr[-3000:]
@@ -97,7 +98,7 @@ def test_bench_gpus_2_self_launch_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(BENCH_SINGLE_DEVICE="1", BENCH_BACKEND="gloo", BENCH_FULL_JSON=os.devnull, HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--graphs-per-gpu", "2", "--nodes", "300", "--knn", "20"], capture_output=True, text=True, timeout=900,
+                          "--graphs-per-gpu", "2", "--nodes", "300", "--knn", "20", "--full"], capture_output=True, text=True, timeout=900,
                          cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -113,3 +114,21 @@ def test_bench_gpus_2_self_launch_two_ranks_on_one_gpu():
         res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
                              capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
         assert res.returncode != 0 and "refusing" in res.stderr and not res.stdout.strip()
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py --gpus 1` run: one loop of exactly --steps timed steps and none of the --full records; --dump-outputs
+    writes the next x_t the last timed step returned (real kernels), bit for bit the same in two runs of the same command."""
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--graphs-per-gpu", "2", "--nodes", "200", "--knn", "20"]
+    dumps = []
+    for k in range(2):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv + ["--dump-outputs", str(tmp_path / f"run{k}")],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 3 and out["repeats"]["n"] == 1 and out["ms_per_step"] > 0 and "dry_run" not in out
+        assert not {"roofline", "cpu_baseline", "workloads", "exact_fp32", "power"} & set(out)
+        dumps.append(np.load(tmp_path / f"run{k}" / "xt.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2 * 200 * 20,)
+    assert set(np.unique(dumps[0])) == {0.0, 1.0}
+    assert np.array_equal(dumps[0], dumps[1])

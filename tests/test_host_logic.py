@@ -663,6 +663,26 @@ def test_bench_stdout_line_is_compact():
     assert rec["full_record"] == "bench_full.json"
 
 
+def test_bench_dump_outputs_caps_the_total_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per array, shape kept while the array fits its share of the cap; a larger array is
+    replaced by the same seeded sample of its elements in every run."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(__file__))
+    spec = importlib.util.spec_from_file_location("bench_module4", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4 * 1000)
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    big = torch.arange(5000, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float32 and np.array_equal(a_small, small.float().numpy())
+    assert a_big.dtype == np.float32 and a_big.shape == (1000,) and np.all(np.diff(a_big) > 0)     # sorted distinct elements
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 2 * 4 * 1000 + 2 * 256
+
+
 def test_node4_fused_vectors():
     """ABI 11: bias / column scales with which the node linear writes the A | B rows in the fused kernel's log2(e) domain."""
     H = 64
