@@ -7,10 +7,10 @@ from .build import LIB_PATH, PROF_LIB_PATH
 
 FLAG_NO_L0_FOLD, FLAG_NO_TAIL_FOLD, FLAG_CHECK_FINITE = 1, 2, 4      # difusco_step_args.flags
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 TASK_TSP, TASK_MIS = 0, 1
 CATEGORICAL, GAUSSIAN = 0, 1
-RAND_NONE, RAND_INJECTED, RAND_PHILOX = 0, 1, 2
+RAND_NONE, RAND_INJECTED, RAND_PHILOX, RAND_PHILOX_INSTANCES = 0, 1, 2, 3
 PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3 = 0, 1, 2, 3
 PRECISIONS = {"fp32": PREC_FP32, "bf16x3": PREC_BF16X3, "bf16x6": PREC_BF16X6, "fp16x3": PREC_FP16X3}
 AGGREGATIONS = {"sum": 0, "mean": 1, "max": 2}      # DIFUSCO_AGG_* (--aggregation, train.py:52; gnn_encoder.py:170-191)
@@ -52,6 +52,8 @@ class StepArgs(ctypes.Structure):
         ("prepared", ctypes.c_void_p), ("tbias", ctypes.c_void_p),      # optional prepared state (ABI 9)
         ("aggregation", ctypes.c_int32), ("reserved0", ctypes.c_int32),   # DIFUSCO_AGG_* (ABI 10)
         ("gen_table", ctypes.c_void_p),                                     # optional generated-input table (ABI 12)
+        ("n_instances", ctypes.c_int32), ("instance_rows", ctypes.c_void_p),  # per-instance Philox streams (ABI 13)
+        ("instance_seeds", ctypes.c_void_p),
     ]
 
 
@@ -108,6 +110,8 @@ def lib():
     L.difusco_tsp_merge_tours.argtypes = [i32, i64, vp, vp, f32p, f32p, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
     L.difusco_tsp_two_opt_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_two_opt.argtypes = [i32, i32, vp, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(i64), vp]
+    L.difusco_tsp_two_opt_grouped_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_two_opt_grouped.argtypes = [i32, i32, i32, vp, vp, i64, vp, ctypes.c_size_t, vp, vp]
     L.difusco_knn_graph_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_knn_graph.argtypes = [i32, i32, vp, i64, vp, vp, vp, ctypes.c_size_t, vp]
     L.difusco_mis_decode_workspace_bytes.argtypes = [i32, ctypes.POINTER(ctypes.c_size_t)]

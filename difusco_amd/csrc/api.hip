@@ -267,7 +267,10 @@ int difusco_denoise_step(const difusco_step_args* a) {
   if (a->n_segments < 1 || (a->n_segments > 1 && !a->seg_ptr))
     return fail(DIFUSCO_EINVAL, "n_segments >= 1, seg_ptr required when > 1");
   if (a->rand_mode == DIFUSCO_RAND_INJECTED && !a->rand) return fail(DIFUSCO_EINVAL, "injected randomness needs rand");
-  if (a->rand_mode < 0 || a->rand_mode > 2) return fail(DIFUSCO_EINVAL, "unknown rand_mode %d", a->rand_mode);
+  if (a->rand_mode < 0 || a->rand_mode > DIFUSCO_RAND_PHILOX_INSTANCES)
+    return fail(DIFUSCO_EINVAL, "unknown rand_mode %d", a->rand_mode);
+  if (a->rand_mode == DIFUSCO_RAND_PHILOX_INSTANCES && (a->n_instances < 1 || !a->instance_rows || !a->instance_seeds))
+    return fail(DIFUSCO_EINVAL, "rand_mode PHILOX_INSTANCES needs n_instances >= 1, instance_rows and instance_seeds");
   if (a->gn_phase < 0 || a->gn_phase > 2) return fail(DIFUSCO_EINVAL, "gn_phase must be 0, 1 or 2");
   if (a->aggregation < DIFUSCO_AGG_SUM || a->aggregation > DIFUSCO_AGG_MAX)
     return fail(DIFUSCO_EINVAL, "unknown aggregation %d (DIFUSCO_AGG_SUM / MEAN / MAX)", a->aggregation);
@@ -515,20 +518,23 @@ int difusco_denoise_step(const difusco_step_args* a) {
   };
 
   // head + posterior (gnn_encoder.py:400-401 / :412-413, pl_tsp_model.py:133-137, pl_meta_model.py:102-175)
+  RandInstances rand_instances;
+  if (a->rand_mode == DIFUSCO_RAND_PHILOX_INSTANCES)
+    rand_instances = RandInstances{a->n_instances, a->instance_rows, a->instance_seeds};
   if (fused && tsp) {
     PROF(PROF_HEAD, launch_head_tiled(C, ws.e, E, gn_blocks_for(out_rows) < 8 ? 8 : gn_blocks_for(out_rows) / 8 * 8,
                                       ws.partial, ws.stats, G(DIFUSCO_W_OUT_GN_W), G(DIFUSCO_W_OUT_GN_B),
                                       G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), a->perm, a->xt, a->post,
                                       a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
                                       gn_fold ? ws.gn_tile : nullptr, a->gn_phase, a->gn_sums,
-                                      a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments))
+                                      a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, rand_instances))
     return finish();
   }
   PROF(PROF_HEAD, launch_head(H, C, tsp ? ws.e : ws.h, a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, out_rows,
                               gn_blocks_for(out_rows), ws.partial, ws.stats, G(DIFUSCO_W_OUT_GN_W), G(DIFUSCO_W_OUT_GN_B),
                               G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), tsp ? a->perm : nullptr, a->xt, a->post,
                               a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
-                              a->gn_phase, a->gn_sums))
+                              a->gn_phase, a->gn_sums, rand_instances))
 #undef PROF
   return finish();
 }
@@ -755,6 +761,8 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
 int difusco_categorical_posterior(const float* logits, const float* xt, const float* post, int rand_mode,
                                   const float* rand, uint64_t seed, uint64_t offset, float* xt_out, float* prob_out,
                                   int64_t n, void* stream) {
+  if (rand_mode < DIFUSCO_RAND_NONE || rand_mode > DIFUSCO_RAND_PHILOX)
+    return fail(DIFUSCO_EINVAL, "posterior: rand_mode must be 0, 1 or 2 (the per-instance mode needs a step)");
   if (!logits || !xt || !post || !xt_out) return fail(DIFUSCO_EINVAL, "null pointer");
   if (post[4] != 0.0f && (rand_mode == DIFUSCO_RAND_NONE || (rand_mode == DIFUSCO_RAND_INJECTED && !rand)))
     return fail(DIFUSCO_EINVAL, "this step draws random numbers: provide rand or use PHILOX");
@@ -765,6 +773,8 @@ int difusco_categorical_posterior(const float* logits, const float* xt, const fl
 
 int difusco_gaussian_posterior(const float* pred, const float* xt, const float* post, int rand_mode, const float* rand,
                                uint64_t seed, uint64_t offset, float* xt_out, int64_t n, void* stream) {
+  if (rand_mode < DIFUSCO_RAND_NONE || rand_mode > DIFUSCO_RAND_PHILOX)
+    return fail(DIFUSCO_EINVAL, "posterior: rand_mode must be 0, 1 or 2 (the per-instance mode needs a step)");
   if (!pred || !xt || !post || !xt_out) return fail(DIFUSCO_EINVAL, "null pointer");
   if (post[4] != 0.0f && (rand_mode == DIFUSCO_RAND_NONE || (rand_mode == DIFUSCO_RAND_INJECTED && !rand)))
     return fail(DIFUSCO_EINVAL, "this step draws random numbers: provide rand or use PHILOX");

@@ -357,7 +357,29 @@ struct PostParams {
   int rand_mode;
   const float* rand;
   unsigned long long seed, offset;
+  // rand_mode 3 (DIFUSCO_RAND_PHILOX_INSTANCES): output-row boundaries [n_inst + 1] (caller order) and keys [n_inst]
+  int n_inst;
+  const long long* inst_rows;
+  const unsigned long long* inst_seeds;
 };
+
+// Philox key and element of caller row idx: the call's (seed, idx), or in mode 3 the (seed, local row) of the instance that
+// holds idx - what a solo call of that instance draws.  The lookup is a binary search over a few cached boundaries.
+__device__ __forceinline__ void draw_key(const PostParams& pp, long long idx, unsigned long long& seed,
+                                         unsigned long long& elem) {
+  if (pp.rand_mode != 3) {
+    seed = pp.seed;
+    elem = (unsigned long long)idx;
+    return;
+  }
+  int lo = 0, hi = pp.n_inst - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pp.inst_rows[mid] <= idx) lo = mid; else hi = mid - 1;
+  }
+  seed = pp.inst_seeds[lo];
+  elem = (unsigned long long)(idx - pp.inst_rows[lo]);
+}
 
 // No multiply-add contraction in the two posteriors: the reference evaluates them as separate fp32 torch operations.  HIP's
 // __fmul_rn / __fadd_rn are plain operators, hipcc's default -ffp-contract=fast fuses them in the backend whatever the source
@@ -382,8 +404,13 @@ __device__ __forceinline__ float categorical_step(float l0, float l1, float xt, 
   if (pp.p[4] != 0.0f) {
     const float pc = fminf(fmaxf(prob, 0.0f), 1.0f);
     float u;
-    if (pp.rand_mode == 1) u = pp.rand[idx];
-    else u = philox_uniform(pp.seed, pp.offset, (unsigned long long)idx);
+    if (pp.rand_mode == 1) {
+      u = pp.rand[idx];
+    } else {
+      unsigned long long seed, elem;
+      draw_key(pp, idx, seed, elem);
+      u = philox_uniform(seed, pp.offset, elem);
+    }
     return u < pc ? 1.0f : 0.0f;
   }
   return fmaxf(prob, 0.0f);
@@ -395,8 +422,13 @@ __device__ __forceinline__ float gaussian_step(float pred, float xt, const PostP
   const float base = rounded(pp.p[0] * rounded(xt - rounded(pp.p[1] * pred)));
   if (pp.p[4] == 0.0f) return base + rounded(pp.p[2] * pred);
   float z;
-  if (pp.rand_mode == 1) z = pp.rand[idx];
-  else z = philox_normal(pp.seed, pp.offset, (unsigned long long)idx);
+  if (pp.rand_mode == 1) {
+    z = pp.rand[idx];
+  } else {
+    unsigned long long seed, elem;
+    draw_key(pp, idx, seed, elem);
+    z = philox_normal(seed, pp.offset, elem);
+  }
   return base + rounded(pp.p[3] * z);
 }
 
@@ -747,20 +779,29 @@ int gn_blocks_for(long long rows) {
   return (int)b;
 }
 
-hipError_t launch_head(int H, int C, const float* feat, const int* seg_ptr, int n_segments, long long total_rows,
-                       int nblk, double* partial, float* stats, const float* gn_w, const float* gn_b,
-                       const float* conv_w, const float* conv_b, const int* perm, const float* xt, const float* post,
-                       int rand_mode, const float* rand, unsigned long long seed, unsigned long long offset,
-                       float* xt_out, float* pred_out, float* prob_out, hipStream_t stream, int gn_phase,
-                       double* gn_sums) {
-  if (total_rows == 0) return hipSuccess;
-  if (gn_phase != 0 && (n_segments != 1 || !gn_sums)) return hipErrorInvalidValue;
+static PostParams make_post(const float* post, int rand_mode, const float* rand, unsigned long long seed,
+                            unsigned long long offset, const RandInstances& ri) {
   PostParams pp;
   for (int i = 0; i < 8; ++i) pp.p[i] = post[i];
   pp.rand_mode = rand_mode;
   pp.rand = rand;
   pp.seed = seed;
   pp.offset = offset;
+  pp.n_inst = ri.n;
+  pp.inst_rows = reinterpret_cast<const long long*>(ri.rows);
+  pp.inst_seeds = reinterpret_cast<const unsigned long long*>(ri.seeds);
+  return pp;
+}
+
+hipError_t launch_head(int H, int C, const float* feat, const int* seg_ptr, int n_segments, long long total_rows,
+                       int nblk, double* partial, float* stats, const float* gn_w, const float* gn_b,
+                       const float* conv_w, const float* conv_b, const int* perm, const float* xt, const float* post,
+                       int rand_mode, const float* rand, unsigned long long seed, unsigned long long offset,
+                       float* xt_out, float* pred_out, float* prob_out, hipStream_t stream, int gn_phase,
+                       double* gn_sums, RandInstances ri) {
+  if (total_rows == 0) return hipSuccess;
+  if (gn_phase != 0 && (n_segments != 1 || !gn_sums)) return hipErrorInvalidValue;
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri);
   dim3 grid((unsigned)nblk, (unsigned)n_segments);
   if (gn_phase != 2) {
     DIFUSCO_VEC_DISPATCH(H, hipLaunchKernelGGL((gn_partial_kernel<VEC>), grid, dim3(256), 0, stream, feat, seg_ptr,
@@ -789,9 +830,7 @@ hipError_t launch_categorical_posterior(const float* logits, const float* xt, co
                                         const float* rand, unsigned long long seed, unsigned long long offset,
                                         float* xt_out, float* prob_out, long long n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  PostParams pp;
-  for (int i = 0; i < 8; ++i) pp.p[i] = post[i];
-  pp.rand_mode = rand_mode; pp.rand = rand; pp.seed = seed; pp.offset = offset;
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, RandInstances{});
   hipLaunchKernelGGL(categorical_posterior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, logits, xt, pp,
                      xt_out, prob_out, n);
   return hipGetLastError();
@@ -801,9 +840,7 @@ hipError_t launch_gaussian_posterior(const float* pred, const float* xt, const f
                                      const float* rand, unsigned long long seed, unsigned long long offset, float* xt_out,
                                      long long n, hipStream_t stream) {
   if (n == 0) return hipSuccess;
-  PostParams pp;
-  for (int i = 0; i < 8; ++i) pp.p[i] = post[i];
-  pp.rand_mode = rand_mode; pp.rand = rand; pp.seed = seed; pp.offset = offset;
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, RandInstances{});
   hipLaunchKernelGGL(gaussian_posterior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, pred, xt, pp,
                      xt_out, n);
   return hipGetLastError();
@@ -876,14 +913,12 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
                              const int* perm, const float* xt, const float* post, int rand_mode, const float* rand,
                              unsigned long long seed, unsigned long long offset, float* xt_out, float* pred_out,
                              float* prob_out, hipStream_t stream, const float* gn_tile, int gn_phase, double* gn_sums,
-                             const int* seg_ptr, int n_segments) {
+                             const int* seg_ptr, int n_segments, RandInstances ri) {
   if (rows == 0) return hipSuccess;
   if (gn_phase != 0 && !gn_sums) return hipErrorInvalidValue;
   if (n_segments > 1) {      // per-segment statistics (dense mode: one segment per sample): a masked pass over e per segment
     if (!seg_ptr || gn_phase != 0) return hipErrorInvalidValue;
-    PostParams pq;
-    for (int i = 0; i < 8; ++i) pq.p[i] = post[i];
-    pq.rand_mode = rand_mode; pq.rand = rand; pq.seed = seed; pq.offset = offset;
+    const PostParams pq = make_post(post, rand_mode, rand, seed, offset, ri);
     const long long n_tiles_s = (rows + 31) / 32;
     int bps = (int)((n_tiles_s / n_segments + 3) / 4);      // ~4 tiles per block
     bps = bps < 1 ? 1 : (bps > 256 ? 256 : bps);
@@ -904,9 +939,7 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
     return hipGetLastError();
   }
   if (nblk < 8 || nblk % 8 != 0) return hipErrorInvalidValue;   // (with gn_tile, partial must hold 256 * 64 doubles)
-  PostParams pp;
-  for (int i = 0; i < 8; ++i) pp.p[i] = post[i];
-  pp.rand_mode = rand_mode; pp.rand = rand; pp.seed = seed; pp.offset = offset;
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri);
   const long long n_tiles = (rows + 31) / 32;
   double* sums_out = gn_phase == 1 ? gn_sums : (double*)nullptr;
   if (gn_phase == 2) {

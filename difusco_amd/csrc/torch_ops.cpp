@@ -9,6 +9,7 @@
 //   prepare_state(weights, points, n_nodes, n_edges, n_segments, workspace, cfg) -> uint8 buffer     difusco_prepare
 //   time_bias_rows(weights, times, cfg) -> float32 [n_t, n_layers, hidden]                            difusco_time_bias_rows
 //   denoise_step_categorical(...) / denoise_step_gaussian(...) -> (xt_next, pred, prob)
+//       (trailing optional instance_rows / instance_seeds: per-instance Philox streams, DIFUSCO_RAND_PHILOX_INSTANCES)
 //       replace {categorical,gaussian}_denoise_step of difusco/pl_tsp_model.py:122-151 / pl_mis_model.py:118-140
 //
 // Built by difusco_amd/build.py into difusco_amd/lib/libdifusco_torch.so (host compiler, links libdifusco_hip.so).
@@ -77,7 +78,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> step_impl(
     const c10::optional<at::Tensor>& points, const at::Tensor& xt, double t, c10::ArrayRef<double> post,
     const c10::optional<at::Tensor>& rand, int64_t seed, int64_t offset, at::Tensor workspace, c10::ArrayRef<int64_t> cfg,
     bool want_pred, bool want_prob, const c10::optional<at::Tensor>& gn_sums, const c10::optional<at::Tensor>& prepared,
-    const c10::optional<at::Tensor>& tbias, const c10::optional<at::Tensor>& gen_table) {
+    const c10::optional<at::Tensor>& tbias, const c10::optional<at::Tensor>& gen_table,
+    const c10::optional<at::Tensor>& instance_rows, const c10::optional<at::Tensor>& instance_seeds) {
   TORCH_CHECK(cfg.size() == 9 || cfg.size() == 10,
               "cfg = {hidden, n_layers, out_channels, task, precision, no_fusion, xt_is_binary, gn_phase, flags[, aggregation]}");
   TORCH_CHECK(post.size() <= 8, "post holds at most 8 constants");
@@ -123,6 +125,19 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> step_impl(
   a.rand_mode = a.rand ? DIFUSCO_RAND_INJECTED : (a.post[4] != 0.0f ? DIFUSCO_RAND_PHILOX : DIFUSCO_RAND_NONE);
   a.seed = (uint64_t)seed;
   a.offset = (uint64_t)offset;
+  // ABI 13: per-instance Philox streams of a batch of instances (instance_rows int64 [B + 1], instance_seeds int64 [B], the
+  // seeds' bits taken as uint64); only a Philox draw switches to them, injected randomness stays as it is
+  const bool instances = ptr_or_null(instance_rows) != nullptr;
+  TORCH_CHECK(instances == (ptr_or_null(instance_seeds) != nullptr), "instance_rows and instance_seeds go together");
+  if (instances) {
+    need(*instance_rows, at::kLong, "instance_rows", true);
+    need(*instance_seeds, at::kLong, "instance_seeds", true);
+    TORCH_CHECK(instance_rows->numel() == instance_seeds->numel() + 1, "instance_rows must hold n_instances + 1 boundaries");
+    a.n_instances = (int32_t)instance_seeds->numel();
+    a.instance_rows = instance_rows->data_ptr<int64_t>();
+    a.instance_seeds = reinterpret_cast<const uint64_t*>(instance_seeds->data_ptr<int64_t>());
+    if (a.rand_mode == DIFUSCO_RAND_PHILOX) a.rand_mode = DIFUSCO_RAND_PHILOX_INSTANCES;
+  }
   a.xt_out = xt_out.data_ptr<float>();
   a.pred_out = want_pred ? pred.data_ptr<float>() : nullptr;
   a.prob_out = (want_prob && C == 2) ? prob.data_ptr<float>() : nullptr;
@@ -223,10 +238,11 @@ at::Tensor gen_table_build(const at::Tensor& weights, c10::ArrayRef<int64_t> cfg
       const c10::optional<at::Tensor>&rand, int64_t seed, int64_t offset, at::Tensor workspace,                         \
       c10::ArrayRef<int64_t> cfg, bool want_pred, bool want_prob, const c10::optional<at::Tensor>&gn_sums,             \
       const c10::optional<at::Tensor>&prepared, const c10::optional<at::Tensor>&tbias,                                  \
-      const c10::optional<at::Tensor>&gen_table
+      const c10::optional<at::Tensor>&gen_table, const c10::optional<at::Tensor>&instance_rows,                          \
+      const c10::optional<at::Tensor>&instance_seeds
 #define STEP_FORWARD                                                                                                     \
   weights, rowptr, col, perm, row, seg_ptr, points, xt, t, post, rand, seed, offset, workspace, cfg, want_pred, want_prob, \
-      gn_sums, prepared, tbias, gen_table
+      gn_sums, prepared, tbias, gen_table, instance_rows, instance_seeds
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> denoise_step_categorical(STEP_SIGNATURE) {
   return step_impl(DIFUSCO_CATEGORICAL, STEP_FORWARD);
@@ -238,7 +254,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> denoise_step_gaussian(STEP_SIGNAT
 const char* kStepSchema =
     "(Tensor weights, Tensor rowptr, Tensor col, Tensor? perm, Tensor? row, Tensor? seg_ptr, Tensor? points, Tensor xt, "
     "float t, float[] post, Tensor? rand, int seed, int offset, Tensor(a!) workspace, int[] cfg, bool want_pred, "
-    "bool want_prob, Tensor(b!)? gn_sums, Tensor? prepared=None, Tensor? tbias=None, Tensor? gen_table=None) -> (Tensor, Tensor, Tensor)";
+    "bool want_prob, Tensor(b!)? gn_sums, Tensor? prepared=None, Tensor? tbias=None, Tensor? gen_table=None, Tensor? instance_rows=None, Tensor? instance_seeds=None) -> (Tensor, Tensor, Tensor)";
 
 }  // namespace
 

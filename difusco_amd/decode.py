@@ -85,6 +85,34 @@ def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0"):
     return tours.cpu().numpy().astype(np.int64), int(it.value)
 
 
+def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0"):
+    """``batched_two_opt_torch`` of G instances at once: ``points`` float64 [G, N, 2], ``tours`` int [G * P, N + 1] with the P
+    tours of instance g at rows g P .. g P + P - 1.  Every instance gets exactly what ``batched_two_opt_torch(points[g],
+    tours[g P:(g+1) P])`` returns (its own stop test and iteration count); runs ``difusco_tsp_two_opt_grouped``, GPU only.
+    Returns ``(tours int64 numpy [G * P, N + 1], iterations int64 numpy [G])``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError("batched_two_opt_grouped runs on the GPU only (no CPU fallback)")
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts, t = _dev(pts, torch.float64, device), _dev(t, torch.int32, device)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_two_opt_grouped_workspace_bytes(n, G, P, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    its = np.zeros(G, dtype=np.int64)
+    _lib.check(L.difusco_tsp_two_opt_grouped(n, G, P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(t.data_ptr()),
+                                             int(max_iterations), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+                                             its.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    return t.cpu().numpy().astype(np.int64), its
+
+
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).

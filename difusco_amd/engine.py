@@ -215,9 +215,16 @@ class DenoiseEngine:
     def step(self, g: CsrGraph, task: int, diffusion: int, xt: torch.Tensor, t: float, post: np.ndarray,
              points: Optional[torch.Tensor] = None, xt_is_binary: bool = False,
              rand: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
-             want_pred: bool = False, want_prob: bool = False, gn_reduce=None, prepared: Optional[torch.Tensor] = None):
+             want_pred: bool = False, want_prob: bool = False, gn_reduce=None, prepared: Optional[torch.Tensor] = None,
+             instances=None):
         """xt: fp32, TSP [E] in caller edge order / MIS [N].  Returns (xt_next, pred|None, prob|None);
         asynchronous on the current stream.
+
+        ``instances``: ``(instance_rows, instance_seeds)``, device int64 tensors [B + 1] / [B]: the call batches B instances,
+        output rows ``instance_rows[b] .. instance_rows[b+1]`` (caller order) being instance b's, and a Philox draw of the step
+        takes the per-instance streams (``DIFUSCO_RAND_PHILOX_INSTANCES``): row r of instance b draws what a solo call with
+        ``seed = instance_seeds[b]`` draws for its row ``r - instance_rows[b]``; ``seed`` is then unused.  Injected ``rand``
+        and steps without a draw ignore it.
 
         ``gn_reduce``: optional callable taking the device tensor of 65 doubles (32 x (sum, sum of squares) of the head
         GroupNorm input over THIS call's rows + the row count) and adding the other shards' values in place - e.g.
@@ -244,6 +251,14 @@ class DenoiseEngine:
             if g.node_order is not None:          # the graph numbers its nodes for locality (graph.build_csr)
                 points = points.reshape(-1, 2).index_select(0, g.node_order)
         draws = float(post[4]) != 0.0
+        if instances is not None:
+            inst_rows, inst_seeds = instances
+            if inst_rows.dtype != torch.int64 or inst_seeds.dtype != torch.int64 or inst_rows.device != dev \
+                    or inst_seeds.device != dev or inst_rows.numel() != inst_seeds.numel() + 1 or inst_seeds.numel() < 1:
+                raise ValueError("instances = (instance_rows int64 [B + 1], instance_seeds int64 [B]) on the engine's device")
+            if gn_reduce is not None and inst_seeds.numel() > 1:
+                raise ValueError("global GroupNorm statistics (gn_reduce) need one instance per call")
+            instances = (inst_rows.contiguous(), inst_seeds.contiguous())
         if rand is not None:
             rand = rand.to(dev, dtype=torch.float32).contiguous().reshape(-1)
             if rand.numel() != rows:
@@ -265,7 +280,7 @@ class DenoiseEngine:
         seed, offset = int(seed) & (2 ** 63 - 1), int(offset) & (2 ** 63 - 1)
         if self.backend == "torch":
             return self._step_torch_op(g, task, diffusion, xt, t, post, points, xt_is_binary, rand, seed, offset,
-                                       want_pred, want_prob, gn_reduce, ws, prepared, tbias, gen_table)
+                                       want_pred, want_prob, gn_reduce, ws, prepared, tbias, gen_table, instances)
 
         a = _lib.StepArgs()
         a.struct_size = ctypes.sizeof(_lib.StepArgs)
@@ -282,6 +297,10 @@ class DenoiseEngine:
         for i in range(8):
             a.post[i] = float(post[i]) if i < len(post) else 0.0
         a.rand_mode = _lib.RAND_INJECTED if rand is not None else (_lib.RAND_PHILOX if draws else _lib.RAND_NONE)
+        if instances is not None:
+            if a.rand_mode == _lib.RAND_PHILOX:
+                a.rand_mode = _lib.RAND_PHILOX_INSTANCES
+            a.n_instances, a.instance_rows, a.instance_seeds = instances[1].numel(), _ptr(instances[0]), _ptr(instances[1])
         a.rand = _ptr(rand)
         a.seed, a.offset = seed, offset
         a.xt_out, a.pred_out, a.prob_out = _ptr(xt_out), _ptr(pred), _ptr(prob)
@@ -312,7 +331,7 @@ class DenoiseEngine:
         return xt_out, pred, prob
 
     def _step_torch_op(self, g, task, diffusion, xt, t, post, points, xt_is_binary, rand, seed, offset, want_pred,
-                       want_prob, gn_reduce, ws, prepared=None, tbias=None, gen_table=None):
+                       want_prob, gn_reduce, ws, prepared=None, tbias=None, gen_table=None, instances=None):
         """The same step through ``torch.ops.difusco.denoise_step_{categorical,gaussian}`` (csrc/torch_ops.cpp)."""
         op = self._ops.denoise_step_categorical if diffusion == _lib.CATEGORICAL else self._ops.denoise_step_gaussian
         cfg = self._cfg(task, xt_is_binary)
@@ -322,7 +341,8 @@ class DenoiseEngine:
         def call(phase, sums):
             cfg[7] = phase
             return _op_call(op, self.blob, g.rowptr, g.col, g.perm, g.row, seg, points, xt, float(t), post, rand, seed, offset, ws,
-                            cfg, want_pred, want_prob, sums, prepared, tbias, gen_table)
+                            cfg, want_pred, want_prob, sums, prepared, tbias, gen_table,
+                            *(instances if instances is not None else ()))
         if gn_reduce is None:
             out = call(0, None)
         else:

@@ -121,6 +121,46 @@ def build_csr(edge_index: torch.Tensor, n_nodes: int, device, seg_rows: Optional
     return g
 
 
+def union_rows(edge_counts, node_counts, task_rows: str):
+    """Boundaries of the instances of a disjoint-union batch: ``(node_offsets [B+1], instance_rows [B+1])`` int64 numpy, the
+    instance rows counting output rows (``"edges"`` for TSP, ``"nodes"`` for MIS) in caller order."""
+    node_off = np.concatenate([[0], np.cumsum(np.asarray(node_counts, dtype=np.int64))])
+    edge_off = np.concatenate([[0], np.cumsum(np.asarray(edge_counts, dtype=np.int64))])
+    return node_off, (edge_off if task_rows == "edges" else node_off)
+
+
+def build_union_csr(edge_indices, node_counts, device, points=None, task_rows: str = "edges"):
+    """Disjoint union of B instances (``pl_meta_model.py:177-184``), each given by its own ``edge_index`` [2, E_b] over its
+    own nodes 0..n_b-1, with ONE head-GroupNorm statistic segment per instance - what the solo call of each instance
+    normalises over.  Returns ``(graph, union_edge_index, instance_rows)``: ``instance_rows`` [B+1] int64 numpy, the output
+    rows (``"edges"``: TSP, ``"nodes"``: MIS) of every instance in caller order.  ``points`` [sum n_b, 2]: node renumbering
+    for locality as in :func:`build_csr`; it never crosses an instance (``_id_blocks``), which is checked: the CSR slots of
+    every instance must stay one contiguous range (otherwise a segment would mix instances)."""
+    eis = [e if isinstance(e, torch.Tensor) else torch.from_numpy(np.asarray(e)) for e in edge_indices]
+    eis = [e.detach().to("cpu", torch.int64) for e in eis]
+    node_off, inst_rows = union_rows([e.shape[1] for e in eis], node_counts, task_rows)
+    for b, e in enumerate(eis):
+        if e.numel() and (int(e.min()) < 0 or int(e.max()) >= int(node_counts[b])):
+            raise ValueError(f"edge_index of instance {b} refers to nodes outside 0..{int(node_counts[b]) - 1}")
+    union = torch.cat([e + int(node_off[b]) for b, e in enumerate(eis)], dim=1)
+    n = int(node_off[-1])
+    B = len(eis)
+    if task_rows == "edges":
+        # CSR slots are ordered by centre node: instance b holds the slots rowptr[node_off[b]] .. rowptr[node_off[b+1]]
+        seg = None
+        g = build_csr(union, n, device, points=points)
+        rowptr = g.rowptr.cpu().numpy().astype(np.int64)
+        seg = rowptr[node_off]
+        if not np.array_equal(seg, inst_rows):
+            raise RuntimeError("instance edges are not contiguous in CSR-slot order (an edge leaves its instance?)")
+        if B > 1:
+            g.seg_ptr = torch.from_numpy(seg.astype(np.int32)).to(device)
+            g.n_segments = B
+    else:
+        g = build_csr(union, n, device, seg_rows=node_off if B > 1 else None, points=points)
+    return g, union, inst_rows
+
+
 def complete_graph_batch(batch: int, n: int, device) -> CsrGraph:
     """Dense mode (``gnn_encoder.py:350-381``): B graphs with all n*n ordered pairs, edge (b,i,j) at slot
     b*n*n + i*n + j - exactly the flattening of the reference's [B,V,V] tensors.  One GroupNorm

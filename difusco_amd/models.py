@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .engine import DenoiseEngine
-from .graph import CsrGraph, build_csr, complete_graph_batch
+from .graph import CsrGraph, build_csr, build_union_csr, complete_graph_batch
 from .schedules import CategoricalDiffusion, GaussianDiffusion, InferenceSchedule
 
 _DEFAULTS = dict(  # difusco/train.py:19-68 (only what the inference path reads)
@@ -183,7 +183,61 @@ class COMetaModel:
                              "pl_meta_model.py:122-123)")
         return False
 
-    def _categorical(self, g, task, points, xt, t, target_t, uniform, return_aux):
+    # ---- batches of instances (sample_batch) -------------------------------------------------------
+    def _instance_tables(self, inst_rows, seeds):
+        """Device tables of the per-instance random streams: (instance_rows int64 [B+1], instance_seeds int64 [B]); the
+        seeds are masked to 63 bits as ``seed=`` of the constructor is."""
+        if seeds is None:
+            seeds = [self.seed] * (len(inst_rows) - 1)
+        seeds = [int(v) & (2 ** 63 - 1) for v in seeds]
+        if len(seeds) != len(inst_rows) - 1:
+            raise ValueError(f"{len(seeds)} seeds for {len(inst_rows) - 1} instances")
+        if self.gn_reduce is not None and len(seeds) > 1:
+            raise ValueError("global GroupNorm statistics (gn_reduce) need one statistic segment per call: "
+                             "sample_batch with several instances cannot use them")
+        rows = torch.as_tensor(np.asarray(inst_rows, dtype=np.int64)).to(self.device)
+        return rows, torch.tensor(seeds, dtype=torch.int64).to(self.device)
+
+    @staticmethod
+    def _initial_noise(shapes, generators, xt0, device):
+        """x_T of every instance, drawn as solo ``sample()`` draws it (``torch.randn(shape, generator=)``), or taken from ``xt0``."""
+        B = len(shapes)
+        if xt0 is not None:
+            if len(xt0) != B:
+                raise ValueError(f"{len(xt0)} xt0 tensors for {B} instances")
+            out = [x.to(device).reshape(-1) for x in xt0]
+            for b, (x, shp) in enumerate(zip(out, shapes)):
+                if x.numel() != int(np.prod(shp)):
+                    raise ValueError(f"xt0[{b}] has {x.numel()} elements, instance {b} needs {int(np.prod(shp))}")
+            return out
+        if generators is not None and len(generators) != B:
+            raise ValueError(f"{len(generators)} generators for {B} instances")
+        out = []
+        for b, shp in enumerate(shapes):
+            gen = None if generators is None else generators[b]
+            out.append(torch.randn(shp, generator=gen, device=device if gen is None else gen.device).to(device).reshape(-1))
+        return out
+
+    def _sample_loop(self, step, xt):
+        """The denoising loop of ``sample()`` over a whole union; ``step(xt, t1, t2)`` is one step of it."""
+        steps = self.args.inference_diffusion_steps
+        sched = InferenceSchedule(inference_schedule=self.args.inference_schedule, T=self.diffusion.T, inference_T=steps)
+        if self.diffusion_type == "categorical":
+            xt = (xt > 0).float()
+        self.prepare_schedule([sched(i)[0] for i in range(steps)])
+        for i in range(steps):
+            t1, t2 = sched(i)
+            xt = step(xt, np.array([t1]).astype(int), np.array([t2]).astype(int))
+        return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
+
+    def _union_step(self, g, task, points, instances):
+        def step(xt, t1, t2):
+            if self.diffusion_type == "gaussian":
+                return self._gaussian(g, task, points, xt, t1, t2, None, False, instances=instances)
+            return self._categorical(g, task, points, xt, t1, t2, None, False, instances=instances)
+        return step
+
+    def _categorical(self, g, task, points, xt, t, target_t, uniform, return_aux, instances=None):
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1                                              # pl_meta_model.py:108-109
@@ -194,13 +248,13 @@ class COMetaModel:
             g, task, _lib.CATEGORICAL, xt, float(t), post, points=points, xt_is_binary=self._xt_is_binary(xt),
             rand=uniform if target_t > 0 else None, seed=self.seed, offset=self._next_offset(),
             want_pred=return_aux, want_prob=return_aux, gn_reduce=self.gn_reduce,
-            prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None)
+            prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None, instances=instances)
         # tensors created under torch.inference_mode() (Lightning's default for trainer.test) have no version counter:
         # for those the held reference + storage identity is the whole key (no host sync in the 50-step loop either way)
         self._binary_out = (out, None if out.is_inference() else out._version) if target_t > 0 else None
         return (out, pred, prob) if return_aux else out
 
-    def _gaussian(self, g, task, points, xt, t, target_t, noise, return_aux):
+    def _gaussian(self, g, task, points, xt, t, target_t, noise, return_aux, instances=None):
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1
@@ -209,7 +263,8 @@ class COMetaModel:
         out, pred, _ = self.model.step(
             g, task, _lib.GAUSSIAN, xt, float(t), post, points=points, xt_is_binary=False,
             rand=noise if post[4] != 0 else None, seed=self.seed, offset=self._next_offset(), want_pred=return_aux,
-            gn_reduce=self.gn_reduce, prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None)
+            gn_reduce=self.gn_reduce, prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None,
+            instances=instances)
         return (out, pred) if return_aux else out
 
 
@@ -273,6 +328,43 @@ class TSPModel(COMetaModel):
                 xt = self.categorical_denoise_step(points, xt, t1, self.device, edge_index, target_t=t2)
         return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
 
+    def sample_batch(self, points, edge_index=None, seeds=None, generators=None, xt0=None):
+        """``sample()`` of B instances in ONE sampling loop over their disjoint union, every instance getting what its own
+        ``sample()`` call returns.  ``points``: list of B tensors, each what ``sample()`` takes for that instance (sparse: [P n_b, 2]
+        with ``edge_index[b]`` [2, P E_b] holding its P parallel samples; dense: [P_b, n, 2], ``edge_index=None``, the same n for
+        all).  ``seeds[b]``: the Philox key of instance b (a solo model built with ``seed=seeds[b]`` draws the same; default:
+        this model's seed for all); ``generators[b]`` / ``xt0[b]``: its initial noise, as in ``sample()``.  Each instance keeps
+        its own head GroupNorm statistics (sparse: one segment per instance, the solo call's; dense: one per sample, as solo)
+        and its own random streams (``DIFUSCO_RAND_PHILOX_INSTANCES``); the step offsets are this engine's call counter, as
+        in ``sample()``.  Returns the list of B heatmaps, each shaped like ``sample()``'s."""
+        B = len(points)
+        if B < 1:
+            raise ValueError("sample_batch needs at least one instance")
+        dev = self.device
+        if edge_index is not None:
+            if len(edge_index) != B:
+                raise ValueError(f"{len(edge_index)} edge_index tensors for {B} instances")
+            pts = [p.reshape(-1, 2) for p in points]
+            g, _, inst_rows = build_union_csr(edge_index, [p.shape[0] for p in pts], dev,
+                                              points=torch.cat([p.detach().cpu() for p in pts]) if self.reorder_nodes else None)
+            union_pts = torch.cat([p.to(dev, torch.float32) for p in pts])
+            shapes = [(int(e.shape[1]),) for e in edge_index]
+            out_shapes = shapes
+        else:
+            if any(p.dim() != 3 for p in points) or len({int(p.shape[1]) for p in points}) != 1:
+                raise ValueError("dense mode expects points [P_b, n, 2] with the same n for every instance")
+            n = int(points[0].shape[1])
+            union_pts = torch.cat([p.to(dev, torch.float32) for p in points])
+            g = self._dense_graph(union_pts.shape[0], n)          # one statistic segment per sample, as solo
+            shapes = [(int(p.shape[0]), n, n) for p in points]
+            out_shapes = shapes
+            inst_rows = np.concatenate([[0], np.cumsum([int(np.prod(s_)) for s_ in shapes])])
+            union_pts = union_pts.reshape(-1, 2)
+        instances = self._instance_tables(inst_rows, seeds)
+        xt = torch.cat(self._initial_noise(shapes, generators, xt0, dev))
+        heat = self._sample_loop(self._union_step(g, _lib.TASK_TSP, union_pts, instances), xt)
+        return [heat[int(inst_rows[b]):int(inst_rows[b + 1])].reshape(out_shapes[b]) for b in range(B)]
+
 
 class MISModel(COMetaModel):
     """Inference half of ``difusco/pl_mis_model.py`` (node features only)."""
@@ -308,3 +400,16 @@ class MISModel(COMetaModel):
             else:
                 xt = self.categorical_denoise_step(xt, t1, self.device, edge_index, target_t=t2)
         return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
+
+    def sample_batch(self, n_nodes, edge_index, seeds=None, generators=None, xt0=None):
+        """``sample()`` of B graphs in ONE sampling loop over their disjoint union: ``n_nodes[b]`` / ``edge_index[b]`` are what
+        ``sample()`` takes for graph b (its P parallel samples already duplicated), ``seeds`` / ``generators`` / ``xt0`` as in
+        ``TSPModel.sample_batch``.  One head statistic segment per graph (= its solo call).  Returns the B node-score tensors."""
+        B = len(n_nodes)
+        if B < 1 or len(edge_index) != B:
+            raise ValueError("sample_batch needs one edge_index per graph and at least one graph")
+        g, _, inst_rows = build_union_csr(edge_index, [int(v) for v in n_nodes], self.device, task_rows="nodes")
+        instances = self._instance_tables(inst_rows, seeds)
+        xt = torch.cat(self._initial_noise([(int(v),) for v in n_nodes], generators, xt0, self.device))
+        heat = self._sample_loop(self._union_step(g, _lib.TASK_MIS, None, instances), xt)
+        return [heat[int(inst_rows[b]):int(inst_rows[b + 1])] for b in range(B)]

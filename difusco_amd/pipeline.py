@@ -1,19 +1,21 @@
 """The inference flow of ``TSPModel.test_step`` (``difusco/pl_tsp_model.py:153-256``) and ``MISModel.test_step``
 (``difusco/pl_mis_model.py:142-209``) without Lightning, every stage on the GPU path of this package: k-NN graph ->
 ``sequential_sampling`` rounds of ``parallel_sampling`` noise samples through the denoising loop -> heatmap -> greedy
-tour merge -> batched 2-opt -> best tour.  One instance per call, like the reference (its test batch size is 1); the
+tour merge -> batched 2-opt -> best tour.  ``solve_tsp`` / ``solve_mis`` take one instance per call, like the reference (its
+test batch size is 1); ``solve_tsp_batch`` / ``solve_mis_batch`` solve many instances per pass with the same per-instance
+answers (one sampling loop over their union, per-instance statistics and random streams, grouped 2-opt).  In both the
 parallel samples form the batch of the denoise steps (disjoint union, ``duplicate_edge_index``), the sequential rounds
 repeat the whole loop with fresh noise and stack the results (``pl_tsp_model.py:185,238,240``).
 
 This is host-side orchestration only - each stage is one of the drop-in entry points (``graph.knn_edge_index_gpu``,
 ``TSPModel.sample``, ``decode.merge_tours``, ``decode.batched_two_opt_torch``) and can be used on its own."""
 import time
-from typing import Dict, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .decode import batched_two_opt_torch, merge_tours
+from .decode import batched_two_opt_grouped, batched_two_opt_torch, merge_tours
 from .graph import knn_edge_index_gpu
 
 
@@ -108,3 +110,134 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     sizes = sol.sum(axis=1)
     best = int(np.argmax(sizes))
     return sol[best], int(sizes[best]), sizes.tolist()
+
+
+def _chunks(B: int, per_call: Optional[int]):
+    if per_call is not None and int(per_call) < 1:
+        raise ValueError("instances_per_call must be >= 1")
+    step = B if per_call is None else int(per_call)
+    return [(s, min(B, s + step)) for s in range(0, B, step)]
+
+
+def _per_instance(v, B: int, name: str):
+    if v is None:
+        return None
+    v = list(v)
+    if len(v) != B:
+        raise ValueError(f"{name}: {len(v)} entries for {B} instances")
+    return v
+
+
+def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 1, sequential_sampling: int = 1,
+                    two_opt_iterations: int = 1000, seeds: Optional[Sequence[int]] = None,
+                    generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
+                    instances_per_call: Optional[int] = None) -> List[tuple]:
+    """``solve_tsp`` of B instances of the same size: ``points`` [B, N, 2].  Returns the list of what ``solve_tsp`` returns for
+    every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
+    ``instances_per_call`` instances (default: all) share one k-NN launch sequence, one sampling loop over their union
+    (``TSPModel.sample_batch``) and one grouped 2-opt; the merge runs per instance.  The step offsets come from the engine's
+    call counter, as in ``solve_tsp``: with a fresh engine the first group of instances matches solo calls on fresh engines."""
+    pts_all = np.ascontiguousarray(points, dtype=np.float64)
+    if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
+        raise ValueError("points must be [B, N, 2] with B >= 1")
+    B, n = pts_all.shape[0], pts_all.shape[1]
+    seeds, generators = _per_instance(seeds, B, "seeds"), _per_instance(generators, B, "generators")
+    dev = model.device
+    sparse = sparse_factor is not None and sparse_factor > 0
+    P = int(parallel_sampling)
+    tick = _ticker(timings, dev)
+    results = []
+    for c0, c1 in _chunks(B, instances_per_call):
+        G = c1 - c0
+        t0 = time.perf_counter()
+        if sparse:
+            ei_all = knn_edge_index_gpu(pts_all[c0:c1].reshape(-1, 2), sparse_factor, device=dev, graphs=G)
+            E = n * sparse_factor
+            eis = [ei_all[:, g * E:(g + 1) * E] - g * n for g in range(G)]
+        tick("knn", t0)
+        pts32 = torch.from_numpy(pts_all[c0:c1].astype(np.float32)).to(dev)           # [G, n, 2], as solve_tsp
+        np_points64 = pts32.cpu().numpy().astype(np.float64)
+        if sparse:
+            pts_rep = [pts32[g].repeat(P, 1) for g in range(G)]
+            ei_rep = [model.duplicate_edge_index(eis[g], n, dev, copies=P) if P > 1 else eis[g] for g in range(G)]
+        else:
+            pts_rep, ei_rep = [pts32[g].reshape(1, n, 2).repeat(P, 1, 1) for g in range(G)], None
+        seeds_c = None if seeds is None else seeds[c0:c1]
+        gens_c = None if generators is None else generators[c0:c1]
+        stacked = [[] for _ in range(G)]
+        merged_costs = [[] for _ in range(G)]
+        merge_its = [0.0] * G
+        ns = np.zeros(G, dtype=np.int64)
+        for _ in range(sequential_sampling):
+            t0 = time.perf_counter()
+            heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c)
+            tick("sampling", t0)
+            t0 = time.perf_counter()
+            tours = []
+            for g in range(G):
+                tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
+                                               parallel_sampling=P, device=dev)
+                tours.append(tg)
+            tick("merge", t0)
+            t0 = time.perf_counter()
+            solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
+                                                 max_iterations=two_opt_iterations, device=dev)
+            tick("two_opt", t0)
+            for g in range(G):
+                stacked[g].append(solved[g * P:(g + 1) * P])
+                merged_costs[g] += [tour_length(np_points64[g], t) for t in tours[g]]
+        for g in range(G):
+            sol = np.concatenate(stacked[g], axis=0)
+            costs = [tour_length(np_points64[g], t) for t in sol]
+            best = int(np.argmin(costs))
+            results.append((sol[best].tolist(), costs[best], costs,
+                            {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]),
+                             "merged_costs": merged_costs[g]}))
+    return results
+
+
+def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sampling: int = 1,
+                    seeds: Optional[Sequence[int]] = None, generators: Optional[Sequence[torch.Generator]] = None,
+                    timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None) -> List[tuple]:
+    """``solve_mis`` of B graphs: ``instances`` = [(n_nodes, edge_index), ...].  Returns the list of what ``solve_mis`` returns
+    for every graph (run with ``seed = seeds[b]``, ``generator = generators[b]``).  Up to ``instances_per_call`` graphs share
+    one sampling loop over their union (``MISModel.sample_batch``) and one greedy decode of the union (``mis_decode_np``: the
+    decode never crosses a component, so every graph gets its own decode)."""
+    from .decode import mis_decode_np
+    from .graph import build_csr
+    instances = list(instances)
+    B = len(instances)
+    if B < 1:
+        raise ValueError("solve_mis_batch needs at least one instance")
+    seeds, generators = _per_instance(seeds, B, "seeds"), _per_instance(generators, B, "generators")
+    dev = model.device
+    P = int(parallel_sampling)
+    tick = _ticker(timings, dev)
+    results = []
+    for c0, c1 in _chunks(B, instances_per_call):
+        ns = [int(instances[b][0]) for b in range(c0, c1)]
+        eis = []
+        for b in range(c0, c1):
+            ei = instances[b][1]
+            ei = (ei if isinstance(ei, torch.Tensor) else torch.from_numpy(np.asarray(ei))).to(dev)
+            eis.append(model.duplicate_edge_index(ei, ns[b - c0], dev, copies=P) if P > 1 else ei)
+        off = np.concatenate([[0], np.cumsum([n * P for n in ns])])
+        union = torch.cat([e + int(off[g]) for g, e in enumerate(eis)], dim=1)
+        graph = build_csr(union, int(off[-1]), dev)
+        sols = [[] for _ in ns]
+        for _ in range(sequential_sampling):
+            t0 = time.perf_counter()
+            scores = model.sample_batch([n * P for n in ns], eis, seeds=None if seeds is None else seeds[c0:c1],
+                                        generators=None if generators is None else generators[c0:c1])
+            tick("sampling", t0)
+            t0 = time.perf_counter()
+            sol = mis_decode_np(torch.cat(scores), graph=graph, device=dev)
+            for g, n in enumerate(ns):
+                sols[g].append(sol[off[g]:off[g + 1]].reshape(P, n))
+            tick("decode", t0)
+        for g in range(len(ns)):
+            sol = np.concatenate(sols[g], axis=0)
+            sizes = sol.sum(axis=1)
+            best = int(np.argmax(sizes))
+            results.append((sol[best], int(sizes[best]), sizes.tolist()))
+    return results

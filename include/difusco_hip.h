@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DIFUSCO_ABI_VERSION 12
+#define DIFUSCO_ABI_VERSION 13
 
 enum {
   DIFUSCO_OK = 0,
@@ -54,7 +54,10 @@ enum {
 enum {
   DIFUSCO_RAND_NONE = 0,     /* no draw: categorical final step (target_t == 0) or DDIM */
   DIFUSCO_RAND_INJECTED = 1, /* caller supplies uniforms (categorical) / normals (gaussian DDPM) */
-  DIFUSCO_RAND_PHILOX = 2    /* on-device Philox4x32-10 keyed by (seed, offset, element) */
+  DIFUSCO_RAND_PHILOX = 2,   /* on-device Philox4x32-10 keyed by (seed, offset, element) */
+  DIFUSCO_RAND_PHILOX_INSTANCES = 3 /* ABI 13: Philox keyed per instance of a batched call: output row r of instance b
+                                       draws with (instance_seeds[b], offset, r - instance_rows[b]), the draw of a solo
+                                       call of that instance with seed = instance_seeds[b] (difusco_step_args) */
 };
 
 int difusco_abi_version(void);
@@ -224,6 +227,14 @@ typedef struct difusco_step_args {
    * per edge; tiles with an edge outside the table or a non-finite x_t, and NULL, take the contraction.  Results differ from the
    * table-free step by fp32 rounding only. */
   const float* gen_table;
+  /* ABI 13.  Per-instance random streams of a call that batches several INSTANCES (each with its own parallel samples):
+   * read with rand_mode == DIFUSCO_RAND_PHILOX_INSTANCES only, ignored otherwise.  instance_rows [n_instances + 1] (device)
+   * are the output-row boundaries of the instances in CALLER order (edges for TSP, nodes for MIS; instance_rows[0] = 0,
+   * instance_rows[n_instances] = rows), instance_seeds [n_instances] (device) their Philox keys.  The head statistics are
+   * not affected: give every instance a statistic segment of its own (n_segments / seg_ptr) to reproduce its solo call. */
+  int32_t n_instances;
+  const int64_t* instance_rows;
+  const uint64_t* instance_seeds;
 } difusco_step_args;
 
 enum {
@@ -314,7 +325,8 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
                              const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
                              const float* scales, void* scratch, void* stream);
 
-/* Elementwise posteriors on already computed predictions (pl_meta_model.py:102-175). */
+/* Elementwise posteriors on already computed predictions (pl_meta_model.py:102-175).  rand_mode 0-2 (the per-instance
+ * mode needs the instance tables of difusco_step_args and is refused here). */
 int difusco_categorical_posterior(const float* logits, const float* xt, const float* post,
                                   int rand_mode, const float* rand, uint64_t seed, uint64_t offset,
                                   float* xt_out, float* prob_out, int64_t n, void* stream);
@@ -371,6 +383,16 @@ int difusco_tsp_merge_tours(int n_nodes, int64_t n_edges, const int32_t* row, co
 int difusco_tsp_two_opt_workspace_bytes(int n_nodes, int batch, size_t* bytes);
 int difusco_tsp_two_opt(int n_nodes, int batch, const double* points, int32_t* tours, int64_t max_iterations,
                         void* workspace, size_t workspace_bytes, int64_t* iterations_out, void* stream);
+
+/* Grouped 2-opt (ABI 13): `groups` independent instances of the same n_nodes, each with `per_group` tours.  points: DEVICE
+ * float64 [groups, n_nodes, 2]; tours: DEVICE int32 [groups * per_group, n_nodes + 1], the tours of group g at rows
+ * g * per_group .. (g + 1) * per_group - 1, refined in place.  Every group follows difusco_tsp_two_opt on its own tours
+ * exactly (its stop test looks at its own tours only); a group that has stopped costs no further work.
+ * iterations_out: HOST int64 [groups], the applied moves of every group.  Blocks until every group is done. */
+int difusco_tsp_two_opt_grouped_workspace_bytes(int n_nodes, int groups, int per_group, size_t* bytes);
+int difusco_tsp_two_opt_grouped(int n_nodes, int groups, int per_group, const double* points, int32_t* tours,
+                                int64_t max_iterations, void* workspace, size_t workspace_bytes, int64_t* iterations_out,
+                                void* stream);
 
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
