@@ -11,8 +11,11 @@ ABI_VERSION = 13
 TASK_TSP, TASK_MIS = 0, 1
 CATEGORICAL, GAUSSIAN = 0, 1
 RAND_NONE, RAND_INJECTED, RAND_PHILOX, RAND_PHILOX_INSTANCES = 0, 1, 2, 3
-PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3 = 0, 1, 2, 3
-PRECISIONS = {"fp32": PREC_FP32, "bf16x3": PREC_BF16X3, "bf16x6": PREC_BF16X6, "fp16x3": PREC_FP16X3}
+PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3, PREC_FP16X1 = 0, 1, 2, 3, 4
+# fp16x1: one fp16 product per edge-GEMM term, the counterpart of the reference's --fp16 (include/difusco_hip.h)
+PRECISIONS = {"fp32": PREC_FP32, "bf16x3": PREC_BF16X3, "bf16x6": PREC_BF16X6, "fp16x3": PREC_FP16X3,
+              "fp16x1": PREC_FP16X1}
+FUSED_PRECISIONS = ("bf16x3", "fp16x3", "fp16x1")      # the precisions with a fused edge-layer kernel (api.hip: `fused`)
 AGGREGATIONS = {"sum": 0, "mean": 1, "max": 2}      # DIFUSCO_AGG_* (--aggregation, train.py:52; gnn_encoder.py:170-191)
 
 # indices into difusco_weights_layout() (mirrors the enums of include/difusco_hip.h)

@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip.so")
 PROF_LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip_prof.so")
-SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "knn.hip", "mis_decode.hip", "formats.hip", "api.hip"]
+SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "knn.hip", "mis_decode.hip", "formats.hip", "api.hip"]
 PROF_SOURCES = SOURCES + ["edge_layer_abl.hip", "stage_lab.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "edge_layer_common.h"), os.path.join(CSRC, "edge_layer_kernel.h"),
            os.path.join(os.path.dirname(PKG), "include", "difusco_hip.h")]
@@ -38,7 +38,7 @@ EXTRA_FLAGS = {}
 # registers - no moves (DIFUSCO_FUSED_PACKED_FP32=1 restores the packed instructions for an A/B).
 NO_PK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _FUSED_NO_PK = os.environ.get("DIFUSCO_FUSED_PACKED_FP32", "0") in ("", "0")
-for _src in ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_abl.hip"):
+for _src in ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "edge_layer_abl.hip"):
     EXTRA_FLAGS[_src] = (["-mllvm", "-amdgpu-sched-strategy=" + _FUSED_SCHED] if _FUSED_SCHED != "default" else []) + \
                         (NO_PK if _FUSED_NO_PK else [])
 
@@ -97,12 +97,12 @@ def rocm_root() -> str:
 # A/B builds of the production sources with different compiler options (benchmarking only; loaded through
 # DIFUSCO_HIP_LIBRARY=<path>): name -> (extra flags, the sources they apply to; None = every source)
 VARIANTS = {
-    "pk_fused": (["-Xclang", "-target-feature", "-Xclang", "+packed-fp32-ops"], ("edge_layer.hip", "edge_layer_bf16.hip")),   # round 3
+    "pk_fused": (["-Xclang", "-target-feature", "-Xclang", "+packed-fp32-ops"], ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip")),   # round 3
     "nopk_all": (NO_PK, None),
     # the fused translation units under LLVM's other instruction-scheduling strategies (round 5 A/B; all compile without scratch)
-    "sched_maxilp": (["-mllvm", "-amdgpu-sched-strategy=max-ilp"], ("edge_layer.hip", "edge_layer_bf16.hip")),
-    "sched_memclause": (["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"], ("edge_layer.hip", "edge_layer_bf16.hip")),
-    "sched_iterilp": (["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], ("edge_layer.hip", "edge_layer_bf16.hip")),
+    "sched_maxilp": (["-mllvm", "-amdgpu-sched-strategy=max-ilp"], ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip")),
+    "sched_memclause": (["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"], ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip")),
+    "sched_iterilp": (["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], ("edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip")),
 }
 
 

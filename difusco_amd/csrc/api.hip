@@ -131,6 +131,23 @@ Workspace carve(void* base, int H, int L, int64_t N, int64_t E, int S, int nblk)
 }
 
 
+// C of layer 0 on the two rows of the edge-input table (table rows 0, 1 -> rows 2, 3; layer-0 fold of the fused step and
+// difusco_prepare).  Exact fp32, except under FP16X1: there the one-product fp16 linear that the fused kernel's GEMM 1 applies to
+// an e tile (each row scaled by its power of two, the hi plane of C), so that folding layer 0 keeps the precision's contract.
+// scale2: two floats of scratch.
+hipError_t table_c_rows(int precision, int H, float* table, const float* c_w, const float* c_planes, float* scale2,
+                        hipStream_t st) {
+  using namespace difusco;
+  if (precision != DIFUSCO_PREC_FP16X1) return launch_two_rows_linear(H, table, c_w, nullptr, table + 2 * H, st);
+  hipError_t er = launch_row_pow2_scale(table, 2, H, scale2, st);
+  if (er != hipSuccess) return er;
+  SplitScale sc;
+  sc.row_scale = scale2;
+  sc.w_inv = c_planes + (long long)5 * H * H / 2;
+  return linear_rows_split(table, reinterpret_cast<const unsigned short*>(c_planes) + (long long)3 * H * H, (long long)H * H,
+                           DIFUSCO_PREC_FP16X1, nullptr, nullptr, table + 2 * H, 2, H, H, H, st, 0, sc);
+}
+
 // Prepared state of a TSP call shape (difusco_step_args.prepared): what a step computes from (weights, points) alone.
 struct Prepared {
   float *h0, *node4_0, *table;      // [N,H], [N,4H], [4,H]
@@ -293,15 +310,18 @@ int difusco_denoise_step(const difusco_step_args* a) {
   auto G = [&](int id) { return W + lo.off[id]; };
   auto LW = [&](int l, int id) { return W + lo.off[DIFUSCO_W_GLOBAL_COUNT + l * DIFUSCO_WL_COUNT + id]; };
   hipStream_t st = (hipStream_t)a->stream;
-  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X3)
+  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X1)
     return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
-  // E-row linear: exact fp32 MFMA or bf16 split planes, same contract
-  auto edge_linear = [&](const float* x, const float* w, const float* planes, const float* b, const float* res,
+  // FP16X1: only the edge-row GEMMs of the layers (C, per_layer_out[l][2]) take the one-product form; every other matrix product
+  // (edge embedding, node linears) runs as FP16X3 - nprec is the precision of those
+  const int nprec = a->precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : a->precision;
+  // E-row linear: exact fp32 MFMA or bf16 split planes, same contract (mode: the precision of this product)
+  auto edge_linear = [&](int mode, const float* x, const float* w, const float* planes, const float* b, const float* res,
                          float* y) -> hipError_t {
-    if (a->precision == DIFUSCO_PREC_FP32) return linear_rows(x, w, b, res, y, E, H, H, H, st);
+    if (mode == DIFUSCO_PREC_FP32) return linear_rows(x, w, b, res, y, E, H, H, H, st);
     const unsigned short* pl = reinterpret_cast<const unsigned short*>(planes);
     SplitScale sc;
-    if (a->precision == DIFUSCO_PREC_FP16X3) {
+    if (mode == DIFUSCO_PREC_FP16X3 || mode == DIFUSCO_PREC_FP16X1) {
       pl += (long long)3 * H * H;   // fp16 planes follow the 3 bf16 planes
       // fp16 planes: per-row power-of-two scale of x (one extra pass over x on this unfused path), weight inverse scales
       hipError_t er = launch_row_pow2_scale(x, E, H, ws.escale, st);
@@ -309,7 +329,7 @@ int difusco_denoise_step(const difusco_step_args* a) {
       sc.row_scale = ws.escale;
       sc.w_inv = planes + (long long)5 * H * H / 2;
     }
-    return linear_rows_split(x, pl, (long long)H * H, a->precision, b, res, y, E, H, H, H, st, 0, sc);
+    return linear_rows_split(x, pl, (long long)H * H, mode, b, res, y, E, H, H, H, st, 0, sc);
   };
 
   // PROF(category, call): HIP_TRY(call), bracketed by a pair of HIP events on `st` when profiling is on
@@ -330,7 +350,8 @@ int difusco_denoise_step(const difusco_step_args* a) {
   // with 2^20 nodes or more it takes the unfused sequence
   const bool agg_max = a->aggregation == DIFUSCO_AGG_MAX;
   const bool fused = H == 256 && !a->no_fusion && E > 0 && !(agg_max && reg_gather) &&
-                     (a->precision == DIFUSCO_PREC_BF16X3 || a->precision == DIFUSCO_PREC_FP16X3);
+                     (a->precision == DIFUSCO_PREC_BF16X3 || a->precision == DIFUSCO_PREC_FP16X3 ||
+                      a->precision == DIFUSCO_PREC_FP16X1);
   if (fused && !a->row) return fail(DIFUSCO_EINVAL, "the fused edge-layer kernel needs args->row");
   const int fused_variant = reg_gather | (agg_max ? 2 : 0);      // (launch_by_mode, edge_layer.hip)
   const int64_t E_pad = (E + 255) / 256 * 256;
@@ -347,7 +368,7 @@ int difusco_denoise_step(const difusco_step_args* a) {
   const bool gn_fold = tail_fold && tsp;
   const bool l0_fold = fused && (a->flags & DIFUSCO_FLAG_NO_L0_FOLD) == 0 && !ablating &&
                        (tsp ? a->xt_is_binary != 0 : true);
-  const bool f16 = a->precision == DIFUSCO_PREC_FP16X3;
+  const bool f16 = nprec == DIFUSCO_PREC_FP16X3;      // fp16 planes (FP16X3 or FP16X1): operand scales are kept
   const int64_t n_tiles_pad = E_pad / 32;
   // prepared state (TSP, fused path only; anything else recomputes - the stateless step is always correct)
   const bool use_prep = a->prepared != nullptr && fused && tsp && !ablating;
@@ -383,9 +404,9 @@ int difusco_denoise_step(const difusco_step_args* a) {
         PROF(PROF_EMBED, launch_two_rows_linear(H, ws.table_in, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_B), ws.table,
                                                 st))
       }
-      if (l0_fold) {   // e0 and C e0 are read from the table by the first fused layer: C on the two rows, exact fp32
+      if (l0_fold) {   // e0 and C e0 are read from the table by the first fused layer: C on the two rows (table_c_rows)
         if (!use_prep)
-          PROF(PROF_EMBED, launch_two_rows_linear(H, ws.table, LW(0, DIFUSCO_WL_C_W), nullptr, ws.table + 2 * H, st))
+          PROF(PROF_EMBED, table_c_rows(a->precision, H, ws.table, LW(0, DIFUSCO_WL_C_W), LW(0, DIFUSCO_WL_C_PLANES), ws.table_in, st))
       }
       else if (fused) {
         PROF(PROF_EMBED, launch_table_rows_tiled(a->xt, a->perm, table, E, ws.e, st))
@@ -395,14 +416,14 @@ int difusco_denoise_step(const difusco_step_args* a) {
     } else {
       if (fused) {   // sinusoidal features generated inside the linear: the E x H embedding never exists in memory
         const unsigned short* pl = reinterpret_cast<const unsigned short*>(G(DIFUSCO_W_EDGE_EMBED_PLANES)) +
-                                   (a->precision == DIFUSCO_PREC_FP16X3 ? (long long)3 * H * H : 0);
-        PROF(PROF_EMBED, launch_edge_embed_tiled(a->xt, a->perm, G(DIFUSCO_W_DIMT_SCALAR), pl, (long long)H * H, a->precision,
+                                   (f16 ? (long long)3 * H * H : 0);
+        PROF(PROF_EMBED, launch_edge_embed_tiled(a->xt, a->perm, G(DIFUSCO_W_DIMT_SCALAR), pl, (long long)H * H, nprec,
                                                  f16 ? G(DIFUSCO_W_EDGE_EMBED_PLANES) + (long long)5 * H * H / 2 : nullptr,
                                                  G(DIFUSCO_W_EDGE_EMBED_B), ws.e, E, f16 ? ws.etmax : nullptr, st, a->gen_table,
                                                  a->gen_table ? reinterpret_cast<int*>(ws.escale) : nullptr))      // (escale: unfused path only - free here)
       } else {
         PROF(PROF_EMBED, launch_scalar_embed(a->xt, a->perm, G(DIFUSCO_W_DIMT_SCALAR), E, H, ws.tmp, st))
-        PROF(PROF_LINEAR_EDGE, edge_linear(ws.tmp, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_PLANES),
+        PROF(PROF_LINEAR_EDGE, edge_linear(nprec, ws.tmp, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_PLANES),
                                            G(DIFUSCO_W_EDGE_EMBED_B), nullptr, ws.e))
       }
     }
@@ -420,7 +441,7 @@ int difusco_denoise_step(const difusco_step_args* a) {
   }
 
   // the GNN layers (gnn_encoder.py:425-449)
-  const long long split_off = a->precision == DIFUSCO_PREC_FP16X3 ? (long long)3 * H * H : 0;  // fp16 planes follow bf16
+  const long long split_off = f16 ? (long long)3 * H * H : 0;  // fp16 planes follow bf16 (FP16X1: the hi plane of FP16X3's pair)
   for (int l = 0; l < (head_only ? 0 : L); ++l) {
     // layer 0 of a step with prepared state: U|V|A|B of h0 and h0 itself come from the prepared buffer
     const bool prep_l = use_prep && l == 0;
@@ -433,7 +454,7 @@ int difusco_denoise_step(const difusco_step_args* a) {
 #endif
     if (a->precision != DIFUSCO_PREC_FP32 && H == 256) {   // node rows on the same split-precision matrix-core path
       const unsigned short* npl = reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_NODE4_PLANES)) +
-                                  (a->precision == DIFUSCO_PREC_FP16X3 ? (long long)3 * 4 * H * H : 0);
+                                  (f16 ? (long long)3 * 4 * H * H : 0);
       SplitScale sc;
       if (f16) {   // row scales of h: left by node_finalize of the previous layer on the fused path, computed here otherwise
         if (!fused || l == 0) PROF(PROF_LINEAR_NODE, launch_row_pow2_scale(ws.h, N, H, ws.hscale, st))
@@ -442,7 +463,7 @@ int difusco_denoise_step(const difusco_step_args* a) {
       }
       // fused edge kernel: A | B rows in its log2(e) domain, b_C folded into the A rows (difusco_hip.h, ABI 11 note)
       if (fused) sc.w_inv = LW(l, DIFUSCO_WL_NODE4_FUSED_S) + (f16 ? 0 : 4 * H);
-      PROF(PROF_LINEAR_NODE, linear_rows_split(ws.h, npl, (long long)4 * H * H, a->precision,
+      PROF(PROF_LINEAR_NODE, linear_rows_split(ws.h, npl, (long long)4 * H * H, nprec,
                                                LW(l, fused ? DIFUSCO_WL_NODE4_FUSED_B : DIFUSCO_WL_NODE4_B),
                                                nullptr, ws.node4, N, H, 4 * H, 4 * H, st, 0, sc))
     } else {
@@ -489,14 +510,14 @@ int difusco_denoise_step(const difusco_step_args* a) {
                                            prep_l ? prep.h0 : nullptr, a->aggregation))
       continue;
     }
-    PROF(PROF_LINEAR_EDGE, edge_linear(ws.e, LW(l, DIFUSCO_WL_C_W), LW(l, DIFUSCO_WL_C_PLANES), LW(l, DIFUSCO_WL_C_B),
+    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.e, LW(l, DIFUSCO_WL_C_W), LW(l, DIFUSCO_WL_C_PLANES), LW(l, DIFUSCO_WL_C_B),
                                        nullptr, ws.tmp))
     PROF(PROF_GATE, launch_edge_gate_aggregate(H, (int)N, a->rowptr, a->col, ws.node4, ws.tmp, ws.h,
                                                LW(l, DIFUSCO_WL_NORM_H_W), LW(l, DIFUSCO_WL_NORM_H_B),
                                                LW(l, DIFUSCO_WL_NORM_E_W), LW(l, DIFUSCO_WL_NORM_E_B),
                                                LW(l, DIFUSCO_WL_OUT_LN_W), LW(l, DIFUSCO_WL_OUT_LN_B),
                                                tbias + (size_t)l * H, tsp ? 1 : 0, st, a->aggregation))
-    PROF(PROF_LINEAR_EDGE, edge_linear(ws.tmp, LW(l, DIFUSCO_WL_OUT_W), LW(l, DIFUSCO_WL_OUT_PLANES),
+    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.tmp, LW(l, DIFUSCO_WL_OUT_W), LW(l, DIFUSCO_WL_OUT_PLANES),
                                        LW(l, DIFUSCO_WL_OUT_B), ws.e, ws.e))
   }
 
@@ -622,7 +643,7 @@ int difusco_prepare(const difusco_step_args* a, void* prepared, size_t prepared_
   if (a->task != DIFUSCO_TASK_TSP) return fail(DIFUSCO_EINVAL, "prepared state exists for TSP only (the MIS node embedding is a function of x_t)");
   const int64_t N = a->n_nodes, E = a->n_edges;
   if (N <= 0 || E < 0 || !a->weights || !a->points || !a->workspace) return fail(DIFUSCO_EINVAL, "null pointer / empty graph");
-  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X3) return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
+  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X1) return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
   const Prepared prep = carve_prepared(prepared, H, N);
   if (prep.bytes > prepared_bytes) return fail(DIFUSCO_EWORKSPACE, "prepared buffer too small: %zu < %zu", prepared_bytes, prep.bytes);
   const int nblk = gn_blocks_for(E > N ? E : N);
@@ -633,7 +654,8 @@ int difusco_prepare(const difusco_step_args* a, void* prepared, size_t prepared_
   auto G = [&](int id) { return W + lo.off[id]; };
   auto LW = [&](int l, int id) { return W + lo.off[DIFUSCO_W_GLOBAL_COUNT + l * DIFUSCO_WL_COUNT + id]; };
   hipStream_t st = (hipStream_t)a->stream;
-  const bool f16 = a->precision == DIFUSCO_PREC_FP16X3;
+  const int nprec = a->precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : a->precision;      // (node linear: as in the step)
+  const bool f16 = nprec == DIFUSCO_PREC_FP16X3;
   // h0 = node_embed(pos_embed(points))  (ws.node4 is the scratch of the sinusoidal features, as in the step)
   HIP_TRY(launch_pos_embed(a->points, G(DIFUSCO_W_DIMT_POS), (int)N, H, ws.node4, st));
   HIP_TRY(linear_rows(ws.node4, G(DIFUSCO_W_NODE_EMBED_W), G(DIFUSCO_W_NODE_EMBED_B), nullptr, prep.h0, N, H, H, H, st));
@@ -649,9 +671,9 @@ int difusco_prepare(const difusco_step_args* a, void* prepared, size_t prepared_
     }
     // the prepared rows are read by the fused edge kernel only (difusco_denoise_step: use_prep requires the fused path), so they
     // are produced in its log2(e) domain whenever the precision has a fused path - same vectors as the step's own node linear
-    const bool fused_prec = a->precision == DIFUSCO_PREC_BF16X3 || a->precision == DIFUSCO_PREC_FP16X3;
+    const bool fused_prec = nprec == DIFUSCO_PREC_BF16X3 || nprec == DIFUSCO_PREC_FP16X3;
     if (fused_prec) sc.w_inv = LW(0, DIFUSCO_WL_NODE4_FUSED_S) + (f16 ? 0 : 4 * H);
-    HIP_TRY(linear_rows_split(prep.h0, npl, (long long)4 * H * H, a->precision,
+    HIP_TRY(linear_rows_split(prep.h0, npl, (long long)4 * H * H, nprec,
                               LW(0, fused_prec ? DIFUSCO_WL_NODE4_FUSED_B : DIFUSCO_WL_NODE4_B), nullptr,
                               prep.node4_0, N, H, 4 * H, 4 * H, st, 0, sc));
     //  a precision without a fused path (BF16X6) computes the reference's rows: converted in place, so that the buffer
@@ -666,7 +688,7 @@ int difusco_prepare(const difusco_step_args* a, void* prepared, size_t prepared_
   // two-row edge-input table of a categorical step (embedding of the bit) and C of layer 0 applied to it
   HIP_TRY(launch_scalar_embed(nullptr, nullptr, G(DIFUSCO_W_DIMT_SCALAR), 2, H, ws.table_in, st));
   HIP_TRY(launch_two_rows_linear(H, ws.table_in, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_B), prep.table, st));
-  HIP_TRY(launch_two_rows_linear(H, prep.table, LW(0, DIFUSCO_WL_C_W), nullptr, prep.table + 2 * H, st));
+  HIP_TRY(table_c_rows(a->precision, H, prep.table, LW(0, DIFUSCO_WL_C_W), LW(0, DIFUSCO_WL_C_PLANES), ws.table_in, st));
   return DIFUSCO_OK;
 }
 
@@ -683,13 +705,13 @@ int difusco_linear_rows_split(const float* x, const void* planes, int precision,
                               const float* residual, float* y, int64_t m, int k, int n_out, int64_t ldy,
                               float* row_scale_scratch, void* stream) {
   if (!x || !planes || !y) return fail(DIFUSCO_EINVAL, "null pointer");
-  if (precision < DIFUSCO_PREC_BF16X3 || precision > DIFUSCO_PREC_FP16X3)
-    return fail(DIFUSCO_EINVAL, "precision must be BF16X3, BF16X6 or FP16X3");
+  if (precision < DIFUSCO_PREC_BF16X3 || precision > DIFUSCO_PREC_FP16X1)
+    return fail(DIFUSCO_EINVAL, "precision must be BF16X3, BF16X6, FP16X3 or FP16X1");
   if (!(k == 64 || k == 128 || k == 256) || (n_out != k && !(k == 256 && n_out > 0 && n_out % 256 == 0)) || ldy < n_out)
     return fail(DIFUSCO_EINVAL, "split path needs k in {64,128,256}, n_out == k (or a multiple of 256 for k = 256), ldy >= n_out");
   const unsigned short* pl = reinterpret_cast<const unsigned short*>(planes);
   difusco::SplitScale sc;
-  if (precision == DIFUSCO_PREC_FP16X3) {
+  if (precision == DIFUSCO_PREC_FP16X3 || precision == DIFUSCO_PREC_FP16X1) {      // (FP16X1: the hi plane of the fp16 pair)
     pl += (long long)3 * n_out * k;
     sc.w_inv = reinterpret_cast<const float*>(planes) + (long long)5 * n_out * k / 2;
     if (row_scale_scratch != nullptr) {
@@ -727,14 +749,15 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
                              const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
                              const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
                              const float* scales, void* scratch, void* stream) {
-  if (precision != DIFUSCO_PREC_BF16X3 && precision != DIFUSCO_PREC_FP16X3)
-    return fail(DIFUSCO_EINVAL, "fused kernel: precision must be BF16X3 or FP16X3");
+  if (precision != DIFUSCO_PREC_BF16X3 && precision != DIFUSCO_PREC_FP16X3 && precision != DIFUSCO_PREC_FP16X1)
+    return fail(DIFUSCO_EINVAL, "fused kernel: precision must be BF16X3, FP16X3 or FP16X1");
   if (!rowptr || !row || !col || !node4 || !e || !h || !planes_c || !planes_o || !b_c || !norm_h_w || !norm_h_b ||
       !norm_e_w || !norm_e_b || !out_ln_w || !out_ln_b || !b_out || !tbias || !scratch)
     return fail(DIFUSCO_EINVAL, "null pointer");
-  if (precision == DIFUSCO_PREC_FP16X3 && !scales)
-    return fail(DIFUSCO_EINVAL, "fused kernel, FP16X3: the operand-scale record of the layer is required");
-  const long long off = precision == DIFUSCO_PREC_FP16X3 ? 3LL * 256 * 256 : 0;
+  const bool f16 = precision == DIFUSCO_PREC_FP16X3 || precision == DIFUSCO_PREC_FP16X1;
+  if (f16 && !scales)
+    return fail(DIFUSCO_EINVAL, "fused kernel, FP16X3 / FP16X1: the operand-scale record of the layer is required");
+  const long long off = f16 ? 3LL * 256 * 256 : 0;
   float* part = reinterpret_cast<float*>(scratch);
   float* direct = part + (fused_part_floats(n_edges) + 63) / 64 * 64;
   float* etmax = direct + (size_t)n_nodes * 256;
@@ -745,7 +768,7 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
   // has no such pass: its node linear produces the rows in that form.)
   float* node4_k = etmax + (n_tiles_pad + 63) / 64 * 64;
   HIP_TRY(difusco::launch_fuse_node_tables(node4, b_c, n_nodes, node4_k, st));
-  if (precision == DIFUSCO_PREC_FP16X3)      // e-stream scale per tile: normally left by the producer of e
+  if (f16)      // e-stream scale per tile: normally left by the producer of e
     HIP_TRY(difusco::launch_tile_absmax_tiled(e, n_tiles_pad, etmax, st));
   HIP_TRY(difusco::launch_edge_layer_fused(precision, e, node4_k, row, col, n_edges,
                                            reinterpret_cast<const unsigned short*>(planes_c) + off,

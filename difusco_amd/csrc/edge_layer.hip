@@ -105,10 +105,11 @@ static hipError_t launch_by_mode(int mode, int kind, int variant, FUSED_KIND_PAR
   }
   if (mode == 1) return launch_fused_bf16(kind, FUSED_KIND_ARGS);     // DIFUSCO_PREC_BF16X3
   if (mode == 3) return launch_fused_fp16(kind, FUSED_KIND_ARGS);     // DIFUSCO_PREC_FP16X3
+  if (mode == 4) return launch_fused_fp16x1(kind, FUSED_KIND_ARGS);   // DIFUSCO_PREC_FP16X1
   return hipErrorInvalidValue;
 }
 
-// mode: 1 = bf16 planes, 3 = fp16 planes (DIFUSCO_PREC_BF16X3 / DIFUSCO_PREC_FP16X3)
+// mode: 1 = bf16 planes, 3 = fp16 planes, 4 = one fp16 plane (DIFUSCO_PREC_BF16X3 / DIFUSCO_PREC_FP16X3 / DIFUSCO_PREC_FP16X1)
 hipError_t launch_edge_layer_fused(int mode, float* e, const float* node4, const int* row, const int* col, int n_edges,
                                    const unsigned short* c_planes, const unsigned short* o_planes,
                                    long long plane_stride, const float* b_c, const float* g_e, const float* b_e,

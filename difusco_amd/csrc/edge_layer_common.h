@@ -18,6 +18,7 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 // activations: in registers) and the scale is undone where the bias is added.  bf16 has the fp32 exponent range.
 struct FBf16 {
   static constexpr bool kScaled = false;
+  static constexpr int kPlanes = 2;      // 16-bit planes per operand: 3 MFMA products (hi*hi, hi*lo, lo*hi)
   typedef v8bf frag;
   __device__ static __forceinline__ unsigned split_pair(float& a, float& b) {
     v2f f = {a, b};
@@ -33,6 +34,7 @@ struct FBf16 {
 };
 struct FFp16 {
   static constexpr bool kScaled = true;
+  static constexpr int kPlanes = 2;
   typedef v8h frag;
   __device__ static __forceinline__ unsigned split_pair(float& a, float& b) {
     v2f f = {a, b};
@@ -47,17 +49,26 @@ struct FFp16 {
   }
 };
 
-// eight fp32 -> two planes of eight 16-bit values (hi, lo)
+// FFp16x1 (DIFUSCO_PREC_FP16X1): the fp16 planes with ONE plane per operand.  Each power-of-two-scaled operand is rounded once
+// to fp16 (RNE, the hi plane of FFp16), the product is the single hi*hi MFMA (exact in the fp32 accumulator); the low weight
+// plane is never loaded.
+struct FFp16x1 : FFp16 {
+  static constexpr int kPlanes = 1;
+};
+
+// eight fp32 -> two planes of eight 16-bit values (hi, lo); one-plane types: hi only (lo is zero and never read)
 template <typename T>
 __device__ __forceinline__ void split8(const float (&x)[8], typename T::frag& hi, typename T::frag& lo) {
   float v[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) v[q] = x[q];
-  v4u h, l;
+  v4u h, l = {0u, 0u, 0u, 0u};
 #pragma unroll
   for (int q = 0; q < 4; ++q) h[q] = T::split_pair(v[2 * q], v[2 * q + 1]);
+  if constexpr (T::kPlanes == 2) {
 #pragma unroll
-  for (int q = 0; q < 4; ++q) l[q] = T::split_pair(v[2 * q], v[2 * q + 1]);
+    for (int q = 0; q < 4; ++q) l[q] = T::split_pair(v[2 * q], v[2 * q + 1]);
+  }
   hi = __builtin_bit_cast(typename T::frag, h);
   lo = __builtin_bit_cast(typename T::frag, l);
 }

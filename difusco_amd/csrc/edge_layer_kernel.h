@@ -19,6 +19,8 @@
 //     {0..3, 8..11, 4..7, 12..15}).
 //   * fp32 operands are split into two 16-bit planes (fp16 planes of power-of-two-scaled operands - see `scales` at the
 //     kernel - or bf16) and multiplied with 3 MFMA products (hi*hi, hi*lo, lo*hi), accumulated in fp32 (see linear_split.hip).
+//     One-plane element type (FFp16x1, DIFUSCO_PREC_FP16X1): the scaled operands are rounded once to fp16, one product (hi*hi),
+//     and only the hi weight plane is streamed through LDS.
 // A wave owns a 32-edge tile end to end; a workgroup is 4 waves (two workgroups per CU, whose phases drift
 // apart so that one's MFMA phases overlap the other's VALU / address-heavy epilogue) - see fused::Geo.
 // Weights stream through LDS in stages of 256 rows of 32 bytes x 2 planes ([256 rows][16 k] slabs for GEMM 1,
@@ -40,7 +42,7 @@
 // First layer (template flag L0): when the edge input is a lookup in a 2-row table (categorical TSP: the embedding
 // of the bit x_t; MIS: zeros) the table sits in LDS and the kernel never reads e - see the L0 notes at the kernel.
 // This header holds the kernel template and its launcher template; the instantiations are spread over
-// edge_layer.hip (fp16 production variants), edge_layer_bf16.hip and edge_layer_abl.hip (profiling-only ablations) so
+// edge_layer.hip (fp16 production variants), edge_layer_bf16.hip, edge_layer_fp16x1.hip and edge_layer_abl.hip (profiling-only ablations) so
 // that the translation units compile in parallel.
 #pragma once
 #include "edge_layer_common.h"
@@ -281,7 +283,7 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
   }
 #define FUSED_DMA_STAGE(t)                                                                                   \
   {                                                                                                          \
-    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl)                                                         \
+    _Pragma("unroll") for (int pl = 0; pl < T::kPlanes; ++pl)                                                \
       _Pragma("unroll") for (int i = 0; i < PP; ++i) FUSED_DMA_PIECE(t, pl, i)                               \
   }
 #define FUSED_PIPE_BEGIN(t)                                         \
@@ -324,6 +326,13 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
     inv2 = scales[1];
     gmul = scales[2];
     s_den = scales[3];
+  }
+  // One plane (FFp16x1): the GEMM 2 operand is rounded to fp16 once, so it must be a power-of-two scaling of a itself, not of
+  // a log2(e): it is produced as SiLU(z) 2^ka (the denominator scale s_den log2(e)) and the accumulator scale is the exact power of
+  // two 2^-(ko+ka) (scales[1] log2(e), rounded to the nearest power of two).
+  if constexpr (T::kPlanes == 1) {
+    s_den = s_den * kLog2e;
+    inv2 = __builtin_bit_cast(float, (__builtin_bit_cast(unsigned, inv2 * kLog2e) + 0x00400000u) & 0xFF800000u);
   }
   // ---- once per workgroup: requests of its first tile, layer parameters -> LDS (thread = feature) ------------------
   if (wt < wt_end) {
@@ -471,7 +480,8 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
 #define FUSED_FRAG1(bi, slot)                                                                        \
   {                                                                                                  \
     fh[slot] = *reinterpret_cast<const frag*>(wb + ((bi) >> 3) * 256 * 16 + ((bi) & 7) * 32 * 16);   \
-    fl[slot] = *reinterpret_cast<const frag*>(wb + PLANE + ((bi) >> 3) * 256 * 16 + ((bi) & 7) * 32 * 16); \
+    if constexpr (T::kPlanes == 2)                                                                   \
+      fl[slot] = *reinterpret_cast<const frag*>(wb + PLANE + ((bi) >> 3) * 256 * 16 + ((bi) & 7) * 32 * 16); \
   }
     if constexpr ((OPT & 2) != 0) {
       // pairs of blocks: fragments of pair bp + 1 are requested before the six MFMAs of pair bp, whose two accumulator
@@ -486,10 +496,12 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
         }
         __builtin_amdgcn_sched_barrier(0);
         const int s0 = 2 * (bp & 1), s1 = s0 + 1, n0 = (2 * bp) & 7, n1 = n0 + 1, sub = (2 * bp) >> 3;
-        acc1[n0] = T::mfma(fl[s0], xh[sub], acc1[n0]);
-        acc1[n1] = T::mfma(fl[s1], xh[sub], acc1[n1]);
-        acc1[n0] = T::mfma(fh[s0], xl[sub], acc1[n0]);
-        acc1[n1] = T::mfma(fh[s1], xl[sub], acc1[n1]);
+        if constexpr (T::kPlanes == 2) {
+          acc1[n0] = T::mfma(fl[s0], xh[sub], acc1[n0]);
+          acc1[n1] = T::mfma(fl[s1], xh[sub], acc1[n1]);
+          acc1[n0] = T::mfma(fh[s0], xl[sub], acc1[n0]);
+          acc1[n1] = T::mfma(fh[s1], xl[sub], acc1[n1]);
+        }
         acc1[n0] = T::mfma(fh[s0], xh[sub], acc1[n0]);
         acc1[n1] = T::mfma(fh[s1], xh[sub], acc1[n1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -502,8 +514,10 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
         if (bi + 2 < 8 * SPS) FUSED_FRAG1(bi + 2, (bi + 2) % 3)
         if constexpr (!kFreeSched) __builtin_amdgcn_sched_barrier(0);
         const int nb = bi & 7, sub = bi >> 3;
-        acc1[nb] = T::mfma(fl[bi % 3], xh[sub], acc1[nb]);
-        acc1[nb] = T::mfma(fh[bi % 3], xl[sub], acc1[nb]);
+        if constexpr (T::kPlanes == 2) {
+          acc1[nb] = T::mfma(fl[bi % 3], xh[sub], acc1[nb]);
+          acc1[nb] = T::mfma(fh[bi % 3], xl[sub], acc1[nb]);
+        }
         acc1[nb] = T::mfma(fh[bi % 3], xh[sub], acc1[nb]);
         if constexpr (!kFreeSched) __builtin_amdgcn_sched_barrier(0);
       }
@@ -995,7 +1009,8 @@ _Pragma("unroll")                                                               
 #define FUSED_FRAG2(bi, slot)                                                                            \
   {                                                                                                      \
     fh[slot] = *reinterpret_cast<const frag*>(wb + (((bi) >> 1) * 64 + ((bi) & 1) * 32) * 16);           \
-    fl[slot] = *reinterpret_cast<const frag*>(wb + PLANE + (((bi) >> 1) * 64 + ((bi) & 1) * 32) * 16);   \
+    if constexpr (T::kPlanes == 2)                                                                       \
+      fl[slot] = *reinterpret_cast<const frag*>(wb + PLANE + (((bi) >> 1) * 64 + ((bi) & 1) * 32) * 16); \
   }
         if constexpr ((OPT & 2) != 0) {
           // the two output blocks of a k slab alternate (independent accumulators acc2[0], acc2[1])
@@ -1010,10 +1025,12 @@ _Pragma("unroll")                                                               
             __builtin_amdgcn_sched_barrier(0);
             const int s0 = 2 * (ksl & 1), s1 = s0 + 1;
             const int sl = KPS * kc + ksl;
-            acc2[0] = T::mfma(fl[s0], ah_[sl >> 1][sl & 1], acc2[0]);
-            acc2[1] = T::mfma(fl[s1], ah_[sl >> 1][sl & 1], acc2[1]);
-            acc2[0] = T::mfma(fh[s0], al_[sl >> 1][sl & 1], acc2[0]);
-            acc2[1] = T::mfma(fh[s1], al_[sl >> 1][sl & 1], acc2[1]);
+            if constexpr (T::kPlanes == 2) {
+              acc2[0] = T::mfma(fl[s0], ah_[sl >> 1][sl & 1], acc2[0]);
+              acc2[1] = T::mfma(fl[s1], ah_[sl >> 1][sl & 1], acc2[1]);
+              acc2[0] = T::mfma(fh[s0], al_[sl >> 1][sl & 1], acc2[0]);
+              acc2[1] = T::mfma(fh[s1], al_[sl >> 1][sl & 1], acc2[1]);
+            }
             acc2[0] = T::mfma(fh[s0], ah_[sl >> 1][sl & 1], acc2[0]);
             acc2[1] = T::mfma(fh[s1], ah_[sl >> 1][sl & 1], acc2[1]);
             __builtin_amdgcn_sched_barrier(0);
@@ -1031,8 +1048,10 @@ _Pragma("unroll")                                                               
             if constexpr (!kFreeSched) __builtin_amdgcn_sched_barrier(0);
             const int ksl = frag_of(bi) >> 1, nbp = frag_of(bi) & 1;
             const int sl = KPS * kc + ksl;        // slab of W_o = features 16 sl .. 16 sl + 15 of the activation
-            acc2[nbp] = T::mfma(fl[bi % 3], ah_[sl >> 1][sl & 1], acc2[nbp]);
-            acc2[nbp] = T::mfma(fh[bi % 3], al_[sl >> 1][sl & 1], acc2[nbp]);
+            if constexpr (T::kPlanes == 2) {
+              acc2[nbp] = T::mfma(fl[bi % 3], ah_[sl >> 1][sl & 1], acc2[nbp]);
+              acc2[nbp] = T::mfma(fh[bi % 3], al_[sl >> 1][sl & 1], acc2[nbp]);
+            }
             acc2[nbp] = T::mfma(fh[bi % 3], ah_[sl >> 1][sl & 1], acc2[nbp]);
             if constexpr (!kFreeSched) __builtin_amdgcn_sched_barrier(0);
           }
@@ -1212,6 +1231,7 @@ hipError_t launch_fused_opt(A... args) {
       part, direct, stream, l0_table, l0_x, l0_perm, gn_tile, scales, etmax_in, etmax_out
 hipError_t launch_fused_fp16(int kind, FUSED_KIND_PARAMS);
 hipError_t launch_fused_bf16(int kind, FUSED_KIND_PARAMS);
+hipError_t launch_fused_fp16x1(int kind, FUSED_KIND_PARAMS);      // one fp16 plane, one product (DIFUSCO_PREC_FP16X1)
 hipError_t launch_fused_ablation(int mask, FUSED_KIND_PARAMS);      // profiling-only variants of the fp16 middle layer
 
 // kinds 4-7 = kinds 0-3 with the neighbour-table rows gathered into REGISTERS by 64-bit addresses (round 2's option set):

@@ -13,6 +13,8 @@
 // first scaled by exact powers of two into [2^14, 2^15) at their maximum (weights per matrix / per row on the
 // host, rows of x by SplitScale::row_scale) and the product of the inverse scales is applied where
 // the bias is added - any finite fp32 operand keeps its 22 bits.
+// A fourth mode (DIFUSCO_PREC_FP16X1) keeps ONE fp16 plane: the scaled operands are rounded once to fp16 (RNE), one exact
+// product, fp32 accumulation - the fused edge kernel's one-plane GEMMs on the unfused path.
 // The node-row shape of a layer ([N,256] x [256,1024]) has its own kernel (node_linear.hip); this one serves the
 // E-row linears of the unfused path and the remaining shapes.
 //
@@ -24,6 +26,8 @@
 // consecutive output features of one data row per accumulator quad).  Weights arrive PRE-SPLIT from the
 // host (weights.py) as planes laid out [K/16 slabs][n_out rows][16 k] bf16, so a slab is one linear
 // stream; X is split on the fly while it is staged into LDS.
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void linear_rows_split_kernel(const float* 
   constexpr int RS = 24;                 // LDS row stride in bf16 elements (32 B data + 16 B pad = 48 B)
   constexpr int WV = (FB * 2 + 255) / 256;  // 16-byte chunks per thread per weight plane per slab
   static_assert(K % BK == 0, "K must be a multiple of 16");
-  static_assert(NS == 2 || NS == 3, "2 or 3 planes");
+  static_assert(NS == 2 || NS == 3 || (NS == 1 && std::is_same<T, Fp16>::value), "2 or 3 planes, or one fp16 plane");
 
   extern __shared__ __attribute__((aligned(16))) unsigned short smem_s[];
   unsigned short* Xs = smem_s;                         // [NS][RB][RS]
@@ -213,8 +217,10 @@ __global__ __launch_bounds__(256, 2) void linear_rows_split_kernel(const float* 
         acc[nb] = T::mfma(wa[0], xb[2], acc[nb]);
         acc[nb] = T::mfma(wa[1], xb[1], acc[nb]);
       }
-      acc[nb] = T::mfma(wa[1], xb[0], acc[nb]);
-      acc[nb] = T::mfma(wa[0], xb[1], acc[nb]);
+      if constexpr (NS >= 2) {
+        acc[nb] = T::mfma(wa[1], xb[0], acc[nb]);
+        acc[nb] = T::mfma(wa[0], xb[1], acc[nb]);
+      }
       acc[nb] = T::mfma(wa[0], xb[0], acc[nb]);
     }
     if (st + 1 < NSTEP) {
@@ -287,12 +293,13 @@ int g_node_linear_depth = 0;
 
 // wp: first plane of the chosen element type, plane p at wp + p*plane_stride, each [K/16][n_out][16]
 // (k-permuted).  mode: 1 = bf16 x 2 planes (3 products), 2 = bf16 x 3 planes (6 products),
-// 3 = fp16 x 2 planes (3 products).  sc: operand scaling of the fp16 path (kernels.h: SplitScale).
+// 3 = fp16 x 2 planes (3 products), 4 = fp16 x 1 plane (1 product; wp: the fp16 hi plane).  sc: operand scaling of the fp16
+// paths (kernels.h: SplitScale).
 hipError_t linear_rows_split(const float* x, const unsigned short* wp, long long plane_stride, int mode,
                              const float* bias, const float* residual, float* y, long long m, int k, int n_out,
                              long long ldy, hipStream_t stream, int tiled_out, SplitScale sc) {
   if (m <= 0) return hipSuccess;
-  if (mode < 1 || mode > 3) return hipErrorInvalidValue;
+  if (mode < 1 || mode > 4) return hipErrorInvalidValue;
   if (tiled_out && (k != 256 || n_out != 256 || residual != nullptr)) return hipErrorInvalidValue;
   if (sc.tile_max != nullptr && !tiled_out) return hipErrorInvalidValue;
 #define DIFUSCO_SPLIT_ARGS x, wp, plane_stride, bias, residual, y, m, n_out, ldy, stream, tiled_out, nullptr, nullptr, sc.row_scale, sc.x_scale, sc.w_inv, sc.tile_max
@@ -300,6 +307,7 @@ hipError_t linear_rows_split(const float* x, const unsigned short* wp, long long
   if (k == KK && n_out % FBB == 0) {                                                  \
     if (mode == 1) return launch_split<KK, FBB, 2, Bf16>(DIFUSCO_SPLIT_ARGS);         \
     if (mode == 2) return launch_split<KK, FBB, 3, Bf16>(DIFUSCO_SPLIT_ARGS);         \
+    if (mode == 4) return launch_split<KK, FBB, 1, Fp16>(DIFUSCO_SPLIT_ARGS);         \
     return launch_split<KK, FBB, 2, Fp16>(DIFUSCO_SPLIT_ARGS);                        \
   }
   // few row tiles (node rows): 128-column blocks give twice the workgroups, i.e. two per CU instead of one

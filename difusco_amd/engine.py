@@ -80,7 +80,7 @@ class DenoiseEngine:
         if aggregation not in _lib.AGGREGATIONS:
             raise ValueError(f"aggregation must be one of {sorted(_lib.AGGREGATIONS)}")
         self.aggregation = aggregation
-        self.fused = fused          # fused edge-layer kernel (H == 256, precision bf16x3 / fp16x3)
+        self.fused = fused          # fused edge-layer kernel (H == 256, precision bf16x3 / fp16x3 / fp16x1)
         self.flags = int(flags)     # difusco_step_args.flags (_lib.FLAG_*): per-call A/B switches of the fused path
         if backend is None:
             # default binding = the PyTorch custom ops (what BASELINE.json's north_star names; same speed as ctypes, bench.py
@@ -133,7 +133,7 @@ class DenoiseEngine:
         """The table that lets a TSP step with a general edge input (Gaussian diffusion, non-binary categorical x_t) evaluate
         ``edge_embed(ScalarEmbeddingSine(x_t))`` (``gnn_encoder.py:230-249,304,395``) by interpolation for |x_t| < 8 - a function of the
         weights only, built once per engine on the fused path (H = 256); None otherwise or when ``use_gen_table`` is False."""
-        if not self.use_gen_table or not (self.fused and self.hidden == 256 and self.precision in ("bf16x3", "fp16x3")):
+        if not self.use_gen_table or not (self.fused and self.hidden == 256 and self.precision in _lib.FUSED_PRECISIONS):
             return None
         if self._gen_table is None:
             if self.backend == "torch":
@@ -178,7 +178,7 @@ class DenoiseEngine:
     def _uses_prepared(self, g: CsrGraph) -> bool:
         """Will ``difusco_denoise_step`` read a prepared buffer for a call on graph ``g``?  The C side's ``fused`` predicate
         (api.hip): H = 256, a split precision with a fused kernel, edges, and not (max aggregation with >= 2^20 nodes)."""
-        return (self.fused and self.hidden == 256 and self.precision in ("bf16x3", "fp16x3") and g.n_edges > 0
+        return (self.fused and self.hidden == 256 and self.precision in _lib.FUSED_PRECISIONS and g.n_edges > 0
                 and not (self.aggregation == "max" and g.n_nodes >= (1 << 20)))
 
     def prepare(self, g: CsrGraph, points: torch.Tensor, force: bool = False) -> Optional[torch.Tensor]:

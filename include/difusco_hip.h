@@ -45,11 +45,21 @@ enum {
   DIFUSCO_PREC_FP32 = 0,   /* E-row linears on v_mfma_f32_32x32x2_f32: exact fp32 (k-ordered fma chain) */
   DIFUSCO_PREC_BF16X3 = 1, /* 2 bf16 planes, 3 products: ~2^-17 relative per product                    */
   DIFUSCO_PREC_BF16X6 = 2, /* 3 bf16 planes, 6 products: all 24 significand bits, fp32-class accuracy    */
-  DIFUSCO_PREC_FP16X3 = 3  /* 2 fp16 planes, 3 products, operands pre-scaled by exact powers of two into the upper
+  DIFUSCO_PREC_FP16X3 = 3, /* 2 fp16 planes, 3 products, operands pre-scaled by exact powers of two into the upper
                               binades of fp16 (weights per matrix / per row on the host, activations per row or per
                               32-edge tile on the device): 22 significand bits for elements within 2^-17 of the
                               largest element of their scaling group, an absolute floor of 2^-39 of that largest
                               element below; any finite fp32 operand scale (no |x| < 65504 restriction)            */
+  DIFUSCO_PREC_FP16X1 = 4  /* half-precision edge GEMMs (the reference's --fp16, Trainer(precision=16), rounds the operands
+                              of these Linears to fp16 under autocast): every product of the edge-row GEMMs of the
+                              layers, C and per_layer_out[l][2] (gnn_encoder.py:104,344), takes ONE fp16 product.  Both
+                              operands are scaled by the powers of two of FP16X3 (weights: the hi fp16 plane of the
+                              existing planes, no layout change; activations: per row, per 32-edge tile, or for the fused kernel's
+                              second GEMM per layer from the bound of DIFUSCO_WL_FUSED_SCALES), rounded once
+                              to fp16 (RNE), multiplied exactly and accumulated in fp32; the outputs stay fp32.  Layer 0
+                              on the two-row table (the L0 fold, difusco_prepare) follows the same rule.  Everything else
+                              - edge embedding, node linears, time MLP, head, posteriors - runs as FP16X3; e / h stay
+                              fp32.  difusco_edge_embed does not take it (the embedding has no FP16X1 form). */
 };
 enum {
   DIFUSCO_RAND_NONE = 0,     /* no draw: categorical final step (target_t == 0) or DDIM */
