@@ -89,6 +89,7 @@ def lib():
     L.difusco_workspace_bytes.restype = ctypes.c_size_t
     L.difusco_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     L.difusco_denoise_step.argtypes = [ctypes.POINTER(StepArgs)]
+    L.difusco_denoise_step_shifted.argtypes = [ctypes.POINTER(StepArgs), vp]
     L.difusco_prepared_bytes.restype = ctypes.c_size_t
     L.difusco_prepared_bytes.argtypes = [i32, i32]
     L.difusco_prepare.argtypes = [ctypes.POINTER(StepArgs), vp, ctypes.c_size_t]

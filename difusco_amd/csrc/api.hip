@@ -54,8 +54,8 @@ struct Layout {
   int64_t layer_stride = 0;  // floats between the same tensor of consecutive layers
 };
 
-// hipMemsetAsync of zero bytes is an error while a stream is being captured into a hipGraph
-hipError_t zero_async(void* p, size_t bytes, hipStream_t st) { return bytes ? hipMemsetAsync(p, 0, bytes, st) : hipSuccess; }
+// the step's buffer resets: a zero-fill kernel (no memset node when the step is captured into a hipGraph; zero bytes is a no-op)
+hipError_t zero_async(void* p, size_t bytes, hipStream_t st) { return difusco::launch_zero_words(p, bytes, st); }
 
 bool hidden_ok(int h) { return h == 64 || h == 128 || h == 256; }
 
@@ -261,7 +261,9 @@ size_t difusco_workspace_bytes(int hidden, int n_layers, int n_nodes, int n_edge
   return carve(nullptr, hidden, n_layers, n_nodes, n_edges, n_segments, difusco::gn_blocks_for(rows)).bytes;
 }
 
-int difusco_denoise_step(const difusco_step_args* a) {
+int difusco_denoise_step(const difusco_step_args* a) { return difusco_denoise_step_shifted(a, nullptr); }
+
+int difusco_denoise_step_shifted(const difusco_step_args* a, const uint64_t* offset_shift) {
   using namespace difusco;
   if (!a) return fail(DIFUSCO_EINVAL, "null args");
   if (a->struct_size != sizeof(difusco_step_args) || a->abi_version != DIFUSCO_ABI_VERSION)
@@ -432,11 +434,11 @@ int difusco_denoise_step(const difusco_step_args* a) {
     PROF(PROF_LINEAR_NODE, linear_rows(ws.node4, G(DIFUSCO_W_NODE_EMBED_W), G(DIFUSCO_W_NODE_EMBED_B), nullptr, ws.h, N,
                                        H, H, H, st))
     if (l0_fold) {   // e = zeros (gnn_encoder.py:407) comes from an all-zero table; only the pad tail must read as zero
-      PROF(PROF_EMBED, hipMemsetAsync(ws.table, 0, sizeof(float) * 4 * H, st))
+      PROF(PROF_EMBED, zero_async(ws.table, sizeof(float) * 4 * H, st))
       PROF(PROF_EMBED, zero_async(ws.e + (E / 32) * 32 * H, sizeof(float) * (E_pad - (E / 32) * 32) * H, st))
     } else if (E > 0) {
-      PROF(PROF_EMBED, hipMemsetAsync(ws.e, 0, sizeof(float) * (fused ? E_pad : E) * H, st))
-      if (fused && f16) PROF(PROF_EMBED, hipMemsetAsync(ws.etmax, 0, sizeof(float) * n_tiles_pad, st))
+      PROF(PROF_EMBED, zero_async(ws.e, sizeof(float) * (fused ? E_pad : E) * H, st))
+      if (fused && f16) PROF(PROF_EMBED, zero_async(ws.etmax, sizeof(float) * n_tiles_pad, st))
     }
   }
 
@@ -548,14 +550,14 @@ int difusco_denoise_step(const difusco_step_args* a) {
                                       G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), a->perm, a->xt, a->post,
                                       a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
                                       gn_fold ? ws.gn_tile : nullptr, a->gn_phase, a->gn_sums,
-                                      a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, rand_instances))
+                                      a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, rand_instances, offset_shift))
     return finish();
   }
   PROF(PROF_HEAD, launch_head(H, C, tsp ? ws.e : ws.h, a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, out_rows,
                               gn_blocks_for(out_rows), ws.partial, ws.stats, G(DIFUSCO_W_OUT_GN_W), G(DIFUSCO_W_OUT_GN_B),
                               G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), tsp ? a->perm : nullptr, a->xt, a->post,
                               a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
-                              a->gn_phase, a->gn_sums, rand_instances))
+                              a->gn_phase, a->gn_sums, rand_instances, offset_shift))
 #undef PROF
   return finish();
 }

@@ -293,7 +293,7 @@ hipError_t launch_edge_embed_tiled(const float* x, const int* perm, const float*
     static std::atomic<unsigned long long> attr_devices{0};
     hipError_t er = ensure_max_dynamic_lds(attr_devices, reinterpret_cast<const void*>(&edge_embed_table_kernel), 160 * 1024);
     if (er != hipSuccess) return er;
-    er = hipMemsetAsync(tile_flag, 0, sizeof(int) * (size_t)grid * 4, stream);
+    er = launch_zero_words(tile_flag, sizeof(int) * (size_t)grid * 4, stream);
     if (er != hipSuccess) return er;
     static std::atomic<int> n_cu{0};
     int cus = n_cu.load(std::memory_order_relaxed);

@@ -361,7 +361,14 @@ struct PostParams {
   int n_inst;
   const long long* inst_rows;
   const unsigned long long* inst_seeds;
+  // difusco_denoise_step_shifted: device word added to `offset` by every Philox draw (nullptr = no shift), so that a captured
+  // graph replays later steps' draws; read only on the draw branch, one uniform load per wave
+  const unsigned long long* offset_shift;
 };
+
+__device__ __forceinline__ unsigned long long draw_offset(const PostParams& pp) {
+  return pp.offset_shift ? pp.offset + *pp.offset_shift : pp.offset;
+}
 
 // Philox key and element of caller row idx: the call's (seed, idx), or in mode 3 the (seed, local row) of the instance that
 // holds idx - what a solo call of that instance draws.  The lookup is a binary search over a few cached boundaries.
@@ -409,7 +416,7 @@ __device__ __forceinline__ float categorical_step(float l0, float l1, float xt, 
     } else {
       unsigned long long seed, elem;
       draw_key(pp, idx, seed, elem);
-      u = philox_uniform(seed, pp.offset, elem);
+      u = philox_uniform(seed, draw_offset(pp), elem);
     }
     return u < pc ? 1.0f : 0.0f;
   }
@@ -427,7 +434,7 @@ __device__ __forceinline__ float gaussian_step(float pred, float xt, const PostP
   } else {
     unsigned long long seed, elem;
     draw_key(pp, idx, seed, elem);
-    z = philox_normal(seed, pp.offset, elem);
+    z = philox_normal(seed, draw_offset(pp), elem);
   }
   return base + rounded(pp.p[3] * z);
 }
@@ -780,7 +787,7 @@ int gn_blocks_for(long long rows) {
 }
 
 static PostParams make_post(const float* post, int rand_mode, const float* rand, unsigned long long seed,
-                            unsigned long long offset, const RandInstances& ri) {
+                            unsigned long long offset, const RandInstances& ri, const uint64_t* offset_shift = nullptr) {
   PostParams pp;
   for (int i = 0; i < 8; ++i) pp.p[i] = post[i];
   pp.rand_mode = rand_mode;
@@ -790,6 +797,7 @@ static PostParams make_post(const float* post, int rand_mode, const float* rand,
   pp.n_inst = ri.n;
   pp.inst_rows = reinterpret_cast<const long long*>(ri.rows);
   pp.inst_seeds = reinterpret_cast<const unsigned long long*>(ri.seeds);
+  pp.offset_shift = reinterpret_cast<const unsigned long long*>(offset_shift);
   return pp;
 }
 
@@ -798,10 +806,10 @@ hipError_t launch_head(int H, int C, const float* feat, const int* seg_ptr, int 
                        const float* conv_w, const float* conv_b, const int* perm, const float* xt, const float* post,
                        int rand_mode, const float* rand, unsigned long long seed, unsigned long long offset,
                        float* xt_out, float* pred_out, float* prob_out, hipStream_t stream, int gn_phase,
-                       double* gn_sums, RandInstances ri) {
+                       double* gn_sums, RandInstances ri, const uint64_t* offset_shift) {
   if (total_rows == 0) return hipSuccess;
   if (gn_phase != 0 && (n_segments != 1 || !gn_sums)) return hipErrorInvalidValue;
-  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri);
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri, offset_shift);
   dim3 grid((unsigned)nblk, (unsigned)n_segments);
   if (gn_phase != 2) {
     DIFUSCO_VEC_DISPATCH(H, hipLaunchKernelGGL((gn_partial_kernel<VEC>), grid, dim3(256), 0, stream, feat, seg_ptr,
@@ -861,6 +869,19 @@ hipError_t launch_count_nonfinite(const float* x, long long n, unsigned* count, 
   return hipGetLastError();
 }
 
+__global__ void zero_words_kernel(unsigned* __restrict__ p, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+hipError_t launch_zero_words(void* p, size_t bytes, hipStream_t stream) {
+  const long long n = (long long)(bytes / 4);
+  if (n <= 0 || p == nullptr) return hipSuccess;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, static_cast<unsigned*>(p), n);
+  return hipGetLastError();
+}
+
 hipError_t launch_tile_absmax_tiled(const float* e, long long n_tiles, float* tile_max, hipStream_t stream) {
   if (n_tiles <= 0) return hipSuccess;
   hipLaunchKernelGGL(tile_absmax_tiled_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, e, n_tiles, tile_max);
@@ -913,12 +934,12 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
                              const int* perm, const float* xt, const float* post, int rand_mode, const float* rand,
                              unsigned long long seed, unsigned long long offset, float* xt_out, float* pred_out,
                              float* prob_out, hipStream_t stream, const float* gn_tile, int gn_phase, double* gn_sums,
-                             const int* seg_ptr, int n_segments, RandInstances ri) {
+                             const int* seg_ptr, int n_segments, RandInstances ri, const uint64_t* offset_shift) {
   if (rows == 0) return hipSuccess;
   if (gn_phase != 0 && !gn_sums) return hipErrorInvalidValue;
   if (n_segments > 1) {      // per-segment statistics (dense mode: one segment per sample): a masked pass over e per segment
     if (!seg_ptr || gn_phase != 0) return hipErrorInvalidValue;
-    const PostParams pq = make_post(post, rand_mode, rand, seed, offset, ri);
+    const PostParams pq = make_post(post, rand_mode, rand, seed, offset, ri, offset_shift);
     const long long n_tiles_s = (rows + 31) / 32;
     int bps = (int)((n_tiles_s / n_segments + 3) / 4);      // ~4 tiles per block
     bps = bps < 1 ? 1 : (bps > 256 ? 256 : bps);
@@ -939,7 +960,7 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
     return hipGetLastError();
   }
   if (nblk < 8 || nblk % 8 != 0) return hipErrorInvalidValue;   // (with gn_tile, partial must hold 256 * 64 doubles)
-  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri);
+  const PostParams pp = make_post(post, rand_mode, rand, seed, offset, ri, offset_shift);
   const long long n_tiles = (rows + 31) / 32;
   double* sums_out = gn_phase == 1 ? gn_sums : (double*)nullptr;
   if (gn_phase == 2) {

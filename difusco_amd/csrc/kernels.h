@@ -76,6 +76,9 @@ hipError_t launch_gen_table_grid(float* x, hipStream_t stream);
 hipError_t launch_row_pow2_scale(const float* x, long long m, int k, float* scale, hipStream_t stream);
 // *count += number of inf / nan values in x[0..n)  (DIFUSCO_FLAG_CHECK_FINITE)
 hipError_t launch_count_nonfinite(const float* x, long long n, unsigned* count, hipStream_t stream);
+// zero `bytes` (a multiple of 4) at p with a kernel: the step's buffer resets stay kernel launches, so a step captured into a HIP graph
+// is a chain of kernel nodes only
+hipError_t launch_zero_words(void* p, size_t bytes, hipStream_t stream);
 // tile_max[t] = max |e| over the 32-edge tile t of a TILED [rows_padded, 256] buffer
 hipError_t launch_tile_absmax_tiled(const float* e, long long n_tiles, float* tile_max, hipStream_t stream);
 
@@ -145,7 +148,7 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
                              unsigned long long seed, unsigned long long offset, float* xt_out, float* pred_out,
                              float* prob_out, hipStream_t stream, const float* gn_tile = nullptr, int gn_phase = 0,
                              double* gn_sums = nullptr, const int* seg_ptr = nullptr, int n_segments = 1,
-                             RandInstances ri = RandInstances{});
+                             RandInstances ri = RandInstances{}, const uint64_t* offset_shift = nullptr);
 hipError_t launch_edge_gate_aggregate(int H, int n_nodes, const int* rowptr, const int* col, const float* node4,
                                       float* ce_act, float* h, const float* nh_w, const float* nh_b, const float* ne_w,
                                       const float* ne_b, const float* ol_w, const float* ol_b, const float* tbias,
@@ -156,7 +159,8 @@ hipError_t launch_head(int H, int C, const float* feat, const int* seg_ptr, int 
                        const float* conv_w, const float* conv_b, const int* perm, const float* xt, const float* post,
                        int rand_mode, const float* rand, unsigned long long seed, unsigned long long offset,
                        float* xt_out, float* pred_out, float* prob_out, hipStream_t stream, int gn_phase = 0,
-                       double* gn_sums = nullptr, RandInstances ri = RandInstances{});
+                       double* gn_sums = nullptr, RandInstances ri = RandInstances{},
+                       const uint64_t* offset_shift = nullptr);
 hipError_t launch_categorical_posterior(const float* logits, const float* xt, const float* post, int rand_mode,
                                         const float* rand, unsigned long long seed, unsigned long long offset,
                                         float* xt_out, float* prob_out, long long n, hipStream_t stream);

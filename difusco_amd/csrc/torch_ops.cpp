@@ -9,7 +9,8 @@
 //   prepare_state(weights, points, n_nodes, n_edges, n_segments, workspace, cfg) -> uint8 buffer     difusco_prepare
 //   time_bias_rows(weights, times, cfg) -> float32 [n_t, n_layers, hidden]                            difusco_time_bias_rows
 //   denoise_step_categorical(...) / denoise_step_gaussian(...) -> (xt_next, pred, prob)
-//       (trailing optional instance_rows / instance_seeds: per-instance Philox streams, DIFUSCO_RAND_PHILOX_INSTANCES)
+//       (trailing optional instance_rows / instance_seeds: per-instance Philox streams, DIFUSCO_RAND_PHILOX_INSTANCES;
+//        offset_shift: one int64/uint64 on the device added to every Philox offset, difusco_denoise_step_shifted)
 //       replace {categorical,gaussian}_denoise_step of difusco/pl_tsp_model.py:122-151 / pl_mis_model.py:118-140
 //
 // Built by difusco_amd/build.py into difusco_amd/lib/libdifusco_torch.so (host compiler, links libdifusco_hip.so).
@@ -79,7 +80,8 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> step_impl(
     const c10::optional<at::Tensor>& rand, int64_t seed, int64_t offset, at::Tensor workspace, c10::ArrayRef<int64_t> cfg,
     bool want_pred, bool want_prob, const c10::optional<at::Tensor>& gn_sums, const c10::optional<at::Tensor>& prepared,
     const c10::optional<at::Tensor>& tbias, const c10::optional<at::Tensor>& gen_table,
-    const c10::optional<at::Tensor>& instance_rows, const c10::optional<at::Tensor>& instance_seeds) {
+    const c10::optional<at::Tensor>& instance_rows, const c10::optional<at::Tensor>& instance_seeds,
+    const c10::optional<at::Tensor>& offset_shift) {
   TORCH_CHECK(cfg.size() == 9 || cfg.size() == 10,
               "cfg = {hidden, n_layers, out_channels, task, precision, no_fusion, xt_is_binary, gn_phase, flags[, aggregation]}");
   TORCH_CHECK(post.size() <= 8, "post holds at most 8 constants");
@@ -166,7 +168,17 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> step_impl(
     TORCH_CHECK(prepared->is_cuda() && prepared->is_contiguous() &&
                     (size_t)prepared->nbytes() >= difusco_prepared_bytes((int)cfg[0], (int)n_nodes),
                 "prepared: contiguous GPU buffer of difusco_prepared_bytes() required");
-  check(difusco_denoise_step(&a), "difusco_denoise_step");
+  // device-side Philox offset shift (difusco_denoise_step_shifted): one 64-bit word on the step's device, read by the kernels
+  const uint64_t* shift = nullptr;
+  if (ptr_or_null(offset_shift)) {
+    TORCH_CHECK(offset_shift->scalar_type() == at::kLong || offset_shift->scalar_type() == at::kUInt64,
+                "offset_shift: int64 or uint64 required");
+    TORCH_CHECK(offset_shift->numel() == 1 && offset_shift->is_contiguous(), "offset_shift must hold exactly one element");
+    TORCH_CHECK(offset_shift->is_cuda() && offset_shift->device() == weights.device(),
+                "offset_shift must live on the step's device");
+    shift = static_cast<const uint64_t*>(offset_shift->data_ptr());
+  }
+  check(difusco_denoise_step_shifted(&a, shift), "difusco_denoise_step");
   return {xt_out, pred, prob};
 }
 
@@ -239,10 +251,10 @@ at::Tensor gen_table_build(const at::Tensor& weights, c10::ArrayRef<int64_t> cfg
       c10::ArrayRef<int64_t> cfg, bool want_pred, bool want_prob, const c10::optional<at::Tensor>&gn_sums,             \
       const c10::optional<at::Tensor>&prepared, const c10::optional<at::Tensor>&tbias,                                  \
       const c10::optional<at::Tensor>&gen_table, const c10::optional<at::Tensor>&instance_rows,                          \
-      const c10::optional<at::Tensor>&instance_seeds
+      const c10::optional<at::Tensor>&instance_seeds, const c10::optional<at::Tensor>&offset_shift
 #define STEP_FORWARD                                                                                                     \
   weights, rowptr, col, perm, row, seg_ptr, points, xt, t, post, rand, seed, offset, workspace, cfg, want_pred, want_prob, \
-      gn_sums, prepared, tbias, gen_table, instance_rows, instance_seeds
+      gn_sums, prepared, tbias, gen_table, instance_rows, instance_seeds, offset_shift
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> denoise_step_categorical(STEP_SIGNATURE) {
   return step_impl(DIFUSCO_CATEGORICAL, STEP_FORWARD);
@@ -254,7 +266,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> denoise_step_gaussian(STEP_SIGNAT
 const char* kStepSchema =
     "(Tensor weights, Tensor rowptr, Tensor col, Tensor? perm, Tensor? row, Tensor? seg_ptr, Tensor? points, Tensor xt, "
     "float t, float[] post, Tensor? rand, int seed, int offset, Tensor(a!) workspace, int[] cfg, bool want_pred, "
-    "bool want_prob, Tensor(b!)? gn_sums, Tensor? prepared=None, Tensor? tbias=None, Tensor? gen_table=None, Tensor? instance_rows=None, Tensor? instance_seeds=None) -> (Tensor, Tensor, Tensor)";
+    "bool want_prob, Tensor(b!)? gn_sums, Tensor? prepared=None, Tensor? tbias=None, Tensor? gen_table=None, Tensor? instance_rows=None, Tensor? instance_seeds=None, Tensor? offset_shift=None) -> (Tensor, Tensor, Tensor)";
 
 }  // namespace
 

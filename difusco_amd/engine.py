@@ -216,7 +216,7 @@ class DenoiseEngine:
              points: Optional[torch.Tensor] = None, xt_is_binary: bool = False,
              rand: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
              want_pred: bool = False, want_prob: bool = False, gn_reduce=None, prepared: Optional[torch.Tensor] = None,
-             instances=None):
+             instances=None, offset_shift: Optional[torch.Tensor] = None):
         """xt: fp32, TSP [E] in caller edge order / MIS [N].  Returns (xt_next, pred|None, prob|None);
         asynchronous on the current stream.
 
@@ -234,7 +234,12 @@ class DenoiseEngine:
 
         ``prepared``: the buffer ``prepare(g, points)`` returned for this graph and these coordinates (TSP): the step skips
         what it holds; ``points`` may then be omitted.  The time-bias rows of ``t`` are taken from the ``prepare_times``
-        cache when present.  Both are bit-identical to the stateless step."""
+        cache when present.  Both are bit-identical to the stateless step.
+
+        ``offset_shift``: optional 1-element int64 / uint64 device tensor; every Philox draw of the step then uses
+        ``offset + offset_shift[0]``, read by the kernels when they run (``difusco_denoise_step_shifted``).  A step captured into
+        a graph thus draws what an eager step at offset ``offset + shift`` draws, once the caller writes ``shift`` before the
+        replay."""
         dev = self.device
         xt = xt.to(dev, dtype=torch.float32).contiguous().reshape(-1)
         rows = g.n_edges if task == _lib.TASK_TSP else g.n_nodes
@@ -278,9 +283,13 @@ class DenoiseEngine:
         gen_table = self.gen_table() if (task == _lib.TASK_TSP and not xt_is_binary) else None
         # the Philox key and offset are 63-bit on both backends (the torch op schema carries signed 64-bit ints)
         seed, offset = int(seed) & (2 ** 63 - 1), int(offset) & (2 ** 63 - 1)
+        if offset_shift is not None and (offset_shift.dtype not in (torch.int64, torch.uint64) or offset_shift.numel() != 1
+                                         or offset_shift.device != dev or not offset_shift.is_contiguous()):
+            raise ValueError("offset_shift must be a 1-element int64 / uint64 tensor on the engine's device")
         if self.backend == "torch":
             return self._step_torch_op(g, task, diffusion, xt, t, post, points, xt_is_binary, rand, seed, offset,
-                                       want_pred, want_prob, gn_reduce, ws, prepared, tbias, gen_table, instances)
+                                       want_pred, want_prob, gn_reduce, ws, prepared, tbias, gen_table, instances,
+                                       offset_shift)
 
         a = _lib.StepArgs()
         a.struct_size = ctypes.sizeof(_lib.StepArgs)
@@ -314,24 +323,25 @@ class DenoiseEngine:
         a.prepared, a.tbias = _ptr(prepared), _ptr(tbias)
         a.gen_table = _ptr(gen_table)
         a.aggregation = _lib.AGGREGATIONS[self.aggregation]
+        shift = _ptr(offset_shift)
         with torch.cuda.device(dev):
             if gn_reduce is None:
-                _lib.check(_lib.lib().difusco_denoise_step(ctypes.byref(a)))
+                _lib.check(_lib.lib().difusco_denoise_step_shifted(ctypes.byref(a), shift))
             else:
                 if g.n_segments != 1:
                     raise ValueError("global GroupNorm statistics need one statistic segment per call")
                 sums = torch.zeros(65, dtype=torch.float64, device=dev)
                 a.gn_sums = _ptr(sums)
                 a.gn_phase = 1
-                _lib.check(_lib.lib().difusco_denoise_step(ctypes.byref(a)))
+                _lib.check(_lib.lib().difusco_denoise_step_shifted(ctypes.byref(a), shift))
                 gn_reduce(sums)
                 a.gn_phase = 2
-                _lib.check(_lib.lib().difusco_denoise_step(ctypes.byref(a)))
+                _lib.check(_lib.lib().difusco_denoise_step_shifted(ctypes.byref(a), shift))
         self.calls += 1
         return xt_out, pred, prob
 
     def _step_torch_op(self, g, task, diffusion, xt, t, post, points, xt_is_binary, rand, seed, offset, want_pred,
-                       want_prob, gn_reduce, ws, prepared=None, tbias=None, gen_table=None, instances=None):
+                       want_prob, gn_reduce, ws, prepared=None, tbias=None, gen_table=None, instances=None, offset_shift=None):
         """The same step through ``torch.ops.difusco.denoise_step_{categorical,gaussian}`` (csrc/torch_ops.cpp)."""
         op = self._ops.denoise_step_categorical if diffusion == _lib.CATEGORICAL else self._ops.denoise_step_gaussian
         cfg = self._cfg(task, xt_is_binary)
@@ -342,7 +352,7 @@ class DenoiseEngine:
             cfg[7] = phase
             return _op_call(op, self.blob, g.rowptr, g.col, g.perm, g.row, seg, points, xt, float(t), post, rand, seed, offset, ws,
                             cfg, want_pred, want_prob, sums, prepared, tbias, gen_table,
-                            *(instances if instances is not None else ()))
+                            *(instances if instances is not None else (None, None)), offset_shift)
         if gn_reduce is None:
             out = call(0, None)
         else:

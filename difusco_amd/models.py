@@ -12,8 +12,10 @@ tensors on ``device``, flattened in sparse mode (``pl_meta_model.py:144-145``).
 
 Extensions beyond the reference signature are keyword-only: ``uniform=`` / ``noise=`` inject the
 random numbers (teacher-forced parity tests), ``return_aux=True`` also returns the network
-prediction and the pre-sampling probability.
+prediction and the pre-sampling probability, ``sample(..., graphed=True)`` replays the whole
+sampling loop as one captured HIP graph (``_GraphedSampler``).
 """
+from collections import OrderedDict
 from types import SimpleNamespace
 from typing import Optional
 
@@ -36,6 +38,50 @@ def _as_int(t) -> int:
     if t is None:
         return None
     return int(np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t).reshape(-1)[0])
+
+
+class _GraphedSampler:
+    """One captured sampling loop (``sample(..., graphed=True)``) for one problem shape: the static device buffers the graph
+    reads (CSR arrays with ``perm`` / ``node_order`` always materialised, points, x_T, the Philox offset shift), the graph, its
+    static output, and strong references to every other buffer whose address the captured launches hold (weights,
+    workspace, time-bias rows, generated-input table, prepared state) - evicting the model's own caches cannot free them."""
+
+    def __init__(self, model, task: int, g: CsrGraph, xt_numel: int):
+        dev = model.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        tsp = task == _lib.TASK_TSP
+        self.graph = CsrGraph(
+            n_nodes=g.n_nodes, n_edges=g.n_edges, rowptr=torch.empty(g.n_nodes + 1, **i32), col=torch.empty(g.n_edges, **i32),
+            perm=torch.empty(g.n_edges, **i32), row=torch.empty(g.n_edges, **i32),
+            seg_ptr=torch.empty(g.n_segments + 1, **i32) if g.n_segments > 1 else None, n_segments=g.n_segments,
+            node_order=torch.empty(g.n_nodes, dtype=torch.int64, device=dev) if tsp else None)
+        self.ident_perm = torch.arange(g.n_edges, **i32)
+        self.ident_order = torch.arange(g.n_nodes, dtype=torch.int64, device=dev) if tsp else None
+        self.points = torch.empty((g.n_nodes, 2), dtype=torch.float32, device=dev) if tsp else None
+        self.xt = torch.empty(xt_numel, dtype=torch.float32, device=dev)
+        self.shift = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.src = None             # the CsrGraph whose arrays the static graph holds now (kept alive: its identity is the test)
+        self.cuda_graph = None
+        self.out = None
+        self.base_calls = 0         # engine call counter the captured offsets start from
+        self.keep = ()
+
+    def load(self, g: CsrGraph, points, xt0: torch.Tensor):
+        """Stream-ordered copies of one instance into the static inputs (the CSR arrays only when the graph changed)."""
+        G = self.graph
+        if self.src is not g:
+            G.rowptr.copy_(g.rowptr)
+            G.col.copy_(g.col)
+            G.row.copy_(g.row)
+            G.perm.copy_(g.perm if g.perm is not None else self.ident_perm)
+            if G.seg_ptr is not None:
+                G.seg_ptr.copy_(g.seg_ptr)
+            if G.node_order is not None:
+                G.node_order.copy_(g.node_order if g.node_order is not None else self.ident_order)
+            self.src = g
+        if self.points is not None:
+            self.points.copy_(points.reshape(-1, 2))
+        self.xt.copy_(xt0.reshape(-1))
 
 
 class COMetaModel:
@@ -98,6 +144,11 @@ class COMetaModel:
         # optional: shard-summing callable for the head GroupNorm statistics (difusco_amd.dist.gn_allreduce); None =
         # statistics of each call's own rows, the reference's behaviour for that call
         self.gn_reduce = gn_reduce
+        # graphed sampling (sample(..., graphed=True)): an LRU of captured loops, one per problem shape
+        self._graphs = OrderedDict()
+        self._capture_stream = None
+        self._graph_captures = 0
+        self._graph_replays = 0
 
     # ---- graph handling --------------------------------------------------------------------------
     def prepare_graph(self, edge_index: torch.Tensor, num_nodes: int, points=None) -> CsrGraph:
@@ -237,13 +288,21 @@ class COMetaModel:
             return self._categorical(g, task, points, xt, t1, t2, None, False, instances=instances)
         return step
 
+    def _post_constants(self, t: int, target_t: int) -> np.ndarray:
+        """``difusco_step_args.post`` of the step t -> target_t."""
+        post = np.zeros(8, dtype=np.float32)
+        if self.diffusion_type == "gaussian":
+            post[:5] = self.diffusion.posterior_constants(t, target_t, self.args.inference_trick)
+        else:
+            post[:4] = self.diffusion.posterior_constants(t, target_t)
+            post[4] = 1.0 if target_t > 0 else 0.0                        # pl_meta_model.py:139-142
+        return post
+
     def _categorical(self, g, task, points, xt, t, target_t, uniform, return_aux, instances=None):
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1                                              # pl_meta_model.py:108-109
-        post = np.zeros(8, dtype=np.float32)
-        post[:4] = self.diffusion.posterior_constants(t, target_t)
-        post[4] = 1.0 if target_t > 0 else 0.0                            # :139-142
+        post = self._post_constants(t, target_t)
         out, pred, prob = self.model.step(
             g, task, _lib.CATEGORICAL, xt, float(t), post, points=points, xt_is_binary=self._xt_is_binary(xt),
             rand=uniform if target_t > 0 else None, seed=self.seed, offset=self._next_offset(),
@@ -258,14 +317,133 @@ class COMetaModel:
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1
-        post = np.zeros(8, dtype=np.float32)
-        post[:5] = self.diffusion.posterior_constants(t, target_t, self.args.inference_trick)
+        post = self._post_constants(t, target_t)
         out, pred, _ = self.model.step(
             g, task, _lib.GAUSSIAN, xt, float(t), post, points=points, xt_is_binary=False,
             rand=noise if post[4] != 0 else None, seed=self.seed, offset=self._next_offset(), want_pred=return_aux,
             gn_reduce=self.gn_reduce, prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None,
             instances=instances)
         return (out, pred) if return_aux else out
+
+    # ---- graphed sampling (sample(..., graphed=True)) ------------------------------------------------
+    GRAPH_POOL = 4      # captured loops kept per model (least recently used evicted first)
+
+    @property
+    def graph_captures(self) -> int:
+        """Sampling loops captured so far (each first graphed call of a new problem shape captures one)."""
+        return self._graph_captures
+
+    @property
+    def graph_replays(self) -> int:
+        """Graphed calls served by replaying an already captured loop."""
+        return self._graph_replays
+
+    def clear_graphs(self) -> None:
+        """Drop every captured loop with its static buffers, graph memory pool and capture-stream workspace."""
+        if self._graphs:
+            torch.cuda.synchronize(self.device)      # (a replay or an output copy may still read the pool)
+            self._graphs.clear()
+        if self._capture_stream is not None:
+            self.model._ws.pop(self._capture_stream.cuda_stream, None)
+
+    def _refuse_graphed(self):
+        """The configurations a captured loop cannot serve (checked before any graph or GPU work of the call)."""
+        if self.gn_reduce is not None:
+            raise ValueError("graphed=True cannot be combined with gn_reduce: the collective between the two phases of a "
+                             "step cannot sit inside a captured graph")
+        if self.model.flags & _lib.FLAG_CHECK_FINITE:
+            raise ValueError("graphed=True cannot be combined with FLAG_CHECK_FINITE: the finiteness check synchronises")
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("graphed=True inside a stream capture: sample() cannot capture its loop into another graph")
+
+    def _graph_key(self, task: int, g: CsrGraph, dense_shape):
+        """What fixes the launches of a captured loop.  seg_ptr is a function of the dense shape (sparse calls of ``sample``
+        have one statistic segment); its values are copied into the static buffer with the other CSR arrays anyway."""
+        e = self.model
+        return (task, self.diffusion_type, self.diffusion_schedule, self.diffusion.T, self.args.inference_diffusion_steps,
+                self.args.inference_schedule, self.args.inference_trick if self.diffusion_type == "gaussian" else None,
+                dense_shape, g.n_nodes, g.n_edges, g.n_segments, e.precision, e.fused, e.backend, e.flags, e.aggregation,
+                e.use_gen_table, self.prepare, self.seed)
+
+    def _graphed_loop(self, s: _GraphedSampler, task: int):
+        """The whole loop of ``sample()`` on the static buffers of ``s``, on the current stream: prepared state, the
+        categorical cast, the steps (Philox offsets shifted by ``s.shift``), the final affine map.  Returns (output,
+        prepared buffer)."""
+        steps = self.args.inference_diffusion_steps
+        sched = InferenceSchedule(inference_schedule=self.args.inference_schedule, T=self.diffusion.T, inference_T=steps)
+        categorical = self.diffusion_type == "categorical"
+        tsp = task == _lib.TASK_TSP
+        prepared = self.model.prepare(s.graph, s.points) if (tsp and self.prepare) else None
+        xt = (s.xt > 0).float() if categorical else s.xt
+        binary = categorical         # x_T > 0 and every Bernoulli output are exactly {0,1}: no device check, no sync
+        for i in range(steps):
+            t1, t2 = sched(i)
+            t1, t2 = _as_int(np.array([t1]).astype(int)), _as_int(np.array([t2]).astype(int))
+            post = self._post_constants(t1, t2)
+            xt, _, _ = self.model.step(
+                s.graph, task, _lib.CATEGORICAL if categorical else _lib.GAUSSIAN, xt, float(t1), post,
+                points=s.points, xt_is_binary=binary, seed=self.seed, offset=self._next_offset(), prepared=prepared,
+                offset_shift=s.shift)
+            binary = categorical and post[4] != 0
+        return (xt + 1e-6 if categorical else xt * 0.5 + 0.5), prepared
+
+    def _sample_graphed(self, task: int, g: CsrGraph, points, shape, xt0, generator, dense_shape):
+        """``sample(..., graphed=True)``: bitwise what the eager loop returns at the same engine call counter, which it
+        advances by the number of steps as the eager loop does.  x_T is drawn as the eager loop draws it.  The first call of a
+        problem shape runs the loop eagerly on the capture stream (its result is the call's) and then captures it; later
+        calls copy the instance into the static buffers, write the offset shift and replay."""
+        dev = self.device
+        if xt0 is None:
+            xt0 = torch.randn(shape, generator=generator, device=dev if generator is None else generator.device)
+        xt0 = xt0.to(dev)
+        if xt0.numel() != int(np.prod(shape)):
+            raise ValueError(f"xt0 has {xt0.numel()} elements, the call needs {int(np.prod(shape))}")
+        if self.diffusion_type == "categorical" and xt0.dtype != torch.float32:
+            xt0 = (xt0 > 0).float()      # (the eager cast compares in xt0's own dtype; a float32 copy could round a value to 0)
+        steps = self.args.inference_diffusion_steps
+        key = self._graph_key(task, g, dense_shape)
+        if self._capture_stream is None:
+            self._capture_stream = torch.cuda.Stream(device=dev)
+        cap, cur = self._capture_stream, torch.cuda.current_stream(dev)
+        s = self._graphs.get(key)
+        cap.wait_stream(cur)
+        with torch.cuda.stream(cap):
+            if s is not None:
+                self._graphs.move_to_end(key)
+                s.load(g, points, xt0)
+                s.shift.fill_(self.model.calls - s.base_calls)
+                s.cuda_graph.replay()
+                self.model.calls += steps
+                self._graph_replays += 1
+                out = s.out
+            else:
+                while len(self._graphs) >= self.GRAPH_POOL:
+                    torch.cuda.synchronize(dev)
+                    self._graphs.popitem(last=False)
+                s = _GraphedSampler(self, task, g, int(np.prod(shape)))
+                s.load(g, points, xt0)
+                # warm-up = this call's result: creates the capture stream's workspace, the time-bias rows and the
+                # generated-input table on this stream (or waits for them once), so no foreign event lands in the capture
+                sched = InferenceSchedule(inference_schedule=self.args.inference_schedule, T=self.diffusion.T, inference_T=steps)
+                times = [sched(i)[0] for i in range(steps)]
+                self.prepare_schedule(times)
+                out, _ = self._graphed_loop(s, task)
+                out.record_stream(cur)
+                s.base_calls = self.model.calls
+                s.cuda_graph = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(s.cuda_graph, stream=cap):
+                        s.out, prepared = self._graphed_loop(s, task)
+                finally:
+                    self.model.calls = s.base_calls      # capturing launched nothing: the counter stays where eager leaves it
+                e = self.model
+                s.keep = (e.blob, e._ws[cap.cuda_stream], prepared, e._gen_table[0] if e._gen_table is not None else None,
+                          [e._tbias[float(_as_int(t))][0] for t in times if float(_as_int(t)) in e._tbias])
+                self._graphs[key] = s
+                self._graph_captures += 1
+        cur.wait_stream(cap)
+        res = out.clone()
+        return res.reshape(dense_shape) if dense_shape is not None else res
 
 
 class TSPModel(COMetaModel):
@@ -305,10 +483,21 @@ class TSPModel(COMetaModel):
             return out.reshape(dense_shape), pred.reshape(dense_shape)
         return res.reshape(dense_shape)
 
-    def sample(self, points, edge_index=None, xt0=None, generator=None):
+    def sample(self, points, edge_index=None, xt0=None, generator=None, *, graphed=False):
         """The sampling loop of ``test_step`` (``pl_tsp_model.py:185-222``) for ONE noise sample per
         graph of the call: returns the heatmap tensor (``+1e-6`` categorical, ``*0.5+0.5`` gaussian),
-        still on the device.  ``points``/``edge_index`` already hold the (possibly duplicated) batch."""
+        still on the device.  ``points``/``edge_index`` already hold the (possibly duplicated) batch.
+        ``graphed=True``: the same bits from one replay of a captured HIP graph of the whole loop (captured on the first
+        call of a problem shape; see ``_sample_graphed``)."""
+        if graphed:
+            self._refuse_graphed()
+            if edge_index is not None:
+                g = self.prepare_graph(edge_index, points.shape[0], points=points)
+                return self._sample_graphed(_lib.TASK_TSP, g, points, (edge_index.shape[1],), xt0, generator, None)
+            if points.dim() != 3:
+                raise ValueError("dense mode expects points [B,V,2] and xt [B,V,V]")
+            B, V = points.shape[0], points.shape[1]
+            return self._sample_graphed(_lib.TASK_TSP, self._dense_graph(B, V), points, (B, V, V), xt0, generator, (B, V, V))
         steps = self.args.inference_diffusion_steps
         sched = InferenceSchedule(inference_schedule=self.args.inference_schedule, T=self.diffusion.T,
                                   inference_T=steps)
@@ -381,8 +570,13 @@ class MISModel(COMetaModel):
         g = self.prepare_graph(edge_index, xt.reshape(-1).shape[0])
         return self._gaussian(g, _lib.TASK_MIS, None, xt.reshape(-1).float(), t, target_t, noise, return_aux)
 
-    def sample(self, n_nodes, edge_index, xt0=None, generator=None):
-        """``pl_mis_model.py:156-192`` for one noise sample per graph of the call."""
+    def sample(self, n_nodes, edge_index, xt0=None, generator=None, *, graphed=False):
+        """``pl_mis_model.py:156-192`` for one noise sample per graph of the call.  ``graphed=True``: the same bits from one
+        replay of a captured HIP graph of the whole loop (``TSPModel.sample``)."""
+        if graphed:
+            self._refuse_graphed()
+            g = self.prepare_graph(edge_index, int(n_nodes))
+            return self._sample_graphed(_lib.TASK_MIS, g, None, (int(n_nodes),), xt0, generator, None)
         steps = self.args.inference_diffusion_steps
         sched = InferenceSchedule(inference_schedule=self.args.inference_schedule, T=self.diffusion.T,
                                   inference_T=steps)

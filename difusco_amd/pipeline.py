@@ -35,11 +35,12 @@ def _ticker(timings, dev):
 
 def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: int = 1, two_opt_iterations: int = 1000,
               generator: Optional[torch.Generator] = None, timings: Optional[Dict[str, float]] = None,
-              sequential_sampling: int = 1):
+              sequential_sampling: int = 1, *, graphed: bool = False):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
-    merge_iterations / 2-opt moves of the LAST round - the quantities the reference logs (``pl_tsp_model.py:244-251``)."""
+    merge_iterations / 2-opt moves of the LAST round - the quantities the reference logs (``pl_tsp_model.py:244-251``).
+    ``graphed=True``: every sampling loop runs as one replay of a captured HIP graph (``TSPModel.sample``), same results."""
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -64,7 +65,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     merge_iterations, ns = 0.0, 0
     for _ in range(sequential_sampling):                                                    # :185
         t0 = time.perf_counter()
-        heat = model.sample(pts_rep, ei_rep, generator=generator)                           # :186-222, on the device
+        heat = model.sample(pts_rep, ei_rep, generator=generator, graphed=graphed)          # :186-222, on the device
         tick("sampling", t0)
         t0 = time.perf_counter()
         tours, merge_iterations = merge_tours(heat, pts32, edge_index, sparse_graph=sparse,  # :226-230
@@ -84,13 +85,14 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
 
 def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, generator: Optional[torch.Generator] = None,
-              timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1):
+              timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1, *, graphed: bool = False):
     """``MISModel.test_step`` (``difusco/pl_mis_model.py:142-206``): ``sequential_sampling`` rounds of
     ``parallel_sampling`` noise samples of ONE graph through the denoising loop (disjoint union), greedy decode of every
     sample, best = largest set.  ``edge_index``: int64 [2,E] in the dataset's layout (both directions + self loops).
     Returns (best 0/1 array, best size, sizes).  Upstream re-duplicates ``edge_index`` inside the sequential loop
     (``pl_mis_model.py:168-169``), which breaks ``parallel > 1 and sequential > 1`` there; here the duplication happens
-    once, which is what that combination means."""
+    once, which is what that combination means.  ``graphed=True``: every sampling loop is one graph replay
+    (``MISModel.sample``), same results."""
     from .decode import mis_decode_np
     dev = model.device
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index))
@@ -101,7 +103,7 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     sols = []
     for _ in range(sequential_sampling):                                                          # :156
         t0 = time.perf_counter()
-        scores = model.sample(n_nodes * parallel_sampling, ei_rep, generator=generator)           # :157-192
+        scores = model.sample(n_nodes * parallel_sampling, ei_rep, generator=generator, graphed=graphed)   # :157-192
         tick("sampling", t0)
         t0 = time.perf_counter()
         sols.append(mis_decode_np(scores, graph=graph, device=dev).reshape(parallel_sampling, n_nodes))   # :195-198

@@ -291,6 +291,13 @@ int difusco_gen_table_build(int hidden, int n_layers, int out_channels, const fl
  * args->stream.  Replaces {categorical,gaussian}_denoise_step of pl_tsp_model.py / pl_mis_model.py. */
 int difusco_denoise_step(const difusco_step_args* args);
 
+/* difusco_denoise_step with a device-side shift of the Philox offset: every Philox draw of the step (categorical Bernoulli,
+ * Gaussian DDPM normal; rand_mode DIFUSCO_RAND_PHILOX and DIFUSCO_RAND_PHILOX_INSTANCES) uses args->offset + *offset_shift.
+ * offset_shift: device pointer to one uint64_t, read by the kernels when they run (never on the host), so a step captured
+ * into a HIP graph draws fresh numbers on each replay once the caller rewrites that word; NULL = difusco_denoise_step.
+ * Additive at ABI 13: difusco_denoise_step(a) is difusco_denoise_step_shifted(a, NULL). */
+int difusco_denoise_step_shifted(const difusco_step_args* args, const uint64_t* offset_shift);
+
 /* ---- single kernels, exported for parity tests and profiling ------------------------------------ */
 /* Y[m, ldy] (cols [0,n_out)) = X[m,k] * W[n_out,k]^T + bias (+ residual, same layout as Y).
  * k in {32,64,128,256}; n_out multiple of 32.  fp32 MFMA (v_mfma_f32_32x32x2_f32). */
