@@ -1,0 +1,360 @@
+"""Evaluate a checkpoint on the reference's test splits without Lightning - the flow of ``difusco/train.py --do_test``
+(``train.py:135-138``) on the GPU stages of this package:
+
+    python -m difusco_amd.evaluate --task tsp --diffusion_type categorical --do_test --storage_path DIR \\
+        --validation_split tsp500_valid.txt --test_split tsp500_test.txt --sparse_factor 50 --validation_examples 8 \\
+        --inference_schedule cosine --inference_diffusion_steps 50 --parallel_sampling 4 --ckpt_path last.ckpt
+
+Every argument of ``train.py:19-68`` is accepted with its name and default, so the reference's evaluation commands run with
+only the program name changed; training-only arguments are ignored and listed as ``ignored_args``.  ``--do_test`` validates on
+the first ``--validation_examples`` instances of ``validation_split`` (split "val", ``pl_meta_model.py:200-205``), then tests
+on all of ``test_split`` (split "test") unless ``--do_valid_only``; data paths are ``os.path.join(storage_path, split)``.
+Every instance goes through ``pipeline.solve_tsp_batch`` / ``solve_mis_batch`` - k-NN, the sampling loop, merge, 2-opt / MIS
+decode on the GPU; the runner does nothing per denoise step.
+
+Per instance it records what ``test_step`` logs (``pl_tsp_model.py:240-256``, ``pl_mis_model.py:194-209``); per split it
+prints one JSON line with the mean of every reference key over the split's instances (``pl_meta_model.py:49-60``) and
+``{split}/gap_pct``, which is not a reference key.  ``--fp16`` selects ``precision="fp16x1"``.
+
+Determinism: instance i of split s draws its Philox stream and its x_T from ``instance_seed(--seed, s, i)``,
+every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are cut from the split alone - the records do not
+depend on the world size, the rank an instance lands on, or what the model ran before.
+
+Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``), ``--device``,
+``--dist_backend``, ``--records PATH`` (JSONL, one line per instance), ``--heatmap_dir`` (where ``--save_numpy_heatmap``
+writes ``numpy_heatmap/{split}-heatmap-{idx}.npy``; default ``<storage_path>/models``), ``--unsafe_checkpoint_load`` (allow a
+checkpoint that needs full unpickling - trusted files only).
+
+Several GPUs: run under ``torch.distributed.run``.  Each rank takes ``cuda:LOCAL_RANK`` (or ``--device``) and whole chunks
+(``dist.shard_range`` over the chunk list); records are gathered on rank 0, which alone prints and writes.  The metrics are the
+mean over all instances of the split.  Lightning's ``sync_dist`` instead averages per-rank means over a ``DistributedSampler``
+that pads the split to a multiple of the world size, so its figure differs when the split does not divide evenly.
+``--dist_backend gloo`` lets ranks share one GPU (tests)."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+import time
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+# difusco/train.py:19-68, in order
+REFERENCE_ARGS = [
+    ("--task", dict(type=str, required=True)),
+    ("--storage_path", dict(type=str, required=True)),
+    ("--training_split", dict(type=str, default="data/tsp/tsp50_train_concorde.txt")),
+    ("--training_split_label_dir", dict(type=str, default=None)),
+    ("--validation_split", dict(type=str, default="data/tsp/tsp50_test_concorde.txt")),
+    ("--test_split", dict(type=str, default="data/tsp/tsp50_test_concorde.txt")),
+    ("--validation_examples", dict(type=int, default=64)),
+    ("--batch_size", dict(type=int, default=64)),
+    ("--num_epochs", dict(type=int, default=50)),
+    ("--learning_rate", dict(type=float, default=1e-4)),
+    ("--weight_decay", dict(type=float, default=0.0)),
+    ("--lr_scheduler", dict(type=str, default="constant")),
+    ("--num_workers", dict(type=int, default=16)),
+    ("--fp16", dict(action="store_true")),
+    ("--use_activation_checkpoint", dict(action="store_true")),
+    ("--diffusion_type", dict(type=str, default="gaussian")),
+    ("--diffusion_schedule", dict(type=str, default="linear")),
+    ("--diffusion_steps", dict(type=int, default=1000)),
+    ("--inference_diffusion_steps", dict(type=int, default=1000)),
+    ("--inference_schedule", dict(type=str, default="linear")),
+    ("--inference_trick", dict(type=str, default="ddim")),
+    ("--sequential_sampling", dict(type=int, default=1)),
+    ("--parallel_sampling", dict(type=int, default=1)),
+    ("--n_layers", dict(type=int, default=12)),
+    ("--hidden_dim", dict(type=int, default=256)),
+    ("--sparse_factor", dict(type=int, default=-1)),
+    ("--aggregation", dict(type=str, default="sum")),
+    ("--two_opt_iterations", dict(type=int, default=1000)),
+    ("--save_numpy_heatmap", dict(action="store_true")),
+    ("--project_name", dict(type=str, default="tsp_diffusion")),
+    ("--wandb_entity", dict(type=str, default=None)),
+    ("--wandb_logger_name", dict(type=str, default=None)),
+    ("--resume_id", dict(type=str, default=None)),
+    ("--ckpt_path", dict(type=str, default=None)),
+    ("--resume_weight_only", dict(action="store_true")),
+    ("--do_train", dict(action="store_true")),
+    ("--do_test", dict(action="store_true")),
+    ("--do_valid_only", dict(action="store_true")),
+]
+# read only by training, Lightning or W&B: accepted, ignored, listed as ignored_args when given
+TRAINING_ONLY = ("training_split", "training_split_label_dir", "batch_size", "num_epochs", "learning_rate", "weight_decay",
+                 "lr_scheduler", "num_workers", "use_activation_checkpoint", "project_name", "wandb_entity",
+                 "wandb_logger_name", "resume_id", "resume_weight_only")
+EXTENSION_ARGS = [
+    ("--seed", dict(type=int, default=0, help="base of the per-instance seeds (instance_seed)")),
+    ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
+    ("--device", dict(type=str, default=None, help="GPU of this process (default: cuda:LOCAL_RANK)")),
+    ("--dist_backend", dict(type=str, default="nccl", help="process-group backend under torch.distributed.run")),
+    ("--records", dict(type=str, default=None, help="write one JSON line per instance to this file")),
+    ("--heatmap_dir", dict(type=str, default=None, help="--save_numpy_heatmap target (default: <storage_path>/models)")),
+    ("--unsafe_checkpoint_load", dict(action="store_true",
+                                      help="allow a checkpoint that needs full unpickling (trusted files only)")),
+]
+REFERENCE_KEYS = {"tsp": ("gt_cost", "solved_cost", "2opt_iterations", "merge_iterations"), "mis": ("gt_cost", "solved_cost")}
+
+
+def build_parser(suppress_defaults: bool = False) -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m difusco_amd.evaluate",
+                                description="Evaluate a DIFUSCO checkpoint on test splits (train.py --do_test without Lightning).")
+    for flag, kw in REFERENCE_ARGS + EXTENSION_ARGS:
+        kw = dict(kw)
+        if suppress_defaults:
+            kw["default"] = argparse.SUPPRESS
+            kw.pop("required", None)
+        p.add_argument(flag, **kw)
+    return p
+
+
+def parse_args(argv=None):
+    """-> (args, ignored_args): the namespace of ``train.py``'s parser plus the extensions, and the sorted names of the
+    training-only arguments given on the command line.  Exits with status 2 on a usage error, ``--do_train`` or no mode."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    given = vars(build_parser(suppress_defaults=True).parse_args(argv))
+    if args.do_train:
+        parser.error("--do_train: training is out of scope; this runner evaluates (--do_test [--do_valid_only])")
+    if not args.do_test:
+        parser.error("nothing to do: pass --do_test (validate, then test) or --do_test --do_valid_only")
+    if args.task not in ("tsp", "mis"):
+        parser.error(f"--task {args.task}: tsp or mis")
+    if args.ckpt_path is None:
+        parser.error("--ckpt_path is required (the weights to evaluate)")
+    ignored = sorted(k for k in given if k in TRAINING_ONLY or (k == "save_numpy_heatmap" and args.task == "mis"))
+    return args, ignored
+
+
+# ---- determinism: seeds and chunks ----------------------------------------------------------------------------------------
+def instance_seed(seed: int, split: str, index: int) -> int:
+    """The seed of instance ``index`` of ``split`` ("val" / "test"): BLAKE2b with an 8-byte digest of the ASCII text
+    ``"{seed}:{split}:{index}"``, read little-endian and masked to 63 bits.  It is both the Philox key of the instance
+    (``seeds[b]``) and the seed of the CPU ``torch.Generator`` that draws its x_T (``generators[b]``).  Pinned by the tests."""
+    digest = hashlib.blake2b(f"{int(seed)}:{split}:{int(index)}".encode("ascii"), digest_size=8).digest()
+    return int.from_bytes(digest, "little") & (2 ** 63 - 1)
+
+
+def instance_generator(s: int):
+    import torch
+    return torch.Generator().manual_seed(int(s))
+
+
+ROWS_PER_CALL = 1 << 18           # output rows of one chunk's union that the default length aims at
+MAX_INSTANCES_PER_CALL = 64
+
+
+def tsp_rows(n: int, sparse_factor: int, parallel_sampling: int) -> int:
+    """Output rows of one TSP instance in a step: P x its edges (n K sparse, n^2 dense)."""
+    return int(parallel_sampling) * int(n) * (int(sparse_factor) if sparse_factor is not None and sparse_factor > 0 else int(n))
+
+
+def mis_rows(n_edges: int, parallel_sampling: int) -> int:
+    """Edge rows of one MIS graph in a step: P x (2|E| + n)."""
+    return int(parallel_sampling) * int(n_edges)
+
+
+def default_instances_per_call(rows: int) -> int:
+    """Default chunk length for instances of ``rows`` rows each (``tsp_rows`` / ``mis_rows``): as many as fit
+    ROWS_PER_CALL = 2^18 rows, at least 1, at most 64.  DESIGN §5b: batching pays up to ~10^5 rows per instance and no longer
+    at 4 x 10^5.  TSP-50 dense: 64 (P = 1), 26 (P = 4); TSP-500 K=50: 10 / 2; TSP-1000 K=100: 2 / 1."""
+    return max(1, min(MAX_INSTANCES_PER_CALL, ROWS_PER_CALL // max(1, int(rows))))
+
+
+def plan_chunks(sizes: Sequence[int], length: Callable[[int], int], equal_size: bool = True) -> List[Tuple[int, int]]:
+    """Cuts instances 0..B-1 into runs [lo, hi) of consecutive instances: a run starts at the first instance not yet taken and
+    holds at most ``length(sizes[lo])`` instances, all of size ``sizes[lo]`` when ``equal_size`` (TSP: one N per k-NN and
+    2-opt launch).  A function of the split alone, so every world size cuts the same chunks (ranks take whole chunks:
+    ``shard_chunks``)."""
+    chunks, lo = [], 0
+    while lo < len(sizes):
+        cap, hi = max(1, int(length(sizes[lo]))), lo + 1
+        while hi < len(sizes) and hi - lo < cap and (not equal_size or sizes[hi] == sizes[lo]):
+            hi += 1
+        chunks.append((lo, hi))
+        lo = hi
+    return chunks
+
+
+def split_chunks(task: str, examples, sparse_factor: int = -1, parallel_sampling: int = 1,
+                 instances_per_call: Optional[int] = None) -> List[Tuple[int, int]]:
+    """The chunks of a split: TSP runs of equal N, MIS runs of graphs of any size; length ``instances_per_call`` or the
+    default for the run's first instance."""
+    if instances_per_call is not None and int(instances_per_call) < 1:
+        raise ValueError("--instances_per_call must be >= 1")
+    if task == "tsp":
+        return plan_chunks([ex.points.shape[0] for ex in examples],
+                           lambda n: instances_per_call or default_instances_per_call(tsp_rows(n, sparse_factor, parallel_sampling)))
+    return plan_chunks([ex.edge_index.shape[1] for ex in examples],
+                       lambda e: instances_per_call or default_instances_per_call(mis_rows(e, parallel_sampling)), equal_size=False)
+
+
+def shard_chunks(chunks: Sequence[Tuple[int, int]], rank: int, world: int) -> List[Tuple[int, int]]:
+    """The whole chunks of ``rank``: a contiguous block of the chunk list (``dist.shard_range``)."""
+    from .dist import shard_range
+    lo, hi = shard_range(len(chunks), rank, world)
+    return list(chunks[lo:hi])
+
+
+# ---- per-instance values and metrics -------------------------------------------------------------------------------------
+def tsp_gt_cost(points, tour) -> float:
+    """``TSPEvaluator(np_points).evaluate(np_gt_tour)`` (``pl_tsp_model.py:241-242``): the closed tour's length over the
+    float32-rounded coordinates the reference evaluates (``pipeline.tour_length``)."""
+    from .pipeline import tour_length
+    return tour_length(np.asarray(points).astype(np.float32).astype(np.float64), tour)
+
+
+def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
+    tour, cost, costs, info = result
+    return {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.points.shape[0]),
+            "gt_cost": tsp_gt_cost(ex.points, ex.tour), "solved_cost": float(cost), "all_costs": [float(c) for c in costs],
+            "merged_costs": [float(c) for c in info["merged_costs"]], "2opt_iterations": int(info["two_opt_iterations"]),
+            "merge_iterations": float(info["merge_iterations"]), "seed": int(seed), "tour": [int(v) for v in tour]}
+
+
+def mis_record(split: str, index: int, ex, seed: int, result) -> dict:
+    sol, size, sizes = result
+    return {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.n_nodes),
+            "gt_cost": float(np.asarray(ex.labels).sum()), "solved_cost": float(size), "all_costs": [float(s) for s in sizes],
+            "seed": int(seed), "mis": np.nonzero(np.asarray(sol))[0].tolist()}
+
+
+def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, Optional[float]]:
+    """The mean over ``records`` of every key ``test_step`` logs (``{split}/gt_cost``, ``{split}/solved_cost``, and for TSP
+    ``{split}/2opt_iterations``, ``{split}/merge_iterations``), and ``{split}/gap_pct``, not a reference key: TSP the mean of
+    100 (solved - gt) / gt, MIS the mean of 100 (gt - solved) / gt over the instances with gt > 0 (None if there is none)."""
+    if not records:
+        raise ValueError(f"split {split}: no instances")
+    out = {f"{split}/{k}": float(np.mean([r[k] for r in records])) for k in REFERENCE_KEYS[task]}
+    if task == "tsp":
+        gaps = [100.0 * (r["solved_cost"] - r["gt_cost"]) / r["gt_cost"] for r in records]
+    else:
+        gaps = [100.0 * (r["gt_cost"] - r["solved_cost"]) / r["gt_cost"] for r in records if r["gt_cost"] > 0]
+    out[f"{split}/gap_pct"] = float(np.mean(gaps)) if gaps else None
+    return out
+
+
+# ---- solving ---------------------------------------------------------------------------------------------------------------
+def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0, sparse_factor: int = -1,
+                parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
+                timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None) -> List[dict]:
+    """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
+    offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
+    (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
+    (``formats.save_numpy_heatmap``) per instance."""
+    from .formats import save_numpy_heatmap
+    from .pipeline import solve_mis_batch, solve_tsp_batch
+    records = []
+    for lo, hi in chunks:
+        idx = list(range(lo, hi))
+        seeds = [instance_seed(seed, split, i) for i in idx]
+        gens = [instance_generator(s) for s in seeds]
+        if task == "tsp":
+            heats = [] if heatmap_dir is not None else None
+            res = solve_tsp_batch(model, np.stack([examples[i].points for i in idx]), sparse_factor,
+                                  parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
+                                  two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
+                                  step_offset=0, heatmaps=heats)
+            for k, i in enumerate(idx):
+                records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
+                if heats is not None:
+                    save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
+        else:
+            res = solve_mis_batch(model, [(examples[i].n_nodes, examples[i].edge_index) for i in idx],
+                                  parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling, seeds=seeds,
+                                  generators=gens, timings=timings, step_offset=0)
+            for k, i in enumerate(idx):
+                records.append(mis_record(split, i, examples[i], seeds[k], res[k]))
+    return records
+
+
+def read_split(task: str, path: str, limit: Optional[int] = None):
+    from .datasets import SplitFormatError, read_mis_split, read_tsp_split
+    examples = read_tsp_split(path, limit) if task == "tsp" else read_mis_split(path, limit=limit)
+    if limit is not None and len(examples) < limit:
+        raise SplitFormatError(f"{path}: {len(examples)} instances, --validation_examples asks for {limit}")
+    if not examples:
+        raise SplitFormatError(f"{path}: no instances")
+    return examples
+
+
+def run(argv=None) -> Tuple[List[dict], List[dict]]:
+    """The whole evaluation; returns (the JSON lines printed, all records) on rank 0 and ([], []) on the other ranks."""
+    args, ignored = parse_args(argv)
+    P, S = args.parallel_sampling, args.sequential_sampling
+    if args.task == "tsp" and args.save_numpy_heatmap and (P > 1 or S > 1):
+        raise NotImplementedError("Save numpy heatmap only support single sampling")      # pl_tsp_model.py:258-260
+    import torch
+    import torch.distributed as dist
+    from .checkpoint import check_config, load_checkpoint
+    from .models import MISModel, TSPModel
+
+    state = load_checkpoint(args.ckpt_path, allow_unsafe=args.unsafe_checkpoint_load)
+    check_config(state, args.hidden_dim, args.n_layers, args.diffusion_type)
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), 0
+    if world > 1:
+        dist.init_process_group(backend=args.dist_backend)
+        rank, world = dist.get_rank(), dist.get_world_size()
+    try:
+        dev = torch.device(args.device or f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
+        torch.cuda.set_device(dev)
+        cls = TSPModel if args.task == "tsp" else MISModel
+        model = cls(vars(args), state, device=dev, **(dict(precision="fp16x1") if args.fp16 else {}))
+        heatmap_dir = None
+        if args.task == "tsp" and args.save_numpy_heatmap:
+            heatmap_dir = args.heatmap_dir or os.path.join(args.storage_path, "models")
+        splits = [("val", args.validation_split, args.validation_examples)]
+        if not args.do_valid_only:
+            splits.append(("test", args.test_split, None))
+        lines, all_records = [], []
+        for split, rel, limit in splits:
+            t_start = time.perf_counter()
+            examples = read_split(args.task, os.path.join(args.storage_path, rel), limit)
+            parse_s = time.perf_counter() - t_start
+            chunks = split_chunks(args.task, examples, args.sparse_factor, P, args.instances_per_call)
+            timings = {}
+            recs = solve_split(model, args.task, examples, split, shard_chunks(chunks, rank, world), seed=args.seed,
+                               sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
+                               two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir)
+            torch.cuda.synchronize(dev)
+            gathered = [(recs, timings)]
+            if world > 1:
+                gathered = [None] * world
+                dist.all_gather_object(gathered, (recs, timings))
+            wall = time.perf_counter() - t_start
+            if rank != 0:
+                continue
+            recs = sorted((r for g in gathered for r in g[0]), key=lambda r: r["index"])
+            stages = {"parse": parse_s}
+            for _, tm in gathered:
+                for k, v in tm.items():
+                    stages[k] = max(stages.get(k, 0.0), v)      # the slowest rank's time of each stage
+            line = {"task": args.task, "split": split, **split_metrics(args.task, split, recs),
+                    "non_reference_keys": [f"{split}/gap_pct"], "instances": len(recs), "wall_s": round(wall, 4),
+                    "instances_per_s": round(len(recs) / wall, 3), "stages_s": {k: round(v, 4) for k, v in stages.items()},
+                    "world_size": world, "precision": model.model.precision,
+                    "instances_per_call": args.instances_per_call if args.instances_per_call else "auto",
+                    "chunks": len(chunks), "chunk_lengths": sorted({hi - lo for lo, hi in chunks}), "seed": args.seed,
+                    "ignored_args": ignored}
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            all_records += recs
+        if rank == 0 and args.records:
+            with open(args.records, "w") as f:
+                for r in all_records:
+                    f.write(json.dumps(r) + "\n")
+        return lines, all_records
+    finally:
+        if world > 1 and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def main(argv=None) -> int:
+    run(argv)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -281,11 +281,19 @@ class COMetaModel:
             xt = step(xt, np.array([t1]).astype(int), np.array([t2]).astype(int))
         return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
 
-    def _union_step(self, g, task, points, instances):
+    def _union_step(self, g, task, points, instances, step_offset=None):
+        """One step of the loop over a union.  ``step_offset``: the k-th step of the loop draws at Philox offset
+        ``step_offset + k`` instead of the engine's call counter (which advances either way); None = the counter."""
+        if step_offset is not None and int(step_offset) < 0:
+            raise ValueError("step_offset must be >= 0")
+        k = [0]
+
         def step(xt, t1, t2):
+            off = None if step_offset is None else int(step_offset) + k[0]
+            k[0] += 1
             if self.diffusion_type == "gaussian":
-                return self._gaussian(g, task, points, xt, t1, t2, None, False, instances=instances)
-            return self._categorical(g, task, points, xt, t1, t2, None, False, instances=instances)
+                return self._gaussian(g, task, points, xt, t1, t2, None, False, instances=instances, offset=off)
+            return self._categorical(g, task, points, xt, t1, t2, None, False, instances=instances, offset=off)
         return step
 
     def _post_constants(self, t: int, target_t: int) -> np.ndarray:
@@ -298,14 +306,15 @@ class COMetaModel:
             post[4] = 1.0 if target_t > 0 else 0.0                        # pl_meta_model.py:139-142
         return post
 
-    def _categorical(self, g, task, points, xt, t, target_t, uniform, return_aux, instances=None):
+    def _categorical(self, g, task, points, xt, t, target_t, uniform, return_aux, instances=None, offset=None):
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1                                              # pl_meta_model.py:108-109
         post = self._post_constants(t, target_t)
         out, pred, prob = self.model.step(
             g, task, _lib.CATEGORICAL, xt, float(t), post, points=points, xt_is_binary=self._xt_is_binary(xt),
-            rand=uniform if target_t > 0 else None, seed=self.seed, offset=self._next_offset(),
+            rand=uniform if target_t > 0 else None, seed=self.seed,
+            offset=self._next_offset() if offset is None else offset,
             want_pred=return_aux, want_prob=return_aux, gn_reduce=self.gn_reduce,
             prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None, instances=instances)
         # tensors created under torch.inference_mode() (Lightning's default for trainer.test) have no version counter:
@@ -313,14 +322,15 @@ class COMetaModel:
         self._binary_out = (out, None if out.is_inference() else out._version) if target_t > 0 else None
         return (out, pred, prob) if return_aux else out
 
-    def _gaussian(self, g, task, points, xt, t, target_t, noise, return_aux, instances=None):
+    def _gaussian(self, g, task, points, xt, t, target_t, noise, return_aux, instances=None, offset=None):
         t, target_t = _as_int(t), _as_int(target_t)
         if target_t is None:
             target_t = t - 1
         post = self._post_constants(t, target_t)
         out, pred, _ = self.model.step(
             g, task, _lib.GAUSSIAN, xt, float(t), post, points=points, xt_is_binary=False,
-            rand=noise if post[4] != 0 else None, seed=self.seed, offset=self._next_offset(), want_pred=return_aux,
+            rand=noise if post[4] != 0 else None, seed=self.seed,
+            offset=self._next_offset() if offset is None else offset, want_pred=return_aux,
             gn_reduce=self.gn_reduce, prepared=self._prepared(g, points) if task == _lib.TASK_TSP else None,
             instances=instances)
         return (out, pred) if return_aux else out
@@ -517,7 +527,7 @@ class TSPModel(COMetaModel):
                 xt = self.categorical_denoise_step(points, xt, t1, self.device, edge_index, target_t=t2)
         return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
 
-    def sample_batch(self, points, edge_index=None, seeds=None, generators=None, xt0=None):
+    def sample_batch(self, points, edge_index=None, seeds=None, generators=None, xt0=None, step_offset=None):
         """``sample()`` of B instances in ONE sampling loop over their disjoint union, every instance getting what its own
         ``sample()`` call returns.  ``points``: list of B tensors, each what ``sample()`` takes for that instance (sparse: [P n_b, 2]
         with ``edge_index[b]`` [2, P E_b] holding its P parallel samples; dense: [P_b, n, 2], ``edge_index=None``, the same n for
@@ -525,7 +535,8 @@ class TSPModel(COMetaModel):
         this model's seed for all); ``generators[b]`` / ``xt0[b]``: its initial noise, as in ``sample()``.  Each instance keeps
         its own head GroupNorm statistics (sparse: one segment per instance, the solo call's; dense: one per sample, as solo)
         and its own random streams (``DIFUSCO_RAND_PHILOX_INSTANCES``); the step offsets are this engine's call counter, as
-        in ``sample()``.  Returns the list of B heatmaps, each shaped like ``sample()``'s."""
+        in ``sample()``, or ``step_offset``, ``step_offset + 1``, ... when given (``step_offset=0``: what a fresh engine draws,
+        whatever this one ran before).  Returns the list of B heatmaps, each shaped like ``sample()``'s."""
         B = len(points)
         if B < 1:
             raise ValueError("sample_batch needs at least one instance")
@@ -551,7 +562,7 @@ class TSPModel(COMetaModel):
             union_pts = union_pts.reshape(-1, 2)
         instances = self._instance_tables(inst_rows, seeds)
         xt = torch.cat(self._initial_noise(shapes, generators, xt0, dev))
-        heat = self._sample_loop(self._union_step(g, _lib.TASK_TSP, union_pts, instances), xt)
+        heat = self._sample_loop(self._union_step(g, _lib.TASK_TSP, union_pts, instances, step_offset), xt)
         return [heat[int(inst_rows[b]):int(inst_rows[b + 1])].reshape(out_shapes[b]) for b in range(B)]
 
 
@@ -595,15 +606,16 @@ class MISModel(COMetaModel):
                 xt = self.categorical_denoise_step(xt, t1, self.device, edge_index, target_t=t2)
         return xt * 0.5 + 0.5 if self.diffusion_type == "gaussian" else xt + 1e-6
 
-    def sample_batch(self, n_nodes, edge_index, seeds=None, generators=None, xt0=None):
+    def sample_batch(self, n_nodes, edge_index, seeds=None, generators=None, xt0=None, step_offset=None):
         """``sample()`` of B graphs in ONE sampling loop over their disjoint union: ``n_nodes[b]`` / ``edge_index[b]`` are what
-        ``sample()`` takes for graph b (its P parallel samples already duplicated), ``seeds`` / ``generators`` / ``xt0`` as in
-        ``TSPModel.sample_batch``.  One head statistic segment per graph (= its solo call).  Returns the B node-score tensors."""
+        ``sample()`` takes for graph b (its P parallel samples already duplicated), ``seeds`` / ``generators`` / ``xt0`` /
+        ``step_offset`` as in ``TSPModel.sample_batch``.  One head statistic segment per graph (= its solo call).  Returns the B
+        node-score tensors."""
         B = len(n_nodes)
         if B < 1 or len(edge_index) != B:
             raise ValueError("sample_batch needs one edge_index per graph and at least one graph")
         g, _, inst_rows = build_union_csr(edge_index, [int(v) for v in n_nodes], self.device, task_rows="nodes")
         instances = self._instance_tables(inst_rows, seeds)
         xt = torch.cat(self._initial_noise([(int(v),) for v in n_nodes], generators, xt0, self.device))
-        heat = self._sample_loop(self._union_step(g, _lib.TASK_MIS, None, instances), xt)
+        heat = self._sample_loop(self._union_step(g, _lib.TASK_MIS, None, instances, step_offset), xt)
         return [heat[int(inst_rows[b]):int(inst_rows[b + 1])] for b in range(B)]

@@ -130,15 +130,26 @@ def _per_instance(v, B: int, name: str):
     return v
 
 
+def _round_offset(model, step_offset: Optional[int], r: int) -> Optional[int]:
+    """First Philox offset of sequential round ``r`` of a call that starts at ``step_offset`` (None: the engine's counter)."""
+    return None if step_offset is None else int(step_offset) + r * int(model.args.inference_diffusion_steps)
+
+
 def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 1, sequential_sampling: int = 1,
                     two_opt_iterations: int = 1000, seeds: Optional[Sequence[int]] = None,
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
-                    instances_per_call: Optional[int] = None) -> List[tuple]:
+                    instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
+                    heatmaps: Optional[list] = None) -> List[tuple]:
     """``solve_tsp`` of B instances of the same size: ``points`` [B, N, 2].  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
     ``instances_per_call`` instances (default: all) share one k-NN launch sequence, one sampling loop over their union
     (``TSPModel.sample_batch``) and one grouped 2-opt; the merge runs per instance.  The step offsets come from the engine's
-    call counter, as in ``solve_tsp``: with a fresh engine the first group of instances matches solo calls on fresh engines."""
+    call counter, as in ``solve_tsp``: with a fresh engine the first group of instances matches solo calls on fresh engines.
+    ``step_offset``: every group of ``instances_per_call`` instances starts its steps at this offset instead (sequential round r
+    at ``step_offset + r * inference_diffusion_steps``): ``step_offset=0`` draws what solo calls on fresh engines draw, whatever
+    ran on this engine before.  ``heatmaps``: a list to which one entry per instance is appended - the host copies (numpy) of
+    its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
+    ``--save_numpy_heatmap``); None (default) copies nothing."""
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -168,11 +179,16 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
         gens_c = None if generators is None else generators[c0:c1]
         stacked = [[] for _ in range(G)]
         merged_costs = [[] for _ in range(G)]
+        heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         ns = np.zeros(G, dtype=np.int64)
-        for _ in range(sequential_sampling):
+        for r in range(sequential_sampling):
             t0 = time.perf_counter()
-            heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c)
+            heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
+                                       step_offset=_round_offset(model, step_offset, r))
+            if heatmaps is not None:
+                for g in range(G):
+                    heat_out[g].append(heats[g].cpu().numpy())
             tick("sampling", t0)
             t0 = time.perf_counter()
             tours = []
@@ -195,16 +211,19 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             results.append((sol[best].tolist(), costs[best], costs,
                             {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]),
                              "merged_costs": merged_costs[g]}))
+        if heatmaps is not None:
+            heatmaps.extend(heat_out)
     return results
 
 
 def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sampling: int = 1,
                     seeds: Optional[Sequence[int]] = None, generators: Optional[Sequence[torch.Generator]] = None,
-                    timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None) -> List[tuple]:
+                    timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None,
+                    step_offset: Optional[int] = None) -> List[tuple]:
     """``solve_mis`` of B graphs: ``instances`` = [(n_nodes, edge_index), ...].  Returns the list of what ``solve_mis`` returns
     for every graph (run with ``seed = seeds[b]``, ``generator = generators[b]``).  Up to ``instances_per_call`` graphs share
     one sampling loop over their union (``MISModel.sample_batch``) and one greedy decode of the union (``mis_decode_np``: the
-    decode never crosses a component, so every graph gets its own decode)."""
+    decode never crosses a component, so every graph gets its own decode).  ``step_offset``: as in ``solve_tsp_batch``."""
     from .decode import mis_decode_np
     from .graph import build_csr
     instances = list(instances)
@@ -227,10 +246,11 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
         union = torch.cat([e + int(off[g]) for g, e in enumerate(eis)], dim=1)
         graph = build_csr(union, int(off[-1]), dev)
         sols = [[] for _ in ns]
-        for _ in range(sequential_sampling):
+        for r in range(sequential_sampling):
             t0 = time.perf_counter()
             scores = model.sample_batch([n * P for n in ns], eis, seeds=None if seeds is None else seeds[c0:c1],
-                                        generators=None if generators is None else generators[c0:c1])
+                                        generators=None if generators is None else generators[c0:c1],
+                                        step_offset=_round_offset(model, step_offset, r))
             tick("sampling", t0)
             t0 = time.perf_counter()
             sol = mis_decode_np(torch.cat(scores), graph=graph, device=dev)
