@@ -103,7 +103,9 @@ def lib():
     L.difusco_fused_scratch_bytes.restype = ctypes.c_size_t
     L.difusco_fused_scratch_bytes.argtypes = [i32, i32]
     L.difusco_edge_layer_fused.argtypes = [i32, i32, i32, vp, vp, vp, f32p, f32p, f32p, vp, vp] + [f32p] * 9 + [i32, f32p, vp, vp]
+    L.difusco_edge_layer_fused_ex.argtypes = L.difusco_edge_layer_fused.argtypes[:-1] + [i32, i32, vp]      # + aggregation, reg_gather
     L.difusco_edge_gate_aggregate.argtypes = [i32, i32, vp, vp, f32p, f32p, f32p] + [f32p] * 7 + [i32, vp]
+    L.difusco_edge_gate_aggregate_ex.argtypes = L.difusco_edge_gate_aggregate.argtypes[:-1] + [i32, vp]      # + aggregation
     L.difusco_categorical_posterior.argtypes = [f32p, f32p, ctypes.POINTER(ctypes.c_float), i32, f32p,
                                                 ctypes.c_uint64, ctypes.c_uint64, f32p, f32p, i64, vp]
     L.difusco_gaussian_posterior.argtypes = [f32p, f32p, ctypes.POINTER(ctypes.c_float), i32, f32p,

@@ -726,16 +726,28 @@ int difusco_linear_rows_split(const float* x, const void* planes, int precision,
   return DIFUSCO_OK;
 }
 
+int difusco_edge_gate_aggregate_ex(int hidden, int n_nodes, const int32_t* rowptr, const int32_t* col, const float* node4,
+                                   float* ce_act, float* h, const float* norm_h_w, const float* norm_h_b,
+                                   const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
+                                   const float* out_ln_b, const float* tbias, int time_on_edge, int aggregation,
+                                   void* stream) {
+  if (!hidden_ok(hidden)) return fail(DIFUSCO_EINVAL, "hidden must be 64, 128 or 256");
+  if (!rowptr || !node4 || !h || !norm_h_w || !norm_h_b || !norm_e_w || !norm_e_b || !out_ln_w || !out_ln_b || !tbias)
+    return fail(DIFUSCO_EINVAL, "null pointer");
+  if (aggregation < DIFUSCO_AGG_SUM || aggregation > DIFUSCO_AGG_MAX)
+    return fail(DIFUSCO_EINVAL, "aggregation must be DIFUSCO_AGG_SUM, _MEAN or _MAX");
+  HIP_TRY(difusco::launch_edge_gate_aggregate(hidden, n_nodes, rowptr, col, node4, ce_act, h, norm_h_w, norm_h_b, norm_e_w,
+                                              norm_e_b, out_ln_w, out_ln_b, tbias, time_on_edge, (hipStream_t)stream,
+                                              aggregation));
+  return DIFUSCO_OK;
+}
+
 int difusco_edge_gate_aggregate(int hidden, int n_nodes, const int32_t* rowptr, const int32_t* col, const float* node4,
                                 float* ce_act, float* h, const float* norm_h_w, const float* norm_h_b,
                                 const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
                                 const float* out_ln_b, const float* tbias, int time_on_edge, void* stream) {
-  if (!hidden_ok(hidden)) return fail(DIFUSCO_EINVAL, "hidden must be 64, 128 or 256");
-  if (!rowptr || !node4 || !h || !norm_h_w || !norm_h_b || !norm_e_w || !norm_e_b || !out_ln_w || !out_ln_b || !tbias)
-    return fail(DIFUSCO_EINVAL, "null pointer");
-  HIP_TRY(difusco::launch_edge_gate_aggregate(hidden, n_nodes, rowptr, col, node4, ce_act, h, norm_h_w, norm_h_b, norm_e_w,
-                                              norm_e_b, out_ln_w, out_ln_b, tbias, time_on_edge, (hipStream_t)stream));
-  return DIFUSCO_OK;
+  return difusco_edge_gate_aggregate_ex(hidden, n_nodes, rowptr, col, node4, ce_act, h, norm_h_w, norm_h_b, norm_e_w, norm_e_b,
+                                        out_ln_w, out_ln_b, tbias, time_on_edge, DIFUSCO_AGG_SUM, stream);
 }
 
 size_t difusco_fused_scratch_bytes(int n_nodes, int n_edges) {
@@ -745,12 +757,17 @@ size_t difusco_fused_scratch_bytes(int n_nodes, int n_edges) {
                           (size_t)n_nodes * 1024) + 256;
 }
 
-int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int32_t* rowptr, const int32_t* row,
-                             const int32_t* col, const float* node4, float* e, float* h, const void* planes_c,
-                             const void* planes_o, const float* b_c, const float* norm_h_w, const float* norm_h_b,
-                             const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
-                             const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
-                             const float* scales, void* scratch, void* stream) {
+int difusco_edge_layer_fused_ex(int precision, int n_nodes, int n_edges, const int32_t* rowptr, const int32_t* row,
+                                const int32_t* col, const float* node4, float* e, float* h, const void* planes_c,
+                                const void* planes_o, const float* b_c, const float* norm_h_w, const float* norm_h_b,
+                                const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
+                                const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
+                                const float* scales, void* scratch, int aggregation, int reg_gather, void* stream) {
+  if (aggregation < DIFUSCO_AGG_SUM || aggregation > DIFUSCO_AGG_MAX)
+    return fail(DIFUSCO_EINVAL, "aggregation must be DIFUSCO_AGG_SUM, _MEAN or _MAX");
+  if (reg_gather != 0 && reg_gather != 1) return fail(DIFUSCO_EINVAL, "reg_gather must be 0 or 1");
+  if (reg_gather && aggregation == DIFUSCO_AGG_MAX)      // (launch_by_mode: no register-gather instantiation of the max kinds)
+    return fail(DIFUSCO_EINVAL, "fused kernel: aggregation = max has no register-gather variant");
   if (precision != DIFUSCO_PREC_BF16X3 && precision != DIFUSCO_PREC_FP16X3 && precision != DIFUSCO_PREC_FP16X1)
     return fail(DIFUSCO_EINVAL, "fused kernel: precision must be BF16X3, FP16X3 or FP16X1");
   if (!rowptr || !row || !col || !node4 || !e || !h || !planes_c || !planes_o || !b_c || !norm_h_w || !norm_h_b ||
@@ -776,11 +793,23 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
                                            reinterpret_cast<const unsigned short*>(planes_c) + off,
                                            reinterpret_cast<const unsigned short*>(planes_o) + off, 256LL * 256, b_c,
                                            norm_e_w, norm_e_b, tbias, out_ln_w, out_ln_b, b_out, time_on_edge, part,
-                                           direct, scales, etmax, etmax, st, n_nodes >= (1 << 20) ? 1 : 0));
+                                           direct, scales, etmax, etmax, st,
+                                           reg_gather | (aggregation == DIFUSCO_AGG_MAX ? 2 : 0)));      // (as the step: fused_variant)
   // (node_finalize reads the U rows, which the conversion copies unchanged: either buffer would do)
   HIP_TRY(difusco::launch_node_finalize(n_nodes, n_edges, rowptr, node4, part, direct, h, norm_h_w, norm_h_b, tbias,
-                                        time_on_edge, nullptr, st));
+                                        time_on_edge, nullptr, st, nullptr, aggregation));
   return DIFUSCO_OK;
+}
+
+int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int32_t* rowptr, const int32_t* row,
+                             const int32_t* col, const float* node4, float* e, float* h, const void* planes_c,
+                             const void* planes_o, const float* b_c, const float* norm_h_w, const float* norm_h_b,
+                             const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
+                             const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
+                             const float* scales, void* scratch, void* stream) {
+  return difusco_edge_layer_fused_ex(precision, n_nodes, n_edges, rowptr, row, col, node4, e, h, planes_c, planes_o, b_c, norm_h_w,
+                                     norm_h_b, norm_e_w, norm_e_b, out_ln_w, out_ln_b, b_out, tbias, time_on_edge, scales, scratch,
+                                     DIFUSCO_AGG_SUM, n_nodes >= (1 << 20) ? 1 : 0, stream);
 }
 
 int difusco_categorical_posterior(const float* logits, const float* xt, const float* post, int rand_mode,

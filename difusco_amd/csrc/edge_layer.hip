@@ -35,6 +35,8 @@ __global__ __launch_bounds__(256) void node_finalize_kernel(int n_nodes, int n_e
       const int first = 32 * t;
       int last = first + 31;
       last = last < n_edges ? last : n_edges - 1;
+      // (a single-segment tile writes part[tile][0] only: a row that covers the whole tile takes the first branch; in the last
+      //  tile `last` is the launch's last edge, whose row the pad lanes extend)
       const float* src;
       if (a <= first) src = part + ((long long)t * 2 + 0) * H;          // owns the tile's first edge
       else if (b > last) src = part + ((long long)t * 2 + 1) * H;       // owns the tile's last edge

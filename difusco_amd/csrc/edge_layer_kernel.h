@@ -36,8 +36,9 @@
 // Neighbour sum.  The gated messages m of a tile are transposed through a wave-private LDS scratch
 // (64 features per round) and summed per centre-node segment by lanes = features.  A segment that is
 // the first or last of its tile may continue in the neighbouring tile: it goes to part[tile][0|1];
-// segments strictly inside a tile are complete and go to direct[node].  node_finalize_kernel adds the
-// pieces of each node in tile order - deterministic, no atomics.
+// segments strictly inside a tile are complete and go to direct[node].  A single-segment tile writes part[tile][0] only; the pad
+// lanes of a launch's last tile repeat the last edge's node, so they extend its segment (with the neutral value: 0, or -inf for
+// max).  node_finalize_kernel adds the pieces of each node in tile order - deterministic, no atomics.
 //
 // First layer (template flag L0): when the edge input is a lookup in a 2-row table (categorical TSP: the embedding
 // of the bit x_t; MIS: zeros) the table sits in LDS and the kernel never reads e - see the L0 notes at the kernel.

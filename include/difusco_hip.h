@@ -323,6 +323,14 @@ int difusco_edge_gate_aggregate(int hidden, int n_nodes, const int32_t* rowptr, 
                                 const float* norm_e_w, const float* norm_e_b,
                                 const float* out_ln_w, const float* out_ln_b,
                                 const float* tbias, int time_on_edge, void* stream);
+/* The same pass with the neighbour aggregation chosen: aggregation = DIFUSCO_AGG_* (sum / mean / max over the edges of the
+ * row; an empty row aggregates to 0).  Additive at ABI 13: difusco_edge_gate_aggregate(..) is this with DIFUSCO_AGG_SUM. */
+int difusco_edge_gate_aggregate_ex(int hidden, int n_nodes, const int32_t* rowptr, const int32_t* col,
+                                   const float* node4, float* ce_act, float* h,
+                                   const float* norm_h_w, const float* norm_h_b,
+                                   const float* norm_e_w, const float* norm_e_b,
+                                   const float* out_ln_w, const float* out_ln_b,
+                                   const float* tbias, int time_on_edge, int aggregation, void* stream);
 
 /* The fused edge pass of one layer + node update (edge_layer.hip), H = 256 only:
  *   e <- e + W_o SiLU(LN_o(ReLU(LN_e(Ah[j]+Bh[i]+C e)) (+t))) + b_o ;  h_i += ReLU(LN_h(Uh_i + sum gate*Vh_j)) (+t)
@@ -341,6 +349,16 @@ int difusco_edge_layer_fused(int precision, int n_nodes, int n_edges, const int3
                              const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
                              const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
                              const float* scales, void* scratch, void* stream);
+/* The same layer with the two choices the step driver makes for it: aggregation = DIFUSCO_AGG_* (the kernel's max kinds and
+ * node_finalize's sum / mean / max) and reg_gather = 0 | 1 (1: the register-gather instantiations that a step uses for calls with
+ * n_nodes >= 2^20; valid at any size).  reg_gather = 1 with DIFUSCO_AGG_MAX is refused (DIFUSCO_EINVAL), as in the step.
+ * Additive at ABI 13: difusco_edge_layer_fused(..) is this with (DIFUSCO_AGG_SUM, n_nodes >= 2^20). */
+int difusco_edge_layer_fused_ex(int precision, int n_nodes, int n_edges, const int32_t* rowptr, const int32_t* row,
+                                const int32_t* col, const float* node4, float* e, float* h, const void* planes_c,
+                                const void* planes_o, const float* b_c, const float* norm_h_w, const float* norm_h_b,
+                                const float* norm_e_w, const float* norm_e_b, const float* out_ln_w,
+                                const float* out_ln_b, const float* b_out, const float* tbias, int time_on_edge,
+                                const float* scales, void* scratch, int aggregation, int reg_gather, void* stream);
 
 /* Elementwise posteriors on already computed predictions (pl_meta_model.py:102-175).  rand_mode 0-2 (the per-instance
  * mode needs the instance tables of difusco_step_args and is refused here). */

@@ -271,7 +271,7 @@ def encoder_sparse_node(p: Params, xt: torch.Tensor, t: torch.Tensor, ei: torch.
 
 
 def encoder_sparse_f64(p: Params, points: Optional[torch.Tensor], xt: torch.Tensor, t: torch.Tensor, ei: torch.Tensor,
-                       node_feature_only: bool = False) -> torch.Tensor:
+                       node_feature_only: bool = False, aggregation: str = "sum") -> torch.Tensor:
     """The same network as encoder_sparse_edge / encoder_sparse_node evaluated in FLOAT64 from the same fp32 inputs and fp32
     parameters: the exact-arithmetic value that every fp32 implementation (the reference, this oracle, the HIP path) approximates.
     Used by the adversarial-weight tests (tests/test_gpu_round6.py) to CALIBRATE a bound: with outlier channels or a residual
@@ -291,7 +291,7 @@ def encoder_sparse_f64(p: Params, points: Optional[torch.Tensor], xt: torch.Tens
         h = _lin(q, "node_embed", position_embedding_sine(points.double(), H))
         e = _lin(q, "edge_embed", scalar_embedding_sine(xt.double(), H))
     for l in range(n_layers_of(q)):
-        h, e = sparse_layer(q, l, h, e, ei, _layer_time_bias(q, l, temb), not node_feature_only)
+        h, e = sparse_layer(q, l, h, e, ei, _layer_time_bias(q, l, temb), not node_feature_only, aggregation=aggregation)
     feat = h if node_feature_only else e
     R = feat.shape[0]
     x = F.group_norm(feat.t().reshape(1, H, R, 1), 32, q["out.0.weight"], q["out.0.bias"], 1e-5)
