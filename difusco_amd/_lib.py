@@ -118,6 +118,13 @@ def lib():
     L.difusco_tsp_two_opt.argtypes = [i32, i32, vp, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(i64), vp]
     L.difusco_tsp_two_opt_grouped_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_two_opt_grouped.argtypes = [i32, i32, i32, vp, vp, i64, vp, ctypes.c_size_t, vp, vp]
+    L.difusco_tsp_two_opt_screen_bound.argtypes = [ctypes.c_double, ctypes.POINTER(ctypes.c_double)]
+    L.difusco_tsp_two_opt_screened_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_two_opt_screened.argtypes = [i32, i32, vp, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(i64),
+                                               ctypes.POINTER(i64), vp]
+    L.difusco_tsp_two_opt_grouped_screened_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_two_opt_grouped_screened.argtypes = [i32, i32, i32, vp, vp, i64, vp, ctypes.c_size_t, vp,
+                                                       ctypes.POINTER(i64), vp]
     L.difusco_knn_graph_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_knn_graph.argtypes = [i32, i32, vp, i64, vp, vp, vp, ctypes.c_size_t, vp]
     L.difusco_mis_decode_workspace_bytes.argtypes = [i32, ctypes.POINTER(ctypes.c_size_t)]

@@ -62,10 +62,34 @@ def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=False, parallel_
     return (tours, merge_iterations, done) if return_completed else (tours, merge_iterations)
 
 
-def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0"):
+TWO_OPT_METHODS = ("exact", "screened")
+
+
+def check_two_opt_method(method):
+    if method not in TWO_OPT_METHODS:
+        raise ValueError(f"two-opt method {method!r}: one of {TWO_OPT_METHODS}")
+    return method
+
+
+def two_opt_screen_bound(max_abs_coord):
+    """The margin ``eps`` of the screened 2-opt for an instance whose largest |coordinate| is ``max_abs_coord``: the float32
+    evaluation of a move's change is proven to lie within ``eps`` of the float64 one (``difusco_tsp_two_opt_screen_bound``, a
+    host function: no GPU).  None when no bound exists (non-finite, or so large or small that float32 over- or underflows); a
+    screened call then runs the exact sweep."""
+    eps = ctypes.c_double()
+    rc = _lib.lib().difusco_tsp_two_opt_screen_bound(float(max_abs_coord), ctypes.byref(eps))
+    if rc < 0:
+        _lib.check(rc)
+    return float(eps.value) if rc == 1 else None
+
+
+def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
     """Drop-in for ``batched_two_opt_torch`` of the reference (``difusco/utils/tsp_utils.py:12-49``): ``points``
     float64 [N,2] numpy, ``tour`` int [B, N+1] numpy (closed tours over the same points); returns
-    ``(tour int64 numpy [B, N+1], iterator)``.  Runs ``difusco_tsp_two_opt``; GPU only."""
+    ``(tour int64 numpy [B, N+1], iterator)``.  Runs ``difusco_tsp_two_opt``; GPU only.  ``method="screened"`` runs
+    ``difusco_tsp_two_opt_screened``: the same tours and iterator, float64 only for the moves a float32 screen cannot rule out;
+    ``stats`` (a dict) then receives ``exact_pairs``, the number of pairs that took the float64 path."""
+    method = check_two_opt_method(method)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.DifuscoHipError("batched_two_opt_torch of difusco_amd runs on the GPU only (no CPU fallback)")
@@ -76,20 +100,30 @@ def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0"):
         raise ValueError("tour must be [batch, N + 1] over the N points")
     n, batch = pts.shape[0], tours.shape[0]
     nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_two_opt_workspace_bytes(n, batch, ctypes.byref(nbytes)))
+    screened = method == "screened"
+    _lib.check((L.difusco_tsp_two_opt_screened_workspace_bytes if screened else L.difusco_tsp_two_opt_workspace_bytes)(
+        n, batch, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    it = ctypes.c_int64()
-    _lib.check(L.difusco_tsp_two_opt(n, batch, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(tours.data_ptr()),
-                                     int(max_iterations), ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(it),
-                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    it, pairs = ctypes.c_int64(), ctypes.c_int64()
+    head = (n, batch, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(tours.data_ptr()), int(max_iterations),
+            ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(it))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if screened:
+        _lib.check(L.difusco_tsp_two_opt_screened(*head, ctypes.byref(pairs), stream))
+        if stats is not None:
+            stats["exact_pairs"] = int(pairs.value)
+    else:
+        _lib.check(L.difusco_tsp_two_opt(*head, stream))
     return tours.cpu().numpy().astype(np.int64), int(it.value)
 
 
-def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0"):
+def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
     """``batched_two_opt_torch`` of G instances at once: ``points`` float64 [G, N, 2], ``tours`` int [G * P, N + 1] with the P
     tours of instance g at rows g P .. g P + P - 1.  Every instance gets exactly what ``batched_two_opt_torch(points[g],
     tours[g P:(g+1) P])`` returns (its own stop test and iteration count); runs ``difusco_tsp_two_opt_grouped``, GPU only.
-    Returns ``(tours int64 numpy [G * P, N + 1], iterations int64 numpy [G])``."""
+    Returns ``(tours int64 numpy [G * P, N + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
+    ``batched_two_opt_torch`` (``difusco_tsp_two_opt_grouped_screened``)."""
+    method = check_two_opt_method(method)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.DifuscoHipError("batched_two_opt_grouped runs on the GPU only (no CPU fallback)")
@@ -103,13 +137,21 @@ def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0")
     pts, t = _dev(pts, torch.float64, device), _dev(t, torch.int32, device)
     L = _lib.lib()
     nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_two_opt_grouped_workspace_bytes(n, G, P, ctypes.byref(nbytes)))
+    screened = method == "screened"
+    _lib.check((L.difusco_tsp_two_opt_grouped_screened_workspace_bytes if screened
+                else L.difusco_tsp_two_opt_grouped_workspace_bytes)(n, G, P, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     its = np.zeros(G, dtype=np.int64)
-    _lib.check(L.difusco_tsp_two_opt_grouped(n, G, P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(t.data_ptr()),
-                                             int(max_iterations), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-                                             its.ctypes.data_as(ctypes.c_void_p),
-                                             ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    pairs = ctypes.c_int64()
+    head = (n, G, P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(t.data_ptr()), int(max_iterations),
+            ctypes.c_void_p(ws.data_ptr()), nbytes.value, its.ctypes.data_as(ctypes.c_void_p))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if screened:
+        _lib.check(L.difusco_tsp_two_opt_grouped_screened(*head, ctypes.byref(pairs), stream))
+        if stats is not None:
+            stats["exact_pairs"] = int(pairs.value)
+    else:
+        _lib.check(L.difusco_tsp_two_opt_grouped(*head, stream))
     return t.cpu().numpy().astype(np.int64), its
 
 

@@ -20,7 +20,8 @@ Determinism: instance i of split s draws its Philox stream and its
 every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are cut from the split alone - the records do not
 depend on the world size, the rank an instance lands on, or what the model ran before.
 
-Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``), ``--device``,
+Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
+``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--device``,
 ``--dist_backend``, ``--records PATH`` (JSONL, one line per instance), ``--heatmap_dir`` (where ``--save_numpy_heatmap``
 writes ``numpy_heatmap/{split}-heatmap-{idx}.npy``; default ``<storage_path>/models``), ``--unsafe_checkpoint_load`` (allow a
 checkpoint that needs full unpickling - trusted files only).
@@ -88,6 +89,8 @@ TRAINING_ONLY = ("training_split", "training_split_label_dir", "batch_size", "nu
 EXTENSION_ARGS = [
     ("--seed", dict(type=int, default=0, help="base of the per-instance seeds (instance_seed)")),
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
+    ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
+                              help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
     ("--device", dict(type=str, default=None, help="GPU of this process (default: cuda:LOCAL_RANK)")),
     ("--dist_backend", dict(type=str, default="nccl", help="process-group backend under torch.distributed.run")),
     ("--records", dict(type=str, default=None, help="write one JSON line per instance to this file")),
@@ -239,7 +242,8 @@ def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, O
 # ---- solving ---------------------------------------------------------------------------------------------------------------
 def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0, sparse_factor: int = -1,
                 parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
-                timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None) -> List[dict]:
+                timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
+                two_opt_method: str = "exact") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -256,7 +260,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
             res = solve_tsp_batch(model, np.stack([examples[i].points for i in idx]), sparse_factor,
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
                                   two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
-                                  step_offset=0, heatmaps=heats)
+                                  step_offset=0, heatmaps=heats, two_opt_method=two_opt_method)
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if heats is not None:
@@ -317,7 +321,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             timings = {}
             recs = solve_split(model, args.task, examples, split, shard_chunks(chunks, rank, world), seed=args.seed,
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
-                               two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir)
+                               two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir,
+                               two_opt_method=args.two_opt_method)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -337,7 +342,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                     "world_size": world, "precision": model.model.precision,
                     "instances_per_call": args.instances_per_call if args.instances_per_call else "auto",
                     "chunks": len(chunks), "chunk_lengths": sorted({hi - lo for lo, hi in chunks}), "seed": args.seed,
-                    "ignored_args": ignored}
+                    "two_opt_method": args.two_opt_method, "ignored_args": ignored}
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

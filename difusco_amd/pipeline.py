@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import batched_two_opt_grouped, batched_two_opt_torch, merge_tours
+from .decode import check_two_opt_method, batched_two_opt_grouped, batched_two_opt_torch, merge_tours
 from .graph import knn_edge_index_gpu
 
 
@@ -35,12 +35,14 @@ def _ticker(timings, dev):
 
 def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: int = 1, two_opt_iterations: int = 1000,
               generator: Optional[torch.Generator] = None, timings: Optional[Dict[str, float]] = None,
-              sequential_sampling: int = 1, *, graphed: bool = False):
+              sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
     merge_iterations / 2-opt moves of the LAST round - the quantities the reference logs (``pl_tsp_model.py:244-251``).
-    ``graphed=True``: every sampling loop runs as one replay of a captured HIP graph (``TSPModel.sample``), same results."""
+    ``graphed=True``: every sampling loop runs as one replay of a captured HIP graph (``TSPModel.sample``), same results.
+    ``two_opt_method``: "exact" or "screened" (``decode.batched_two_opt_torch``), same results."""
+    check_two_opt_method(two_opt_method)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -73,7 +75,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
         tick("merge", t0)
         t0 = time.perf_counter()
         solved, ns = batched_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),   # :233-236
-                                           max_iterations=two_opt_iterations, device=dev)
+                                           max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
         tick("two_opt", t0)
         stacked.append(solved)
         merged_costs += [tour_length(np_points64, t) for t in tours]
@@ -139,7 +141,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     two_opt_iterations: int = 1000, seeds: Optional[Sequence[int]] = None,
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
                     instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
-                    heatmaps: Optional[list] = None) -> List[tuple]:
+                    heatmaps: Optional[list] = None, *, two_opt_method: str = "exact") -> List[tuple]:
     """``solve_tsp`` of B instances of the same size: ``points`` [B, N, 2].  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
     ``instances_per_call`` instances (default: all) share one k-NN launch sequence, one sampling loop over their union
@@ -149,7 +151,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     at ``step_offset + r * inference_diffusion_steps``): ``step_offset=0`` draws what solo calls on fresh engines draw, whatever
     ran on this engine before.  ``heatmaps``: a list to which one entry per instance is appended - the host copies (numpy) of
     its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
-    ``--save_numpy_heatmap``); None (default) copies nothing."""
+    ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``."""
+    check_two_opt_method(two_opt_method)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -199,7 +202,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             tick("merge", t0)
             t0 = time.perf_counter()
             solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
-                                                 max_iterations=two_opt_iterations, device=dev)
+                                                 max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g * P:(g + 1) * P])

@@ -429,6 +429,26 @@ int difusco_tsp_two_opt_grouped(int n_nodes, int groups, int per_group, const do
                                 int64_t max_iterations, void* workspace, size_t workspace_bytes, int64_t* iterations_out,
                                 void* stream);
 
+/* Screened 2-opt (additive to ABI 13): the arguments, semantics and results of difusco_tsp_two_opt / _grouped - the same moves,
+ * tours and iteration counts, bit for bit.  Every pair is first evaluated in float32; only a pair that the float32 value cannot
+ * rule out, given the proven bound |c32 - c64| <= eps(M), is evaluated in float64 (M = the largest |coordinate| of the
+ * instance, reduced on the device once per call).  exact_pairs_out (HOST, optional): the number of pairs of the whole call that
+ * took the float64 path.  The workspaces are larger than the exact entries' (their own _workspace_bytes).  At most 65535 tours
+ * per call.
+ * difusco_tsp_two_opt_screen_bound is a HOST function (no GPU): returns 1 and *eps = the margin the kernels use for an instance
+ * whose largest |coordinate| is max_abs_coord, 0 (and *eps = 0) when no bound exists - max_abs_coord not finite or outside
+ * [2^-32, 2^60], where float32 under- or overflows; a screened call with such a group runs the exact sweep instead, with the
+ * same results.  Negative on a null pointer. */
+int difusco_tsp_two_opt_screen_bound(double max_abs_coord, double* eps);
+int difusco_tsp_two_opt_screened_workspace_bytes(int n_nodes, int batch, size_t* bytes);
+int difusco_tsp_two_opt_screened(int n_nodes, int batch, const double* points, int32_t* tours, int64_t max_iterations,
+                                 void* workspace, size_t workspace_bytes, int64_t* iterations_out, int64_t* exact_pairs_out,
+                                 void* stream);
+int difusco_tsp_two_opt_grouped_screened_workspace_bytes(int n_nodes, int groups, int per_group, size_t* bytes);
+int difusco_tsp_two_opt_grouped_screened(int n_nodes, int groups, int per_group, const double* points, int32_t* tours,
+                                         int64_t max_iterations, void* workspace, size_t workspace_bytes,
+                                         int64_t* iterations_out, int64_t* exact_pairs_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
