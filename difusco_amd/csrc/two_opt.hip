@@ -14,6 +14,8 @@
 // Invalid entries (j < i + 2) are zeros in the reference's matrix, so the minimum is never positive and the argmin of
 // an all-non-improving matrix is flat index 0 = a no-op reversal: the running best starts at (0.0, 0).
 // The host only polls a `done` flag every few iterations; once set, the remaining launches return immediately.
+// Three shapes of a call share the per-block code (best_tile, screen_tile, screened_best_tile, tour_argmin, apply_move): one
+// batch (difusco_tsp_two_opt), groups of one n (_grouped) and groups of different n (_ragged, at the end of the namespace).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -41,6 +43,19 @@ struct TwoOptState {       // device-resident loop state
   long long iterations;
 };
 
+// entry k of one tour's tp / dlen (pointers at the tour's own arrays, `points` at its group's coordinates)
+__device__ __forceinline__ void prep_entry(const double* __restrict__ points, const int* __restrict__ tour, int n, int k,
+                                           double2* __restrict__ tp, double* __restrict__ dlen) {
+  const int c = tour[k];
+  const double2 p = make_double2(points[2 * c], points[2 * c + 1]);
+  tp[k] = p;
+  if (k < n) {
+    const int c1 = tour[k + 1];
+    const double dx = p.x - points[2 * c1], dy = p.y - points[2 * c1 + 1];
+    dlen[k] = dist2d(dx, dy);                                   // A_i,i+1 (tsp_utils.py:28)
+  }
+}
+
 // GROUPED (difusco_tsp_two_opt_grouped): tour b belongs to group b / per_group, which has points of its own
 // (points + group * 2 n) and a done flag of its own (gdone[group]); otherwise one state for the whole batch.
 template <bool GROUPED>
@@ -55,32 +70,27 @@ __global__ void two_opt_prep_kernel(const double* __restrict__ points, const int
     if (st->done) return;
   }
   if (k > n) return;
-  const int* tour = tours + (long long)b * (n + 1);
-  const int c = tour[k];
-  const double2 p = make_double2(points[2 * c], points[2 * c + 1]);
-  tp[(long long)b * (n + 1) + k] = p;
-  if (k < n) {
-    const int c1 = tour[k + 1];
-    const double dx = p.x - points[2 * c1], dy = p.y - points[2 * c1 + 1];
-    dlen[(long long)b * n + k] = dist2d(dx, dy);                // A_i,i+1 (tsp_utils.py:28)
-  }
+  prep_entry(points, tours + (long long)b * (n + 1), n, k, tp + (long long)b * (n + 1), dlen + (long long)b * n);
 }
 
 constexpr int TI = 16;     // rows per block
 constexpr int JPT = 4;     // columns per thread per sweep (256 threads x 4 = 1024 columns per sweep)
 
-template <bool GROUPED>
-__global__ __launch_bounds__(256) void two_opt_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                           int n, Best* __restrict__ partial, const TwoOptState* st,
-                                                           const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.y, i0 = blockIdx.x * TI;
-  if constexpr (GROUPED) {
-    if (gdone[b / per_group]) return;
-  } else {
-    if (st->done) return;
+// (min, first flat index) over the 256 threads of a block; the result is valid in thread 0
+__device__ __forceinline__ Best block_best(Best best) {
+  __shared__ Best red[256];
+  red[threadIdx.x] = best;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s && better(red[threadIdx.x + s].v, red[threadIdx.x + s].idx, red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
+    __syncthreads();
   }
-  const double2* P = tp + (long long)b * (n + 1);
-  const double* D = dlen + (long long)b * n;
+  return red[0];
+}
+
+// one block of the exact sweep: rows i0 .. i0 + TI - 1 of the tour (P = its tp, D = its dlen, n nodes) against all their columns;
+// returns the block's best move in thread 0.  The flat index is i * n + j with the tour's own n.
+__device__ __forceinline__ Best best_tile(const double2* __restrict__ P, const double* __restrict__ D, int n, int i0) {
   __shared__ double2 pi[TI + 1];
   __shared__ double di[TI];
   for (int t = threadIdx.x; t <= TI; t += blockDim.x)
@@ -123,37 +133,54 @@ __global__ __launch_bounds__(256) void two_opt_best_kernel(const double2* __rest
       }
     }
   }
-  // block reduction (min value, then lowest flat index)
-  __shared__ Best red[256];
-  red[threadIdx.x] = best;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s && better(red[threadIdx.x + s].v, red[threadIdx.x + s].idx, red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
-    __syncthreads();
+  return block_best(best);                                      // min value, then lowest flat index
+}
+
+template <bool GROUPED>
+__global__ __launch_bounds__(256) void two_opt_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
+                                                           int n, Best* __restrict__ partial, const TwoOptState* st,
+                                                           const int* __restrict__ gdone, int per_group) {
+  const int b = blockIdx.y, i0 = blockIdx.x * TI;
+  if constexpr (GROUPED) {
+    if (gdone[b / per_group]) return;
+  } else {
+    if (st->done) return;
   }
-  if (threadIdx.x == 0) partial[(long long)b * gridDim.x + blockIdx.x] = red[0];
+  const Best r = best_tile(tp + (long long)b * (n + 1), dlen + (long long)b * n, n, i0);
+  if (threadIdx.x == 0) partial[(long long)b * gridDim.x + blockIdx.x] = r;
+}
+
+// the apply kernels' steps on one tour: argmin over its partials (valid in thread 0) ...
+__device__ __forceinline__ Best tour_argmin(const Best* __restrict__ part, int nblk) {
+  Best best{0.0, 0};
+  for (int t = threadIdx.x; t < nblk; t += blockDim.x) {
+    const Best c = part[t];
+    if (better(c.v, c.idx, best)) best = c;
+  }
+  return block_best(best);
+}
+
+// ... and its best move: tour[mi+1 .. mj] reversed (tsp_utils.py:41), idx = mi * n + mj
+__device__ __forceinline__ void apply_move(int* __restrict__ tour, long long idx, int n) {
+  const int mi = (int)(idx / n), mj = (int)(idx % n);
+  const int len = mj - mi;
+  for (int t = threadIdx.x; t < len / 2; t += blockDim.x) {
+    const int x = mi + 1 + t, y = mj - t;
+    const int tmp = tour[x];
+    tour[x] = tour[y];
+    tour[y] = tmp;
+  }
 }
 
 __global__ __launch_bounds__(256) void two_opt_apply_kernel(int* __restrict__ tours, int n, int batch, int nblk,
                                                             const Best* __restrict__ partial, long long max_iterations,
                                                             TwoOptState* st, Best* __restrict__ chosen) {
   if (st->done) return;
-  __shared__ Best red[256];
   __shared__ double gmin;
   // per tour: argmin over its partials
   for (int b = 0; b < batch; ++b) {
-    Best best{0.0, 0};
-    for (int t = threadIdx.x; t < nblk; t += blockDim.x) {
-      const Best c = partial[(long long)b * nblk + t];
-      if (better(c.v, c.idx, best)) best = c;
-    }
-    red[threadIdx.x] = best;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s && better(red[threadIdx.x + s].v, red[threadIdx.x + s].idx, red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) chosen[b] = red[0];
+    const Best r = tour_argmin(partial + (long long)b * nblk, nblk);
+    if (threadIdx.x == 0) chosen[b] = r;
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -166,18 +193,7 @@ __global__ __launch_bounds__(256) void two_opt_apply_kernel(int* __restrict__ to
     if (threadIdx.x == 0) st->done = 1;
     return;
   }
-  for (int b = 0; b < batch; ++b) {
-    const long long idx = chosen[b].idx;
-    const int mi = (int)(idx / n), mj = (int)(idx % n);
-    int* tour = tours + (long long)b * (n + 1);
-    const int len = mj - mi;                              // tour[mi+1 .. mj] reversed (tsp_utils.py:41)
-    for (int t = threadIdx.x; t < len / 2; t += blockDim.x) {
-      const int x = mi + 1 + t, y = mj - t;
-      const int tmp = tour[x];
-      tour[x] = tour[y];
-      tour[y] = tmp;
-    }
-  }
+  for (int b = 0; b < batch; ++b) apply_move(tours + (long long)b * (n + 1), chosen[b].idx, n);
   if (threadIdx.x == 0) {
     st->iterations += 1;
     if (st->iterations >= max_iterations) st->done = 1;   // tsp_utils.py:46-47
@@ -193,22 +209,11 @@ __global__ __launch_bounds__(256) void two_opt_apply_grouped_kernel(int* __restr
                                                                     long long* __restrict__ giters, Best* __restrict__ chosen) {
   const int g = blockIdx.x;
   if (gdone[g]) return;
-  __shared__ Best red[256];
   __shared__ double gmin;
   const int b0 = g * per_group;
   for (int b = b0; b < b0 + per_group; ++b) {
-    Best best{0.0, 0};
-    for (int t = threadIdx.x; t < nblk; t += blockDim.x) {
-      const Best c = partial[(long long)b * nblk + t];
-      if (better(c.v, c.idx, best)) best = c;
-    }
-    red[threadIdx.x] = best;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (threadIdx.x < s && better(red[threadIdx.x + s].v, red[threadIdx.x + s].idx, red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) chosen[b] = red[0];
+    const Best r = tour_argmin(partial + (long long)b * nblk, nblk);
+    if (threadIdx.x == 0) chosen[b] = r;
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -224,18 +229,7 @@ __global__ __launch_bounds__(256) void two_opt_apply_grouped_kernel(int* __restr
     }
     return;
   }
-  for (int b = b0; b < b0 + per_group; ++b) {
-    const long long idx = chosen[b].idx;
-    const int mi = (int)(idx / n), mj = (int)(idx % n);
-    int* tour = tours + (long long)b * (n + 1);
-    const int len = mj - mi;
-    for (int t = threadIdx.x; t < len / 2; t += blockDim.x) {
-      const int x = mi + 1 + t, y = mj - t;
-      const int tmp = tour[x];
-      tour[x] = tour[y];
-      tour[y] = tmp;
-    }
-  }
+  for (int b = b0; b < b0 + per_group; ++b) apply_move(tours + (long long)b * (n + 1), chosen[b].idx, n);
   if (threadIdx.x == 0) {
     giters[g] += 1;
     if (giters[g] >= max_iterations) {
@@ -312,6 +306,8 @@ GroupedLayout grouped_layout(int n, int groups, int per_group) {
 //  slack (96 - 62.5) u M > 2^-52 covers both.  Overflow: the largest intermediate is s' <= 8 M^2 (1 + u)^4 < 2^124 for
 //  M <= 2^60.  Outside 2^-32 <= M <= 2^60, or with a non-finite coordinate (M = inf / NaN), no bound is claimed:
 //  difusco_tsp_two_opt_screen_bound says so and the call runs the exact sweep.
+//  Nothing above depends on n: the bound is per pair, from M alone, so in a ragged call (difusco_tsp_two_opt_ragged) it holds
+//  for every tour with the M of its own group, whatever the sizes of the other groups.
 constexpr double kScreenEpsPerM = 0x1.8p-18;       // 96 * 2^-24
 constexpr double kScreenMinM = 0x1p-32, kScreenMaxM = 0x1p60;
 constexpr int SCH = 256 * JPT;                     // columns per chunk of the screen
@@ -348,6 +344,23 @@ __global__ void two_opt_maxabs_kernel(const double* __restrict__ points, int n2,
   if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + g, m);
 }
 
+// prep_entry plus the float32 copies of the screen (pointers at the tour's own arrays)
+__device__ __forceinline__ void prep_screen_entry(const double* __restrict__ points, const int* __restrict__ tour, int n, int k,
+                                                  double2* __restrict__ tp, double* __restrict__ dlen, float4* __restrict__ q,
+                                                  float* __restrict__ d32) {
+  const int c = tour[k];
+  const double2 p = make_double2(points[2 * c], points[2 * c + 1]);
+  tp[k] = p;
+  if (k < n) {
+    const int c1 = tour[k + 1];
+    const double2 p1 = make_double2(points[2 * c1], points[2 * c1 + 1]);
+    const double d = dist2d(p.x - p1.x, p.y - p1.y);           // as prep_entry
+    dlen[k] = d;
+    q[k] = make_float4((float)p.x, (float)p.y, (float)p1.x, (float)p1.y);
+    d32[k] = (float)d;
+  }
+}
+
 __global__ void two_opt_prep_screen_kernel(const double* __restrict__ points, const int* __restrict__ tours, int n,
                                            double2* __restrict__ tp, double* __restrict__ dlen, float4* __restrict__ q,
                                            float* __restrict__ d32, unsigned* __restrict__ tmin,
@@ -356,19 +369,9 @@ __global__ void two_opt_prep_screen_kernel(const double* __restrict__ points, co
   if (gdone[b / per_group]) return;
   points += (long long)(b / per_group) * 2 * n;
   if (k > n) return;
-  const int* tour = tours + (long long)b * (n + 1);
-  const int c = tour[k];
-  const double2 p = make_double2(points[2 * c], points[2 * c + 1]);
-  tp[(long long)b * (n + 1) + k] = p;
   if (k == 0) tmin[b] = f32_key(0.0f);                         // m32 starts at the value of the no-op move
-  if (k < n) {
-    const int c1 = tour[k + 1];
-    const double2 p1 = make_double2(points[2 * c1], points[2 * c1 + 1]);
-    const double d = dist2d(p.x - p1.x, p.y - p1.y);           // as two_opt_prep_kernel
-    dlen[(long long)b * n + k] = d;
-    q[(long long)b * n + k] = make_float4((float)p.x, (float)p.y, (float)p1.x, (float)p1.y);
-    d32[(long long)b * n + k] = (float)d;
-  }
+  const long long row = (long long)b * n;
+  prep_screen_entry(points, tours + (long long)b * (n + 1), n, k, tp + (long long)b * (n + 1), dlen + row, q + row, d32 + row);
 }
 
 // the columns of a chunk: thread t holds columns jbase + u * 256 + t; a column past the tour gets d_j = -inf, which makes its
@@ -384,14 +387,9 @@ __device__ __forceinline__ void load_columns32(const float4* __restrict__ Q, con
   }
 }
 
-__global__ __launch_bounds__(256) void two_opt_screen_kernel(const float4* __restrict__ q, const float* __restrict__ d32, int n,
-                                                             float* __restrict__ bmin, unsigned* __restrict__ tmin,
-                                                             const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.z, i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
-  if (jbase + SCH <= i0 + 2) return;                           // the chunk lies left of the triangle
-  if (gdone[b / per_group]) return;
-  const float4* __restrict__ Q = q + (long long)b * n;
-  const float* __restrict__ D = d32 + (long long)b * n;
+// one block of the screen: min c32 over rows i0 .. i0 + TI - 1 and the chunk's columns of the tour (Q = its q, D = its d32,
+// n nodes); the result is valid in thread 0.  Q and D must be block-uniform: the row data then arrive by scalar loads.
+__device__ __forceinline__ float screen_tile(const float4* __restrict__ Q, const float* __restrict__ D, int n, int i0, int jbase) {
   float4 c[JPT];
   float dj[JPT];
   int jj[JPT];
@@ -422,29 +420,36 @@ __global__ __launch_bounds__(256) void two_opt_screen_kernel(const float4* __res
   __shared__ float wm[4];
   if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    m = fminf(fminf(wm[0], wm[1]), fminf(wm[2], wm[3]));
-    bmin[((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y] = m;
-    // the minimum is order-independent, so m32 is deterministic; the relaxed device-scope read only saves atomics
-    const unsigned key = f32_key(m);
-    if (key < __hip_atomic_load(tmin + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(tmin + b, key);
-  }
+  return fminf(fminf(wm[0], wm[1]), fminf(wm[2], wm[3]));
 }
 
-__global__ __launch_bounds__(256) void two_opt_screened_best_kernel(
-    const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q, const float* __restrict__ d32,
-    int n, int nchunk, const float* __restrict__ bmin, const unsigned* __restrict__ tmin, const double* __restrict__ gmax,
-    Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs, const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.y, i0 = blockIdx.x * TI, g = b / per_group;
-  if (gdone[g]) return;
-  const double eps = screen_eps(gmax[g]);
-  const double upper = fmin(0.0, (double)f32_unkey(tmin[b]) + eps);       // U >= V*
+// thread 0 of a screen block: its minimum into bmin and into the tour's m32
+__device__ __forceinline__ void screen_publish(float m, float* __restrict__ bmin_slot, unsigned* __restrict__ tmin_slot) {
+  *bmin_slot = m;
+  // the minimum is order-independent, so m32 is deterministic; the relaxed device-scope read only saves atomics
+  const unsigned key = f32_key(m);
+  if (key < __hip_atomic_load(tmin_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(tmin_slot, key);
+}
+
+__global__ __launch_bounds__(256) void two_opt_screen_kernel(const float4* __restrict__ q, const float* __restrict__ d32, int n,
+                                                             float* __restrict__ bmin, unsigned* __restrict__ tmin,
+                                                             const int* __restrict__ gdone, int per_group) {
+  const int b = blockIdx.z, i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
+  if (jbase + SCH <= i0 + 2) return;                           // the chunk lies left of the triangle
+  if (gdone[b / per_group]) return;
+  const float m = screen_tile(q + (long long)b * n, d32 + (long long)b * n, n, i0, jbase);
+  if (threadIdx.x == 0) screen_publish(m, bmin + ((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y, tmin + b);
+}
+
+// one block of the screened best move: rows i0 .. i0 + TI - 1 of the tour (P, D64: tp, dlen; Q, D: q, d32; n nodes, nchunk
+// chunks, bm = the bmin row of this tile); m32 = the tour's screen minimum, eps from its group's M.  The block's best move is
+// written to *partial_slot and its float64 evaluations are added to *exact_pairs.
+__device__ __forceinline__ void screened_best_tile(const double2* __restrict__ P, const double* __restrict__ D64,
+                                                   const float4* __restrict__ Q, const float* __restrict__ D, int n, int nchunk,
+                                                   int i0, const float* __restrict__ bm, float m32, double eps,
+                                                   Best* __restrict__ partial_slot, unsigned long long* __restrict__ exact_pairs) {
+  const double upper = fmin(0.0, (double)m32 + eps);                       // U >= V*
   const float thr = __double2float_ru(upper + eps);
-  const double2* P = tp + (long long)b * (n + 1);
-  const double* D64 = dlen + (long long)b * n;
-  const float4* __restrict__ Q = q + (long long)b * n;
-  const float* __restrict__ D = d32 + (long long)b * n;
-  const float* bm = bmin + ((long long)b * gridDim.x + blockIdx.x) * nchunk;
   Best best{0.0, 0};
   unsigned cnt = 0;
   for (int chunk = (i0 + 2) / SCH; chunk < nchunk; ++chunk) {
@@ -486,9 +491,21 @@ __global__ __launch_bounds__(256) void two_opt_screened_best_kernel(
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    partial[(long long)b * gridDim.x + blockIdx.x] = red[0];
+    *partial_slot = red[0];
     if (cred[0]) atomicAdd(exact_pairs, (unsigned long long)cred[0]);
   }
+}
+
+__global__ __launch_bounds__(256) void two_opt_screened_best_kernel(
+    const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q, const float* __restrict__ d32,
+    int n, int nchunk, const float* __restrict__ bmin, const unsigned* __restrict__ tmin, const double* __restrict__ gmax,
+    Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs, const int* __restrict__ gdone, int per_group) {
+  const int b = blockIdx.y, i0 = blockIdx.x * TI, g = b / per_group;
+  if (gdone[g]) return;
+  const long long row = (long long)b * n;
+  screened_best_tile(tp + (long long)b * (n + 1), dlen + row, q + row, d32 + row, n, nchunk, i0,
+                     bmin + ((long long)b * gridDim.x + blockIdx.x) * nchunk, f32_unkey(tmin[b]), screen_eps(gmax[g]),
+                     partial + (long long)b * gridDim.x + blockIdx.x, exact_pairs);
 }
 
 struct ScreenedLayout {    // the exact entries' layout first (the exact sweep runs on the same workspace), then the screen's arrays
@@ -595,6 +612,218 @@ int two_opt_screened_run(int n, int groups, int per_group, const double* points,
   if (er == hipSuccess) er = hipStreamSynchronize(s);
   if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt_screened iterations: %s", hipGetErrorString(er));
   if (exact_pairs_out) *exact_pairs_out = (int64_t)pairs;
+  return DIFUSCO_OK;
+}
+
+// ---- ragged 2-opt (difusco_tsp_two_opt_ragged): groups of different n in one launch sequence ---------------------------------
+//
+// The same move as the grouped entries (prep, best or screen + screened best, apply with one block per group), with every
+// kernel reading its tour's n and array bases from a descriptor table instead of computing them from one n.  The table is built
+// on the host from group_n / group_tours and written to the workspace once per call.  A block reads desc[its tour], an index that
+// is uniform over the block, so the descriptor and every base derived from it stay in scalar registers and the row data of the
+// screen still arrive by scalar loads.
+// Grids: the call's maxima (nblk_max, [nchunk_max,] tours); a block beyond its own tour's nblk / nchunk returns at once.  With
+// equal sizes the grids are exactly those of the grouped entries.  A flat work list with a search over a prefix array would
+// launch no idle block, but every block would pay the search and equal sizes would no longer map to the grouped grid; an idle
+// block costs a descriptor load and an exit.
+struct RaggedTour {        // 64 bytes; offsets in elements of the array they index
+  int group, n, nblk, nchunk;
+  long long points;        // the group's first coordinate in `points` (doubles)
+  long long tours;         // the tour's first entry in `tours` (n + 1 per tour)
+  long long tp;            //                       in tp (n + 1 per tour)
+  long long cols;          //                       in dlen, q and d32 (n per tour each: one offset serves the three)
+  long long partial;       //                       in partial (nblk per tour)
+  long long bmin;          //                       in bmin (nblk * nchunk per tour)
+};
+
+struct RaggedGroup {       // what the apply block and the max |coordinate| reduction of a group need
+  int first, count;        // its tours: desc[first .. first + count - 1], all of n nodes and nblk partials,
+  int n, nblk;
+  long long points;
+  long long tours, partial;   // so tour p of the group starts at tours + p (n + 1) and partial + p nblk: no descriptor per tour
+};
+
+__global__ void two_opt_prep_ragged_kernel(const double* __restrict__ points, const int* __restrict__ tours,
+                                           const RaggedTour* __restrict__ desc, double2* __restrict__ tp, double* __restrict__ dlen,
+                                           const int* __restrict__ tdone) {
+  const RaggedTour d = desc[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > d.n || tdone[blockIdx.y]) return;
+  prep_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols);
+}
+
+__global__ __launch_bounds__(256) void two_opt_best_ragged_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
+                                                                  const RaggedTour* __restrict__ desc, Best* __restrict__ partial,
+                                                                  const int* __restrict__ tdone) {
+  const RaggedTour d = desc[blockIdx.y];
+  if ((int)blockIdx.x >= d.nblk || tdone[blockIdx.y]) return;
+  const Best r = best_tile(tp + d.tp, dlen + d.cols, d.n, blockIdx.x * TI);
+  if (threadIdx.x == 0) partial[d.partial + blockIdx.x] = r;
+}
+
+__global__ void two_opt_maxabs_ragged_kernel(const double* __restrict__ points, const RaggedGroup* __restrict__ grp,
+                                             unsigned long long* __restrict__ gmax) {
+  const RaggedGroup G = grp[blockIdx.y];
+  const double* pts = points + G.points;
+  unsigned long long m = 0;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 2 * G.n; k += gridDim.x * blockDim.x) {
+    const unsigned long long v = (unsigned long long)__double_as_longlong(fabs(pts[k]));
+    m = v > m ? v : m;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(m, off);
+    m = o > m ? o : m;
+  }
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + blockIdx.y, m);
+}
+
+__global__ void two_opt_prep_screen_ragged_kernel(const double* __restrict__ points, const int* __restrict__ tours,
+                                                  const RaggedTour* __restrict__ desc, double2* __restrict__ tp,
+                                                  double* __restrict__ dlen, float4* __restrict__ q, float* __restrict__ d32,
+                                                  unsigned* __restrict__ tmin, const int* __restrict__ tdone) {
+  const RaggedTour d = desc[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > d.n || tdone[blockIdx.y]) return;
+  if (k == 0) tmin[blockIdx.y] = f32_key(0.0f);
+  prep_screen_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols, q + d.cols, d32 + d.cols);
+}
+
+__global__ __launch_bounds__(256) void two_opt_screen_ragged_kernel(const float4* __restrict__ q, const float* __restrict__ d32,
+                                                                    const RaggedTour* __restrict__ desc, float* __restrict__ bmin,
+                                                                    unsigned* __restrict__ tmin, const int* __restrict__ tdone) {
+  const RaggedTour d = desc[blockIdx.z];
+  const int i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
+  if ((int)blockIdx.x >= d.nblk || (int)blockIdx.y >= d.nchunk) return;   // beyond the tour's own tiles
+  if (jbase + SCH <= i0 + 2) return;                                       // the chunk lies left of the triangle
+  if (tdone[blockIdx.z]) return;
+  const float m = screen_tile(q + d.cols, d32 + d.cols, d.n, i0, jbase);
+  if (threadIdx.x == 0) screen_publish(m, bmin + d.bmin + (long long)blockIdx.x * d.nchunk + blockIdx.y, tmin + blockIdx.z);
+}
+
+__global__ __launch_bounds__(256) void two_opt_screened_best_ragged_kernel(
+    const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q, const float* __restrict__ d32,
+    const RaggedTour* __restrict__ desc, const float* __restrict__ bmin, const unsigned* __restrict__ tmin,
+    const double* __restrict__ gmax, Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs,
+    const int* __restrict__ tdone) {
+  const RaggedTour d = desc[blockIdx.y];
+  if ((int)blockIdx.x >= d.nblk || tdone[blockIdx.y]) return;
+  screened_best_tile(tp + d.tp, dlen + d.cols, q + d.cols, d32 + d.cols, d.n, d.nchunk, blockIdx.x * TI,
+                     bmin + d.bmin + (long long)blockIdx.x * d.nchunk, f32_unkey(tmin[blockIdx.y]), screen_eps(gmax[d.group]),
+                     partial + d.partial + blockIdx.x, exact_pairs);
+}
+
+// two_opt_apply_grouped_kernel with the group's tours and their n from the tables.  A group that stops also sets tdone of its
+// tours: the other kernels read their tour's flag by the block's own index, alongside the descriptor and not after it.
+__global__ __launch_bounds__(256) void two_opt_apply_ragged_kernel(int* __restrict__ tours,
+                                                                   const RaggedGroup* __restrict__ grp,
+                                                                   const Best* __restrict__ partial, long long max_iterations,
+                                                                   TwoOptState* st, int* __restrict__ gdone,
+                                                                   int* __restrict__ tdone, long long* __restrict__ giters,
+                                                                   Best* __restrict__ chosen) {
+  const int g = blockIdx.x;
+  if (gdone[g]) return;
+  __shared__ double gmin;
+  const RaggedGroup G = grp[g];
+  auto stop = [&]() {                                          // thread 0
+    gdone[g] = 1;
+    for (int b = G.first; b < G.first + G.count; ++b) tdone[b] = 1;
+    atomicAdd(&st->done, 1);
+  };
+  for (int p = 0; p < G.count; ++p) {
+    const Best r = tour_argmin(partial + G.partial + (long long)p * G.nblk, G.nblk);
+    if (threadIdx.x == 0) chosen[G.first + p] = r;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double m = chosen[G.first].v;
+    for (int b = G.first + 1; b < G.first + G.count; ++b) m = chosen[b].v < m ? chosen[b].v : m;
+    gmin = m;
+  }
+  __syncthreads();
+  if (!(gmin < -1e-6)) {
+    if (threadIdx.x == 0) stop();
+    return;
+  }
+  for (int p = 0; p < G.count; ++p) apply_move(tours + G.tours + (long long)p * (G.n + 1), chosen[G.first + p].idx, G.n);
+  if (threadIdx.x == 0) {
+    giters[g] += 1;
+    if (giters[g] >= max_iterations) stop();
+  }
+}
+
+struct RaggedLayout {      // byte offsets; the screen's arrays (q ..) only with method 1
+  size_t desc, grp, tp, dlen, partial, chosen, gdone, tdone, giters, st, q, d32, bmin, tmin, gmax, counter, total;
+  int tours, nmax, nblk_max, nchunk_max;
+};
+
+constexpr int kRaggedMaxTours = 65535;             // a grid dimension
+constexpr int kRaggedMaxNodes = 65535 * TI;
+
+// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
+int ragged_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, int method, RaggedLayout* L,
+                  std::vector<RaggedTour>* tab, std::vector<RaggedGroup>* gtab) {
+  if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
+  if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
+  if (method != 0 && method != 1) return set_error(DIFUSCO_EINVAL, "%s: method %d (0 exact, 1 screened)", who, method);
+  long long T = 0;
+  for (int g = 0; g < groups; ++g) {
+    if (group_n[g] < 4) return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, needs n >= 4", who, g, group_n[g]);
+    if (group_n[g] > kRaggedMaxNodes)
+      return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, at most %d nodes", who, g, group_n[g], kRaggedMaxNodes);
+    if (group_tours[g] < 1) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d tours, needs at least 1", who, g, group_tours[g]);
+    T += group_tours[g];
+    if (T > kRaggedMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kRaggedMaxTours);
+  }
+  if (tab) tab->clear();
+  if (gtab) gtab->clear();
+  size_t points = 0, closed = 0, cols = 0, nblks = 0, tiles = 0;
+  L->nmax = L->nblk_max = L->nchunk_max = 0;
+  for (int g = 0; g < groups; ++g) {
+    const int n = group_n[g], nblk = (n + TI - 1) / TI, nchunk = (n + SCH - 1) / SCH;
+    L->nmax = n > L->nmax ? n : L->nmax;
+    L->nblk_max = nblk > L->nblk_max ? nblk : L->nblk_max;
+    L->nchunk_max = nchunk > L->nchunk_max ? nchunk : L->nchunk_max;
+    if (gtab)
+      gtab->push_back(RaggedGroup{(int)(tab ? tab->size() : 0), group_tours[g], n, nblk, (long long)points, (long long)closed,
+                                  (long long)nblks});
+    for (int p = 0; p < group_tours[g]; ++p) {
+      if (tab)
+        tab->push_back(RaggedTour{g, n, nblk, nchunk, (long long)points, (long long)closed, (long long)closed, (long long)cols,
+                                  (long long)nblks, (long long)tiles});
+      closed += (size_t)n + 1;
+      cols += (size_t)n;
+      nblks += (size_t)nblk;
+      tiles += (size_t)nblk * nchunk;
+    }
+    points += 2 * (size_t)n;
+  }
+  L->tours = (int)T;
+  size_t off = 0;
+  auto take = [&off](size_t bytes) {
+    const size_t at = off;
+    off += up256(bytes);
+    return at;
+  };
+  L->desc = take(sizeof(RaggedTour) * T);
+  L->grp = take(sizeof(RaggedGroup) * groups);
+  L->tp = take(sizeof(double2) * closed);
+  L->dlen = take(sizeof(double) * cols);
+  L->partial = take(sizeof(Best) * nblks);
+  L->chosen = take(sizeof(Best) * T);
+  L->gdone = take(sizeof(int) * groups);                       // gdone .. st are cleared by one memset
+  L->tdone = take(sizeof(int) * T);
+  L->giters = take(sizeof(long long) * groups);
+  L->st = take(sizeof(TwoOptState));
+  L->q = L->d32 = L->bmin = L->tmin = L->gmax = L->counter = off;
+  if (method == 1) {
+    L->q = take(sizeof(float4) * cols);
+    L->d32 = take(sizeof(float) * cols);
+    L->bmin = take(sizeof(float) * tiles);
+    L->tmin = take(sizeof(unsigned) * T);
+    L->gmax = take(sizeof(double) * groups);
+    L->counter = take(sizeof(unsigned long long));
+  }
+  L->total = off;
   return DIFUSCO_OK;
 }
 
@@ -765,6 +994,107 @@ int difusco_tsp_two_opt_screened(int n_nodes, int batch, const double* points, i
                                       exact_pairs_out, stream);
   if (rc == DIFUSCO_OK && iterations_out) *iterations_out = iterations;
   return rc;
+}
+
+int difusco_tsp_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int method,
+                                               size_t* bytes) {
+  using namespace difusco;
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "two_opt_ragged_workspace_bytes: bytes is null");
+  RaggedLayout lay;
+  const int rc = ragged_layout("two_opt_ragged_workspace_bytes", groups, group_n, group_tours, method, &lay, nullptr, nullptr);
+  if (rc == DIFUSCO_OK) *bytes = lay.total;
+  return rc;
+}
+
+int difusco_tsp_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                               int32_t* tours, int64_t max_iterations, int method, void* workspace, size_t workspace_bytes,
+                               int64_t* iterations_out, int64_t* exact_pairs_out, void* stream) {
+  using namespace difusco;
+  RaggedLayout lay;
+  std::vector<RaggedTour> tab;
+  std::vector<RaggedGroup> gtab;
+  const int rc = ragged_layout("tsp_two_opt_ragged", groups, group_n, group_tours, method, &lay, &tab, &gtab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!points || !tours || !workspace || !iterations_out || max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "tsp_two_opt_ragged: needs non-null device arrays, a host iterations_out[groups] and "
+                                     "max_iterations >= 0");
+  if (workspace_bytes < lay.total)
+    return set_error(DIFUSCO_EINVAL, "tsp_two_opt_ragged: workspace %zu < %zu bytes", workspace_bytes, lay.total);
+  char* w = (char*)workspace;
+  RaggedTour* desc = (RaggedTour*)(w + lay.desc);
+  RaggedGroup* grp = (RaggedGroup*)(w + lay.grp);
+  double2* tp = (double2*)(w + lay.tp);
+  double* dlen = (double*)(w + lay.dlen);
+  Best* partial = (Best*)(w + lay.partial);
+  Best* chosen = (Best*)(w + lay.chosen);
+  int* gdone = (int*)(w + lay.gdone);
+  int* tdone = (int*)(w + lay.tdone);
+  long long* giters = (long long*)(w + lay.giters);
+  TwoOptState* st = (TwoOptState*)(w + lay.st);
+  float4* q = (float4*)(w + lay.q);
+  float* d32 = (float*)(w + lay.d32);
+  float* bmin = (float*)(w + lay.bmin);
+  unsigned* tmin = (unsigned*)(w + lay.tmin);
+  unsigned long long* gmax = (unsigned long long*)(w + lay.gmax);
+  unsigned long long* counter = (unsigned long long*)(w + lay.counter);
+  hipStream_t s = (hipStream_t)stream;
+  const int T = lay.tours;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(RaggedTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(RaggedGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(gdone, 0, (char*)st + sizeof(TwoOptState) - (char*)gdone, s);
+  if (er == hipSuccess && method == 1) er = hipMemsetAsync(gmax, 0, lay.total - lay.gmax, s);
+  bool screened = method == 1;
+  if (er == hipSuccess && screened) {                          // M per group decides, once per call, whether the screen has a bound
+    const int mblocks = (2 * lay.nmax + 255) / 256 < 64 ? (2 * lay.nmax + 255) / 256 : 64;
+    hipLaunchKernelGGL(two_opt_maxabs_ragged_kernel, dim3(mblocks, groups), dim3(256), 0, s, points, grp, gmax);
+    std::vector<double> maxabs(groups);
+    er = hipMemcpyAsync(maxabs.data(), gmax, sizeof(double) * groups, hipMemcpyDeviceToHost, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);
+    for (int g = 0; er == hipSuccess && g < groups; ++g) {
+      double eps = 0.0;
+      screened = screened && difusco_tsp_two_opt_screen_bound(maxabs[g], &eps) == 1;   // one group without a bound: exact sweep
+    }
+  } else if (er == hipSuccess) {
+    er = hipStreamSynchronize(s);
+  }
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_two_opt_ragged setup: %s", hipGetErrorString(er));
+  TwoOptState host{0, 0, 0};
+  const int poll = 8;
+  const long long loops = max_iterations > 0 ? max_iterations : 1;   // as difusco_tsp_two_opt
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
+  for (long long it = 0; it < loops; ++it) {
+    if (screened) {
+      hipLaunchKernelGGL(two_opt_prep_screen_ragged_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, q, d32, tmin,
+                         tdone);
+      hipLaunchKernelGGL(two_opt_screen_ragged_kernel, dim3(lay.nblk_max, lay.nchunk_max, T), dim3(256), 0, s, q, d32, desc, bmin,
+                         tmin, tdone);
+      hipLaunchKernelGGL(two_opt_screened_best_ragged_kernel, best_grid, dim3(256), 0, s, tp, dlen, q, d32, desc, bmin, tmin,
+                         (const double*)gmax, partial, counter, tdone);
+    } else {
+      hipLaunchKernelGGL(two_opt_prep_ragged_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, tdone);
+      hipLaunchKernelGGL(two_opt_best_ragged_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, partial, tdone);
+    }
+    hipLaunchKernelGGL(two_opt_apply_ragged_kernel, dim3(groups), dim3(256), 0, s, tours, grp, partial,
+                       (long long)max_iterations, st, gdone, tdone, giters, chosen);
+    if ((it + 1) % poll == 0 || it + 1 == loops) {
+      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  unsigned long long pairs = 0;
+  er = hipMemcpyAsync(iterations_out, giters, sizeof(long long) * groups, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess && screened) er = hipMemcpyAsync(&pairs, counter, sizeof(pairs), hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_two_opt_ragged iterations: %s", hipGetErrorString(er));
+  if (!screened)                                               // every pair of every sweep that did work, in float64
+    for (int g = 0; g < groups; ++g)
+      pairs += (unsigned long long)(evaluations(iterations_out[g], max_iterations) * group_tours[g] *
+                                    ((long long)(group_n[g] - 1) * (group_n[g] - 2) / 2));
+  if (exact_pairs_out) *exact_pairs_out = (int64_t)pairs;
+  return DIFUSCO_OK;
 }
 
 }  // extern "C"

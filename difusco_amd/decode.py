@@ -155,6 +155,50 @@ def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0",
     return t.cpu().numpy().astype(np.int64), its
 
 
+def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
+    """``batched_two_opt_torch`` of G instances of ANY sizes at once: ``points_list[g]`` float64 [n_g, 2], ``tours_list[g]`` int
+    [P_g, n_g + 1] closed tours over them.  Every instance gets exactly what ``batched_two_opt_torch(points_list[g],
+    tours_list[g])`` returns (its own stop test, iteration count and tie rule); runs ``difusco_tsp_two_opt_ragged``, GPU only.
+    Returns ``(list of int64 numpy [P_g, n_g + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
+    ``batched_two_opt_torch``; with ``method="exact"`` ``exact_pairs`` counts every pair of every sweep."""
+    method = check_two_opt_method(method)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError("batched_two_opt_ragged runs on the GPU only (no CPU fallback)")
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    G = len(pts)
+    if G < 1 or len(trs) != G:
+        raise ValueError(f"{len(trs)} tour arrays for {G} instances (at least one instance)")
+    for g, (p, t) in enumerate(zip(pts, trs)):
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"points_list[{g}] must be [n, 2]")
+        if t.ndim != 2 or t.shape[1] != p.shape[0] + 1 or t.shape[0] < 1:
+            raise ValueError(f"tours_list[{g}] must be [P, {p.shape[0] + 1}] closed tours over the {p.shape[0]} points, P >= 1")
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    code = TWO_OPT_METHODS.index(method)
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_two_opt_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data, code,
+                                                            ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    its = np.zeros(G, dtype=np.int64)
+    pairs = ctypes.c_int64()
+    _lib.check(L.difusco_tsp_two_opt_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
+                                            ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), code,
+                                            ctypes.c_void_p(ws.data_ptr()), nbytes.value, its.ctypes.data_as(ctypes.c_void_p),
+                                            ctypes.byref(pairs),
+                                            ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats["exact_pairs"] = int(pairs.value)
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
+
+
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).

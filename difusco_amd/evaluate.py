@@ -21,7 +21,8 @@ every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are c
 depend on the world size, the rank an instance lands on, or what the model ran before.
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
-``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--device``,
+``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--mixed_size_chunks``
+(TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
 ``--dist_backend``, ``--records PATH`` (JSONL, one line per instance), ``--heatmap_dir`` (where ``--save_numpy_heatmap``
 writes ``numpy_heatmap/{split}-heatmap-{idx}.npy``; default ``<storage_path>/models``), ``--unsafe_checkpoint_load`` (allow a
 checkpoint that needs full unpickling - trusted files only).
@@ -91,6 +92,8 @@ EXTENSION_ARGS = [
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
     ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
+    ("--mixed_size_chunks", dict(action="store_true",
+                                 help="TSP: chunks are runs of consecutive instances of any N (default: runs of equal N)")),
     ("--device", dict(type=str, default=None, help="GPU of this process (default: cuda:LOCAL_RANK)")),
     ("--dist_backend", dict(type=str, default="nccl", help="process-group backend under torch.distributed.run")),
     ("--records", dict(type=str, default=None, help="write one JSON line per instance to this file")),
@@ -194,6 +197,27 @@ def split_chunks(task: str, examples, sparse_factor: int = -1, parallel_sampling
                        lambda e: instances_per_call or default_instances_per_call(mis_rows(e, parallel_sampling)), equal_size=False)
 
 
+def mixed_size_chunks(sizes: Sequence[int], sparse_factor: int = -1, parallel_sampling: int = 1,
+                      instances_per_call: Optional[int] = None) -> List[Tuple[int, int]]:
+    """``--mixed_size_chunks``: greedy runs [lo, hi) of consecutive TSP instances of any N.  A run closes when the output rows
+    of its instances (``tsp_rows``) would exceed ROWS_PER_CALL - an instance above the budget forms a run of its own - and at
+    ``instances_per_call`` instances (default MAX_INSTANCES_PER_CALL).  Like ``plan_chunks`` a function of the split and the
+    arguments alone, never of the world size."""
+    if instances_per_call is not None and int(instances_per_call) < 1:
+        raise ValueError("--instances_per_call must be >= 1")
+    cap = int(instances_per_call) if instances_per_call else MAX_INSTANCES_PER_CALL
+    chunks, lo, rows = [], 0, 0
+    for i, n in enumerate(sizes):
+        r = tsp_rows(n, sparse_factor, parallel_sampling)
+        if i > lo and (rows + r > ROWS_PER_CALL or i - lo >= cap):
+            chunks.append((lo, i))
+            lo, rows = i, 0
+        rows += r
+    if len(sizes) > lo:
+        chunks.append((lo, len(sizes)))
+    return chunks
+
+
 def shard_chunks(chunks: Sequence[Tuple[int, int]], rank: int, world: int) -> List[Tuple[int, int]]:
     """The whole chunks of ``rank``: a contiguous block of the chunk list (``dist.shard_range``)."""
     from .dist import shard_range
@@ -257,7 +281,9 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
         gens = [instance_generator(s) for s in seeds]
         if task == "tsp":
             heats = [] if heatmap_dir is not None else None
-            res = solve_tsp_batch(model, np.stack([examples[i].points for i in idx]), sparse_factor,
+            pts = [examples[i].points for i in idx]
+            # a chunk of one N takes the array form, a mixed chunk (--mixed_size_chunks) the list form of solve_tsp_batch
+            res = solve_tsp_batch(model, np.stack(pts) if len({p.shape[0] for p in pts}) == 1 else pts, sparse_factor,
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
                                   two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
                                   step_offset=0, heatmaps=heats, two_opt_method=two_opt_method)
@@ -317,7 +343,11 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             t_start = time.perf_counter()
             examples = read_split(args.task, os.path.join(args.storage_path, rel), limit)
             parse_s = time.perf_counter() - t_start
-            chunks = split_chunks(args.task, examples, args.sparse_factor, P, args.instances_per_call)
+            mixed = args.task == "tsp" and args.mixed_size_chunks
+            if mixed:
+                chunks = mixed_size_chunks([ex.points.shape[0] for ex in examples], args.sparse_factor, P, args.instances_per_call)
+            else:
+                chunks = split_chunks(args.task, examples, args.sparse_factor, P, args.instances_per_call)
             timings = {}
             recs = solve_split(model, args.task, examples, split, shard_chunks(chunks, rank, world), seed=args.seed,
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
@@ -343,6 +373,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                     "instances_per_call": args.instances_per_call if args.instances_per_call else "auto",
                     "chunks": len(chunks), "chunk_lengths": sorted({hi - lo for lo, hi in chunks}), "seed": args.seed,
                     "two_opt_method": args.two_opt_method, "ignored_args": ignored}
+            if mixed:
+                line["mixed_size_chunks"] = True
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

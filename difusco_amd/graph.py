@@ -177,6 +177,30 @@ def complete_graph_batch(batch: int, n: int, device) -> CsrGraph:
     return g
 
 
+def complete_graph_union(sample_sizes, device) -> CsrGraph:
+    """:func:`complete_graph_batch` for samples of different n: sample s holds all n_s * n_s ordered pairs of its own nodes
+    ``node_off_s .. node_off_s + n_s - 1``, edge (s, i, j) at slot ``off_s + i * n_s + j`` (``off_s`` = the sum of n^2 over the
+    samples before it), one GroupNorm statistic segment per sample.  Equal sizes give the arrays of ``complete_graph_batch``."""
+    ns = np.asarray(list(sample_sizes), dtype=np.int64)
+    if ns.ndim != 1 or ns.size < 1 or (ns < 1).any():
+        raise ValueError("sample_sizes: at least one sample, every n >= 1")
+    if int((ns * ns).sum()) >= 2 ** 31:
+        raise ValueError("the union has 2^31 edges or more")
+    node_off = np.concatenate([[0], np.cumsum(ns)])
+    deg = np.repeat(ns, ns)                                       # node -> its degree = the n of its sample
+    rowptr = np.concatenate([[0], np.cumsum(deg)])
+    row = np.repeat(np.arange(node_off[-1], dtype=np.int64), deg)
+    first = np.repeat(np.repeat(node_off[:-1], ns), deg)          # slot -> first node of its sample
+    col = first + (np.arange(rowptr[-1], dtype=np.int64) - rowptr[row])
+    g = CsrGraph(n_nodes=int(node_off[-1]), n_edges=int(rowptr[-1]), rowptr=torch.from_numpy(rowptr.astype(np.int32)).to(device),
+                 col=torch.from_numpy(col.astype(np.int32)).to(device), perm=None,
+                 row=torch.from_numpy(row.astype(np.int32)).to(device))
+    if ns.size > 1:
+        g.seg_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(ns * ns)]).astype(np.int32)).to(device)
+        g.n_segments = int(ns.size)
+    return g
+
+
 def edge_tiled_offsets(n_edges: int) -> torch.Tensor:
     """Flat offsets [E_pad, 256] (int64) of the tiled edge-feature layout the fused path keeps ``e`` in
     (``csrc/kernels.h: edge_tiled_offset``): rows padded to a multiple of 256 edges, tile = 32 edges,
@@ -200,27 +224,44 @@ def from_tiled(buf: torch.Tensor, n_edges: int) -> torch.Tensor:
     return buf[off[:n_edges].reshape(-1)].reshape(n_edges, 256)
 
 
-def knn_edge_index_gpu(points, k: int, device="cuda:0", graphs: int = 1) -> torch.Tensor:
+def knn_edge_index_gpu(points, k: int, device="cuda:0", graphs: int = 1, sizes=None) -> torch.Tensor:
     """``edge_index`` int64 [2, G*n*k] on ``device`` in the reference's layout (``co_datasets/tsp_graph_dataset.py:
     53-62``; batch = disjoint union with node ids offset by g*n, ``pl_meta_model.py:177-184``), built by
-    ``difusco_knn_graph``.  ``points``: float64 [G*n, 2] (numpy or tensor), G graphs of n points each."""
+    ``difusco_knn_graph``.  ``points``: float64 [G*n, 2] (numpy or tensor), G graphs of n points each.
+    ``sizes=[n_0, ...]``: graphs of different sizes instead, ``points`` their concatenation [sum n_g, 2]; graph g holds the
+    ``n_g * k`` columns after those of the graphs before it, its node ids offset by ``n_0 + ... + n_{g-1}``."""
     import ctypes
     L = _lib.lib()
     device = torch.device(device)
     if isinstance(points, np.ndarray):
         points = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64))
+    if sizes is None:
+        n = points.shape[0] // graphs
+        if n * graphs != points.shape[0]:
+            raise ValueError("points must hold `graphs` instances of equal size")
+        sizes = [n] * graphs
+    else:
+        sizes = [int(n) for n in sizes]
+        if graphs != 1:
+            raise ValueError("give either `graphs` (equal sizes) or `sizes`")
+        if len(sizes) < 1 or sum(sizes) != points.shape[0]:
+            raise ValueError(f"sizes sum to {sum(sizes)}, points holds {points.shape[0]}")
+        for g, n in enumerate(sizes):
+            if n < k:
+                raise ValueError(f"instance {g} has {n} nodes, fewer than k = {k}")
     pts = points.to(device=device, dtype=torch.float64).contiguous()
-    n = pts.shape[0] // graphs
-    if n * graphs != pts.shape[0]:
-        raise ValueError("points must hold `graphs` instances of equal size")
-    ei = torch.empty((2, graphs * n * k), dtype=torch.int64, device=device)
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_knn_graph_workspace_bytes(n, k, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ei = torch.empty((2, sum(sizes) * k), dtype=torch.int64, device=device)
+    nbytes, need = ctypes.c_size_t(), 0
+    for n in sorted(set(sizes)):                                  # one workspace, large enough for every size of the call
+        _lib.check(L.difusco_knn_graph_workspace_bytes(n, k, ctypes.byref(nbytes)))
+        need = max(need, nbytes.value)
+    ws = torch.empty(need, dtype=torch.uint8, device=device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    for g in range(graphs):
-        _lib.check(L.difusco_knn_graph(n, k, ctypes.c_void_p(pts[g * n:].data_ptr()), g * n,
-                                       ctypes.c_void_p(ei[0, g * n * k:].data_ptr()),
-                                       ctypes.c_void_p(ei[1, g * n * k:].data_ptr()),
-                                       ctypes.c_void_p(ws.data_ptr()), nbytes.value, stream))
+    node, col = 0, 0
+    for n in sizes:
+        _lib.check(L.difusco_knn_graph(n, k, ctypes.c_void_p(pts[node:].data_ptr()), node,
+                                       ctypes.c_void_p(ei[0, col:].data_ptr()),
+                                       ctypes.c_void_p(ei[1, col:].data_ptr()),
+                                       ctypes.c_void_p(ws.data_ptr()), need, stream))
+        node, col = node + n, col + n * k
     return ei

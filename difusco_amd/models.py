@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .engine import DenoiseEngine
-from .graph import CsrGraph, build_csr, build_union_csr, complete_graph_batch
+from .graph import CsrGraph, build_csr, build_union_csr, complete_graph_batch, complete_graph_union
 from .schedules import CategoricalDiffusion, GaussianDiffusion, InferenceSchedule
 
 _DEFAULTS = dict(  # difusco/train.py:19-68 (only what the inference path reads)
@@ -174,6 +174,22 @@ class COMetaModel:
         g = self._graph_cache.get(key)
         if g is None:
             g = (complete_graph_batch(batch, n, self.device), None)
+            self._graph_cache[key] = g
+        return g[0]
+
+    def _dense_union_graph(self, sample_sizes) -> CsrGraph:
+        """Dense samples of different n (``sample_batch``), cached on the tuple of sizes; equal sizes keep ``_dense_graph``'s
+        key and graph."""
+        sizes = tuple(int(n) for n in sample_sizes)
+        if len(set(sizes)) == 1:
+            return self._dense_graph(len(sizes), sizes[0])
+        key = ("dense_union", sizes)
+        g = self._graph_cache.get(key)
+        if g is None:
+            if len(self._graph_cache) > 8:
+                self._graph_cache.clear()
+                self._prep_cache.clear()
+            g = (complete_graph_union(sizes, self.device), None)
             self._graph_cache[key] = g
         return g[0]
 
@@ -530,8 +546,8 @@ class TSPModel(COMetaModel):
     def sample_batch(self, points, edge_index=None, seeds=None, generators=None, xt0=None, step_offset=None):
         """``sample()`` of B instances in ONE sampling loop over their disjoint union, every instance getting what its own
         ``sample()`` call returns.  ``points``: list of B tensors, each what ``sample()`` takes for that instance (sparse: [P n_b, 2]
-        with ``edge_index[b]`` [2, P E_b] holding its P parallel samples; dense: [P_b, n, 2], ``edge_index=None``, the same n for
-        all).  ``seeds[b]``: the Philox key of instance b (a solo model built with ``seed=seeds[b]`` draws the same; default:
+        with ``edge_index[b]`` [2, P E_b] holding its P parallel samples; dense: [P_b, n_b, 2], ``edge_index=None``, any n_b:
+        instance b returns [P_b, n_b, n_b]).  ``seeds[b]``: the Philox key of instance b (a solo model built with ``seed=seeds[b]`` draws the same; default:
         this model's seed for all); ``generators[b]`` / ``xt0[b]``: its initial noise, as in ``sample()``.  Each instance keeps
         its own head GroupNorm statistics (sparse: one segment per instance, the solo call's; dense: one per sample, as solo)
         and its own random streams (``DIFUSCO_RAND_PHILOX_INSTANCES``); the step offsets are this engine's call counter, as
@@ -551,15 +567,14 @@ class TSPModel(COMetaModel):
             shapes = [(int(e.shape[1]),) for e in edge_index]
             out_shapes = shapes
         else:
-            if any(p.dim() != 3 for p in points) or len({int(p.shape[1]) for p in points}) != 1:
-                raise ValueError("dense mode expects points [P_b, n, 2] with the same n for every instance")
-            n = int(points[0].shape[1])
-            union_pts = torch.cat([p.to(dev, torch.float32) for p in points])
-            g = self._dense_graph(union_pts.shape[0], n)          # one statistic segment per sample, as solo
-            shapes = [(int(p.shape[0]), n, n) for p in points]
+            if any(p.dim() != 3 or p.shape[2] != 2 for p in points):
+                raise ValueError("dense mode expects points [P_b, n_b, 2] for every instance")
+            # one statistic segment per sample, as solo; instances may differ in n
+            g = self._dense_union_graph([int(p.shape[1]) for p in points for _ in range(int(p.shape[0]))])
+            union_pts = torch.cat([p.to(dev, torch.float32).reshape(-1, 2) for p in points])
+            shapes = [(int(p.shape[0]), int(p.shape[1]), int(p.shape[1])) for p in points]
             out_shapes = shapes
             inst_rows = np.concatenate([[0], np.cumsum([int(np.prod(s_)) for s_ in shapes])])
-            union_pts = union_pts.reshape(-1, 2)
         instances = self._instance_tables(inst_rows, seeds)
         xt = torch.cat(self._initial_noise(shapes, generators, xt0, dev))
         heat = self._sample_loop(self._union_step(g, _lib.TASK_TSP, union_pts, instances, step_offset), xt)

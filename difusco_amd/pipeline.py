@@ -3,7 +3,8 @@
 ``sequential_sampling`` rounds of ``parallel_sampling`` noise samples through the denoising loop -> heatmap -> greedy
 tour merge -> batched 2-opt -> best tour.  ``solve_tsp`` / ``solve_mis`` take one instance per call, like the reference (its
 test batch size is 1); ``solve_tsp_batch`` / ``solve_mis_batch`` solve many instances per pass with the same per-instance
-answers (one sampling loop over their union, per-instance statistics and random streams, grouped 2-opt).  In both the
+answers (one sampling loop over their union, per-instance statistics and random streams, grouped 2-opt; TSP instances of
+different sizes as a list: ragged k-NN and ragged 2-opt).  In both the
 parallel samples form the batch of the denoise steps (disjoint union, ``duplicate_edge_index``), the sequential rounds
 repeat the whole loop with fresh noise and stack the results (``pl_tsp_model.py:185,238,240``).
 
@@ -15,7 +16,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import check_two_opt_method, batched_two_opt_grouped, batched_two_opt_torch, merge_tours
+from .decode import (check_two_opt_method, batched_two_opt_grouped, batched_two_opt_ragged, batched_two_opt_torch,
+                     merge_tours)
 from .graph import knn_edge_index_gpu
 
 
@@ -142,7 +144,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
                     instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
                     heatmaps: Optional[list] = None, *, two_opt_method: str = "exact") -> List[tuple]:
-    """``solve_tsp`` of B instances of the same size: ``points`` [B, N, 2].  Returns the list of what ``solve_tsp`` returns for
+    """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
+    sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
     ``instances_per_call`` instances (default: all) share one k-NN launch sequence, one sampling loop over their union
     (``TSPModel.sample_batch``) and one grouped 2-opt; the merge runs per instance.  The step offsets come from the engine's
@@ -153,6 +156,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
     ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``."""
     check_two_opt_method(two_opt_method)
+    if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
+        return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
+                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -213,6 +219,84 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             best = int(np.argmin(costs))
             results.append((sol[best].tolist(), costs[best], costs,
                             {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]),
+                             "merged_costs": merged_costs[g]}))
+        if heatmaps is not None:
+            heatmaps.extend(heat_out)
+    return results
+
+
+def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
+                    instances_per_call, step_offset, heatmaps, two_opt_method) -> List[tuple]:
+    """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
+    pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
+                for p in points]
+    B = len(pts_list)
+    if B < 1:
+        raise ValueError("points must hold at least one instance")
+    sparse = sparse_factor is not None and sparse_factor > 0
+    for b, p in enumerate(pts_list):
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"points[{b}] must be [n, 2], got {list(p.shape)}")
+        if p.shape[0] < 4:
+            raise ValueError(f"points[{b}] has {p.shape[0]} nodes, a tour needs at least 4")
+        if sparse and p.shape[0] < sparse_factor:
+            raise ValueError(f"points[{b}] has {p.shape[0]} nodes, fewer than sparse_factor = {sparse_factor}")
+    seeds, generators = _per_instance(seeds, B, "seeds"), _per_instance(generators, B, "generators")
+    dev = model.device
+    tick = _ticker(timings, dev)
+    results = []
+    for c0, c1 in _chunks(B, instances_per_call):
+        G = c1 - c0
+        ns = [p.shape[0] for p in pts_list[c0:c1]]
+        t0 = time.perf_counter()
+        if sparse:
+            ei_all = knn_edge_index_gpu(np.concatenate(pts_list[c0:c1]), sparse_factor, device=dev, sizes=ns)
+            e_off = np.concatenate([[0], np.cumsum([n * sparse_factor for n in ns])])
+            n_off = np.concatenate([[0], np.cumsum(ns)])
+            eis = [ei_all[:, e_off[g]:e_off[g + 1]] - int(n_off[g]) for g in range(G)]
+        tick("knn", t0)
+        pts32 = [torch.from_numpy(p.astype(np.float32)).to(dev) for p in pts_list[c0:c1]]     # as solve_tsp
+        np_points64 = [p.cpu().numpy().astype(np.float64) for p in pts32]
+        if sparse:
+            pts_rep = [pts32[g].repeat(P, 1) for g in range(G)]
+            ei_rep = [model.duplicate_edge_index(eis[g], ns[g], dev, copies=P) if P > 1 else eis[g] for g in range(G)]
+        else:
+            pts_rep, ei_rep = [pts32[g].reshape(1, ns[g], 2).repeat(P, 1, 1) for g in range(G)], None
+        seeds_c = None if seeds is None else seeds[c0:c1]
+        gens_c = None if generators is None else generators[c0:c1]
+        stacked = [[] for _ in range(G)]
+        merged_costs = [[] for _ in range(G)]
+        heat_out = [[] for _ in range(G)]
+        merge_its = [0.0] * G
+        its = np.zeros(G, dtype=np.int64)
+        for r in range(sequential_sampling):
+            t0 = time.perf_counter()
+            heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
+                                       step_offset=_round_offset(model, step_offset, r))
+            if heatmaps is not None:
+                for g in range(G):
+                    heat_out[g].append(heats[g].cpu().numpy())
+            tick("sampling", t0)
+            t0 = time.perf_counter()
+            tours = []
+            for g in range(G):
+                tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
+                                               parallel_sampling=P, device=dev)
+                tours.append(tg)
+            tick("merge", t0)
+            t0 = time.perf_counter()
+            solved, its = batched_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
+                                                 max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+            tick("two_opt", t0)
+            for g in range(G):
+                stacked[g].append(solved[g])
+                merged_costs[g] += [tour_length(np_points64[g], t) for t in tours[g]]
+        for g in range(G):
+            sol = np.concatenate(stacked[g], axis=0)
+            costs = [tour_length(np_points64[g], t) for t in sol]
+            best = int(np.argmin(costs))
+            results.append((sol[best].tolist(), costs[best], costs,
+                            {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]),
                              "merged_costs": merged_costs[g]}))
         if heatmaps is not None:
             heatmaps.extend(heat_out)

@@ -449,6 +449,21 @@ int difusco_tsp_two_opt_grouped_screened(int n_nodes, int groups, int per_group,
                                          int64_t max_iterations, void* workspace, size_t workspace_bytes,
                                          int64_t* iterations_out, int64_t* exact_pairs_out, void* stream);
 
+/* Ragged 2-opt (additive to ABI 13): the grouped entries for groups of DIFFERENT sizes.  group_n, group_tours: HOST int32
+ * [groups], the nodes and the number of tours of every group.  points: DEVICE float64, the groups' [n_g, 2] blocks back to back;
+ * tours: DEVICE int32, back to back in group order, every tour of group g n_g + 1 long, refined in place.  Group g gets exactly
+ * what difusco_tsp_two_opt(n_g, group_tours[g], ...) gives its tours alone: its own stop test and iteration count, the flat
+ * index i * n_g + j of its own size on ties, the shared max_iterations.  method: 0 the exact sweep, 1 the screened one (eps from
+ * the group's own largest |coordinate|; one group without a bound sends the whole call to the exact sweep).
+ * iterations_out: HOST int64 [groups].  exact_pairs_out (HOST, optional): the pairs of the call evaluated in float64 (method 0,
+ * or no bound: every pair of every sweep).  DIFUSCO_EINVAL before any GPU work on: groups < 1, a null array, an n_g < 4 or above
+ * 65535 * 16, a group without tours, more than 65535 tours, a method other than 0 / 1, a workspace below _workspace_bytes. */
+int difusco_tsp_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int method,
+                                               size_t* bytes);
+int difusco_tsp_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                               int32_t* tours, int64_t max_iterations, int method, void* workspace, size_t workspace_bytes,
+                               int64_t* iterations_out, int64_t* exact_pairs_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
