@@ -114,6 +114,8 @@ def lib():
     L.difusco_tsp_merge_tour.argtypes = [i32, i64, vp, vp, f32p, f32p, vp, ctypes.c_size_t, vp,
                                          ctypes.POINTER(i64), ctypes.POINTER(i32), vp]
     L.difusco_tsp_merge_tours.argtypes = [i32, i64, vp, vp, f32p, f32p, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.difusco_tsp_merge_batch_workspace_bytes.argtypes = [i32, vp, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_merge_batch.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp, ctypes.c_size_t, vp, vp, vp, vp]
     L.difusco_tsp_two_opt_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_two_opt.argtypes = [i32, i32, vp, vp, i64, vp, ctypes.c_size_t, ctypes.POINTER(i64), vp]
     L.difusco_tsp_two_opt_grouped_workspace_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_size_t)]

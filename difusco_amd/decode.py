@@ -62,6 +62,83 @@ def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=False, parallel_
     return (tours, merge_iterations, done) if return_completed else (tours, merge_iterations)
 
 
+MERGE_METHODS = ("loop", "batched")
+MERGE_STATES = ("auto", "global")
+MERGE_STATE_GLOBAL = 1          # DIFUSCO_MERGE_STATE_GLOBAL
+
+
+def check_merge_method(method):
+    if method not in MERGE_METHODS:
+        raise ValueError(f"merge method {method!r}: one of {MERGE_METHODS}")
+    return method
+
+
+def merge_tours_batch(heats, points, edge_indices, sparse_graph=False, parallel_sampling=1, *, device="cuda:0",
+                      return_completed=False, state="auto"):
+    """``merge_tours`` of G instances of ANY sizes in one library call (``difusco_tsp_merge_batch``: one launch sequence, the
+    greedy insertion on the GPU, one wave per sample).  One entry per instance: ``heats[g]`` as ``sample_batch`` returns it
+    ([P * E_g] sparse, [P, n_g, n_g] dense), ``points[g]`` [n_g, 2], ``edge_indices[g]`` [2, E_g] with node ids 0..n_g-1
+    (``edge_indices=None`` for dense heatmaps: no index arrays are built).  ``parallel_sampling``: P, or one P per instance.
+    ``state``: ``"auto"`` keeps a sample's path state in LDS when it fits, ``"global"`` in the workspace at any size (same
+    results).  Returns, per instance, what ``merge_tours`` returns for it."""
+    if state not in MERGE_STATES:
+        raise ValueError(f"merge state {state!r}: one of {MERGE_STATES}")
+    heats, points = list(heats), list(points)
+    G = len(heats)
+    if G < 1 or len(points) != G:
+        raise ValueError(f"{len(points)} point arrays for {G} heatmaps (at least one instance)")
+    if sparse_graph:
+        if edge_indices is None or len(edge_indices) != G:
+            raise ValueError(f"sparse heatmaps need one edge_index per instance ({G})")
+    elif edge_indices is not None and any(e is not None for e in edge_indices):
+        raise ValueError("dense heatmaps take edge_indices=None")
+    par = [int(parallel_sampling)] * G if np.ndim(parallel_sampling) == 0 else [int(v) for v in parallel_sampling]
+    if len(par) != G or min(par) < 1:
+        raise ValueError(f"parallel_sampling: one value >= 1, or one per instance ({G})")
+    device = torch.device(device)
+    L = _lib.lib()
+    pts = [_dev(p, torch.float32, device).reshape(-1, 2) for p in points]
+    ns = [int(p.shape[0]) for p in pts]
+    if sparse_graph:
+        eis = [_dev(e, torch.int32, device) for e in edge_indices]
+        Es = [int(e.shape[1]) for e in eis]
+    else:
+        Es = [n * n for n in ns]
+    hs = [_dev(h, torch.float32, device).reshape(par[g], -1) for g, h in enumerate(heats)]
+    for g in range(G):
+        if hs[g].shape[1] != Es[g]:
+            raise ValueError(f"heats[{g}] holds {hs[g].shape[1]} values per sample for {Es[g]} edges")
+    graph_n, graph_e, graph_p = np.array(ns, dtype=np.int32), np.array(Es, dtype=np.int64), np.array(par, dtype=np.int32)
+    heat = torch.cat([h.reshape(-1) for h in hs])
+    pts_all = torch.cat(pts).contiguous()
+    if sparse_graph:
+        row, col = torch.cat([e[0] for e in eis]).contiguous(), torch.cat([e[1] for e in eis]).contiguous()
+        row_p, col_p = ctypes.c_void_p(row.data_ptr()), ctypes.c_void_p(col.data_ptr())
+    else:
+        row_p = col_p = None
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_merge_batch_workspace_bytes(G, graph_n.ctypes.data, graph_e.ctypes.data, graph_p.ctypes.data,
+                                                         ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    S = int(graph_p.sum())
+    tours_np = np.empty(int(((graph_n.astype(np.int64) + 1) * graph_p).sum()), dtype=np.int32)
+    iters, done_np = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int32)
+    _lib.check(L.difusco_tsp_merge_batch(G, graph_n.ctypes.data, graph_e.ctypes.data, graph_p.ctypes.data, row_p, col_p,
+                                         ctypes.c_void_p(heat.data_ptr()), ctypes.c_void_p(pts_all.data_ptr()),
+                                         MERGE_STATE_GLOBAL if state == "global" else 0, ctypes.c_void_p(ws.data_ptr()),
+                                         nbytes.value, tours_np.ctypes.data, iters.ctypes.data, done_np.ctypes.data,
+                                         ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    out, t0, s0 = [], 0, 0
+    for g in range(G):
+        t1, s1 = t0 + par[g] * (ns[g] + 1), s0 + par[g]
+        tours = [t.tolist() for t in tours_np[t0:t1].reshape(par[g], ns[g] + 1)]
+        merge_iterations = float(np.mean(iters[s0:s1]))
+        done = [bool(v) for v in done_np[s0:s1]]
+        out.append((tours, merge_iterations, done) if return_completed else (tours, merge_iterations))
+        t0, s0 = t1, s1
+    return out
+
+
 TWO_OPT_METHODS = ("exact", "screened")
 
 

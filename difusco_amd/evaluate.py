@@ -21,7 +21,8 @@ every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are c
 depend on the world size, the rank an instance lands on, or what the model ran before.
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
-``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--mixed_size_chunks``
+``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--merge_method {loop,batched}``
+(``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
 ``--dist_backend``, ``--records PATH`` (JSONL, one line per instance), ``--heatmap_dir`` (where ``--save_numpy_heatmap``
 writes ``numpy_heatmap/{split}-heatmap-{idx}.npy``; default ``<storage_path>/models``), ``--unsafe_checkpoint_load`` (allow a
@@ -92,6 +93,8 @@ EXTENSION_ARGS = [
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
     ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
+    ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
+                            help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
     ("--mixed_size_chunks", dict(action="store_true",
                                  help="TSP: chunks are runs of consecutive instances of any N (default: runs of equal N)")),
     ("--device", dict(type=str, default=None, help="GPU of this process (default: cuda:LOCAL_RANK)")),
@@ -267,7 +270,7 @@ def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, O
 def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0, sparse_factor: int = -1,
                 parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
-                two_opt_method: str = "exact") -> List[dict]:
+                two_opt_method: str = "exact", merge_method: str = "loop") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -286,7 +289,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
             res = solve_tsp_batch(model, np.stack(pts) if len({p.shape[0] for p in pts}) == 1 else pts, sparse_factor,
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
                                   two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
-                                  step_offset=0, heatmaps=heats, two_opt_method=two_opt_method)
+                                  step_offset=0, heatmaps=heats, two_opt_method=two_opt_method,
+                                  merge_method=merge_method)
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if heats is not None:
@@ -352,7 +356,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             recs = solve_split(model, args.task, examples, split, shard_chunks(chunks, rank, world), seed=args.seed,
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
                                two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir,
-                               two_opt_method=args.two_opt_method)
+                               two_opt_method=args.two_opt_method, merge_method=args.merge_method)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:

@@ -16,8 +16,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import (check_two_opt_method, batched_two_opt_grouped, batched_two_opt_ragged, batched_two_opt_torch,
-                     merge_tours)
+from .decode import (check_merge_method, check_two_opt_method, batched_two_opt_grouped, batched_two_opt_ragged,
+                     batched_two_opt_torch, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
 
@@ -143,7 +143,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     two_opt_iterations: int = 1000, seeds: Optional[Sequence[int]] = None,
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
                     instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
-                    heatmaps: Optional[list] = None, *, two_opt_method: str = "exact") -> List[tuple]:
+                    heatmaps: Optional[list] = None, *, two_opt_method: str = "exact",
+                    merge_method: str = "loop") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -154,11 +155,15 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     at ``step_offset + r * inference_diffusion_steps``): ``step_offset=0`` draws what solo calls on fresh engines draw, whatever
     ran on this engine before.  ``heatmaps``: a list to which one entry per instance is appended - the host copies (numpy) of
     its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
-    ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``."""
+    ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``.  ``merge_method``:
+    ``"loop"`` (default) merges instance by instance (``decode.merge_tours``), ``"batched"`` merges the chunk in one library
+    call (``decode.merge_tours_batch``): the same tours and counters."""
     check_two_opt_method(two_opt_method)
+    check_merge_method(merge_method)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
-                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method)
+                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
+                               merge_method)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -201,10 +206,16 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             tick("sampling", t0)
             t0 = time.perf_counter()
             tours = []
-            for g in range(G):
-                tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
-                                               parallel_sampling=P, device=dev)
-                tours.append(tg)
+            if merge_method == "batched":
+                for g, (tg, it) in enumerate(merge_tours_batch(heats, pts32, eis if sparse else None, sparse_graph=sparse,
+                                                               parallel_sampling=P, device=dev)):
+                    merge_its[g] = it
+                    tours.append(tg)
+            else:
+                for g in range(G):
+                    tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
+                                                   parallel_sampling=P, device=dev)
+                    tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
             solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
@@ -226,7 +237,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 
 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
-                    instances_per_call, step_offset, heatmaps, two_opt_method) -> List[tuple]:
+                    instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop") -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
                 for p in points]
@@ -279,10 +290,16 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             tick("sampling", t0)
             t0 = time.perf_counter()
             tours = []
-            for g in range(G):
-                tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
-                                               parallel_sampling=P, device=dev)
-                tours.append(tg)
+            if merge_method == "batched":
+                for g, (tg, it) in enumerate(merge_tours_batch(heats, pts32, eis if sparse else None, sparse_graph=sparse,
+                                                               parallel_sampling=P, device=dev)):
+                    merge_its[g] = it
+                    tours.append(tg)
+            else:
+                for g in range(G):
+                    tg, merge_its[g] = merge_tours(heats[g], pts32[g], eis[g] if sparse else None, sparse_graph=sparse,
+                                                   parallel_sampling=P, device=dev)
+                    tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
             solved, its = batched_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],

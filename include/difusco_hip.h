@@ -409,6 +409,28 @@ int difusco_tsp_merge_tours(int n_nodes, int64_t n_edges, const int32_t* row, co
                             const float* points, int n_samples, void* workspace, size_t workspace_bytes,
                             int32_t* tours_out, int64_t* merge_iterations, int32_t* completed, void* stream);
 
+/* Batched merge (additive to ABI 13): the heatmaps of `graphs` graphs of ANY sizes, graph g with graph_samples[g] samples,
+ * in one launch sequence; the greedy insertion runs on the GPU, one 64-lane wave per (graph, sample).  graph_n, graph_edges,
+ * graph_samples: HOST tables [graphs].  row / col: DEVICE, the graphs' directed edge lists back to back, node ids local to
+ * their graph (0 .. n_g - 1); row == col == NULL: every graph is complete, entry (i, j) at i * n_g + j, graph_edges[g] = n_g^2.
+ * heat: DEVICE, graph after graph [P_g][E_g]; points: DEVICE float32, the [n_g, 2] blocks back to back.  tours_out (HOST):
+ * the closed tours back to back in (graph, sample) order, n_g + 1 ints each; merge_iterations / completed (HOST, optional):
+ * one entry per sample in the same order.  Every (graph, sample) gets exactly what difusco_tsp_merge_tours gives that graph
+ * alone: tour, merge_iterations and completed.  A sample whose positive scores end before its n_g - 1 insertions (completed
+ * = 0) is finished on the host by the code the per-graph entries use.  flags: DIFUSCO_MERGE_STATE_GLOBAL keeps the per-node
+ * path state (12 bytes per node) in the workspace at any size; without it a sample's state lives in LDS when 12 * n_g <= 160 KiB
+ * (n_g <= 13653).  DIFUSCO_EINVAL before any GPU work on: graphs < 1, a null required array, only one of row / col null, an
+ * n_g < 3, an E_g <= 0 or above 2^32, a complete graph with E_g != n_g^2, a P_g < 1, an unknown flag bit, a workspace below
+ * _workspace_bytes; also on more than 2^32 list entries (the sum of P_g * E_g) in one call, or when the graph index and the
+ * largest pair key n_g^2 do not fit 64 bits together.  Blocks until done. */
+#define DIFUSCO_MERGE_STATE_GLOBAL 1u
+int difusco_tsp_merge_batch_workspace_bytes(int graphs, const int32_t* graph_n, const int64_t* graph_edges,
+                                            const int32_t* graph_samples, size_t* bytes);
+int difusco_tsp_merge_batch(int graphs, const int32_t* graph_n, const int64_t* graph_edges, const int32_t* graph_samples,
+                            const int32_t* row, const int32_t* col, const float* heat, const float* points, uint32_t flags,
+                            void* workspace, size_t workspace_bytes, int32_t* tours_out, int64_t* merge_iterations,
+                            int32_t* completed, void* stream);
+
 /* ---- batched 2-opt: difusco/utils/tsp_utils.py:12-49 (batched_two_opt_torch).  points: DEVICE
  * float64 [n_nodes,2]; tours: DEVICE int32 [batch, n_nodes+1] closed tours, refined in place.  Every iteration
  * finds, per tour, the move (i,j), j >= i+2, that minimises d(t_i,t_j) + d(t_i+1,t_j+1) - d(t_i,t_i+1) - d(t_j,t_j+1)

@@ -2,6 +2,7 @@
 reference's batch size 1) against many instances per pass (``solve_tsp_batch`` / ``solve_mis_batch``), split by stage.
 
     python scripts/bench_batch_solve.py [--out profiles/r07/batch_solve.json] [--only tsp500] [--mode batch] [--P 1 4]
+                                        [--merge_method batched]
 
 Synthetic weights (H 256, 12 layers, categorical) and synthetic instances (uniform points; ER graphs); the numbers are
 throughput, the answers are not looked at (the GPU tests pin them to the solo calls).  Every workload runs a small warm-up
@@ -60,12 +61,13 @@ def run(name, P, args, dev, engine):
         gens = [torch.Generator().manual_seed(int(b)) for b in idx]
         if task == "tsp":
             solve_tsp_batch(m, data[idx], k, parallel_sampling=P, two_opt_iterations=args.two_opt, seeds=[seeds[int(b)] for b in idx],
-                            generators=gens, timings=timings, instances_per_call=args.per_call)
+                            generators=gens, timings=timings, instances_per_call=args.per_call, merge_method=args.merge_method)
         else:
             solve_mis_batch(m, [data[b] for b in idx], parallel_sampling=P, seeds=[seeds[int(b)] for b in idx], generators=gens,
                             timings=timings, instances_per_call=args.per_call)
 
-    rec = {"workload": name, "instances": B, "parallel_sampling": P, "inference_steps": args.steps}
+    rec = {"workload": name, "instances": B, "parallel_sampling": P, "inference_steps": args.steps,
+           "merge_method": args.merge_method}
     for mode, fn in (("solo_loop", solo), ("batch", batch)):
         if args.mode not in ("both", mode):
             continue
@@ -95,6 +97,7 @@ def main():
     ap.add_argument("--steps", type=int, default=50, help="inference diffusion steps")
     ap.add_argument("--two-opt", dest="two_opt", type=int, default=1000)
     ap.add_argument("--per-call", dest="per_call", type=int, default=None, help="instances_per_call (default: all)")
+    ap.add_argument("--merge_method", choices=("loop", "batched"), default="loop", help="heatmap -> tour merge of the batch mode")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     engine = DenoiseEngine(random_state_dict(256, 12, 2, seed=0), device=dev)

@@ -2,6 +2,7 @@
 it can be compared with, and the ragged 2-opt entry against the grouped one at equal sizes.
 
     python scripts/bench_mixed_solve.py [--out-dir profiles/mixed_sizes] [--only dense_20_100 sparse_300_700 two_opt_equal]
+                                        [--merge_method batched]
 
 Synthetic weights (H 256, 12 layers, categorical), 50 steps, P = 1, uniform points; the numbers are throughput, the answers are
 not looked at (tests/test_gpu_mixed_sizes.py pins them to the solo calls).
@@ -65,14 +66,14 @@ def run_solve(name, args, dev, engine):
         return [torch.Generator().manual_seed(b) for b in range(B)]
 
     def mixed_batch(t):
-        solve_tsp_batch(m, mixed, k, seeds=list(range(B)), generators=gens(), timings=t, **kw)
+        solve_tsp_batch(m, mixed, k, seeds=list(range(B)), generators=gens(), timings=t, merge_method=args.merge_method, **kw)
 
     def solo_loop(t):
         for b, g in enumerate(gens()):
             solve_tsp(m, mixed[b], k, generator=g, timings=t, **kw)
 
     def equal_size_batch(t):
-        solve_tsp_batch(m, equal, k, seeds=list(range(B)), generators=gens(), timings=t, **kw)
+        solve_tsp_batch(m, equal, k, seeds=list(range(B)), generators=gens(), timings=t, merge_method=args.merge_method, **kw)
 
     modes = (("mixed_batch", mixed_batch), ("solo_loop", solo_loop), ("equal_size_batch", equal_size_batch))
     for _, fn in modes:                                          # warm-up: every shape of the timed passes
@@ -89,7 +90,8 @@ def run_solve(name, args, dev, engine):
             walls[mode].append(time.perf_counter() - t0)
             stages[mode].append(t)
     rec = {"workload": name, "instances": B, "sparse_factor": k, "sizes": sizes, "mean_n": mean_n, "parallel_sampling": 1,
-           "inference_steps": args.steps, "two_opt_iterations": args.two_opt, "repeats": args.repeats}
+           "inference_steps": args.steps, "two_opt_iterations": args.two_opt, "repeats": args.repeats,
+           "merge_method": args.merge_method}
     for mode, _ in modes:
         rec[mode] = {"wall_s": spread(walls[mode]),
                      "instances_per_s": spread([B / w for w in walls[mode]]),
@@ -172,6 +174,7 @@ def main():
     ap.add_argument("--two-opt-entries", dest="two_opt_entries", nargs="*", default=["grouped", "ragged"],
                     choices=("grouped", "ragged"), help="(c): one entry alone, for a kernel trace of it")
     ap.add_argument("--repeats-two-opt", dest="repeats_two_opt", type=int, default=9)
+    ap.add_argument("--merge_method", choices=("loop", "batched"), default="loop", help="heatmap -> tour merge of the batched modes")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_mixed_solve measures on the GPU: no device found")
