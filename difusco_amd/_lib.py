@@ -16,6 +16,7 @@ PREC_FP32, PREC_BF16X3, PREC_BF16X6, PREC_FP16X3, PREC_FP16X1 = 0, 1, 2, 3, 4
 PRECISIONS = {"fp32": PREC_FP32, "bf16x3": PREC_BF16X3, "bf16x6": PREC_BF16X6, "fp16x3": PREC_FP16X3,
               "fp16x1": PREC_FP16X1}
 FUSED_PRECISIONS = ("bf16x3", "fp16x3", "fp16x1")      # the precisions with a fused edge-layer kernel (api.hip: `fused`)
+GRAPH_PERM_IDENTITY, GRAPH_ORDER_IDENTITY, GRAPH_BAD_EDGE = 1, 2, 4      # DIFUSCO_GRAPH_* (difusco_graph_build flags_out[0])
 AGGREGATIONS = {"sum": 0, "mean": 1, "max": 2}      # DIFUSCO_AGG_* (--aggregation, train.py:52; gnn_encoder.py:170-191)
 
 # indices into difusco_weights_layout() (mirrors the enums of include/difusco_hip.h)
@@ -86,6 +87,9 @@ def lib():
     L.difusco_last_error.restype = ctypes.c_char_p
     L.difusco_weights_layout.argtypes = [i32, i32, i32, ctypes.POINTER(i64), i32, ctypes.POINTER(i64)]
     L.difusco_csr_from_coo_host.argtypes = [vp, i64, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
+    L.difusco_graph_build_workspace_bytes.argtypes = [i64, i64, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_graph_build.argtypes = [i64, i64, vp, vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint32), vp,
+                                      ctypes.c_size_t, vp]
     L.difusco_workspace_bytes.restype = ctypes.c_size_t
     L.difusco_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     L.difusco_denoise_step.argtypes = [ctypes.POINTER(StepArgs)]

@@ -276,11 +276,12 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
 
 
-def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0"):
+def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).
     Returns the 0/1 int numpy array.  Instead of a scipy matrix the caller may pass the ``CsrGraph`` of the denoise
-    steps (``graph=``, no host round trip) or the ``edge_index`` the adjacency was built from.  GPU only."""
+    steps (``graph=``, no host round trip) or the ``edge_index`` the adjacency was built from (``graph_build``: the method of
+    ``graph.build_csr`` for it).  GPU only."""
     from .graph import build_csr
     device = torch.device(device)
     L = _lib.lib()
@@ -291,7 +292,7 @@ def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, 
             coo = adj_matrix.tocoo()
             edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
         graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
-                          n, device)
+                          n, device, method=graph_build)
     nbytes = ctypes.c_size_t()
     _lib.check(L.difusco_mis_decode_workspace_bytes(n, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)

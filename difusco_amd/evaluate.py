@@ -22,7 +22,8 @@ depend on the world size, the rank an instance lands on, or what the model ran b
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
 ``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--merge_method {loop,batched}``
-(``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--mixed_size_chunks``
+(``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
+(``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
 ``--dist_backend``, ``--records PATH`` (JSONL, one line per instance), ``--heatmap_dir`` (where ``--save_numpy_heatmap``
 writes ``numpy_heatmap/{split}-heatmap-{idx}.npy``; default ``<storage_path>/models``), ``--unsafe_checkpoint_load`` (allow a
@@ -95,6 +96,8 @@ EXTENSION_ARGS = [
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
     ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
                             help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
+    ("--graph_build", dict(type=str, default="host", choices=("host", "device"),
+                           help="COO -> CSR and node order: host (C helper + numpy) or device (difusco_graph_build, same arrays)")),
     ("--mixed_size_chunks", dict(action="store_true",
                                  help="TSP: chunks are runs of consecutive instances of any N (default: runs of equal N)")),
     ("--device", dict(type=str, default=None, help="GPU of this process (default: cuda:LOCAL_RANK)")),
@@ -335,7 +338,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
         dev = torch.device(args.device or f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}")
         torch.cuda.set_device(dev)
         cls = TSPModel if args.task == "tsp" else MISModel
-        model = cls(vars(args), state, device=dev, **(dict(precision="fp16x1") if args.fp16 else {}))
+        model = cls(vars(args), state, device=dev, graph_build=args.graph_build,
+                    **(dict(precision="fp16x1") if args.fp16 else {}))
         heatmap_dir = None
         if args.task == "tsp" and args.save_numpy_heatmap:
             heatmap_dir = args.heatmap_dir or os.path.join(args.storage_path, "models")
@@ -376,7 +380,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                     "world_size": world, "precision": model.model.precision,
                     "instances_per_call": args.instances_per_call if args.instances_per_call else "auto",
                     "chunks": len(chunks), "chunk_lengths": sorted({hi - lo for lo, hi in chunks}), "seed": args.seed,
-                    "two_opt_method": args.two_opt_method, "ignored_args": ignored}
+                    "two_opt_method": args.two_opt_method, "graph_build": model.graph_build, "ignored_args": ignored}
             if mixed:
                 line["mixed_size_chunks"] = True
             print(json.dumps(line), flush=True)

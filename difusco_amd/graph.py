@@ -5,7 +5,8 @@ j; TSP k-NN graphs are row-sorted with constant degree and include the self edge
 (``co_datasets/tsp_graph_dataset.py:53-62``); MIS graphs are undirected edges + reversed copy + self
 loops, not row-sorted (``co_datasets/mis_dataset.py:43-48``); a batch is the disjoint union with node
 ids offset per graph (``pl_meta_model.py:177-184``).  The conversion runs once per instance, outside
-the denoising loop, on the host (C helper ``difusco_csr_from_coo_host``).
+the denoising loop: on the host by default (C helper ``difusco_csr_from_coo_host``), or with ``method="device"`` on the GPU
+(``difusco_graph_build``, csrc/graph_build.hip: the same arrays bit for bit, the graph never leaves the device).
 """
 import ctypes
 from dataclasses import dataclass
@@ -92,12 +93,64 @@ def locality_node_order(rowptr: np.ndarray, col: np.ndarray, points: np.ndarray)
     return np.lexsort((_morton_keys(points), _id_blocks(rowptr, col, n))).astype(np.int64)
 
 
+GRAPH_BUILDS = ("host", "device")
+
+
+def check_graph_build(method):
+    if method not in GRAPH_BUILDS:
+        raise ValueError(f"graph build {method!r}: one of {GRAPH_BUILDS}")
+    return method
+
+
+def _build_csr_device(edge_index, n_nodes: int, device, points=None) -> CsrGraph:
+    """``build_csr`` through ``difusco_graph_build``: ``edge_index`` / ``points`` from any device (moved to ``device`` if
+    needed), outputs and workspace torch tensors, the current stream.  One small readback (the flags) inside the library."""
+    L = _lib.lib()
+    device = torch.device(device)
+    n_nodes = int(n_nodes)
+    if not isinstance(edge_index, torch.Tensor):
+        edge_index = torch.from_numpy(np.asarray(edge_index))
+    ei = edge_index.detach().to(device=device, dtype=torch.int64).contiguous()
+    assert ei.dim() == 2 and ei.shape[0] == 2
+    E = int(ei.shape[1])
+    pts = None
+    if points is not None and n_nodes > 1 and E > 0:
+        pts = points.detach() if isinstance(points, torch.Tensor) else torch.from_numpy(np.asarray(points))
+        # float32 coordinates are widened on the device; everything else is widened here, as np.asarray(.., float64) would
+        pts = pts.to(device=device, dtype=torch.float32 if pts.dtype == torch.float32 else torch.float64)
+        pts = pts.reshape(-1, 2)[:n_nodes].contiguous()
+        if pts.shape[0] != n_nodes:
+            raise ValueError(f"points holds {pts.shape[0]} nodes, the graph has {n_nodes}")
+    i32 = dict(dtype=torch.int32, device=device)
+    rowptr, col, row, perm = (torch.empty(n_nodes + 1, **i32), torch.empty(E, **i32), torch.empty(E, **i32),
+                              torch.empty(E, **i32))
+    order = torch.empty(n_nodes, dtype=torch.int64, device=device) if pts is not None else None
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_graph_build_workspace_bytes(n_nodes, E, int(pts is not None), ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    flags = (ctypes.c_uint32 * 2)()
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None      # noqa: E731
+    _lib.check(L.difusco_graph_build(n_nodes, E, ptr(ei), ptr(pts), int(pts is not None and pts.dtype == torch.float64),
+                                     ptr(rowptr), ptr(col), ptr(row), ptr(perm), ptr(order), flags, ptr(ws), nbytes.value,
+                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    return CsrGraph(n_nodes=n_nodes, n_edges=E, rowptr=rowptr, col=col,
+                    perm=None if flags[0] & _lib.GRAPH_PERM_IDENTITY else perm, row=row,
+                    node_order=None if flags[0] & _lib.GRAPH_ORDER_IDENTITY else order)
+
+
 def build_csr(edge_index: torch.Tensor, n_nodes: int, device, seg_rows: Optional[np.ndarray] = None,
-              points=None) -> CsrGraph:
+              points=None, method: str = "host") -> CsrGraph:
     """edge_index int64 [2,E] (any device).  ``seg_rows``: boundaries [S+1] of the head-GroupNorm
     statistic segments over output rows (None = one segment = the reference's sparse behaviour).
     ``points`` ([n_nodes,2], optional): renumber the nodes for locality (``locality_node_order``); invisible to the
-    caller - edge outputs keep the caller's edge order through ``perm``, ``node_order`` gathers the point input."""
+    caller - edge outputs keep the caller's edge order through ``perm``, ``node_order`` gathers the point input.
+    ``method``: ``"host"`` (C helper + numpy) or ``"device"`` (``difusco_graph_build``: equal arrays, built on the GPU)."""
+    if check_graph_build(method) == "device":
+        g = _build_csr_device(edge_index, n_nodes, device, points)
+        if seg_rows is not None and len(seg_rows) > 2:
+            g.seg_ptr = torch.from_numpy(np.asarray(seg_rows, dtype=np.int32)).to(device)
+            g.n_segments = len(seg_rows) - 1
+        return g
     ei = edge_index.detach().cpu().numpy()
     rowptr, col, _row, perm, ident = csr_from_coo_host(ei, n_nodes)
     order = None
@@ -129,13 +182,59 @@ def union_rows(edge_counts, node_counts, task_rows: str):
     return node_off, (edge_off if task_rows == "edges" else node_off)
 
 
-def build_union_csr(edge_indices, node_counts, device, points=None, task_rows: str = "edges"):
+def _build_union_csr_device(edge_indices, node_counts, device, points, task_rows):
+    """``build_union_csr`` without per-instance host round trips: the union is concatenated and checked on the device, and ONE
+    readback carries both checks (the first instance with an edge outside its nodes, the CSR slot at every instance start)."""
+    device = torch.device(device)
+    eis = [e if isinstance(e, torch.Tensor) else torch.from_numpy(np.asarray(e)) for e in edge_indices]
+    eis = [e.detach().to(device, torch.int64) for e in eis]
+    counts = [int(e.shape[1]) for e in eis]
+    node_off, inst_rows = union_rows(counts, node_counts, task_rows)
+    n, B = int(node_off[-1]), len(eis)
+    off_d = torch.from_numpy(node_off).to(device)
+    union = torch.cat([e + int(node_off[b]) for b, e in enumerate(eis)], dim=1)
+    if union.shape[1]:
+        inst = torch.repeat_interleave(torch.arange(B, device=device), torch.tensor(counts, device=device),
+                                       output_size=union.shape[1])
+        outside = ((union < off_d[inst]) | (union >= off_d[inst + 1])).any(dim=0)
+        first_bad = torch.where(outside, inst, B).min().reshape(1)
+    else:
+        first_bad = torch.full((1,), B, dtype=torch.int64, device=device)
+
+    def refuse(b):
+        if b < B:
+            raise ValueError(f"edge_index of instance {b} refers to nodes outside 0..{int(node_counts[b]) - 1}")
+
+    try:
+        g = build_csr(union, n, device, seg_rows=node_off if (B > 1 and task_rows != "edges") else None, points=points,
+                      method="device")
+    except _lib.DifuscoHipError:      # an endpoint outside the whole union: name the instance, as the host method does
+        refuse(int(first_bad.cpu()))
+        raise
+    if task_rows == "edges":
+        back = torch.cat([first_bad, g.rowptr[off_d].to(torch.int64)]).cpu().numpy()
+        refuse(int(back[0]))
+        if not np.array_equal(back[1:], inst_rows):
+            raise RuntimeError("instance edges are not contiguous in CSR-slot order (an edge leaves its instance?)")
+        if B > 1:
+            g.seg_ptr = torch.from_numpy(inst_rows.astype(np.int32)).to(device)
+            g.n_segments = B
+    else:
+        refuse(int(first_bad.cpu()))
+    return g, union, inst_rows
+
+
+def build_union_csr(edge_indices, node_counts, device, points=None, task_rows: str = "edges", method: str = "host"):
     """Disjoint union of B instances (``pl_meta_model.py:177-184``), each given by its own ``edge_index`` [2, E_b] over its
     own nodes 0..n_b-1, with ONE head-GroupNorm statistic segment per instance - what the solo call of each instance
     normalises over.  Returns ``(graph, union_edge_index, instance_rows)``: ``instance_rows`` [B+1] int64 numpy, the output
     rows (``"edges"``: TSP, ``"nodes"``: MIS) of every instance in caller order.  ``points`` [sum n_b, 2]: node renumbering
     for locality as in :func:`build_csr`; it never crosses an instance (``_id_blocks``), which is checked: the CSR slots of
-    every instance must stay one contiguous range (otherwise a segment would mix instances)."""
+    every instance must stay one contiguous range (otherwise a segment would mix instances).
+    ``method="device"``: the same graph, errors and ``instance_rows`` through ``difusco_graph_build``; the union is concatenated
+    and checked on the device (one synchronising readback for both checks) and ``union_edge_index`` stays there."""
+    if check_graph_build(method) == "device":
+        return _build_union_csr_device(edge_indices, node_counts, device, points, task_rows)
     eis = [e if isinstance(e, torch.Tensor) else torch.from_numpy(np.asarray(e)) for e in edge_indices]
     eis = [e.detach().to("cpu", torch.int64) for e in eis]
     node_off, inst_rows = union_rows([e.shape[1] for e in eis], node_counts, task_rows)

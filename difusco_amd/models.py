@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .engine import DenoiseEngine
-from .graph import CsrGraph, build_csr, build_union_csr, complete_graph_batch, complete_graph_union
+from .graph import CsrGraph, build_csr, build_union_csr, check_graph_build, complete_graph_batch, complete_graph_union
 from .schedules import CategoricalDiffusion, GaussianDiffusion, InferenceSchedule
 
 _DEFAULTS = dict(  # difusco/train.py:19-68 (only what the inference path reads)
@@ -88,14 +88,18 @@ class COMetaModel:
     """Inference-side state of the reference's ``COMetaModel`` (``pl_meta_model.py:16-47``): the
     diffusion tables, the denoiser weights (as a ``DenoiseEngine``) and the two posteriors."""
 
+    graph_build = "host"      # (class default: the host build, also for a model assembled without the constructor)
+
     def __init__(self, param_args=None, state_dict=None, node_feature_only=False, device="cuda:0",
                  seed: Optional[int] = None, engine: Optional[DenoiseEngine] = None, precision: str = "fp16x3",
                  fused: bool = True, gn_reduce=None, reorder_nodes: bool = True, backend: Optional[str] = None, flags: int = 0,
-                 prepare: bool = True, strict_binary_check: bool = False):
+                 prepare: bool = True, strict_binary_check: bool = False, graph_build: str = "host"):
         args = dict(_DEFAULTS)
         if param_args is not None:
             args.update(vars(param_args) if not isinstance(param_args, dict) else param_args)
         self.args = SimpleNamespace(**args)
+        # where edge_index becomes the CSR: "host" or "device" (graph.build_csr: the same arrays either way)
+        self.graph_build = check_graph_build(graph_build)
         self.diffusion_type = self.args.diffusion_type
         self.diffusion_schedule = self.args.diffusion_schedule
         self.diffusion_steps = self.args.diffusion_steps
@@ -164,7 +168,8 @@ class COMetaModel:
             if len(self._graph_cache) > 8:
                 self._graph_cache.clear()
                 self._prep_cache.clear()      # (prepared buffers hold their graphs alive)
-            g = build_csr(edge_index, int(num_nodes), self.device, points=points if self.reorder_nodes else None)
+            g = build_csr(edge_index, int(num_nodes), self.device, points=points if self.reorder_nodes else None,
+                          method=self.graph_build)
             self._graph_cache[key] = (g, edge_index)   # keep edge_index alive: data_ptr stays unique
             return g
         return g[0]
@@ -561,8 +566,10 @@ class TSPModel(COMetaModel):
             if len(edge_index) != B:
                 raise ValueError(f"{len(edge_index)} edge_index tensors for {B} instances")
             pts = [p.reshape(-1, 2) for p in points]
+            on = dev if self.graph_build == "device" else "cpu"      # the device build reads the points where they are
             g, _, inst_rows = build_union_csr(edge_index, [p.shape[0] for p in pts], dev,
-                                              points=torch.cat([p.detach().cpu() for p in pts]) if self.reorder_nodes else None)
+                                              points=torch.cat([p.detach().to(on) for p in pts]) if self.reorder_nodes else None,
+                                              method=self.graph_build)
             union_pts = torch.cat([p.to(dev, torch.float32) for p in pts])
             shapes = [(int(e.shape[1]),) for e in edge_index]
             out_shapes = shapes
@@ -629,7 +636,8 @@ class MISModel(COMetaModel):
         B = len(n_nodes)
         if B < 1 or len(edge_index) != B:
             raise ValueError("sample_batch needs one edge_index per graph and at least one graph")
-        g, _, inst_rows = build_union_csr(edge_index, [int(v) for v in n_nodes], self.device, task_rows="nodes")
+        g, _, inst_rows = build_union_csr(edge_index, [int(v) for v in n_nodes], self.device, task_rows="nodes",
+                                          method=self.graph_build)
         instances = self._instance_tables(inst_rows, seeds)
         xt = torch.cat(self._initial_noise([(int(v),) for v in n_nodes], generators, xt0, self.device))
         heat = self._sample_loop(self._union_step(g, _lib.TASK_MIS, None, instances, step_offset), xt)

@@ -348,7 +348,7 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
             eis.append(model.duplicate_edge_index(ei, ns[b - c0], dev, copies=P) if P > 1 else ei)
         off = np.concatenate([[0], np.cumsum([n * P for n in ns])])
         union = torch.cat([e + int(off[g]) for g, e in enumerate(eis)], dim=1)
-        graph = build_csr(union, int(off[-1]), dev)
+        graph = build_csr(union, int(off[-1]), dev, method=getattr(model, "graph_build", "host"))
         sols = [[] for _ in ns]
         for r in range(sequential_sampling):
             t0 = time.perf_counter()

@@ -145,6 +145,29 @@ int difusco_csr_from_coo_host(const int64_t* edge_index, int64_t n_edges, int64_
                               int32_t* rowptr, int32_t* col, int32_t* row, int32_t* perm,
                               int* identity);
 
+/* The same conversion on the DEVICE, with the optional node renumbering of difusco_amd/graph.py (build_csr): the outputs are bit
+ * for bit the arrays the host path produces for the same input.  edge_index: DEVICE int64 [2, n_edges] (row 0 = centre node);
+ * points: DEVICE [n_nodes, 2], float32 (points_f64 = 0) or float64 (points_f64 = 1), or NULL = no renumbering.  With points the
+ * nodes are renumbered first (graph.py locality_node_order): inside every block of node ids that no edge leaves (_id_blocks) by
+ * the 2 x 16-bit Morton key of the coordinates over the bounding box of the call, computed in float64 (_morton_keys), ties in id
+ * order; node_order[new] = old (DEVICE int64 [n_nodes]).  As on the host the renumbering is skipped (node_order not written, the
+ * ORDER_IDENTITY flag set) when points is NULL, n_nodes <= 1 or n_edges == 0.  rowptr [n_nodes + 1], col / row / perm [n_edges]:
+ * DEVICE int32, the stable sort of the edges by (renumbered) centre node, perm[slot] = caller edge id, col renumbered.
+ * flags_out: HOST uint32 [2]: [0] = DIFUSCO_GRAPH_* bits, [1] = the smallest edge id with an endpoint outside [0, n_nodes) when
+ * DIFUSCO_GRAPH_BAD_EDGE is set.  Such an edge is never used as an index; the call then returns DIFUSCO_EINVAL (the message
+ * names the edge like the host helper's) and the outputs are unspecified.  Runs on `stream`, copies the flags back (the one
+ * device-to-host copy of the call) and synchronises the stream: on return the arrays are complete.  Limits as the host helper:
+ * n_edges <= INT32_MAX, n_nodes < INT32_MAX.  DIFUSCO_EINVAL before any GPU work on: a negative or too large size, a null
+ * rowptr / flags_out / workspace, a null edge_index / col / row / perm with n_edges > 0, a null node_order when the renumbering
+ * runs, points_f64 outside {0, 1}, a workspace smaller than difusco_graph_build_workspace_bytes (with_points: points != NULL). */
+#define DIFUSCO_GRAPH_PERM_IDENTITY 1u  /* perm[s] == s for every slot: the input was row-sorted (after the renumbering) */
+#define DIFUSCO_GRAPH_ORDER_IDENTITY 2u /* node_order[i] == i for every node, or no renumbering ran */
+#define DIFUSCO_GRAPH_BAD_EDGE 4u
+int difusco_graph_build_workspace_bytes(int64_t n_nodes, int64_t n_edges, int with_points, size_t* bytes);
+int difusco_graph_build(int64_t n_nodes, int64_t n_edges, const int64_t* edge_index, const void* points, int points_f64,
+                        int32_t* rowptr, int32_t* col, int32_t* row, int32_t* perm, int64_t* node_order, uint32_t* flags_out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the denoise step -------------------------------------------------------------------------- */
 typedef struct difusco_step_args {
   uint32_t struct_size;   /* = sizeof(difusco_step_args), checked */
