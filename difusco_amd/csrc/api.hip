@@ -93,6 +93,54 @@ Layout make_layout(int H, int L, int C) {
   return lo;
 }
 
+// ---- named views of the packed weight blob --------------------------------------------------------
+// A split weight record of an [n_out, k] matrix: 3 bf16 planes, 2 fp16 planes (16-bit elements), then the fp32 inverse scales of
+// the fp16 planes.  The planes of one precision and their inverse scales (null for bf16: unscaled).
+struct SplitPlanes {
+  const unsigned short* planes;
+  const float* w_inv;
+};
+SplitPlanes split_planes(const void* record, long long n_out, long long k, bool f16) {
+  const long long nk = n_out * k;
+  return {reinterpret_cast<const unsigned short*>(record) + (f16 ? 3 * nk : 0),
+          f16 ? reinterpret_cast<const float*>(record) + 5 * nk / 2 : nullptr};
+}
+// fp16 planes (FP16X3, and FP16X1: the hi plane of FP16X3's pair)?
+bool f16_planes(int precision) { return precision == DIFUSCO_PREC_FP16X3 || precision == DIFUSCO_PREC_FP16X1; }
+
+// the tensors of layer l (DIFUSCO_WL_*)
+struct LayerW {
+  const float *node4_w, *node4_b, *c_w, *c_b, *norm_h_w, *norm_h_b, *norm_e_w, *norm_e_b, *out_ln_w, *out_ln_b, *out_w, *out_b,
+      *c_planes, *out_planes, *node4_planes, *fused_scales, *node4_fused_b, *node4_fused_s;
+};
+struct Weights {
+  Layout lo;
+  const float* base;
+  Weights(const float* w, int H, int L, int C) : lo(make_layout(H, L, C)), base(w) {}
+  const float* g(int id) const { return base + lo.off[id]; }      // DIFUSCO_W_*
+  LayerW layer(int l) const {
+    const int64_t* o = lo.off.data() + DIFUSCO_W_GLOBAL_COUNT + l * DIFUSCO_WL_COUNT;
+    auto at = [&](int id) { return base + o[id]; };
+    return {at(DIFUSCO_WL_NODE4_W), at(DIFUSCO_WL_NODE4_B), at(DIFUSCO_WL_C_W), at(DIFUSCO_WL_C_B), at(DIFUSCO_WL_NORM_H_W),
+            at(DIFUSCO_WL_NORM_H_B), at(DIFUSCO_WL_NORM_E_W), at(DIFUSCO_WL_NORM_E_B), at(DIFUSCO_WL_OUT_LN_W),
+            at(DIFUSCO_WL_OUT_LN_B), at(DIFUSCO_WL_OUT_W), at(DIFUSCO_WL_OUT_B), at(DIFUSCO_WL_C_PLANES),
+            at(DIFUSCO_WL_OUT_PLANES), at(DIFUSCO_WL_NODE4_PLANES), at(DIFUSCO_WL_FUSED_SCALES),
+            at(DIFUSCO_WL_NODE4_FUSED_B), at(DIFUSCO_WL_NODE4_FUSED_S)};
+  }
+};
+
+// hands out consecutive pieces of a buffer, each on a 256-byte boundary (null base: sizes only)
+struct Carver {
+  char* base;
+  size_t cur = 0;
+  template <typename T = float>
+  T* take(size_t bytes) {
+    const size_t at = cur;
+    cur = (cur + bytes + 255) / 256 * 256;
+    return base ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
 struct Workspace {
   float *h, *node4, *e, *tmp, *tbias, *table_in, *table, *stats, *part, *direct, *gn_tile, *etmax, *hscale, *escale;
   double* partial;
@@ -104,48 +152,25 @@ size_t fused_part_floats(int64_t E) { return (size_t)((E + 255) / 256) * 8 * 2 *
 
 Workspace carve(void* base, int H, int L, int64_t N, int64_t E, int S, int nblk) {
   Workspace w;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = cur;
-    cur = (cur + bytes + 255) / 256 * 256;
-    return base ? (void*)((char*)base + at) : (void*)nullptr;
-  };
-  w.h = (float*)take(sizeof(float) * N * H);
-  w.node4 = (float*)take(sizeof(float) * N * 4 * H);
-  w.e = (float*)take(sizeof(float) * (H == 256 ? (E + 255) / 256 * 256 : E) * H);   // fused path: tiles of 256 edges
-  w.tmp = (float*)take(sizeof(float) * (E > 2 ? E : 2) * H);
-  w.tbias = (float*)take(sizeof(float) * L * H);
-  w.table_in = (float*)take(sizeof(float) * 2 * H);
-  w.table = (float*)take(sizeof(float) * 4 * H);      // rows 0,1: edge-input table; rows 2,3: C of layer 0 applied to them
-  w.stats = (float*)take(sizeof(float) * S * 64);
-  w.partial = (double*)take(sizeof(double) * (size_t)S * (nblk < 256 ? 256 : nblk) * 64);
-  w.part = (float*)take(H == 256 ? sizeof(float) * fused_part_floats(E) : 0);
-  w.direct = (float*)take(H == 256 ? sizeof(float) * N * H : 0);
-  w.gn_tile = (float*)take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) * 64 : 0);   // per 32-edge tile: 32 x (sum, sumsq)
+  Carver c{(char*)base};
+  w.h = c.take(sizeof(float) * N * H);
+  w.node4 = c.take(sizeof(float) * N * 4 * H);
+  w.e = c.take(sizeof(float) * (H == 256 ? (E + 255) / 256 * 256 : E) * H);   // fused path: tiles of 256 edges
+  w.tmp = c.take(sizeof(float) * (E > 2 ? E : 2) * H);
+  w.tbias = c.take(sizeof(float) * L * H);
+  w.table_in = c.take(sizeof(float) * 2 * H);
+  w.table = c.take(sizeof(float) * 4 * H);      // rows 0,1: edge-input table; rows 2,3: C of layer 0 applied to them
+  w.stats = c.take(sizeof(float) * S * 64);
+  w.partial = c.take<double>(sizeof(double) * (size_t)S * (nblk < 256 ? 256 : nblk) * 64);
+  w.part = c.take(H == 256 ? sizeof(float) * fused_part_floats(E) : 0);
+  w.direct = c.take(H == 256 ? sizeof(float) * N * H : 0);
+  w.gn_tile = c.take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) * 64 : 0);   // per 32-edge tile: 32 x (sum, sumsq)
   // operand scales of the fp16 split path: max |e| per 32-edge tile (fused kernel), one power of two per node row / edge row
-  w.etmax = (float*)take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) : 0);
-  w.hscale = (float*)take(sizeof(float) * N);
-  w.escale = (float*)take(sizeof(float) * E);
-  w.bytes = cur;
+  w.etmax = c.take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) : 0);
+  w.hscale = c.take(sizeof(float) * N);
+  w.escale = c.take(sizeof(float) * E);
+  w.bytes = c.cur;
   return w;
-}
-
-
-// C of layer 0 on the two rows of the edge-input table (table rows 0, 1 -> rows 2, 3; layer-0 fold of the fused step and
-// difusco_prepare).  Exact fp32, except under FP16X1: there the one-product fp16 linear that the fused kernel's GEMM 1 applies to
-// an e tile (each row scaled by its power of two, the hi plane of C), so that folding layer 0 keeps the precision's contract.
-// scale2: two floats of scratch.
-hipError_t table_c_rows(int precision, int H, float* table, const float* c_w, const float* c_planes, float* scale2,
-                        hipStream_t st) {
-  using namespace difusco;
-  if (precision != DIFUSCO_PREC_FP16X1) return launch_two_rows_linear(H, table, c_w, nullptr, table + 2 * H, st);
-  hipError_t er = launch_row_pow2_scale(table, 2, H, scale2, st);
-  if (er != hipSuccess) return er;
-  SplitScale sc;
-  sc.row_scale = scale2;
-  sc.w_inv = c_planes + (long long)5 * H * H / 2;
-  return linear_rows_split(table, reinterpret_cast<const unsigned short*>(c_planes) + (long long)3 * H * H, (long long)H * H,
-                           DIFUSCO_PREC_FP16X1, nullptr, nullptr, table + 2 * H, 2, H, H, H, st, 0, sc);
 }
 
 // Prepared state of a TSP call shape (difusco_step_args.prepared): what a step computes from (weights, points) alone.
@@ -155,16 +180,11 @@ struct Prepared {
 };
 Prepared carve_prepared(void* base, int H, int64_t N) {
   Prepared p;
-  size_t cur = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = cur;
-    cur = (cur + bytes + 255) / 256 * 256;
-    return base ? (float*)((char*)base + at) : (float*)nullptr;
-  };
-  p.h0 = take(sizeof(float) * N * H);
-  p.node4_0 = take(sizeof(float) * N * 4 * H);
-  p.table = take(sizeof(float) * 4 * H);
-  p.bytes = cur;
+  Carver c{(char*)base};
+  p.h0 = c.take(sizeof(float) * N * H);
+  p.node4_0 = c.take(sizeof(float) * N * 4 * H);
+  p.table = c.take(sizeof(float) * 4 * H);
+  p.bytes = c.cur;
   return p;
 }
 
@@ -187,7 +207,8 @@ struct ProfScope {
   hipStream_t st;
   bool active;
   hipEvent_t end;      // handle copied while the lock is held: the destructor never touches the shared vectors
-  ProfScope(int category, hipStream_t s) : st(s), active(false), end(nullptr) {
+  ProfScope(int category, hipStream_t s) : st(s), active(false), end(nullptr) {      // category < 0: no bracket
+    if (category < 0) return;
     std::lock_guard<std::mutex> lk(g_prof_mu);
     if (!g_prof.on || (g_prof.dominant_only && category != PROF_LINEAR_EDGE) || g_prof.used * 2 + 2 > g_prof.ev.size()) return;
     const size_t slot = g_prof.used++;
@@ -200,11 +221,334 @@ struct ProfScope {
   }
 };
 
-}  // namespace
-
 #ifdef DIFUSCO_PROFILING
-static int g_step_skip = 0;      // difusco_debug_set key 11 (profiling library): launches of the step that are skipped for an upper-bound timing
+int g_step_skip = 0;      // difusco_debug_set key 11 (profiling library): launches of the step that are skipped for an upper-bound timing
 #endif
+
+// PROF(category, call): HIP_TRY(call), bracketed by a pair of HIP events on `st` when profiling is on.
+// PROF_IF(on, ..): the same inside the helpers that difusco_prepare shares with the step - its launches are never bracketed.
+#define PROF_IF(on, cat, call) { ProfScope ps_((on) ? (cat) : -1, st); HIP_TRY(call); }
+#define PROF(cat, call) PROF_IF(true, cat, call)
+#define STAGE(call) do { const int rc_ = (call); if (rc_ != DIFUSCO_OK) return rc_; } while (0)
+
+using namespace difusco;
+
+// ---- the launch plan of a step ---------------------------------------------------------------------
+// the header of a difusco_step_args block: struct size, ABI, model shape, precision (the step and difusco_prepare)
+int validate_header(const difusco_step_args* a) {
+  if (a->struct_size != sizeof(difusco_step_args) || a->abi_version != DIFUSCO_ABI_VERSION)
+    return fail(DIFUSCO_EINVAL, "ABI mismatch: struct_size %u (want %zu), abi %u (want %d)", a->struct_size,
+                sizeof(difusco_step_args), a->abi_version, DIFUSCO_ABI_VERSION);
+  if (!hidden_ok(a->hidden)) return fail(DIFUSCO_EINVAL, "hidden must be 64, 128 or 256 (got %d)", a->hidden);
+  if (a->n_layers < 1) return fail(DIFUSCO_EINVAL, "n_layers must be >= 1");
+  if (a->out_channels != 1 && a->out_channels != 2) return fail(DIFUSCO_EINVAL, "out_channels must be 1 or 2 (got %d)", a->out_channels);
+  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X1) return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
+  return DIFUSCO_OK;
+}
+
+// Every path decision and derived size of a step, computed once from the argument block: after make_plan nothing in the driver
+// re-derives one.
+struct StepPlan {
+  int H, L, C;
+  int64_t N, E, out_rows, E_pad, n_tiles_pad;      // fused path: e is kept in tiles of 256 edges (32-edge tiles: n_tiles_pad)
+  bool tsp, head_only;
+  int nprec;                       // precision of every matrix product but the edge-row GEMMs of the layers
+  bool f16;                        // fp16 planes (FP16X3 or FP16X1): operand scales are kept
+  bool fused;
+  int fused_variant;               // launch_edge_layer_fused: bit 0 register gathers, bit 1 max aggregation
+  bool l0_fold, tail_fold, gn_fold, use_prep;
+};
+
+StepPlan make_plan(const difusco_step_args* a) {
+  StepPlan p;
+  p.H = a->hidden, p.L = a->n_layers, p.C = a->out_channels;
+  p.N = a->n_nodes, p.E = a->n_edges;
+  p.tsp = a->task == DIFUSCO_TASK_TSP;
+  p.out_rows = p.tsp ? p.E : p.N;
+  p.head_only = a->gn_phase == 2;   // everything up to the statistics was done by the phase-1 call
+  // FP16X1: only the edge-row GEMMs of the layers (C, per_layer_out[l][2]) take the one-product form; every other matrix product
+  // (edge embedding, node linears) runs as FP16X3 - nprec is the precision of those
+  p.nprec = a->precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : a->precision;
+  p.f16 = p.nprec == DIFUSCO_PREC_FP16X3;
+  // fused edge-layer path: H = 256, 16-bit split planes, one GroupNorm statistic segment; e is then kept in the
+  // tiled layout (kernels.h: edge_tiled_offset) from the embedding to the head
+  // (per-sample statistic segments - the dense mode of TSP-50 / 100 with parallel_sampling > 1 - run the same fused layers;
+  // only the head differs: masked per-segment statistics and a per-row segment look-up, launch_head_tiled)
+  // the full-line neighbour-table gathers address node rows by 32-bit byte offsets (4 KB per node): calls with 2^20 nodes or
+  // more take the register-gather instantiation of the same kernel (64-bit addresses, bit-identical results, ~3 % slower)
+  const int reg_gather = p.N >= (1 << 20) ? 1 : 0;
+  // aggregation = max has fused instantiations of its own (the per-tile pieces are maxima) for the full-line gather form only:
+  // with 2^20 nodes or more it takes the unfused sequence
+  const bool agg_max = a->aggregation == DIFUSCO_AGG_MAX;
+  p.fused = p.H == 256 && !a->no_fusion && p.E > 0 && !(agg_max && reg_gather) &&
+            (a->precision == DIFUSCO_PREC_BF16X3 || a->precision == DIFUSCO_PREC_FP16X3 ||
+             a->precision == DIFUSCO_PREC_FP16X1);
+  p.fused_variant = reg_gather | (agg_max ? 2 : 0);
+  p.E_pad = (p.E + 255) / 256 * 256;
+  p.n_tiles_pad = p.E_pad / 32;
+#ifdef DIFUSCO_PROFILING
+  const bool ablating = difusco::g_fused_ablate != 0;      // (the ablation variants exist for the middle layer only: no folds)
+#else
+  const bool ablating = false;
+#endif
+  // first layer: when the edge input is a table lookup (categorical TSP: embedding of the bit; MIS: zeros) the fused
+  // kernel takes it from the table and the pass that would write e0 to HBM is skipped
+  p.l0_fold = p.fused && (a->flags & DIFUSCO_FLAG_NO_L0_FOLD) == 0 && !ablating && (p.tsp ? a->xt_is_binary != 0 : true);
+  // last layer (at least two layers).  TSP: the fused kernel also emits the head's GroupNorm partial sums per tile and
+  // skips the node update nobody reads; MIS: it skips the edge output nobody reads.
+  p.tail_fold = p.fused && p.L >= 2 && (a->flags & DIFUSCO_FLAG_NO_TAIL_FOLD) == 0 && !ablating;
+  p.gn_fold = p.tail_fold && p.tsp;
+  // prepared state (TSP, fused path only; anything else recomputes - the stateless step is always correct)
+  p.use_prep = a->prepared != nullptr && p.fused && p.tsp && !ablating;
+  return p;
+}
+
+// ---- pieces that difusco_prepare shares with the step: the same kernels on the same operands, `dst` in the workspace or in the
+// prepared buffer ------------------------------------------------------------------------------------
+// per-layer time bias rows of n_t diffusion times (HOST array): tbias[i][l][:] = time_layer_l(time_embed(timestep_embedding(t_i)))
+hipError_t time_bias_rows(const Weights& w, int H, int L, const float* t_host, int n_t, float* out, hipStream_t st) {
+  const int64_t* l0 = w.lo.off.data() + DIFUSCO_W_GLOBAL_COUNT;      // layer 0's tensors; the others follow at layer_stride
+  return difusco::launch_time_bias(t_host, n_t, H, L, w.g(DIFUSCO_W_TIME_FREQS), w.g(DIFUSCO_W_TIME0_W), w.g(DIFUSCO_W_TIME0_B),
+                                   w.g(DIFUSCO_W_TIME2_W), w.g(DIFUSCO_W_TIME2_B), w.base + l0[0], w.lo.layer_stride,
+                                   l0[DIFUSCO_WL_TIME_W] - l0[0], l0[DIFUSCO_WL_TIME_B] - l0[0], out, st);
+}
+
+// h0 = node_embed(pos_embed(points))  (gnn_encoder.py:394); `feat`: [N,H] scratch for the sinusoidal features
+int embed_tsp_nodes(const Weights& w, int H, int64_t N, const float* points, float* feat, float* h0, hipStream_t st, bool prof) {
+  PROF_IF(prof, PROF_EMBED, launch_pos_embed(points, w.g(DIFUSCO_W_DIMT_POS), (int)N, H, feat, st))
+  PROF_IF(prof, PROF_LINEAR_NODE, linear_rows(feat, w.g(DIFUSCO_W_NODE_EMBED_W), w.g(DIFUSCO_W_NODE_EMBED_B), nullptr, h0, N, H, H, H, st))
+  return DIFUSCO_OK;
+}
+
+// U | V | A | B rows of h for one layer -> dst [N,4H].  scale_pass: compute the row scales of h (fp16 planes) here - they are left by
+// node_finalize of the previous layer on the fused path.  fused_domain: the rows are read by the fused edge kernel, i.e. A | B in
+// its log2(e) domain with b_C folded into the A rows (difusco_hip.h, ABI 11 note): the node linear of a precision with a fused
+// path writes them so (fused bias / column-scale vectors); any other precision computes the reference's rows and converts them in
+// place, so that a prepared buffer is in the kernel's domain WHATEVER precision prepared it.
+int node_rows(int precision, int H, int64_t N, const LayerW& lw, const float* h, float* hscale, bool scale_pass, bool fused_domain,
+              float* dst, hipStream_t st, bool prof) {
+  const int nprec = precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : precision;
+  const bool f16 = nprec == DIFUSCO_PREC_FP16X3;
+  bool converted = false;      // rows already in the fused kernel's domain
+  if (precision != DIFUSCO_PREC_FP32 && H == 256) {   // node rows on the same split-precision matrix-core path
+    const SplitPlanes np = split_planes(lw.node4_planes, 4 * H, H, f16);
+    SplitScale sc;
+    if (f16) {
+      if (scale_pass) PROF_IF(prof, PROF_LINEAR_NODE, launch_row_pow2_scale(h, N, H, hscale, st))
+      sc.row_scale = hscale;
+      sc.w_inv = np.w_inv;
+    }
+    converted = fused_domain && (nprec == DIFUSCO_PREC_BF16X3 || nprec == DIFUSCO_PREC_FP16X3);
+    if (converted) sc.w_inv = lw.node4_fused_s + (f16 ? 0 : 4 * H);
+    PROF_IF(prof, PROF_LINEAR_NODE, linear_rows_split(h, np.planes, (long long)4 * H * H, nprec, converted ? lw.node4_fused_b : lw.node4_b,
+                                                      nullptr, dst, N, H, 4 * H, 4 * H, st, 0, sc))
+  } else {
+    PROF_IF(prof, PROF_LINEAR_NODE, linear_rows(h, lw.node4_w, lw.node4_b, nullptr, dst, N, H, 4 * H, 4 * H, st))
+  }
+  if (fused_domain && !converted && H == 256) PROF_IF(prof, PROF_LINEAR_NODE, launch_fuse_node_tables(dst, lw.c_b, (int)N, dst, st))
+  return DIFUSCO_OK;
+}
+
+// C of layer 0 on the two rows of the edge-input table (table rows 0, 1 -> rows 2, 3; layer-0 fold of the fused step and
+// difusco_prepare).  Exact fp32, except under FP16X1: there the one-product fp16 linear that the fused kernel's GEMM 1 applies to
+// an e tile (each row scaled by its power of two, the hi plane of C), so that folding layer 0 keeps the precision's contract.
+// scale2: two floats of scratch.
+hipError_t table_c_rows(int precision, int H, float* table, const LayerW& lw, float* scale2, hipStream_t st) {
+  if (precision != DIFUSCO_PREC_FP16X1) return launch_two_rows_linear(H, table, lw.c_w, nullptr, table + 2 * H, st);
+  hipError_t er = launch_row_pow2_scale(table, 2, H, scale2, st);
+  if (er != hipSuccess) return er;
+  const SplitPlanes cp = split_planes(lw.c_planes, H, H, true);
+  SplitScale sc;
+  sc.row_scale = scale2;
+  sc.w_inv = cp.w_inv;
+  return linear_rows_split(table, cp.planes, (long long)H * H, DIFUSCO_PREC_FP16X1, nullptr, nullptr, table + 2 * H, 2, H, H, H, st, 0, sc);
+}
+
+// two-row edge-input table of a categorical TSP step (the embedding of the bit x_t, gnn_encoder.py:395) -> table rows 0, 1;
+// with_c: C of layer 0 applied to it -> rows 2, 3.  table_in: [2,H] scratch.
+int edge_input_table(int precision, int H, const Weights& w, float* table_in, float* table, bool with_c, hipStream_t st, bool prof) {
+  PROF_IF(prof, PROF_EMBED, launch_scalar_embed(nullptr, nullptr, w.g(DIFUSCO_W_DIMT_SCALAR), 2, H, table_in, st))
+  PROF_IF(prof, PROF_EMBED, launch_two_rows_linear(H, table_in, w.g(DIFUSCO_W_EDGE_EMBED_W), w.g(DIFUSCO_W_EDGE_EMBED_B), table, st))
+  if (with_c) PROF_IF(prof, PROF_EMBED, table_c_rows(precision, H, table, w.layer(0), table_in, st))
+  return DIFUSCO_OK;
+}
+
+// ---- one step: what every stage reads, and the stages in launch order ------------------------------------
+struct Step {
+  const difusco_step_args* a;
+  StepPlan p;
+  int H;
+  Workspace ws;
+  Prepared prep;
+  Weights w;
+  const float* tbias;      // [L,H] time-bias rows of this t: the caller's, or ws.tbias
+  const float* table;      // two-row edge-input table (+ C of layer 0 applied to it): prepared or ws.table
+  hipStream_t st;
+
+  // E-row linear of the unfused sequence: exact fp32 MFMA or split planes, same contract (mode: the precision of this product)
+  hipError_t edge_linear(int mode, const float* x, const float* w, const float* planes, const float* b,
+                         const float* res, float* y) const {
+    if (mode == DIFUSCO_PREC_FP32) return linear_rows(x, w, b, res, y, p.E, H, H, H, st);
+    const SplitPlanes sp = split_planes(planes, H, H, f16_planes(mode));
+    SplitScale sc;
+    if (f16_planes(mode)) {
+      // fp16 planes: per-row power-of-two scale of x (one extra pass over x on this unfused path), weight inverse scales
+      hipError_t er = launch_row_pow2_scale(x, p.E, H, ws.escale, st);
+      if (er != hipSuccess) return er;
+      sc.row_scale = ws.escale;
+      sc.w_inv = sp.w_inv;
+    }
+    return linear_rows_split(x, sp.planes, (long long)H * H, mode, b, res, y, p.E, H, H, H, st, 0, sc);
+  }
+
+  // the pad lanes of e's last tiles must read as zero in every later kernel of the fused path (zero bytes when E fills its tiles)
+  hipError_t zero_pad_tail() const {
+    const int64_t done = (p.E / 32) * 32;
+    return zero_async(ws.e + done * H, sizeof(float) * (p.E_pad - done) * H, st);
+  }
+
+  // input embeddings of a TSP step (gnn_encoder.py:394-395).  ws.node4 doubles as scratch for the sinusoidal node features before
+  // the first layer overwrites it.
+  int embed_tsp() const {
+    if (!p.use_prep) STAGE(embed_tsp_nodes(w, H, p.N, a->points, ws.node4, ws.h, st, true));
+    if (p.fused) PROF(PROF_EMBED, zero_pad_tail())
+    if (a->xt_is_binary) {
+      // (l0_fold: e0 and C e0 are read from the table by the first fused layer)
+      if (!p.use_prep) STAGE(edge_input_table(a->precision, H, w, ws.table_in, ws.table, p.l0_fold, st, true));
+      if (p.l0_fold) return DIFUSCO_OK;
+      if (p.fused) {
+        PROF(PROF_EMBED, launch_table_rows_tiled(a->xt, a->perm, table, p.E, ws.e, st))
+        if (p.f16) PROF(PROF_EMBED, launch_tile_absmax_tiled(ws.e, p.n_tiles_pad, ws.etmax, st))
+      } else {
+        PROF(PROF_EMBED, launch_table_rows(a->xt, a->perm, table, p.E, H, ws.e, st))
+      }
+    } else if (p.fused) {   // sinusoidal features generated inside the linear: the E x H embedding never exists in memory
+      const SplitPlanes ep = split_planes(w.g(DIFUSCO_W_EDGE_EMBED_PLANES), H, H, p.f16);
+      PROF(PROF_EMBED, launch_edge_embed_tiled(a->xt, a->perm, w.g(DIFUSCO_W_DIMT_SCALAR), ep.planes, (long long)H * H, p.nprec, ep.w_inv,
+                                               w.g(DIFUSCO_W_EDGE_EMBED_B), ws.e, p.E, p.f16 ? ws.etmax : nullptr, st, a->gen_table,
+                                               a->gen_table ? reinterpret_cast<int*>(ws.escale) : nullptr))      // (escale: unfused path only - free here)
+    } else {
+      PROF(PROF_EMBED, launch_scalar_embed(a->xt, a->perm, w.g(DIFUSCO_W_DIMT_SCALAR), p.E, H, ws.tmp, st))
+      PROF(PROF_LINEAR_EDGE, edge_linear(p.nprec, ws.tmp, w.g(DIFUSCO_W_EDGE_EMBED_W), w.g(DIFUSCO_W_EDGE_EMBED_PLANES),
+                                         w.g(DIFUSCO_W_EDGE_EMBED_B), nullptr, ws.e))
+    }
+    return DIFUSCO_OK;
+  }
+
+  // input embeddings of a MIS step (gnn_encoder.py:405-407): h from x_t, e = zeros
+  int embed_mis() const {
+    PROF(PROF_EMBED, launch_scalar_embed(a->xt, nullptr, w.g(DIFUSCO_W_DIMT_SCALAR), p.N, H, ws.node4, st))
+    PROF(PROF_LINEAR_NODE, linear_rows(ws.node4, w.g(DIFUSCO_W_NODE_EMBED_W), w.g(DIFUSCO_W_NODE_EMBED_B), nullptr, ws.h, p.N, H, H, H, st))
+    if (p.l0_fold) {   // e = zeros comes from an all-zero table; only the pad tail must read as zero
+      PROF(PROF_EMBED, zero_async(ws.table, sizeof(float) * 4 * H, st))
+      PROF(PROF_EMBED, zero_pad_tail())
+    } else if (p.E > 0) {
+      PROF(PROF_EMBED, zero_async(ws.e, sizeof(float) * (p.fused ? p.E_pad : p.E) * H, st))
+      if (p.fused && p.f16) PROF(PROF_EMBED, zero_async(ws.etmax, sizeof(float) * p.n_tiles_pad, st))
+    }
+    return DIFUSCO_OK;
+  }
+
+  // edge pass + node update of layer l on the fused path: one launch record, the kind says what the step still needs from the layer
+  int fused_layer(int l, const LayerW& lw, const float* node4, const float* h_in) const {
+    const float* tb = tbias + (size_t)l * H;
+    FusedLayerArgs fa;
+    fa.e = ws.e, fa.node4 = node4, fa.row = a->row, fa.col = a->col, fa.n_edges = (int)p.E;
+    fa.c_planes = split_planes(lw.c_planes, H, H, p.f16).planes;      // (FP16X1: the hi plane of FP16X3's pair)
+    fa.o_planes = split_planes(lw.out_planes, H, H, p.f16).planes;
+    fa.plane_stride = (long long)H * H;
+    fa.b_c = lw.c_b, fa.g_e = lw.norm_e_w, fa.b_e = lw.norm_e_b, fa.tbias = tb;
+    fa.g_o = lw.out_ln_w, fa.b_o = lw.out_ln_b, fa.b_out = lw.out_b;
+    fa.time_on_edge = p.tsp ? 1 : 0;
+    fa.part = ws.part, fa.direct = ws.direct, fa.scales = lw.fused_scales, fa.stream = st;
+    FusedKind kind = FusedKind::Middle;
+    if (l == 0 && p.l0_fold) {
+      kind = FusedKind::FirstFromTable;
+      fa.l0_table = table, fa.l0_x = p.tsp ? a->xt : nullptr, fa.l0_perm = p.tsp ? a->perm : nullptr;
+      fa.etmax_out = ws.etmax;
+    } else if (p.tail_fold && l == p.L - 1) {
+      kind = p.tsp ? FusedKind::TailTsp : FusedKind::TailMis;
+      fa.gn_tile = ws.gn_tile, fa.etmax_in = ws.etmax;
+    } else {
+      fa.etmax_in = fa.etmax_out = ws.etmax;
+    }
+    PROF(PROF_LINEAR_EDGE, launch_edge_layer_fused(a->precision, kind, p.fused_variant, fa))
+    if (p.gn_fold && l == p.L - 1) return DIFUSCO_OK;     // TSP: h is not read after the last layer
+#ifdef DIFUSCO_PROFILING
+    if (g_step_skip & 1) return DIFUSCO_OK;      // (timing only, WRONG results: what any fold of node_finalize could save at most)
+#endif
+    PROF(PROF_GATE, launch_node_finalize((int)p.N, (int)p.E, a->rowptr, node4, ws.part, ws.direct, ws.h, lw.norm_h_w, lw.norm_h_b, tb,
+                                         p.tsp ? 1 : 0, p.f16 ? ws.hscale : nullptr, st, h_in, a->aggregation))
+    return DIFUSCO_OK;
+  }
+
+  // the same layer as three launches: C e, gate + aggregation + norms, per_layer_out (+ residual)
+  int unfused_layer(int l, const LayerW& lw) const {
+    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.e, lw.c_w, lw.c_planes, lw.c_b, nullptr, ws.tmp))
+    PROF(PROF_GATE, launch_edge_gate_aggregate(H, (int)p.N, a->rowptr, a->col, ws.node4, ws.tmp, ws.h, lw.norm_h_w, lw.norm_h_b,
+                                               lw.norm_e_w, lw.norm_e_b, lw.out_ln_w, lw.out_ln_b, tbias + (size_t)l * H,
+                                               p.tsp ? 1 : 0, st, a->aggregation))
+    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.tmp, lw.out_w, lw.out_planes, lw.out_b, ws.e, ws.e))
+    return DIFUSCO_OK;
+  }
+
+  // the GNN layers (gnn_encoder.py:425-449)
+  int run_layers() const {
+    for (int l = 0; l < p.L; ++l) {
+      const LayerW lw = w.layer(l);
+      // layer 0 of a step with prepared state: U|V|A|B of h0 and h0 itself come from the prepared buffer
+      const bool prep_l = p.use_prep && l == 0;
+      bool node_linear = !prep_l;
+#ifdef DIFUSCO_PROFILING
+      if ((g_step_skip & 2) && l >= 2) node_linear = false;      // (timing only, WRONG results: no node-linear launches from layer 2 on)
+#endif
+      if (node_linear)
+        STAGE(node_rows(a->precision, H, p.N, lw, ws.h, ws.hscale, !p.fused || l == 0, p.fused, ws.node4, st, true));
+      STAGE(p.fused ? fused_layer(l, lw, prep_l ? prep.node4_0 : ws.node4, prep_l ? prep.h0 : nullptr) : unfused_layer(l, lw));
+    }
+    return DIFUSCO_OK;
+  }
+
+  // head + posterior (gnn_encoder.py:400-401 / :412-413, pl_tsp_model.py:133-137, pl_meta_model.py:102-175)
+  int run_head(const uint64_t* offset_shift) const {
+    RandInstances ri;
+    if (a->rand_mode == DIFUSCO_RAND_PHILOX_INSTANCES) ri = RandInstances{a->n_instances, a->instance_rows, a->instance_seeds};
+    const int* seg_ptr = a->n_segments > 1 ? a->seg_ptr : nullptr;
+    const int nblk = gn_blocks_for(p.out_rows);
+    if (p.fused && p.tsp) {
+      PROF(PROF_HEAD, launch_head_tiled(p.C, ws.e, p.E, nblk < 8 ? 8 : nblk / 8 * 8, ws.partial, ws.stats, w.g(DIFUSCO_W_OUT_GN_W),
+                                        w.g(DIFUSCO_W_OUT_GN_B), w.g(DIFUSCO_W_OUT_CONV_W), w.g(DIFUSCO_W_OUT_CONV_B), a->perm, a->xt,
+                                        a->post, a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
+                                        p.gn_fold ? ws.gn_tile : nullptr, a->gn_phase, a->gn_sums, seg_ptr, a->n_segments, ri,
+                                        offset_shift))
+      return DIFUSCO_OK;
+    }
+    PROF(PROF_HEAD, launch_head(H, p.C, p.tsp ? ws.e : ws.h, seg_ptr, a->n_segments, p.out_rows, nblk, ws.partial, ws.stats,
+                                w.g(DIFUSCO_W_OUT_GN_W), w.g(DIFUSCO_W_OUT_GN_B), w.g(DIFUSCO_W_OUT_CONV_W), w.g(DIFUSCO_W_OUT_CONV_B),
+                                p.tsp ? a->perm : nullptr, a->xt, a->post, a->rand_mode, a->rand, a->seed, a->offset, a->xt_out,
+                                a->pred_out, a->prob_out, st, a->gn_phase, a->gn_sums, ri, offset_shift))
+    return DIFUSCO_OK;
+  }
+
+  // DIFUSCO_FLAG_CHECK_FINITE: count inf / nan in the outputs (the statistics scratch is free after the head), synchronise
+  int check_finite() const {
+    if ((a->flags & DIFUSCO_FLAG_CHECK_FINITE) == 0 || a->gn_phase == 1) return DIFUSCO_OK;
+    unsigned* cnt = reinterpret_cast<unsigned*>(ws.partial);
+    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned), st));
+    HIP_TRY(launch_count_nonfinite(a->xt_out, p.out_rows, cnt, st));
+    // head GroupNorm mean / rstd: nan as soon as the final state holds one (a sampled bit hides it)
+    HIP_TRY(launch_count_nonfinite(ws.stats, (long long)a->n_segments * 64, cnt, st));
+    HIP_TRY(launch_count_nonfinite(a->pred_out, p.out_rows * p.C, cnt, st));
+    HIP_TRY(launch_count_nonfinite(a->prob_out, a->diffusion == DIFUSCO_CATEGORICAL ? p.out_rows : 0, cnt, st));
+    unsigned bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad) return fail(DIFUSCO_ENONFINITE, "denoise step produced %u non-finite output values", bad);
+    return DIFUSCO_OK;
+  }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -264,19 +608,13 @@ size_t difusco_workspace_bytes(int hidden, int n_layers, int n_nodes, int n_edge
 int difusco_denoise_step(const difusco_step_args* a) { return difusco_denoise_step_shifted(a, nullptr); }
 
 int difusco_denoise_step_shifted(const difusco_step_args* a, const uint64_t* offset_shift) {
-  using namespace difusco;
   if (!a) return fail(DIFUSCO_EINVAL, "null args");
-  if (a->struct_size != sizeof(difusco_step_args) || a->abi_version != DIFUSCO_ABI_VERSION)
-    return fail(DIFUSCO_EINVAL, "ABI mismatch: struct_size %u (want %zu), abi %u (want %d)", a->struct_size,
-                sizeof(difusco_step_args), a->abi_version, DIFUSCO_ABI_VERSION);
-  const int H = a->hidden, L = a->n_layers, C = a->out_channels;
-  if (!hidden_ok(H)) return fail(DIFUSCO_EINVAL, "hidden must be 64, 128 or 256 (got %d)", H);
-  if (L < 1) return fail(DIFUSCO_EINVAL, "n_layers must be >= 1");
+  STAGE(validate_header(a));
   if (a->task != DIFUSCO_TASK_TSP && a->task != DIFUSCO_TASK_MIS) return fail(DIFUSCO_EINVAL, "unknown task %d", a->task);
   if (a->diffusion != DIFUSCO_CATEGORICAL && a->diffusion != DIFUSCO_GAUSSIAN)
     return fail(DIFUSCO_EINVAL, "unknown diffusion %d", a->diffusion);
-  if (C != (a->diffusion == DIFUSCO_CATEGORICAL ? 2 : 1))
-    return fail(DIFUSCO_EINVAL, "out_channels %d does not match diffusion type", C);
+  if (a->out_channels != (a->diffusion == DIFUSCO_CATEGORICAL ? 2 : 1))
+    return fail(DIFUSCO_EINVAL, "out_channels %d does not match diffusion type", a->out_channels);
   const int64_t N = a->n_nodes, E = a->n_edges;
   if (N <= 0 || E < 0) return fail(DIFUSCO_EINVAL, "n_nodes must be > 0, n_edges >= 0");
   if (!a->weights || !a->rowptr || (E > 0 && !a->col) || !a->xt || !a->xt_out || !a->workspace)
@@ -295,271 +633,29 @@ int difusco_denoise_step_shifted(const difusco_step_args* a, const uint64_t* off
     return fail(DIFUSCO_EINVAL, "unknown aggregation %d (DIFUSCO_AGG_SUM / MEAN / MAX)", a->aggregation);
   if (a->gn_phase != 0 && (a->n_segments != 1 || !a->gn_sums))
     return fail(DIFUSCO_EINVAL, "gn_phase %d needs n_segments == 1 and a gn_sums buffer of 65 doubles", a->gn_phase);
-  const bool head_only = a->gn_phase == 2;   // everything up to the statistics was done by the phase-1 call
-  const bool needs_draw = a->post[4] != 0.0f;
-  if (needs_draw && a->rand_mode == DIFUSCO_RAND_NONE)
+  if (a->post[4] != 0.0f && a->rand_mode == DIFUSCO_RAND_NONE)
     return fail(DIFUSCO_EINVAL, "this step draws random numbers: rand_mode must not be NONE");
 
-  const bool tsp = a->task == DIFUSCO_TASK_TSP;
-  const int64_t out_rows = tsp ? E : N;
-  const int nblk = gn_blocks_for(E > N ? E : N);
-  Workspace ws = carve(a->workspace, H, L, N, E, a->n_segments, nblk);
+  const StepPlan p = make_plan(a);
+  const Workspace ws = carve(a->workspace, p.H, p.L, N, E, a->n_segments, gn_blocks_for(E > N ? E : N));
   if (ws.bytes > a->workspace_bytes)
     return fail(DIFUSCO_EWORKSPACE, "workspace too small: %zu < %zu", a->workspace_bytes, ws.bytes);
-
-  const Layout lo = make_layout(H, L, C);
-  const float* W = a->weights;
-  auto G = [&](int id) { return W + lo.off[id]; };
-  auto LW = [&](int l, int id) { return W + lo.off[DIFUSCO_W_GLOBAL_COUNT + l * DIFUSCO_WL_COUNT + id]; };
-  hipStream_t st = (hipStream_t)a->stream;
-  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X1)
-    return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
-  // FP16X1: only the edge-row GEMMs of the layers (C, per_layer_out[l][2]) take the one-product form; every other matrix product
-  // (edge embedding, node linears) runs as FP16X3 - nprec is the precision of those
-  const int nprec = a->precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : a->precision;
-  // E-row linear: exact fp32 MFMA or bf16 split planes, same contract (mode: the precision of this product)
-  auto edge_linear = [&](int mode, const float* x, const float* w, const float* planes, const float* b, const float* res,
-                         float* y) -> hipError_t {
-    if (mode == DIFUSCO_PREC_FP32) return linear_rows(x, w, b, res, y, E, H, H, H, st);
-    const unsigned short* pl = reinterpret_cast<const unsigned short*>(planes);
-    SplitScale sc;
-    if (mode == DIFUSCO_PREC_FP16X3 || mode == DIFUSCO_PREC_FP16X1) {
-      pl += (long long)3 * H * H;   // fp16 planes follow the 3 bf16 planes
-      // fp16 planes: per-row power-of-two scale of x (one extra pass over x on this unfused path), weight inverse scales
-      hipError_t er = launch_row_pow2_scale(x, E, H, ws.escale, st);
-      if (er != hipSuccess) return er;
-      sc.row_scale = ws.escale;
-      sc.w_inv = planes + (long long)5 * H * H / 2;
-    }
-    return linear_rows_split(x, pl, (long long)H * H, mode, b, res, y, E, H, H, H, st, 0, sc);
-  };
-
-  // PROF(category, call): HIP_TRY(call), bracketed by a pair of HIP events on `st` when profiling is on
-#define PROF(cat, call)      \
-  {                          \
-    ProfScope ps_(cat, st);  \
-    HIP_TRY(call);           \
-  }
-
-  // fused edge-layer path: H = 256, 16-bit split planes, one GroupNorm statistic segment; e is then kept in the
-  // tiled layout (kernels.h: edge_tiled_offset) from the embedding to the head
-  // (per-sample statistic segments - the dense mode of TSP-50 / 100 with parallel_sampling > 1 - run the same fused layers;
-  // only the head differs: masked per-segment statistics and a per-row segment look-up, launch_head_tiled)
-  // the full-line neighbour-table gathers address node rows by 32-bit byte offsets (4 KB per node): calls with 2^20 nodes or
-  // more take the register-gather instantiation of the same kernel (64-bit addresses, bit-identical results, ~3 % slower)
-  const int reg_gather = N >= (1 << 20) ? 1 : 0;
-  // aggregation = max has fused instantiations of its own (the per-tile pieces are maxima) for the full-line gather form only:
-  // with 2^20 nodes or more it takes the unfused sequence
-  const bool agg_max = a->aggregation == DIFUSCO_AGG_MAX;
-  const bool fused = H == 256 && !a->no_fusion && E > 0 && !(agg_max && reg_gather) &&
-                     (a->precision == DIFUSCO_PREC_BF16X3 || a->precision == DIFUSCO_PREC_FP16X3 ||
-                      a->precision == DIFUSCO_PREC_FP16X1);
-  if (fused && !a->row) return fail(DIFUSCO_EINVAL, "the fused edge-layer kernel needs args->row");
-  const int fused_variant = reg_gather | (agg_max ? 2 : 0);      // (launch_by_mode, edge_layer.hip)
-  const int64_t E_pad = (E + 255) / 256 * 256;
-  // first layer: when the edge input is a table lookup (categorical TSP: embedding of the bit; MIS: zeros) the fused
-  // kernel takes it from the table and the pass that would write e0 to HBM is skipped
-  // last layer (at least two layers).  TSP: the fused kernel also emits the head's GroupNorm partial sums per tile and
-  // skips the node update nobody reads; MIS: it skips the edge output nobody reads.
-#ifdef DIFUSCO_PROFILING
-  const bool ablating = difusco::g_fused_ablate != 0;
-#else
-  const bool ablating = false;
-#endif
-  const bool tail_fold = fused && L >= 2 && (a->flags & DIFUSCO_FLAG_NO_TAIL_FOLD) == 0 && !ablating;
-  const bool gn_fold = tail_fold && tsp;
-  const bool l0_fold = fused && (a->flags & DIFUSCO_FLAG_NO_L0_FOLD) == 0 && !ablating &&
-                       (tsp ? a->xt_is_binary != 0 : true);
-  const bool f16 = nprec == DIFUSCO_PREC_FP16X3;      // fp16 planes (FP16X3 or FP16X1): operand scales are kept
-  const int64_t n_tiles_pad = E_pad / 32;
-  // prepared state (TSP, fused path only; anything else recomputes - the stateless step is always correct)
-  const bool use_prep = a->prepared != nullptr && fused && tsp && !ablating;
-  const Prepared prep = carve_prepared(const_cast<void*>(a->prepared), H, N);
-  const float* table = use_prep ? prep.table : ws.table;      // two-row edge-input table (+ C of layer 0 applied to it)
-  if (tsp && !a->points && !use_prep && !head_only)
+  if (p.fused && !a->row) return fail(DIFUSCO_EINVAL, "the fused edge-layer kernel needs args->row");
+  if (p.tsp && !a->points && !p.use_prep && !p.head_only)
     return fail(DIFUSCO_EINVAL, "TSP needs points (only a fused-path step with prepared state runs without them)");
+  const Prepared prep = carve_prepared(const_cast<void*>(a->prepared), p.H, N);
+  hipStream_t st = (hipStream_t)a->stream;
+  const Step s{a, p, p.H, ws, prep, Weights(a->weights, p.H, p.L, p.C),
+               a->tbias ? a->tbias : ws.tbias,      // (caller-prepared rows of this t, or computed here)
+               p.use_prep ? prep.table : ws.table, st};
 
-  // per-layer time bias rows: time_layer_l(time_embed(timestep_embedding(t)))   [L,H]
-  const float* tbias = a->tbias ? a->tbias : ws.tbias;      // (caller-prepared rows of this t, or computed here)
-  if (!head_only && !a->tbias)
-  PROF(PROF_EMBED, launch_time_bias(&a->t, 1, H, L, G(DIFUSCO_W_TIME_FREQS), G(DIFUSCO_W_TIME0_W), G(DIFUSCO_W_TIME0_B),
-                                    G(DIFUSCO_W_TIME2_W), G(DIFUSCO_W_TIME2_B), LW(0, 0), lo.layer_stride,
-                                    lo.off[DIFUSCO_W_GLOBAL_COUNT + DIFUSCO_WL_TIME_W] - lo.off[DIFUSCO_W_GLOBAL_COUNT],
-                                    lo.off[DIFUSCO_W_GLOBAL_COUNT + DIFUSCO_WL_TIME_B] - lo.off[DIFUSCO_W_GLOBAL_COUNT],
-                                    ws.tbias, st))
-
-  // input embeddings (gnn_encoder.py:394-395 TSP, :405-407 MIS).  node4 doubles as scratch for the
-  // sinusoidal node features before the first layer overwrites it.
-  if (head_only) {
-    // (phase 2: e / h of the phase-1 call are still in the workspace)
-  } else if (tsp) {
-    if (!use_prep) {
-      PROF(PROF_EMBED, launch_pos_embed(a->points, G(DIFUSCO_W_DIMT_POS), (int)N, H, ws.node4, st))
-      PROF(PROF_LINEAR_NODE, linear_rows(ws.node4, G(DIFUSCO_W_NODE_EMBED_W), G(DIFUSCO_W_NODE_EMBED_B), nullptr, ws.h, N,
-                                         H, H, H, st))
-    }
-    if (fused)   // pad lanes of the last tiles must read as zero in every later kernel
-      PROF(PROF_EMBED, zero_async(ws.e + (E / 32) * 32 * H, sizeof(float) * (E_pad - (E / 32) * 32) * H, st))
-    if (a->xt_is_binary) {
-      if (!use_prep) {
-        PROF(PROF_EMBED, launch_scalar_embed(nullptr, nullptr, G(DIFUSCO_W_DIMT_SCALAR), 2, H, ws.table_in, st))
-        PROF(PROF_EMBED, launch_two_rows_linear(H, ws.table_in, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_B), ws.table,
-                                                st))
-      }
-      if (l0_fold) {   // e0 and C e0 are read from the table by the first fused layer: C on the two rows (table_c_rows)
-        if (!use_prep)
-          PROF(PROF_EMBED, table_c_rows(a->precision, H, ws.table, LW(0, DIFUSCO_WL_C_W), LW(0, DIFUSCO_WL_C_PLANES), ws.table_in, st))
-      }
-      else if (fused) {
-        PROF(PROF_EMBED, launch_table_rows_tiled(a->xt, a->perm, table, E, ws.e, st))
-        if (f16) PROF(PROF_EMBED, launch_tile_absmax_tiled(ws.e, n_tiles_pad, ws.etmax, st))
-      }
-      else PROF(PROF_EMBED, launch_table_rows(a->xt, a->perm, table, E, H, ws.e, st))
-    } else {
-      if (fused) {   // sinusoidal features generated inside the linear: the E x H embedding never exists in memory
-        const unsigned short* pl = reinterpret_cast<const unsigned short*>(G(DIFUSCO_W_EDGE_EMBED_PLANES)) +
-                                   (f16 ? (long long)3 * H * H : 0);
-        PROF(PROF_EMBED, launch_edge_embed_tiled(a->xt, a->perm, G(DIFUSCO_W_DIMT_SCALAR), pl, (long long)H * H, nprec,
-                                                 f16 ? G(DIFUSCO_W_EDGE_EMBED_PLANES) + (long long)5 * H * H / 2 : nullptr,
-                                                 G(DIFUSCO_W_EDGE_EMBED_B), ws.e, E, f16 ? ws.etmax : nullptr, st, a->gen_table,
-                                                 a->gen_table ? reinterpret_cast<int*>(ws.escale) : nullptr))      // (escale: unfused path only - free here)
-      } else {
-        PROF(PROF_EMBED, launch_scalar_embed(a->xt, a->perm, G(DIFUSCO_W_DIMT_SCALAR), E, H, ws.tmp, st))
-        PROF(PROF_LINEAR_EDGE, edge_linear(nprec, ws.tmp, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_PLANES),
-                                           G(DIFUSCO_W_EDGE_EMBED_B), nullptr, ws.e))
-      }
-    }
-  } else {
-    PROF(PROF_EMBED, launch_scalar_embed(a->xt, nullptr, G(DIFUSCO_W_DIMT_SCALAR), N, H, ws.node4, st))
-    PROF(PROF_LINEAR_NODE, linear_rows(ws.node4, G(DIFUSCO_W_NODE_EMBED_W), G(DIFUSCO_W_NODE_EMBED_B), nullptr, ws.h, N,
-                                       H, H, H, st))
-    if (l0_fold) {   // e = zeros (gnn_encoder.py:407) comes from an all-zero table; only the pad tail must read as zero
-      PROF(PROF_EMBED, zero_async(ws.table, sizeof(float) * 4 * H, st))
-      PROF(PROF_EMBED, zero_async(ws.e + (E / 32) * 32 * H, sizeof(float) * (E_pad - (E / 32) * 32) * H, st))
-    } else if (E > 0) {
-      PROF(PROF_EMBED, zero_async(ws.e, sizeof(float) * (fused ? E_pad : E) * H, st))
-      if (fused && f16) PROF(PROF_EMBED, zero_async(ws.etmax, sizeof(float) * n_tiles_pad, st))
-    }
+  if (!p.head_only) {      // (phase 2: e / h of the phase-1 call are still in the workspace)
+    if (!a->tbias) PROF(PROF_EMBED, time_bias_rows(s.w, p.H, p.L, &a->t, 1, ws.tbias, st))
+    STAGE(p.tsp ? s.embed_tsp() : s.embed_mis());
+    STAGE(s.run_layers());
   }
-
-  // the GNN layers (gnn_encoder.py:425-449)
-  const long long split_off = f16 ? (long long)3 * H * H : 0;  // fp16 planes follow bf16 (FP16X1: the hi plane of FP16X3's pair)
-  for (int l = 0; l < (head_only ? 0 : L); ++l) {
-    // layer 0 of a step with prepared state: U|V|A|B of h0 and h0 itself come from the prepared buffer
-    const bool prep_l = use_prep && l == 0;
-    const float* node4 = prep_l ? prep.node4_0 : ws.node4;
-    if (prep_l) {
-    } else
-#ifdef DIFUSCO_PROFILING
-    if ((g_step_skip & 2) && l >= 2) {      // (timing only, WRONG results: the node linear's launches from layer 2 on are skipped)
-    } else
-#endif
-    if (a->precision != DIFUSCO_PREC_FP32 && H == 256) {   // node rows on the same split-precision matrix-core path
-      const unsigned short* npl = reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_NODE4_PLANES)) +
-                                  (f16 ? (long long)3 * 4 * H * H : 0);
-      SplitScale sc;
-      if (f16) {   // row scales of h: left by node_finalize of the previous layer on the fused path, computed here otherwise
-        if (!fused || l == 0) PROF(PROF_LINEAR_NODE, launch_row_pow2_scale(ws.h, N, H, ws.hscale, st))
-        sc.row_scale = ws.hscale;
-        sc.w_inv = LW(l, DIFUSCO_WL_NODE4_PLANES) + (long long)5 * 4 * H * H / 2;
-      }
-      // fused edge kernel: A | B rows in its log2(e) domain, b_C folded into the A rows (difusco_hip.h, ABI 11 note)
-      if (fused) sc.w_inv = LW(l, DIFUSCO_WL_NODE4_FUSED_S) + (f16 ? 0 : 4 * H);
-      PROF(PROF_LINEAR_NODE, linear_rows_split(ws.h, npl, (long long)4 * H * H, nprec,
-                                               LW(l, fused ? DIFUSCO_WL_NODE4_FUSED_B : DIFUSCO_WL_NODE4_B),
-                                               nullptr, ws.node4, N, H, 4 * H, 4 * H, st, 0, sc))
-    } else {
-      PROF(PROF_LINEAR_NODE, linear_rows(ws.h, LW(l, DIFUSCO_WL_NODE4_W), LW(l, DIFUSCO_WL_NODE4_B), nullptr, ws.node4,
-                                         N, H, 4 * H, 4 * H, st))
-    }
-    if (fused && l == 0 && l0_fold) {
-      PROF(PROF_LINEAR_EDGE,
-           launch_edge_layer_fused_l0(a->precision, ws.e, node4, a->row, a->col, (int)E,
-                                      reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_C_PLANES)) + split_off,
-                                      reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_OUT_PLANES)) + split_off,
-                                      (long long)H * H, LW(l, DIFUSCO_WL_C_B), LW(l, DIFUSCO_WL_NORM_E_W),
-                                      LW(l, DIFUSCO_WL_NORM_E_B), tbias + (size_t)l * H, LW(l, DIFUSCO_WL_OUT_LN_W),
-                                      LW(l, DIFUSCO_WL_OUT_LN_B), LW(l, DIFUSCO_WL_OUT_B), tsp ? 1 : 0, ws.part, ws.direct,
-                                      table, tsp ? a->xt : nullptr, tsp ? a->perm : nullptr,
-                                      LW(l, DIFUSCO_WL_FUSED_SCALES), ws.etmax, st, fused_variant))
-    } else if (fused && tail_fold && l == L - 1) {
-      PROF(PROF_LINEAR_EDGE,
-           launch_edge_layer_fused_tail(a->precision, tsp ? 1 : 2, ws.e, node4, a->row, a->col, (int)E,
-                                      reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_C_PLANES)) + split_off,
-                                      reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_OUT_PLANES)) + split_off,
-                                      (long long)H * H, LW(l, DIFUSCO_WL_C_B), LW(l, DIFUSCO_WL_NORM_E_W),
-                                      LW(l, DIFUSCO_WL_NORM_E_B), tbias + (size_t)l * H, LW(l, DIFUSCO_WL_OUT_LN_W),
-                                      LW(l, DIFUSCO_WL_OUT_LN_B), LW(l, DIFUSCO_WL_OUT_B), tsp ? 1 : 0, ws.part, ws.direct,
-                                      ws.gn_tile, LW(l, DIFUSCO_WL_FUSED_SCALES), ws.etmax, st, fused_variant))
-    } else if (fused) {
-      PROF(PROF_LINEAR_EDGE,
-           launch_edge_layer_fused(a->precision, ws.e, node4, a->row, a->col, (int)E,
-                                   reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_C_PLANES)) + split_off,
-                                   reinterpret_cast<const unsigned short*>(LW(l, DIFUSCO_WL_OUT_PLANES)) + split_off,
-                                   (long long)H * H, LW(l, DIFUSCO_WL_C_B), LW(l, DIFUSCO_WL_NORM_E_W),
-                                   LW(l, DIFUSCO_WL_NORM_E_B), tbias + (size_t)l * H, LW(l, DIFUSCO_WL_OUT_LN_W),
-                                   LW(l, DIFUSCO_WL_OUT_LN_B), LW(l, DIFUSCO_WL_OUT_B), tsp ? 1 : 0, ws.part, ws.direct,
-                                   LW(l, DIFUSCO_WL_FUSED_SCALES), ws.etmax, ws.etmax, st, fused_variant))
-    }
-    if (fused && gn_fold && l == L - 1) continue;     // TSP: h is not read after the last layer
-    if (fused) {
-#ifdef DIFUSCO_PROFILING
-      if (g_step_skip & 1) continue;      // (timing only, WRONG results: what any fold of node_finalize could save at most)
-#endif
-      PROF(PROF_GATE, launch_node_finalize((int)N, (int)E, a->rowptr, node4, ws.part, ws.direct, ws.h,
-                                           LW(l, DIFUSCO_WL_NORM_H_W), LW(l, DIFUSCO_WL_NORM_H_B),
-                                           tbias + (size_t)l * H, tsp ? 1 : 0, f16 ? ws.hscale : nullptr, st,
-                                           prep_l ? prep.h0 : nullptr, a->aggregation))
-      continue;
-    }
-    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.e, LW(l, DIFUSCO_WL_C_W), LW(l, DIFUSCO_WL_C_PLANES), LW(l, DIFUSCO_WL_C_B),
-                                       nullptr, ws.tmp))
-    PROF(PROF_GATE, launch_edge_gate_aggregate(H, (int)N, a->rowptr, a->col, ws.node4, ws.tmp, ws.h,
-                                               LW(l, DIFUSCO_WL_NORM_H_W), LW(l, DIFUSCO_WL_NORM_H_B),
-                                               LW(l, DIFUSCO_WL_NORM_E_W), LW(l, DIFUSCO_WL_NORM_E_B),
-                                               LW(l, DIFUSCO_WL_OUT_LN_W), LW(l, DIFUSCO_WL_OUT_LN_B),
-                                               tbias + (size_t)l * H, tsp ? 1 : 0, st, a->aggregation))
-    PROF(PROF_LINEAR_EDGE, edge_linear(a->precision, ws.tmp, LW(l, DIFUSCO_WL_OUT_W), LW(l, DIFUSCO_WL_OUT_PLANES),
-                                       LW(l, DIFUSCO_WL_OUT_B), ws.e, ws.e))
-  }
-
-  // DIFUSCO_FLAG_CHECK_FINITE: count inf / nan in the outputs (the statistics scratch is free after the head), synchronise
-  auto finish = [&]() -> int {
-    if ((a->flags & DIFUSCO_FLAG_CHECK_FINITE) == 0 || a->gn_phase == 1) return DIFUSCO_OK;
-    unsigned* cnt = reinterpret_cast<unsigned*>(ws.partial);
-    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(unsigned), st));
-    HIP_TRY(launch_count_nonfinite(a->xt_out, out_rows, cnt, st));
-    HIP_TRY(launch_count_nonfinite(ws.stats, (long long)a->n_segments * 64, cnt, st));   // head GroupNorm mean / rstd: nan as soon as the
-                                                                                         // final state holds one (a sampled bit hides it)
-    HIP_TRY(launch_count_nonfinite(a->pred_out, out_rows * C, cnt, st));
-    HIP_TRY(launch_count_nonfinite(a->prob_out, a->diffusion == DIFUSCO_CATEGORICAL ? out_rows : 0, cnt, st));
-    unsigned bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (bad) return fail(DIFUSCO_ENONFINITE, "denoise step produced %u non-finite output values", bad);
-    return DIFUSCO_OK;
-  };
-
-  // head + posterior (gnn_encoder.py:400-401 / :412-413, pl_tsp_model.py:133-137, pl_meta_model.py:102-175)
-  RandInstances rand_instances;
-  if (a->rand_mode == DIFUSCO_RAND_PHILOX_INSTANCES)
-    rand_instances = RandInstances{a->n_instances, a->instance_rows, a->instance_seeds};
-  if (fused && tsp) {
-    PROF(PROF_HEAD, launch_head_tiled(C, ws.e, E, gn_blocks_for(out_rows) < 8 ? 8 : gn_blocks_for(out_rows) / 8 * 8,
-                                      ws.partial, ws.stats, G(DIFUSCO_W_OUT_GN_W), G(DIFUSCO_W_OUT_GN_B),
-                                      G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), a->perm, a->xt, a->post,
-                                      a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
-                                      gn_fold ? ws.gn_tile : nullptr, a->gn_phase, a->gn_sums,
-                                      a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, rand_instances, offset_shift))
-    return finish();
-  }
-  PROF(PROF_HEAD, launch_head(H, C, tsp ? ws.e : ws.h, a->n_segments > 1 ? a->seg_ptr : nullptr, a->n_segments, out_rows,
-                              gn_blocks_for(out_rows), ws.partial, ws.stats, G(DIFUSCO_W_OUT_GN_W), G(DIFUSCO_W_OUT_GN_B),
-                              G(DIFUSCO_W_OUT_CONV_W), G(DIFUSCO_W_OUT_CONV_B), tsp ? a->perm : nullptr, a->xt, a->post,
-                              a->rand_mode, a->rand, a->seed, a->offset, a->xt_out, a->pred_out, a->prob_out, st,
-                              a->gn_phase, a->gn_sums, rand_instances, offset_shift))
-#undef PROF
-  return finish();
+  STAGE(s.run_head(offset_shift));
+  return s.check_finite();
 }
 
 size_t difusco_prepared_bytes(int hidden, int n_nodes) {
@@ -569,17 +665,10 @@ size_t difusco_prepared_bytes(int hidden, int n_nodes) {
 
 int difusco_time_bias_rows(int hidden, int n_layers, int out_channels, const float* weights, const float* t_host, int n_t,
                            float* out, void* stream) {
-  using namespace difusco;
   if (!hidden_ok(hidden) || n_layers < 1 || (out_channels != 1 && out_channels != 2))
     return fail(DIFUSCO_EINVAL, "hidden in {64,128,256}, n_layers >= 1, out_channels in {1,2} required");
   if (!weights || !t_host || !out || n_t < 1) return fail(DIFUSCO_EINVAL, "null pointer or n_t < 1");
-  const Layout lo = make_layout(hidden, n_layers, out_channels);
-  auto G = [&](int id) { return weights + lo.off[id]; };
-  HIP_TRY(launch_time_bias(t_host, n_t, hidden, n_layers, G(DIFUSCO_W_TIME_FREQS), G(DIFUSCO_W_TIME0_W), G(DIFUSCO_W_TIME0_B),
-                           G(DIFUSCO_W_TIME2_W), G(DIFUSCO_W_TIME2_B), weights + lo.off[DIFUSCO_W_GLOBAL_COUNT], lo.layer_stride,
-                           lo.off[DIFUSCO_W_GLOBAL_COUNT + DIFUSCO_WL_TIME_W] - lo.off[DIFUSCO_W_GLOBAL_COUNT],
-                           lo.off[DIFUSCO_W_GLOBAL_COUNT + DIFUSCO_WL_TIME_B] - lo.off[DIFUSCO_W_GLOBAL_COUNT], out,
-                           (hipStream_t)stream));
+  HIP_TRY(time_bias_rows(Weights(weights, hidden, n_layers, out_channels), hidden, n_layers, t_host, n_t, out, (hipStream_t)stream));
   return DIFUSCO_OK;
 }
 
@@ -593,105 +682,58 @@ size_t difusco_gen_table_bytes(int hidden) {
 
 int difusco_gen_table_build(int hidden, int n_layers, int out_channels, const float* weights, float* table, size_t table_bytes,
                             void* stream) {
-  using namespace difusco;
   if (hidden != 256) return fail(DIFUSCO_EINVAL, "difusco_gen_table_build: hidden = 256 required");
   if (n_layers < 1 || (out_channels != 1 && out_channels != 2) || !weights || !table) return fail(DIFUSCO_EINVAL, "bad model shape / null pointer");
   if (table_bytes < difusco_gen_table_bytes(hidden)) return fail(DIFUSCO_EWORKSPACE, "gen table buffer too small: %zu < %zu", table_bytes, difusco_gen_table_bytes(hidden));
-  const Layout lo = make_layout(hidden, n_layers, out_channels);
-  auto G = [&](int id) { return weights + lo.off[id]; };
+  const Weights w(weights, hidden, n_layers, out_channels);
   const int H = hidden;
   hipStream_t st = (hipStream_t)stream;
   float* feat = table + (size_t)kGenRows * H;
   float* grid = feat + (size_t)kGenRows * H;
   HIP_TRY(launch_gen_table_grid(grid, st));
-  HIP_TRY(launch_scalar_embed(grid, nullptr, G(DIFUSCO_W_DIMT_SCALAR), kGenRows, H, feat, st));       // precise sin / cos of x / dim_t
-  HIP_TRY(linear_rows(feat, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_B), nullptr, table, kGenRows, H, H, H, st));   // exact fp32 MFMA
+  HIP_TRY(launch_scalar_embed(grid, nullptr, w.g(DIFUSCO_W_DIMT_SCALAR), kGenRows, H, feat, st));       // precise sin / cos of x / dim_t
+  HIP_TRY(linear_rows(feat, w.g(DIFUSCO_W_EDGE_EMBED_W), w.g(DIFUSCO_W_EDGE_EMBED_B), nullptr, table, kGenRows, H, H, H, st));   // exact fp32 MFMA
   return DIFUSCO_OK;
 }
 
 int difusco_edge_embed(int hidden, int n_layers, int out_channels, const float* weights, int precision, const float* xt,
                        const int32_t* perm, int64_t n_edges, float* e_tiled, float* tile_max, const float* gen_table, void* stream) {
-  using namespace difusco;
   if (hidden != 256) return fail(DIFUSCO_EINVAL, "difusco_edge_embed: the tiled kernel exists for hidden = 256");
   if (n_layers < 1 || (out_channels != 1 && out_channels != 2)) return fail(DIFUSCO_EINVAL, "n_layers >= 1, out_channels in {1,2} required");
   if (precision != DIFUSCO_PREC_BF16X3 && precision != DIFUSCO_PREC_FP16X3)
     return fail(DIFUSCO_EINVAL, "difusco_edge_embed: precision must be BF16X3 or FP16X3");
   if (!weights || !xt || !e_tiled || n_edges < 0 || n_edges > 0x7fffffff) return fail(DIFUSCO_EINVAL, "null pointer / bad n_edges");
-  const Layout lo = make_layout(hidden, n_layers, out_channels);
-  auto G = [&](int id) { return weights + lo.off[id]; };
+  const Weights w(weights, hidden, n_layers, out_channels);
   const int H = hidden;
-  const bool f16 = precision == DIFUSCO_PREC_FP16X3;
-  const unsigned short* pl = reinterpret_cast<const unsigned short*>(G(DIFUSCO_W_EDGE_EMBED_PLANES)) + (f16 ? (long long)3 * H * H : 0);
+  const SplitPlanes ep = split_planes(w.g(DIFUSCO_W_EDGE_EMBED_PLANES), H, H, precision == DIFUSCO_PREC_FP16X3);
   // (stand-alone entry: the tile flags live in the table buffer's build scratch - enough for 581,632 edges; the step uses its workspace)
   int* flags = gen_table ? reinterpret_cast<int*>(const_cast<float*>(gen_table) + (size_t)kGenRows * H) : nullptr;
   if (gen_table && (n_edges + 127) / 128 * 4 > (int64_t)kGenRows * H)
     return fail(DIFUSCO_EINVAL, "difusco_edge_embed with a table: at most %d edges per call (use the step for larger inputs)", kGenRows * H * 32);
-  HIP_TRY(launch_edge_embed_tiled(xt, perm, G(DIFUSCO_W_DIMT_SCALAR), pl, (long long)H * H, precision,
-                                  f16 ? G(DIFUSCO_W_EDGE_EMBED_PLANES) + (long long)5 * H * H / 2 : nullptr, G(DIFUSCO_W_EDGE_EMBED_B),
-                                  e_tiled, n_edges, tile_max, (hipStream_t)stream, gen_table, flags));
+  HIP_TRY(launch_edge_embed_tiled(xt, perm, w.g(DIFUSCO_W_DIMT_SCALAR), ep.planes, (long long)H * H, precision, ep.w_inv,
+                                  w.g(DIFUSCO_W_EDGE_EMBED_B), e_tiled, n_edges, tile_max, (hipStream_t)stream, gen_table, flags));
   return DIFUSCO_OK;
 }
 
-// The step-invariant part of a TSP step, with the kernels (and therefore the bits) of the stateless step: node embedding,
-// row scales, layer 0's node linear, the two-row edge-input table and C of layer 0 applied to it.
+// The step-invariant part of a TSP step, by the helpers the stateless step itself calls (and therefore with its bits): node
+// embedding, row scales, layer 0's node linear, the two-row edge-input table and C of layer 0 applied to it.
 int difusco_prepare(const difusco_step_args* a, void* prepared, size_t prepared_bytes) {
-  using namespace difusco;
   if (!a || !prepared) return fail(DIFUSCO_EINVAL, "null args / buffer");
-  if (a->struct_size != sizeof(difusco_step_args) || a->abi_version != DIFUSCO_ABI_VERSION)
-    return fail(DIFUSCO_EINVAL, "ABI mismatch: struct_size %u (want %zu), abi %u (want %d)", a->struct_size,
-                sizeof(difusco_step_args), a->abi_version, DIFUSCO_ABI_VERSION);
-  const int H = a->hidden, L = a->n_layers, C = a->out_channels;
-  if (!hidden_ok(H) || L < 1 || (C != 1 && C != 2)) return fail(DIFUSCO_EINVAL, "bad model shape");
+  STAGE(validate_header(a));
+  const int H = a->hidden, L = a->n_layers;
   if (a->task != DIFUSCO_TASK_TSP) return fail(DIFUSCO_EINVAL, "prepared state exists for TSP only (the MIS node embedding is a function of x_t)");
   const int64_t N = a->n_nodes, E = a->n_edges;
   if (N <= 0 || E < 0 || !a->weights || !a->points || !a->workspace) return fail(DIFUSCO_EINVAL, "null pointer / empty graph");
-  if (a->precision < DIFUSCO_PREC_FP32 || a->precision > DIFUSCO_PREC_FP16X1) return fail(DIFUSCO_EINVAL, "unknown precision %d", a->precision);
   const Prepared prep = carve_prepared(prepared, H, N);
   if (prep.bytes > prepared_bytes) return fail(DIFUSCO_EWORKSPACE, "prepared buffer too small: %zu < %zu", prepared_bytes, prep.bytes);
-  const int nblk = gn_blocks_for(E > N ? E : N);
-  Workspace ws = carve(a->workspace, H, L, N, E, a->n_segments < 1 ? 1 : a->n_segments, nblk);
+  const Workspace ws = carve(a->workspace, H, L, N, E, a->n_segments < 1 ? 1 : a->n_segments, gn_blocks_for(E > N ? E : N));
   if (ws.bytes > a->workspace_bytes) return fail(DIFUSCO_EWORKSPACE, "workspace too small: %zu < %zu", a->workspace_bytes, ws.bytes);
-  const Layout lo = make_layout(H, L, C);
-  const float* W = a->weights;
-  auto G = [&](int id) { return W + lo.off[id]; };
-  auto LW = [&](int l, int id) { return W + lo.off[DIFUSCO_W_GLOBAL_COUNT + l * DIFUSCO_WL_COUNT + id]; };
+  const Weights w(a->weights, H, L, a->out_channels);
   hipStream_t st = (hipStream_t)a->stream;
-  const int nprec = a->precision == DIFUSCO_PREC_FP16X1 ? DIFUSCO_PREC_FP16X3 : a->precision;      // (node linear: as in the step)
-  const bool f16 = nprec == DIFUSCO_PREC_FP16X3;
-  // h0 = node_embed(pos_embed(points))  (ws.node4 is the scratch of the sinusoidal features, as in the step)
-  HIP_TRY(launch_pos_embed(a->points, G(DIFUSCO_W_DIMT_POS), (int)N, H, ws.node4, st));
-  HIP_TRY(linear_rows(ws.node4, G(DIFUSCO_W_NODE_EMBED_W), G(DIFUSCO_W_NODE_EMBED_B), nullptr, prep.h0, N, H, H, H, st));
-  // layer 0's U|V|A|B rows of h0
-  if (a->precision != DIFUSCO_PREC_FP32 && H == 256) {
-    const unsigned short* npl = reinterpret_cast<const unsigned short*>(LW(0, DIFUSCO_WL_NODE4_PLANES)) +
-                                (f16 ? (long long)3 * 4 * H * H : 0);
-    SplitScale sc;
-    if (f16) {
-      HIP_TRY(launch_row_pow2_scale(prep.h0, N, H, ws.hscale, st));
-      sc.row_scale = ws.hscale;
-      sc.w_inv = LW(0, DIFUSCO_WL_NODE4_PLANES) + (long long)5 * 4 * H * H / 2;
-    }
-    // the prepared rows are read by the fused edge kernel only (difusco_denoise_step: use_prep requires the fused path), so they
-    // are produced in its log2(e) domain whenever the precision has a fused path - same vectors as the step's own node linear
-    const bool fused_prec = nprec == DIFUSCO_PREC_BF16X3 || nprec == DIFUSCO_PREC_FP16X3;
-    if (fused_prec) sc.w_inv = LW(0, DIFUSCO_WL_NODE4_FUSED_S) + (f16 ? 0 : 4 * H);
-    HIP_TRY(linear_rows_split(prep.h0, npl, (long long)4 * H * H, nprec,
-                              LW(0, fused_prec ? DIFUSCO_WL_NODE4_FUSED_B : DIFUSCO_WL_NODE4_B), nullptr,
-                              prep.node4_0, N, H, 4 * H, 4 * H, st, 0, sc));
-    //  a precision without a fused path (BF16X6) computes the reference's rows: converted in place, so that the buffer
-    // is in the fused kernel's domain WHATEVER precision prepared it - a step that runs a fused precision on it then differs by
-    // the rounding of the node linear only (as under ABI 10), never by a missing b_C / log2(e)
-    if (!fused_prec) HIP_TRY(launch_fuse_node_tables(prep.node4_0, LW(0, DIFUSCO_WL_C_B), (int)N, prep.node4_0, st));
-  } else {
-    HIP_TRY(linear_rows(prep.h0, LW(0, DIFUSCO_WL_NODE4_W), LW(0, DIFUSCO_WL_NODE4_B), nullptr, prep.node4_0, N, H, 4 * H,
-                        4 * H, st));
-    if (H == 256) HIP_TRY(launch_fuse_node_tables(prep.node4_0, LW(0, DIFUSCO_WL_C_B), (int)N, prep.node4_0, st));      // (FP32: same rule)
-  }
-  // two-row edge-input table of a categorical step (embedding of the bit) and C of layer 0 applied to it
-  HIP_TRY(launch_scalar_embed(nullptr, nullptr, G(DIFUSCO_W_DIMT_SCALAR), 2, H, ws.table_in, st));
-  HIP_TRY(launch_two_rows_linear(H, ws.table_in, G(DIFUSCO_W_EDGE_EMBED_W), G(DIFUSCO_W_EDGE_EMBED_B), prep.table, st));
-  HIP_TRY(table_c_rows(a->precision, H, prep.table, LW(0, DIFUSCO_WL_C_W), LW(0, DIFUSCO_WL_C_PLANES), ws.table_in, st));
-  return DIFUSCO_OK;
+  STAGE(embed_tsp_nodes(w, H, N, a->points, ws.node4, prep.h0, st, false));
+  // the prepared rows are read by the fused edge kernel only (make_plan: use_prep requires the fused path): always in its domain
+  STAGE(node_rows(a->precision, H, N, w.layer(0), prep.h0, ws.hscale, true, true, prep.node4_0, st, false));
+  return edge_input_table(a->precision, H, w, ws.table_in, prep.table, true, st, false);
 }
 
 int difusco_linear_rows(const float* x, const float* w, const float* bias, const float* residual, float* y, int64_t m,
@@ -711,17 +753,14 @@ int difusco_linear_rows_split(const float* x, const void* planes, int precision,
     return fail(DIFUSCO_EINVAL, "precision must be BF16X3, BF16X6, FP16X3 or FP16X1");
   if (!(k == 64 || k == 128 || k == 256) || (n_out != k && !(k == 256 && n_out > 0 && n_out % 256 == 0)) || ldy < n_out)
     return fail(DIFUSCO_EINVAL, "split path needs k in {64,128,256}, n_out == k (or a multiple of 256 for k = 256), ldy >= n_out");
-  const unsigned short* pl = reinterpret_cast<const unsigned short*>(planes);
+  const SplitPlanes sp = split_planes(planes, n_out, k, f16_planes(precision));      // (FP16X1: the hi plane of the fp16 pair)
   difusco::SplitScale sc;
-  if (precision == DIFUSCO_PREC_FP16X3 || precision == DIFUSCO_PREC_FP16X1) {      // (FP16X1: the hi plane of the fp16 pair)
-    pl += (long long)3 * n_out * k;
-    sc.w_inv = reinterpret_cast<const float*>(planes) + (long long)5 * n_out * k / 2;
-    if (row_scale_scratch != nullptr) {
-      HIP_TRY(difusco::launch_row_pow2_scale(x, m, k, row_scale_scratch, (hipStream_t)stream));
-      sc.row_scale = row_scale_scratch;
-    }
+  sc.w_inv = sp.w_inv;
+  if (sp.w_inv != nullptr && row_scale_scratch != nullptr) {
+    HIP_TRY(difusco::launch_row_pow2_scale(x, m, k, row_scale_scratch, (hipStream_t)stream));
+    sc.row_scale = row_scale_scratch;
   }
-  HIP_TRY(difusco::linear_rows_split(x, pl, (long long)n_out * k, precision, bias, residual, y, m, k, n_out, ldy,
+  HIP_TRY(difusco::linear_rows_split(x, sp.planes, (long long)n_out * k, precision, bias, residual, y, m, k, n_out, ldy,
                                      (hipStream_t)stream, 0, sc));
   return DIFUSCO_OK;
 }
@@ -766,35 +805,39 @@ int difusco_edge_layer_fused_ex(int precision, int n_nodes, int n_edges, const i
   if (aggregation < DIFUSCO_AGG_SUM || aggregation > DIFUSCO_AGG_MAX)
     return fail(DIFUSCO_EINVAL, "aggregation must be DIFUSCO_AGG_SUM, _MEAN or _MAX");
   if (reg_gather != 0 && reg_gather != 1) return fail(DIFUSCO_EINVAL, "reg_gather must be 0 or 1");
-  if (reg_gather && aggregation == DIFUSCO_AGG_MAX)      // (launch_by_mode: no register-gather instantiation of the max kinds)
+  if (reg_gather && aggregation == DIFUSCO_AGG_MAX)      // (launch_edge_layer_fused: no register-gather instantiation of the max kinds)
     return fail(DIFUSCO_EINVAL, "fused kernel: aggregation = max has no register-gather variant");
   if (precision != DIFUSCO_PREC_BF16X3 && precision != DIFUSCO_PREC_FP16X3 && precision != DIFUSCO_PREC_FP16X1)
     return fail(DIFUSCO_EINVAL, "fused kernel: precision must be BF16X3, FP16X3 or FP16X1");
   if (!rowptr || !row || !col || !node4 || !e || !h || !planes_c || !planes_o || !b_c || !norm_h_w || !norm_h_b ||
       !norm_e_w || !norm_e_b || !out_ln_w || !out_ln_b || !b_out || !tbias || !scratch)
     return fail(DIFUSCO_EINVAL, "null pointer");
-  const bool f16 = precision == DIFUSCO_PREC_FP16X3 || precision == DIFUSCO_PREC_FP16X1;
+  const bool f16 = f16_planes(precision);
   if (f16 && !scales)
     return fail(DIFUSCO_EINVAL, "fused kernel, FP16X3 / FP16X1: the operand-scale record of the layer is required");
-  const long long off = f16 ? 3LL * 256 * 256 : 0;
-  float* part = reinterpret_cast<float*>(scratch);
-  float* direct = part + (fused_part_floats(n_edges) + 63) / 64 * 64;
-  float* etmax = direct + (size_t)n_nodes * 256;
   hipStream_t st = (hipStream_t)stream;
   const long long n_tiles_pad = ((long long)n_edges + 255) / 256 * 8;
+  Carver sc{(char*)scratch};
+  float* part = sc.take(sizeof(float) * fused_part_floats(n_edges));
+  float* direct = sc.take(sizeof(float) * (size_t)n_nodes * 256);
+  float* etmax = sc.take(sizeof(float) * n_tiles_pad);
   // The caller's node4 is the reference's U h | V h | A h | B h (gnn_encoder.py:94-103).  The kernel reads the A | B rows in its
   // log2(e) domain with b_C folded into the A rows (difusco_hip.h, ABI 11 note): converted copy in the scratch.  (The step driver
   // has no such pass: its node linear produces the rows in that form.)
-  float* node4_k = etmax + (n_tiles_pad + 63) / 64 * 64;
+  float* node4_k = sc.take(sizeof(float) * (size_t)n_nodes * 1024);
   HIP_TRY(difusco::launch_fuse_node_tables(node4, b_c, n_nodes, node4_k, st));
   if (f16)      // e-stream scale per tile: normally left by the producer of e
     HIP_TRY(difusco::launch_tile_absmax_tiled(e, n_tiles_pad, etmax, st));
-  HIP_TRY(difusco::launch_edge_layer_fused(precision, e, node4_k, row, col, n_edges,
-                                           reinterpret_cast<const unsigned short*>(planes_c) + off,
-                                           reinterpret_cast<const unsigned short*>(planes_o) + off, 256LL * 256, b_c,
-                                           norm_e_w, norm_e_b, tbias, out_ln_w, out_ln_b, b_out, time_on_edge, part,
-                                           direct, scales, etmax, etmax, st,
-                                           reg_gather | (aggregation == DIFUSCO_AGG_MAX ? 2 : 0)));      // (as the step: fused_variant)
+  difusco::FusedLayerArgs fa;
+  fa.e = e, fa.node4 = node4_k, fa.row = row, fa.col = col, fa.n_edges = n_edges;
+  fa.c_planes = split_planes(planes_c, 256, 256, f16).planes;
+  fa.o_planes = split_planes(planes_o, 256, 256, f16).planes;
+  fa.plane_stride = 256LL * 256;
+  fa.b_c = b_c, fa.g_e = norm_e_w, fa.b_e = norm_e_b, fa.tbias = tbias, fa.g_o = out_ln_w, fa.b_o = out_ln_b, fa.b_out = b_out;
+  fa.time_on_edge = time_on_edge, fa.part = part, fa.direct = direct, fa.scales = scales;
+  fa.etmax_in = fa.etmax_out = etmax, fa.stream = st;
+  HIP_TRY(difusco::launch_edge_layer_fused(precision, difusco::FusedKind::Middle,
+                                           reg_gather | (aggregation == DIFUSCO_AGG_MAX ? 2 : 0), fa));      // (as the step: fused_variant)
   // (node_finalize reads the U rows, which the conversion copies unchanged: either buffer would do)
   HIP_TRY(difusco::launch_node_finalize(n_nodes, n_edges, rowptr, node4, part, direct, h, norm_h_w, norm_h_b, tbias,
                                         time_on_edge, nullptr, st, nullptr, aggregation));

@@ -1,5 +1,6 @@
-// Fused edge pass of one DIFUSCO GNN layer for gfx950 (H = 256): launchers, the node update that follows the edge pass,
-// and the fp16 production instantiations of the kernel template in edge_layer_kernel.h.
+// Fused edge pass of one DIFUSCO GNN layer for gfx950 (H = 256): the launcher (one entry, launch_edge_layer_fused, taking a
+// FusedLayerArgs record), the node update that follows the edge pass, and the fp16 production instantiations of the kernel
+// template in edge_layer_kernel.h.
 #include "edge_layer_kernel.h"
 
 namespace difusco {
@@ -93,74 +94,26 @@ int g_fused_opt = FUSED_OPT;   // key 7: A/B variants of the scheduling options
 unsigned long long* g_fused_dbg = nullptr;   // device buffer for phase timestamps, [n_tiles][16]
 #endif
 
-hipError_t launch_fused_fp16(int kind, FUSED_KIND_PARAMS) { return launch_fused_kind<FFp16>(kind, FUSED_KIND_ARGS); }
+hipError_t launch_fused_fp16(int kind, const FusedLayerArgs& a) { return launch_fused_kind<FFp16>(kind, a); }
 
-// variant bit 0: the register-gather instantiation of the same kind (kind + 4; calls with n_nodes >= 2^20);
-// variant bit 1: aggregation = "max" (kind + 8 for the kinds that aggregate; not combined with bit 0)
-static hipError_t launch_by_mode(int mode, int kind, int variant, FUSED_KIND_PARAMS) {
-  if (n_edges <= 0) return hipSuccess;
+// The one launcher of the fused edge pass (kernels.h: FusedKind, FusedLayerArgs, mode, variant).
+hipError_t launch_edge_layer_fused(int mode, FusedKind fk, int variant, const FusedLayerArgs& a) {
+  if (a.n_edges <= 0) return hipSuccess;
+#ifdef DIFUSCO_PROFILING
+  // profiling-only variants exist for the fp16 middle layer
+  if (fk == FusedKind::Middle && mode == 3 && g_fused_ablate != 0) return launch_fused_ablation(g_fused_ablate, a);
+#endif
+  int kind = (int)fk;      // kinds of launch_fused_kind: + 4 register gathers, + 8 max aggregation
   if (variant & 2) {
     if (variant & 1) return hipErrorInvalidValue;
-    if (kind != 2) kind += 8;
+    if (fk != FusedKind::TailTsp) kind += 8;      // (the last layer of a TSP step has no neighbour aggregation)
   } else if (variant & 1) {
     kind += 4;
   }
-  if (mode == 1) return launch_fused_bf16(kind, FUSED_KIND_ARGS);     // DIFUSCO_PREC_BF16X3
-  if (mode == 3) return launch_fused_fp16(kind, FUSED_KIND_ARGS);     // DIFUSCO_PREC_FP16X3
-  if (mode == 4) return launch_fused_fp16x1(kind, FUSED_KIND_ARGS);   // DIFUSCO_PREC_FP16X1
+  if (mode == 1) return launch_fused_bf16(kind, a);     // DIFUSCO_PREC_BF16X3
+  if (mode == 3) return launch_fused_fp16(kind, a);     // DIFUSCO_PREC_FP16X3
+  if (mode == 4) return launch_fused_fp16x1(kind, a);   // DIFUSCO_PREC_FP16X1
   return hipErrorInvalidValue;
-}
-
-// mode: 1 = bf16 planes, 3 = fp16 planes, 4 = one fp16 plane (DIFUSCO_PREC_BF16X3 / DIFUSCO_PREC_FP16X3 / DIFUSCO_PREC_FP16X1)
-hipError_t launch_edge_layer_fused(int mode, float* e, const float* node4, const int* row, const int* col, int n_edges,
-                                   const unsigned short* c_planes, const unsigned short* o_planes,
-                                   long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                   const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                   int time_on_edge, float* part, float* direct, const float* scales,
-                                   const float* etmax_in, float* etmax_out, hipStream_t stream, int reg_gather) {
-  const float *l0_table = nullptr, *l0_x = nullptr;
-  const int* l0_perm = nullptr;
-  float* gn_tile = nullptr;
-#ifdef DIFUSCO_PROFILING
-  if (mode == 3 && g_fused_ablate != 0) {      // profiling-only variants exist for the fp16 middle layer
-    if (n_edges <= 0) return hipSuccess;
-    return launch_fused_ablation(g_fused_ablate, FUSED_KIND_ARGS);
-  }
-#endif
-  return launch_by_mode(mode, 0, reg_gather, FUSED_KIND_ARGS);
-}
-
-// Last layer of a step.  tail 1 (TSP: the head normalises e): the per-tile GroupNorm partial sums
-// gn_tile[ceil(n_edges / 32)][32][2] of the new edge state are emitted and the node update is skipped (no
-// node_finalize after it).  tail 2 (MIS: the head reads h): the kernel stops after the neighbour sum, e is not updated.
-hipError_t launch_edge_layer_fused_tail(int mode, int tail, float* e, const float* node4, const int* row, const int* col,
-                                        int n_edges, const unsigned short* c_planes, const unsigned short* o_planes,
-                                        long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                        const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                        int time_on_edge, float* part, float* direct, float* gn_tile,
-                                        const float* scales, const float* etmax_in, hipStream_t stream, int reg_gather) {
-  const float *l0_table = nullptr, *l0_x = nullptr;
-  const int* l0_perm = nullptr;
-  float* etmax_out = nullptr;
-  if (tail != 1 && tail != 2) return hipErrorInvalidValue;
-  return launch_by_mode(mode, tail == 1 ? 2 : 3, reg_gather, FUSED_KIND_ARGS);
-}
-
-// First layer of a step whose edge input is a table lookup (see the L0 notes in the kernel): same as
-// launch_edge_layer_fused, but e is only written.  table: [4][256] floats (rows 0, 1 the input rows, rows 2, 3 C applied
-// to them), x: per caller-edge values (null = row 0), perm: CSR slot -> caller edge id (null = identity).
-hipError_t launch_edge_layer_fused_l0(int mode, float* e, const float* node4, const int* row, const int* col, int n_edges,
-                                      const unsigned short* c_planes, const unsigned short* o_planes,
-                                      long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                      const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                      int time_on_edge, float* part, float* direct, const float* table, const float* x,
-                                      const int* perm, const float* scales, float* etmax_out, hipStream_t stream,
-                                      int reg_gather) {
-  const float *l0_table = table, *l0_x = x;
-  const int* l0_perm = perm;
-  float* gn_tile = nullptr;
-  const float* etmax_in = nullptr;
-  return launch_by_mode(mode, 1, reg_gather, FUSED_KIND_ARGS);
 }
 
 // The reference's node rows -> the fused kernel's log2(e) domain (only the stand-alone layer entry difusco_edge_layer_fused needs

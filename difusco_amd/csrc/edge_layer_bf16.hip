@@ -2,5 +2,5 @@
 #include "edge_layer_kernel.h"
 
 namespace difusco {
-hipError_t launch_fused_bf16(int kind, FUSED_KIND_PARAMS) { return launch_fused_kind<FBf16>(kind, FUSED_KIND_ARGS); }
+hipError_t launch_fused_bf16(int kind, const FusedLayerArgs& a) { return launch_fused_kind<FBf16>(kind, a); }
 }  // namespace difusco

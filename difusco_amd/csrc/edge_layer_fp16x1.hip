@@ -2,5 +2,5 @@
 #include "edge_layer_kernel.h"
 
 namespace difusco {
-hipError_t launch_fused_fp16x1(int kind, FUSED_KIND_PARAMS) { return launch_fused_kind<FFp16x1>(kind, FUSED_KIND_ARGS); }
+hipError_t launch_fused_fp16x1(int kind, const FusedLayerArgs& a) { return launch_fused_kind<FFp16x1>(kind, a); }
 }  // namespace difusco

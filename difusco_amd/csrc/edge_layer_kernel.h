@@ -42,7 +42,8 @@
 //
 // First layer (template flag L0): when the edge input is a lookup in a 2-row table (categorical TSP: the embedding
 // of the bit x_t; MIS: zeros) the table sits in LDS and the kernel never reads e - see the L0 notes at the kernel.
-// This header holds the kernel template and its launcher template; the instantiations are spread over
+// This header holds the kernel template and its launcher templates - they pass one FusedLayerArgs record (kernels.h) down to
+// launch_fused_t, the one place that unpacks it into the kernel's argument list; the instantiations are spread over
 // edge_layer.hip (fp16 production variants), edge_layer_bf16.hip, edge_layer_fp16x1.hip and edge_layer_abl.hip (profiling-only ablations) so
 // that the translation units compile in parallel.
 #pragma once
@@ -1160,13 +1161,7 @@ _Pragma("unroll")                                                               
 #define FUSED_NW 4          // production workgroup geometry (see fused::Geo): measured 0.97-1.00 ms vs 1.05-1.18 ms (NW = 8) per layer
 
 template <typename T, int ABL, int NW, bool L0 = false, bool GNP = false, int TAIL = 0, int OPT = FUSED_OPT_R2, bool NOTB = false>
-hipError_t launch_fused_t(float* e, const float* node4, const int* row, const int* col, int n_edges,
-                                 const unsigned short* c_planes, const unsigned short* o_planes, long long plane_stride,
-                                 const float* b_c, const float* g_e, const float* b_e, const float* tbias,
-                                 const float* g_o, const float* b_o, const float* b_out, int time_on_edge, float* part,
-                                 float* direct, hipStream_t stream, const float* l0_table, const float* l0_x,
-                                 const int* l0_perm, float* gn_tile, const float* scales, const float* etmax_in,
-                                 float* etmax_out) {
+hipError_t launch_fused_t(const FusedLayerArgs& a) {
   static std::atomic<unsigned long long> attr_devices{0};      // per kernel instantiation: devices already configured
   {
     hipError_t er = ensure_max_dynamic_lds(attr_devices, reinterpret_cast<const void*>(&edge_layer_fused_kernel<T, ABL, NW, L0, GNP, TAIL, OPT, NOTB>),
@@ -1174,7 +1169,7 @@ hipError_t launch_fused_t(float* e, const float* node4, const int* row, const in
     if (er != hipSuccess) return er;
   }
   constexpr int WV = fused::geo_waves(NW);
-  unsigned grid = (unsigned)((n_edges + 32 * WV - 1) / (32 * WV));
+  unsigned grid = (unsigned)((a.n_edges + 32 * WV - 1) / (32 * WV));
   if constexpr ((OPT & 4096) != 0) {      // persistent workgroups: two per CU (what the LDS footprint admits), a multiple of 8
     static std::atomic<int> resident{0};
     int r = resident.load(std::memory_order_relaxed);
@@ -1189,71 +1184,63 @@ hipError_t launch_fused_t(float* e, const float* node4, const int* row, const in
   }
   // profiling builds: FUSED_LDS_PAD extra bytes of dynamic LDS lower the number of co-resident workgroups per CU
   hipLaunchKernelGGL((edge_layer_fused_kernel<T, ABL, NW, L0, GNP, TAIL, OPT, NOTB>), dim3(grid), dim3(64 * WV),
-                     fused::Geo<NW>::LDS_TOTAL + FUSED_LDS_PAD, stream,
-                     e, node4, row, col, n_edges, c_planes, o_planes, plane_stride, b_c, g_e, b_e, tbias, g_o, b_o, b_out,
-                     time_on_edge, part, direct, FUSED_DBG, l0_table, l0_x, l0_perm, gn_tile, scales, etmax_in, etmax_out, FUSED_START_DELAY);
+                     fused::Geo<NW>::LDS_TOTAL + FUSED_LDS_PAD, a.stream,
+                     a.e, a.node4, a.row, a.col, a.n_edges, a.c_planes, a.o_planes, a.plane_stride, a.b_c, a.g_e, a.b_e, a.tbias,
+                     a.g_o, a.b_o, a.b_out, a.time_on_edge, a.part, a.direct, FUSED_DBG, a.l0_table, a.l0_x, a.l0_perm, a.gn_tile,
+                     a.scales, a.etmax_in, a.etmax_out, FUSED_START_DELAY);
   return hipGetLastError();
 }
 
 // production geometry, no ablation.  Profiling builds (-DDIFUSCO_PROFILING, libdifusco_hip_prof.so) also hold the A/B
 // variants of the scheduling options, selected by g_fused_opt; the production library has the production set only.
-template <typename T, bool L0, bool GNP, int TAIL, bool NOTB = false, typename... A>
-hipError_t launch_fused_opt(A... args) {
+template <typename T, bool L0, bool GNP, int TAIL, bool NOTB = false>
+hipError_t launch_fused_opt(const FusedLayerArgs& args) {
 #ifndef DIFUSCO_PROFILING
-  return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT, NOTB>(args...);
+  return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT, NOTB>(args);
 #else
   switch (g_fused_opt) {      // (the variants without bits 6 / 11 - serial sums, scalar element-wise code - and bits 13, 16, 18 were removed in round 5)
-    case FUSED_OPT | 4096: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 4096, NOTB>(args...);    // 155507 (A/B: production + persistent workgroups)
-    case 3955: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 3955, NOTB>(args...);      // (A/B: round 2's production: register gathers)
-    case FUSED_OPT | 32768: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 32768, NOTB>(args...);  // 184179 (A/B: ... + two gather units, counted waits)
-    case 20339: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 20339, NOTB>(args...);    // (A/B: round 3's production: no neighbour-sum fast path)
-    case 150899: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 150899, NOTB>(args...);  // (A/B: production without the raised issue priority)
-    case 151411: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 151411, NOTB>(args...);  // (A/B: rounds 2-4's production: + alternating MFMA chains, bit 1)
-    case 151377: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 151377, NOTB>(args...);  // (A/B: production without the two-stage cover of the e stream, bit 5)
-    case FUSED_OPT | 2097152: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 2097152, NOTB>(args...);  // 2248561 (A/B: no scheduling fences around the MFMA triples)
-    case FUSED_OPT | 1048576: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 1048576, NOTB>(args...);  // 1199985 (A/B: GEMM 2 block-major inside a stage)
-    default: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT, NOTB>(args...);
+    case FUSED_OPT | 4096: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 4096, NOTB>(args);    // 155507 (A/B: production + persistent workgroups)
+    case 3955: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 3955, NOTB>(args);      // (A/B: round 2's production: register gathers)
+    case FUSED_OPT | 32768: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 32768, NOTB>(args);  // 184179 (A/B: ... + two gather units, counted waits)
+    case 20339: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 20339, NOTB>(args);    // (A/B: round 3's production: no neighbour-sum fast path)
+    case 150899: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 150899, NOTB>(args);  // (A/B: production without the raised issue priority)
+    case 151411: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 151411, NOTB>(args);  // (A/B: rounds 2-4's production: + alternating MFMA chains, bit 1)
+    case 151377: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, 151377, NOTB>(args);  // (A/B: production without the two-stage cover of the e stream, bit 5)
+    case FUSED_OPT | 2097152: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 2097152, NOTB>(args);  // 2248561 (A/B: no scheduling fences around the MFMA triples)
+    case FUSED_OPT | 1048576: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT | 1048576, NOTB>(args);  // 1199985 (A/B: GEMM 2 block-major inside a stage)
+    default: return launch_fused_t<T, 0, FUSED_NW, L0, GNP, TAIL, FUSED_OPT, NOTB>(args);
   }
 #endif
 }
 
 // one entry point per element type / purpose, each defined in its own translation unit.
-// kind: 0 middle layer, 1 first layer from the 2-row table (L0), 2 last layer of a TSP step (GNP, TAIL 1),
-//       3 last layer of a MIS step (TAIL 2);  + 4: the register-gather instantiation (n_nodes >= 2^20);
-//       + 8 (kinds 0, 1, 3): aggregation = "max"
-#define FUSED_KIND_PARAMS                                                                                              \
-  float *e, const float *node4, const int *row, const int *col, int n_edges, const unsigned short *c_planes,          \
-      const unsigned short *o_planes, long long plane_stride, const float *b_c, const float *g_e, const float *b_e,   \
-      const float *tbias, const float *g_o, const float *b_o, const float *b_out, int time_on_edge, float *part,      \
-      float *direct, hipStream_t stream, const float *l0_table, const float *l0_x, const int *l0_perm, float *gn_tile,  \
-      const float *scales, const float *etmax_in, float *etmax_out
-#define FUSED_KIND_ARGS                                                                                                \
-  e, node4, row, col, n_edges, c_planes, o_planes, plane_stride, b_c, g_e, b_e, tbias, g_o, b_o, b_out, time_on_edge, \
-      part, direct, stream, l0_table, l0_x, l0_perm, gn_tile, scales, etmax_in, etmax_out
-hipError_t launch_fused_fp16(int kind, FUSED_KIND_PARAMS);
-hipError_t launch_fused_bf16(int kind, FUSED_KIND_PARAMS);
-hipError_t launch_fused_fp16x1(int kind, FUSED_KIND_PARAMS);      // one fp16 plane, one product (DIFUSCO_PREC_FP16X1)
-hipError_t launch_fused_ablation(int mask, FUSED_KIND_PARAMS);      // profiling-only variants of the fp16 middle layer
+// kind: 0-3 = FusedKind (kernels.h: middle layer | first layer from the 2-row table, L0 | last layer of a TSP step, GNP + TAIL 1 |
+//       last layer of a MIS step, TAIL 2);  + 4: the register-gather instantiation (n_nodes >= 2^20);
+//       + 8 (kinds 0, 1, 3): aggregation = "max".  The record is unpacked into the kernel's argument list in launch_fused_t only.
+hipError_t launch_fused_fp16(int kind, const FusedLayerArgs& a);
+hipError_t launch_fused_bf16(int kind, const FusedLayerArgs& a);
+hipError_t launch_fused_fp16x1(int kind, const FusedLayerArgs& a);      // one fp16 plane, one product (DIFUSCO_PREC_FP16X1)
+hipError_t launch_fused_ablation(int mask, const FusedLayerArgs& a);      // profiling-only variants of the fp16 middle layer
 
 // kinds 4-7 = kinds 0-3 with the neighbour-table rows gathered into REGISTERS by 64-bit addresses (round 2's option set):
 // the full-line gathers address node rows by 32-bit byte offsets (4 KB per row), which wrap at n_nodes = 2^20.  The step
 // driver (api.hip) picks these for such calls; results are bit-identical to the full-line kernels.
 template <typename T>
-hipError_t launch_fused_kind(int kind, FUSED_KIND_PARAMS) {
+hipError_t launch_fused_kind(int kind, const FusedLayerArgs& a) {
   switch (kind) {
     // (a layer without a time bias on e - MIS, gnn_encoder.py:447 - takes the NOTB instantiation: no bias reads, no adds)
-    case 0: return time_on_edge ? launch_fused_opt<T, false, false, 0>(FUSED_KIND_ARGS) : launch_fused_opt<T, false, false, 0, true>(FUSED_KIND_ARGS);
-    case 1: return time_on_edge ? launch_fused_opt<T, true, false, 0>(FUSED_KIND_ARGS) : launch_fused_opt<T, true, false, 0, true>(FUSED_KIND_ARGS);
-    case 2: return launch_fused_opt<T, false, true, 1>(FUSED_KIND_ARGS);
-    case 3: return launch_fused_opt<T, false, false, 2>(FUSED_KIND_ARGS);
-    case 4: return launch_fused_t<T, 0, FUSED_NW, false, false, 0, FUSED_OPT_R2>(FUSED_KIND_ARGS);
-    case 5: return launch_fused_t<T, 0, FUSED_NW, true, false, 0, FUSED_OPT_R2>(FUSED_KIND_ARGS);
-    case 6: return launch_fused_t<T, 0, FUSED_NW, false, true, 1, FUSED_OPT_R2>(FUSED_KIND_ARGS);
-    case 7: return launch_fused_t<T, 0, FUSED_NW, false, false, 2, FUSED_OPT_R2>(FUSED_KIND_ARGS);
+    case 0: return a.time_on_edge ? launch_fused_opt<T, false, false, 0>(a) : launch_fused_opt<T, false, false, 0, true>(a);
+    case 1: return a.time_on_edge ? launch_fused_opt<T, true, false, 0>(a) : launch_fused_opt<T, true, false, 0, true>(a);
+    case 2: return launch_fused_opt<T, false, true, 1>(a);
+    case 3: return launch_fused_opt<T, false, false, 2>(a);
+    case 4: return launch_fused_t<T, 0, FUSED_NW, false, false, 0, FUSED_OPT_R2>(a);
+    case 5: return launch_fused_t<T, 0, FUSED_NW, true, false, 0, FUSED_OPT_R2>(a);
+    case 6: return launch_fused_t<T, 0, FUSED_NW, false, true, 1, FUSED_OPT_R2>(a);
+    case 7: return launch_fused_t<T, 0, FUSED_NW, false, false, 2, FUSED_OPT_R2>(a);
     // aggregation = "max" (OPT bit 19); the last layer of a TSP step has no neighbour aggregation: kind 2 serves it
-    case 8: return launch_fused_t<T, 0, FUSED_NW, false, false, 0, FUSED_OPT | 524288>(FUSED_KIND_ARGS);
-    case 9: return launch_fused_t<T, 0, FUSED_NW, true, false, 0, FUSED_OPT | 524288>(FUSED_KIND_ARGS);
-    case 11: return launch_fused_t<T, 0, FUSED_NW, false, false, 2, FUSED_OPT | 524288>(FUSED_KIND_ARGS);
+    case 8: return launch_fused_t<T, 0, FUSED_NW, false, false, 0, FUSED_OPT | 524288>(a);
+    case 9: return launch_fused_t<T, 0, FUSED_NW, true, false, 0, FUSED_OPT | 524288>(a);
+    case 11: return launch_fused_t<T, 0, FUSED_NW, false, false, 2, FUSED_OPT | 524288>(a);
     default: return hipErrorInvalidValue;
   }
 }

@@ -1,4 +1,4 @@
-// Internal launcher declarations (implemented in linear.hip / graph_kernels.hip).
+// Internal launcher declarations (implemented in the .hip files of this directory).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,27 +82,40 @@ hipError_t launch_zero_words(void* p, size_t bytes, hipStream_t stream);
 // tile_max[t] = max |e| over the 32-edge tile t of a TILED [rows_padded, 256] buffer
 hipError_t launch_tile_absmax_tiled(const float* e, long long n_tiles, float* tile_max, hipStream_t stream);
 
-hipError_t launch_edge_layer_fused(int mode, float* e, const float* node4, const int* row, const int* col, int n_edges,
-                                   const unsigned short* c_planes, const unsigned short* o_planes,
-                                   long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                   const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                   int time_on_edge, float* part, float* direct, const float* scales,
-                                   const float* etmax_in, float* etmax_out, hipStream_t stream, int reg_gather = 0);
-hipError_t launch_edge_layer_fused_l0(int mode, float* e, const float* node4, const int* row, const int* col, int n_edges,
-                                      const unsigned short* c_planes, const unsigned short* o_planes,
-                                      long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                      const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                      int time_on_edge, float* part, float* direct, const float* table, const float* x,
-                                      const int* perm, const float* scales, float* etmax_out, hipStream_t stream,
-                                      int reg_gather = 0);
-hipError_t launch_edge_layer_fused_tail(int mode, int tail, float* e, const float* node4, const int* row, const int* col,
-                                        int n_edges, const unsigned short* c_planes, const unsigned short* o_planes,
-                                        long long plane_stride, const float* b_c, const float* g_e, const float* b_e,
-                                        const float* tbias, const float* g_o, const float* b_o, const float* b_out,
-                                        int time_on_edge, float* part, float* direct, float* gn_tile,
-                                        const float* scales, const float* etmax_in, hipStream_t stream, int reg_gather = 0);
-// reg_gather != 0: the variant of the kernel that gathers neighbour-table rows into registers by 64-bit addresses - for calls
-// with n_nodes >= 2^20, where the 32-bit byte offsets of the full-line (LDS-DMA) gathers would wrap (4 KB per node row)
+// The fused edge pass of one GNN layer (edge_layer_kernel.h).  Which part of a layer a launch computes:
+enum class FusedKind {
+  Middle = 0,      // everything: e is read, updated in place, the neighbour-sum pieces are written
+  FirstFromTable,  // first layer of a step whose edge input is a lookup in the two-row l0_table: e is only written
+  TailTsp,         // last layer of a TSP step (the head normalises e): the GroupNorm partial sums of the new e go to gn_tile,
+                   // the node update is skipped (no node_finalize after it)
+  TailMis,         // last layer of a MIS step (the head reads h): ends after the neighbour sum, e is not updated
+};
+// Everything the kernel takes.  The per-kind fields stay null for the kinds that do not read them.
+struct FusedLayerArgs {
+  float* e = nullptr;                  // [ceil(n_edges / 256) * 256, 256], tiled (edge_tiled_offset)
+  const float* node4 = nullptr;        // [n_nodes, 4 * 256] rows U | V | A | B in the kernel's log2(e) domain
+  const int *row = nullptr, *col = nullptr;
+  int n_edges = 0;
+  const unsigned short *c_planes = nullptr, *o_planes = nullptr;      // split planes of C / per_layer_out[l][2], of the launch's precision
+  long long plane_stride = 0;
+  const float *b_c = nullptr, *g_e = nullptr, *b_e = nullptr, *tbias = nullptr, *g_o = nullptr, *b_o = nullptr, *b_out = nullptr;
+  int time_on_edge = 0;
+  float *part = nullptr, *direct = nullptr;      // pieces of the neighbour sum: [tiles][2][256] | [n_nodes][256]
+  const float* scales = nullptr;       // DIFUSCO_WL_FUSED_SCALES of the layer (fp16 planes)
+  const float* etmax_in = nullptr;     // max |e| per 32-edge tile left by the producer of e (fp16 planes; not FirstFromTable)
+  float* etmax_out = nullptr;          // the same for the next layer (null: not written - the tails)
+  // FirstFromTable: l0_table [4][256], rows 0, 1 the input rows, rows 2, 3 C applied to them; l0_x per caller-edge values (null =
+  // row 0); l0_perm CSR slot -> caller edge id (null = identity).  TailTsp: gn_tile [ceil(n_edges / 32)][32][2]
+  const float *l0_table = nullptr, *l0_x = nullptr;
+  const int* l0_perm = nullptr;
+  float* gn_tile = nullptr;
+  hipStream_t stream = nullptr;
+};
+// mode: 1 = bf16 planes, 3 = fp16 planes, 4 = one fp16 plane (DIFUSCO_PREC_BF16X3 / DIFUSCO_PREC_FP16X3 / DIFUSCO_PREC_FP16X1).
+// variant bit 0: the instantiation that gathers neighbour-table rows into registers by 64-bit addresses - for calls with
+// n_nodes >= 2^20, where the 32-bit byte offsets of the full-line (LDS-DMA) gathers would wrap (4 KB per node row);
+// variant bit 1: aggregation = "max" (not combined with bit 0).
+hipError_t launch_edge_layer_fused(int mode, FusedKind kind, int variant, const FusedLayerArgs& a);
 #ifdef DIFUSCO_PROFILING
 extern int g_fused_ablate;
 extern int g_fused_lds_pad;
