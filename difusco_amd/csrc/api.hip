@@ -164,7 +164,7 @@ Workspace carve(void* base, int H, int L, int64_t N, int64_t E, int S, int nblk)
   w.partial = c.take<double>(sizeof(double) * (size_t)S * (nblk < 256 ? 256 : nblk) * 64);
   w.part = c.take(H == 256 ? sizeof(float) * fused_part_floats(E) : 0);
   w.direct = c.take(H == 256 ? sizeof(float) * N * H : 0);
-  w.gn_tile = c.take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) * 64 : 0);   // per 32-edge tile: 32 x (sum, sumsq)
+  w.gn_tile = c.take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) * 96 : 0);   // per 32-edge tile: 32 x (sum, sumsq of x - pivot), 32 pivots
   // operand scales of the fp16 split path: max |e| per 32-edge tile (fused kernel), one power of two per node row / edge row
   w.etmax = c.take(H == 256 ? sizeof(float) * ((E + 255) / 256 * 8) : 0);
   w.hscale = c.take(sizeof(float) * N);

@@ -110,8 +110,10 @@ __global__ __launch_bounds__(64 * fused::geo_waves(NW), 2) void edge_layer_fused
   // ends after the neighbour sum (no LayerNorms, no GEMM 2, no store of e).  The reference computes both and discards
   // them (gnn_encoder.py:400-401 / :412-413 read one of the two states).
   // GNP (last layer of a step whose head reads e): per tile and GroupNorm group (8 channels = the two lane halves of
-  // one (quarter, block, quad)), the sum and the sum of squares of the NEW e values go to gn_tile[tile][32][2]; the
-  // head then needs no statistics pass over e (nn.py:93-100, gnn_encoder.py:400-401).
+  // one (quarter, block, quad)), a pivot p (one of the group's NEW e values of the tile) and the sum and the sum of squares
+  // of x - p over the group's new e values go to gn_tile[tile] (96 floats: [32][sum, sum of squares], [32] pivots);
+  // gn_tiles_reduce_kernel recombines them in double.  The head then needs no statistics pass over e (nn.py:93-100,
+  // gnn_encoder.py:400-401).
   // L0 (first layer of a step whose edge input is a table lookup): e_in[s] = l0_table[x > 0.5 ? 1 : 0] with
   // x = l0_x[l0_perm ? l0_perm[s] : s] (categorical TSP: the edge embedding of the bit x_t, gnn_encoder.py:395) or
   // row 0 when l0_x is null (MIS: e = zeros, gnn_encoder.py:407).  The kernel then never reads e, and it has no GEMM 1
@@ -1069,9 +1071,9 @@ _Pragma("unroll")                                                               
 #pragma unroll
       for (int nbp = 0; nbp < 2; ++nbp) asm volatile("" ::"v"(acc2[nbp]));   // keep the MFMAs alive
     }
-    float gs[8], gq[8];      // GNP: this lane's share of the 8 groups of the quarter
+    float gs[8], gq[8], gp[8];      // GNP: this lane's share of the 8 groups of the quarter; gp: the groups' pivots (wave uniform)
 #pragma unroll
-    for (int u = 0; u < 8; ++u) gs[u] = gq[u] = 0.0f;
+    for (int u = 0; u < 8; ++u) gs[u] = gq[u] = gp[u] = 0.0f;
     if (valid && !skip_gemm2 && !skip_out) {
 #pragma unroll
       for (int nbp = 0; nbp < 2; ++nbp)
@@ -1092,8 +1094,14 @@ _Pragma("unroll")                                                               
             tmx = __builtin_fmaxf(__builtin_fmaxf(tmx, __builtin_fabsf(v[2])), __builtin_fabsf(v[3]));
           }
           if constexpr (GNP) {
-            gs[nbp * 4 + g] = (v[0] + v[1]) + (v[2] + v[3]);
-            gq[nbp * 4 + g] = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+            // pivot of (tile, group): the group's first channel on the tile's first edge (lane 0: valid whenever this branch
+            // runs).  The sums are taken of d = x - pivot, |d| ~ the spread of the group whatever its mean: a one-pass
+            // fp32 sum of x^2 loses 2 log2(|mean| / sigma) bits of the variance (measured: 2.7e-3 on the output at |mean| / sigma = 850)
+            const float pv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[0]), 0));
+            gp[nbp * 4 + g] = pv;
+            const float d0 = v[0] - pv, d1 = v[1] - pv, d2 = v[2] - pv, d3 = v[3] - pv;
+            gs[nbp * 4 + g] = (d0 + d1) + (d2 + d3);
+            gq[nbp * 4 + g] = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
           }
         }
     }
@@ -1117,8 +1125,13 @@ _Pragma("unroll")                                                               
       tot += __shfl_xor(tot, 16, 64);
       tot += __shfl_xor(tot, 32, 64);
       __builtin_amdgcn_wave_barrier();
-      // gn_tile[tile][8 qt + u][sum, sum of squares]
-      if (lane < 16) gn_tile[(long long)tile * 64 + qt * 16 + 2 * (gv & 7) + (gv >> 3)] = tot;
+      // gn_tile[tile]: [8 qt + u][sum d, sum d^2] (64 floats), then the 32 pivots [8 qt + u]
+      if (lane < 16) gn_tile[(long long)tile * 96 + qt * 16 + 2 * (gv & 7) + (gv >> 3)] = tot;
+      if (lane == 0) {
+        float* const pdst = gn_tile + (long long)tile * 96 + 64 + 8 * qt;
+        *reinterpret_cast<v4f*>(pdst) = v4f{gp[0], gp[1], gp[2], gp[3]};
+        *reinterpret_cast<v4f*>(pdst + 4) = v4f{gp[4], gp[5], gp[6], gp[7]};
+      }
     }
     if (qt == 0) { FUSED_STAMP(8) }
   }

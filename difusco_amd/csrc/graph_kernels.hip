@@ -621,14 +621,22 @@ __global__ __launch_bounds__(256) void gn_partial_tiled_seg_kernel(const float* 
   }
 }
 
-// GroupNorm partial sums that the last fused edge layer left per tile (gn_tile[tile][32 groups][sum, sumsq] floats)
+// GroupNorm partial sums that the last fused edge layer left per tile: gn_tile[tile] = 96 floats, [32 groups][sum d, sum d^2]
+// and [32 groups] pivots p, d = x - p over the 8 x (valid rows) values of the group in that tile.  Recombined in double,
+//   sum x = sum d + n p,   sum x^2 = sum d^2 + 2 p sum d + n p^2,
 // -> partial[256 blocks][64] doubles in the all-groups-per-block layout of gn_finalize_kernel (group stride 1).
-__global__ __launch_bounds__(256) void gn_tiles_reduce_kernel(const float* __restrict__ gn_tile, long long n_tiles,
+__global__ __launch_bounds__(256) void gn_tiles_reduce_kernel(const float* __restrict__ gn_tile, long long n_tiles, long long rows,
                                                               double* __restrict__ partial) {
   __shared__ double red[4][64];
   const int c = threadIdx.x & 63, r = threadIdx.x >> 6;
   double acc = 0.0;
-  for (long long t = (long long)blockIdx.x * 4 + r; t < n_tiles; t += (long long)gridDim.x * 4) acc += (double)gn_tile[t * 64 + c];
+  for (long long t = (long long)blockIdx.x * 4 + r; t < n_tiles; t += (long long)gridDim.x * 4) {
+    const float* src = gn_tile + t * 96;
+    const long long left = rows - t * 32;
+    const double n = 8.0 * (double)(left < 32 ? left : 32);
+    const double p = (double)src[64 + (c >> 1)], sd = (double)src[c & ~1];
+    acc += (c & 1) ? (double)src[c] + 2.0 * p * sd + n * p * p : sd + n * p;
+  }
   red[r][c] = acc;
   __syncthreads();
   if (r == 0) partial[(long long)blockIdx.x * 64 + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
@@ -966,7 +974,7 @@ hipError_t launch_head_tiled(int C, const float* feat, long long rows, int nblk,
   if (gn_phase == 2) {
     hipLaunchKernelGGL(gn_stats_from_sums_kernel, dim3(1), dim3(64), 0, stream, gn_sums, 8, stats);
   } else if (gn_tile) {   // statistics come from the last fused layer: no pass over feat
-    hipLaunchKernelGGL(gn_tiles_reduce_kernel, dim3(256), dim3(256), 0, stream, gn_tile, n_tiles, partial);
+    hipLaunchKernelGGL(gn_tiles_reduce_kernel, dim3(256), dim3(256), 0, stream, gn_tile, n_tiles, rows, partial);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(1), dim3(1024), 0, stream, partial, (const int*)nullptr, rows, 256, 8, 1, stats,
                        sums_out);
   } else {

@@ -105,7 +105,7 @@ struct FusedLayerArgs {
   const float* etmax_in = nullptr;     // max |e| per 32-edge tile left by the producer of e (fp16 planes; not FirstFromTable)
   float* etmax_out = nullptr;          // the same for the next layer (null: not written - the tails)
   // FirstFromTable: l0_table [4][256], rows 0, 1 the input rows, rows 2, 3 C applied to them; l0_x per caller-edge values (null =
-  // row 0); l0_perm CSR slot -> caller edge id (null = identity).  TailTsp: gn_tile [ceil(n_edges / 32)][32][2]
+  // row 0); l0_perm CSR slot -> caller edge id (null = identity).  TailTsp: gn_tile [ceil(n_edges / 32)][96] (32 x (sum, sum of squares) of x - pivot, 32 pivots)
   const float *l0_table = nullptr, *l0_x = nullptr;
   const int* l0_perm = nullptr;
   float* gn_tile = nullptr;
