@@ -1,0 +1,123 @@
+// What the 2-opt entries (two_opt.hip) and the local search (or_opt.hip) share: the float64 distance, the (min, first flat
+// index) reductions, the prep entry, one block of the exact 2-opt sweep and the segment reversal.  Every function is
+// per translation unit (anonymous namespace): the kernels that use them are compiled where they are launched.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+namespace difusco {
+namespace {
+
+// float64 distance exactly as torch evaluates sqrt(sum((p - q) ** 2, -1)): two products, one sum, no fused multiply-add
+__device__ __forceinline__ double dist2d(double dx, double dy) { return sqrt(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy))); }
+
+struct Best {
+  double v;
+  long long idx;
+};
+
+__device__ __forceinline__ bool better(double v, long long idx, const Best& b) { return v < b.v || (v == b.v && idx < b.idx); }
+
+// entry k of one tour's tp / dlen (pointers at the tour's own arrays, `points` at its group's coordinates)
+__device__ __forceinline__ void prep_entry(const double* __restrict__ points, const int* __restrict__ tour, int n, int k,
+                                           double2* __restrict__ tp, double* __restrict__ dlen) {
+  const int c = tour[k];
+  const double2 p = make_double2(points[2 * c], points[2 * c + 1]);
+  tp[k] = p;
+  if (k < n) {
+    const int c1 = tour[k + 1];
+    const double dx = p.x - points[2 * c1], dy = p.y - points[2 * c1 + 1];
+    dlen[k] = dist2d(dx, dy);                                   // A_i,i+1 (tsp_utils.py:28)
+  }
+}
+
+constexpr int TI = 16;     // rows per block
+constexpr int JPT = 4;     // columns per thread per sweep (256 threads x 4 = 1024 columns per sweep)
+
+// (min, first flat index) over the 256 threads of a block; the result is valid in thread 0
+__device__ __forceinline__ Best block_best(Best best) {
+  __shared__ Best red[256];
+  red[threadIdx.x] = best;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s && better(red[threadIdx.x + s].v, red[threadIdx.x + s].idx, red[threadIdx.x])) red[threadIdx.x] = red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// one block of the exact sweep: rows i0 .. i0 + TI - 1 of the tour (P = its tp, D = its dlen, n nodes) against all their columns;
+// returns the block's best move in thread 0.  The flat index is i * n + j with the tour's own n.
+__device__ __forceinline__ Best best_tile(const double2* __restrict__ P, const double* __restrict__ D, int n, int i0) {
+  __shared__ double2 pi[TI + 1];
+  __shared__ double di[TI];
+  for (int t = threadIdx.x; t <= TI; t += blockDim.x)
+    if (i0 + t <= n) pi[t] = P[i0 + t];
+  for (int t = threadIdx.x; t < TI; t += blockDim.x)
+    if (i0 + t < n) di[t] = D[i0 + t];
+  __syncthreads();
+  Best best{0.0, 0};
+  const int rows = (n - i0) < TI ? (n - i0) : TI;
+  // columns j >= i0 + 2 matter for this tile; sweep them in chunks of 256 * JPT
+  for (int jbase = i0 + 2; jbase < n; jbase += 256 * JPT) {
+    double2 pj[JPT], pj1[JPT];
+    double dj[JPT];
+    int jj[JPT];
+#pragma unroll
+    for (int u = 0; u < JPT; ++u) {
+      const int j = jbase + u * 256 + threadIdx.x;
+      jj[u] = j;
+      if (j < n) {
+        pj[u] = P[j];
+        pj1[u] = P[j + 1];
+        dj[u] = D[j];
+      }
+    }
+    for (int r = 0; r < rows; ++r) {
+      const int i = i0 + r;
+      const double2 a = pi[r], a1 = pi[r + 1];
+      const double d_i = di[r];
+#pragma unroll
+      for (int u = 0; u < JPT; ++u) {
+        const int j = jj[u];
+        if (j < n && j >= i + 2) {
+          const double x0 = a.x - pj[u].x, y0 = a.y - pj[u].y;
+          const double x1 = a1.x - pj1[u].x, y1 = a1.y - pj1[u].y;
+          // change = A_ij + A_i+1,j+1 - A_i,i+1 - A_j,j+1, evaluated left to right (tsp_utils.py:31)
+          const double change = __dsub_rn(__dsub_rn(__dadd_rn(dist2d(x0, y0), dist2d(x1, y1)), d_i), dj[u]);
+          const long long idx = (long long)i * n + j;
+          if (better(change, idx, best)) best = Best{change, idx};
+        }
+      }
+    }
+  }
+  return block_best(best);                                      // min value, then lowest flat index
+}
+
+// the apply kernels' steps on one tour: argmin over its partials (valid in thread 0) ...
+__device__ __forceinline__ Best tour_argmin(const Best* __restrict__ part, int nblk) {
+  Best best{0.0, 0};
+  for (int t = threadIdx.x; t < nblk; t += blockDim.x) {
+    const Best c = part[t];
+    if (better(c.v, c.idx, best)) best = c;
+  }
+  return block_best(best);
+}
+
+// ... and its best move: tour[mi+1 .. mj] reversed (tsp_utils.py:41), idx = mi * n + mj
+__device__ __forceinline__ void apply_move(int* __restrict__ tour, long long idx, int n) {
+  const int mi = (int)(idx / n), mj = (int)(idx % n);
+  const int len = mj - mi;
+  for (int t = threadIdx.x; t < len / 2; t += blockDim.x) {
+    const int x = mi + 1 + t, y = mj - t;
+    const int tmp = tour[x];
+    tour[x] = tour[y];
+    tour[y] = tmp;
+  }
+}
+
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+}  // namespace
+}  // namespace difusco

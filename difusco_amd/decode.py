@@ -276,6 +276,109 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
 
 
+LOCAL_SEARCHES = ("2opt", "2opt+oropt")
+
+
+def check_local_search(local_search, two_opt_method="exact"):
+    if local_search not in LOCAL_SEARCHES:
+        raise ValueError(f"local search {local_search!r}: one of {LOCAL_SEARCHES}")
+    if local_search != "2opt" and two_opt_method != "exact":
+        raise ValueError(f"local_search={local_search!r} runs the exact 2-opt sweep: two_opt_method={two_opt_method!r} is not built")
+    return local_search
+
+
+def _local_search_checked(who, pts, trs, max_iterations, max_rounds, device):
+    """The argument checks of the three local-search functions (before any library call) on float64 point arrays ``pts`` and
+    int32 tour arrays ``trs``, one per group."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError(f"{who} runs on the GPU only (no CPU fallback)")
+    if int(max_iterations) != max_iterations or max_iterations < 0:
+        raise ValueError(f"max_iterations = {max_iterations!r}: an integer >= 0")
+    if int(max_rounds) != max_rounds or max_rounds < 1:
+        raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 1")
+    if len(pts) < 1 or len(trs) != len(pts):
+        raise ValueError(f"{len(trs)} tour arrays for {len(pts)} instances (at least one instance)")
+    for g, (p, t) in enumerate(zip(pts, trs)):
+        if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 4:
+            raise ValueError(f"points of instance {g} must be [n, 2] with n >= 4")
+        if t.ndim != 2 or t.shape[1] != p.shape[0] + 1 or t.shape[0] < 1:
+            raise ValueError(f"tours of instance {g} must be [P, {p.shape[0] + 1}] closed tours over the {p.shape[0]} points, P >= 1")
+    return device
+
+
+def _local_search_run(pts, trs, max_iterations, max_rounds, device):
+    """One ``difusco_tsp_local_search_ragged`` call on checked arguments.  Returns (int64 tours per group, two_opt_iterations,
+    or_opt_iterations [G] int64, rounds [G] int32)."""
+    G = len(pts)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_local_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
+                                                                 ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    two, orr, rounds = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int32)
+    _lib.check(L.difusco_tsp_local_search_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
+                                                 ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), int(max_rounds),
+                                                 ctypes.c_void_p(ws.data_ptr()), nbytes.value, two.ctypes.data, orr.ctypes.data,
+                                                 rounds.ctypes.data,
+                                                 ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], two, orr, rounds
+
+
+def batched_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+    """2-opt + Or-opt local search of the tours of ONE instance, the arguments of ``batched_two_opt_torch``: rounds of a 2-opt
+    phase (exactly ``batched_two_opt_torch`` with ``max_iterations``) and an Or-opt phase (every tour moves its best segment of
+    1-3 cities, forwards or reversed, while that shortens it by more than 1e-6; at most ``max_iterations`` iterations) until an
+    Or-opt phase applies nothing or ``max_rounds`` rounds ran (``difusco_tsp_local_search_ragged``, include/difusco_hip.h; GPU
+    only).  No tour ends longer than 2-opt alone leaves it.  Returns ``(tour int64 numpy [B, N+1], two_opt_iterations)``;
+    ``stats`` (a dict) receives ``or_opt_iterations`` and ``rounds``."""
+    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
+    device = _local_search_checked("batched_local_search_torch", pts, trs, max_iterations, max_rounds, device)
+    out, two, orr, rounds = _local_search_run(pts, trs, max_iterations, max_rounds, device)
+    if stats is not None:
+        stats["or_opt_iterations"], stats["rounds"] = int(orr[0]), int(rounds[0])
+    return out[0], int(two[0])
+
+
+def batched_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+    """``batched_local_search_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points`` float64
+    [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_local_search_torch`` call returns.
+    Returns ``(tours int64 numpy [G * P, N + 1], two_opt_iterations int64 numpy [G])``; ``stats`` receives ``or_opt_iterations``
+    (int64 [G]) and ``rounds`` (int32 [G])."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts_l = [np.ascontiguousarray(p) for p in pts]
+    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
+    device = _local_search_checked("batched_local_search_grouped", pts_l, trs, max_iterations, max_rounds, device)
+    out, two, orr, rounds = _local_search_run(pts_l, trs, max_iterations, max_rounds, device)
+    if stats is not None:
+        stats["or_opt_iterations"], stats["rounds"] = orr, rounds
+    return np.concatenate(out, axis=0), two
+
+
+def batched_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+    """``batched_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.  Returns
+    ``(list of int64 numpy [P_g, n_g + 1], two_opt_iterations int64 numpy [G])``; ``stats``: as ``batched_local_search_grouped``."""
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    device = _local_search_checked("batched_local_search_ragged", pts, trs, max_iterations, max_rounds, device)
+    out, two, orr, rounds = _local_search_run(pts, trs, max_iterations, max_rounds, device)
+    if stats is not None:
+        stats["or_opt_iterations"], stats["rounds"] = orr, rounds
+    return out, two
+
+
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).

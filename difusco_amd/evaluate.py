@@ -21,7 +21,9 @@ every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are c
 depend on the world size, the rank an instance lands on, or what the model ran before.
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
-``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--merge_method {loop,batched}``
+``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--local_search
+{2opt,2opt+oropt}`` (``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
+``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -94,6 +96,9 @@ EXTENSION_ARGS = [
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
     ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
+    ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt"),
+                             help="tour refinement: 2opt (the reference's) or 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
+                                  "records gain or_opt_iterations and local_search_rounds)")),
     ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
                             help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
     ("--graph_build", dict(type=str, default="host", choices=("host", "device"),
@@ -136,6 +141,8 @@ def parse_args(argv=None):
         parser.error(f"--task {args.task}: tsp or mis")
     if args.ckpt_path is None:
         parser.error("--ckpt_path is required (the weights to evaluate)")
+    if args.local_search != "2opt" and args.two_opt_method != "exact":
+        parser.error(f"--local_search {args.local_search} runs the exact 2-opt sweep: --two_opt_method {args.two_opt_method} is not built")
     ignored = sorted(k for k in given if k in TRAINING_ONLY or (k == "save_numpy_heatmap" and args.task == "mis"))
     return args, ignored
 
@@ -241,10 +248,14 @@ def tsp_gt_cost(points, tour) -> float:
 
 def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
     tour, cost, costs, info = result
-    return {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.points.shape[0]),
-            "gt_cost": tsp_gt_cost(ex.points, ex.tour), "solved_cost": float(cost), "all_costs": [float(c) for c in costs],
-            "merged_costs": [float(c) for c in info["merged_costs"]], "2opt_iterations": int(info["two_opt_iterations"]),
-            "merge_iterations": float(info["merge_iterations"]), "seed": int(seed), "tour": [int(v) for v in tour]}
+    rec = {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.points.shape[0]),
+           "gt_cost": tsp_gt_cost(ex.points, ex.tour), "solved_cost": float(cost), "all_costs": [float(c) for c in costs],
+           "merged_costs": [float(c) for c in info["merged_costs"]], "2opt_iterations": int(info["two_opt_iterations"]),
+           "merge_iterations": float(info["merge_iterations"]), "seed": int(seed), "tour": [int(v) for v in tour]}
+    for k in ("or_opt_iterations", "local_search_rounds"):      # --local_search 2opt+oropt
+        if k in info:
+            rec[k] = int(info[k])
+    return rec
 
 
 def mis_record(split: str, index: int, ex, seed: int, result) -> dict:
@@ -273,7 +284,7 @@ def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, O
 def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0, sparse_factor: int = -1,
                 parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
-                two_opt_method: str = "exact", merge_method: str = "loop") -> List[dict]:
+                two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -293,7 +304,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
                                   two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
                                   step_offset=0, heatmaps=heats, two_opt_method=two_opt_method,
-                                  merge_method=merge_method)
+                                  merge_method=merge_method, local_search=local_search)
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if heats is not None:
@@ -360,7 +371,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             recs = solve_split(model, args.task, examples, split, shard_chunks(chunks, rank, world), seed=args.seed,
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
                                two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir,
-                               two_opt_method=args.two_opt_method, merge_method=args.merge_method)
+                               two_opt_method=args.two_opt_method, merge_method=args.merge_method,
+                               local_search=args.local_search)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -383,6 +395,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                     "two_opt_method": args.two_opt_method, "graph_build": model.graph_build, "ignored_args": ignored}
             if mixed:
                 line["mixed_size_chunks"] = True
+            if args.local_search != "2opt":
+                line["local_search"] = args.local_search
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

@@ -16,7 +16,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import (check_merge_method, check_two_opt_method, batched_two_opt_grouped, batched_two_opt_ragged,
+from .decode import (check_local_search, check_merge_method, check_two_opt_method, batched_local_search_grouped,
+                     batched_local_search_ragged, batched_local_search_torch, batched_two_opt_grouped, batched_two_opt_ragged,
                      batched_two_opt_torch, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
@@ -37,14 +38,18 @@ def _ticker(timings, dev):
 
 def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: int = 1, two_opt_iterations: int = 1000,
               generator: Optional[torch.Generator] = None, timings: Optional[Dict[str, float]] = None,
-              sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact"):
+              sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact",
+              local_search: str = "2opt"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
     merge_iterations / 2-opt moves of the LAST round - the quantities the reference logs (``pl_tsp_model.py:244-251``).
     ``graphed=True``: every sampling loop runs as one replay of a captured HIP graph (``TSPModel.sample``), same results.
-    ``two_opt_method``: "exact" or "screened" (``decode.batched_two_opt_torch``), same results."""
+    ``two_opt_method``: "exact" or "screened" (``decode.batched_two_opt_torch``), same results.  ``local_search``: "2opt"
+    (default) or "2opt+oropt" (``decode.batched_local_search_torch`` with ``max_iterations=two_opt_iterations``: never a longer
+    tour; info gains ``or_opt_iterations`` and ``local_search_rounds`` of the last round; exact sweep only)."""
     check_two_opt_method(two_opt_method)
+    check_local_search(local_search, two_opt_method)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -67,6 +72,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
     stacked, merged_costs = [], []
     merge_iterations, ns = 0.0, 0
+    ls_stats = {}
     for _ in range(sequential_sampling):                                                    # :185
         t0 = time.perf_counter()
         heat = model.sample(pts_rep, ei_rep, generator=generator, graphed=graphed)          # :186-222, on the device
@@ -76,16 +82,22 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
                                               parallel_sampling=parallel_sampling, device=dev)
         tick("merge", t0)
         t0 = time.perf_counter()
-        solved, ns = batched_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),   # :233-236
-                                           max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+        if local_search == "2opt":
+            solved, ns = batched_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),   # :233-236
+                                               max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+        else:
+            solved, ns = batched_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
+                                                    max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
         tick("two_opt", t0)
         stacked.append(solved)
         merged_costs += [tour_length(np_points64, t) for t in tours]
     solved = np.concatenate(stacked, axis=0)                                                # :238
     costs = [tour_length(np_points64, t) for t in solved]                                   # :240-246
     best = int(np.argmin(costs))
-    return solved[best].tolist(), costs[best], costs, {"merge_iterations": merge_iterations, "two_opt_iterations": ns,
-                                                       "merged_costs": merged_costs}
+    info = {"merge_iterations": merge_iterations, "two_opt_iterations": ns, "merged_costs": merged_costs}
+    if local_search != "2opt":
+        info.update(or_opt_iterations=ls_stats["or_opt_iterations"], local_search_rounds=ls_stats["rounds"])
+    return solved[best].tolist(), costs[best], costs, info
 
 
 def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, generator: Optional[torch.Generator] = None,
@@ -144,7 +156,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
                     instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
                     heatmaps: Optional[list] = None, *, two_opt_method: str = "exact",
-                    merge_method: str = "loop") -> List[tuple]:
+                    merge_method: str = "loop", local_search: str = "2opt") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -157,13 +169,14 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
     ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``.  ``merge_method``:
     ``"loop"`` (default) merges instance by instance (``decode.merge_tours``), ``"batched"`` merges the chunk in one library
-    call (``decode.merge_tours_batch``): the same tours and counters."""
+    call (``decode.merge_tours_batch``): the same tours and counters.  ``local_search``: as ``solve_tsp``, per instance."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
+    check_local_search(local_search, two_opt_method)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
-                               merge_method)
+                               merge_method, local_search)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -196,6 +209,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         ns = np.zeros(G, dtype=np.int64)
+        ls_stats = {}
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
@@ -218,8 +232,12 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
-            solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
-                                                 max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+            if local_search == "2opt":
+                solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
+                                                     max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+            else:
+                solved, ns = batched_local_search_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
+                                                          max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g * P:(g + 1) * P])
@@ -228,17 +246,20 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             sol = np.concatenate(stacked[g], axis=0)
             costs = [tour_length(np_points64[g], t) for t in sol]
             best = int(np.argmin(costs))
-            results.append((sol[best].tolist(), costs[best], costs,
-                            {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]),
-                             "merged_costs": merged_costs[g]}))
+            info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]), "merged_costs": merged_costs[g]}
+            if local_search != "2opt":
+                info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+            results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)
     return results
 
 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
-                    instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop") -> List[tuple]:
+                    instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop",
+                    local_search="2opt") -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
+    check_local_search(local_search, two_opt_method)
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
                 for p in points]
     B = len(pts_list)
@@ -280,6 +301,7 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         its = np.zeros(G, dtype=np.int64)
+        ls_stats = {}
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
@@ -302,8 +324,12 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
                     tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
-            solved, its = batched_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
-                                                 max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+            if local_search == "2opt":
+                solved, its = batched_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
+                                                     max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
+            else:
+                solved, its = batched_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
+                                                          max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g])
@@ -312,9 +338,10 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             sol = np.concatenate(stacked[g], axis=0)
             costs = [tour_length(np_points64[g], t) for t in sol]
             best = int(np.argmin(costs))
-            results.append((sol[best].tolist(), costs[best], costs,
-                            {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]),
-                             "merged_costs": merged_costs[g]}))
+            info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]), "merged_costs": merged_costs[g]}
+            if local_search != "2opt":
+                info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+            results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)
     return results

@@ -509,6 +509,29 @@ int difusco_tsp_two_opt_ragged(int groups, const int32_t* group_n, const int32_t
                                int32_t* tours, int64_t max_iterations, int method, void* workspace, size_t workspace_bytes,
                                int64_t* iterations_out, int64_t* exact_pairs_out, void* stream);
 
+/* Local search, 2-opt + Or-opt (additive to ABI 13): the arrays, conventions and limits of difusco_tsp_two_opt_ragged.  Every
+ * group runs rounds of two phases on its own tours, independent of the other groups:
+ *   2-opt phase   exactly difusco_tsp_two_opt(n_g, group_tours[g], ...) with max_iterations (the exact sweep) -> a moves;
+ *   Or-opt phase  per iteration every tour applies its own best Or-opt move if its delta < -1e-6; an iteration counts if a
+ *                 tour of the group moved; the phase ends after an iteration without a move or after max_iterations counted
+ *                 iterations (none with max_iterations = 0) -> b;
+ * and stops after a round with b = 0 or after max_rounds rounds.  An Or-opt candidate (v, i, j) moves the segment at positions
+ * i+1 .. i+L of the closed tour, 0 <= i <= n-1-L (positions 0 and n never move), between positions j and j+1, 0 <= j <= n-1,
+ * j outside [i, i+L]; (L, reversed) = variant v of [(1,no), (2,no), (2,yes), (3,no), (3,yes)].  With P_k the point at position
+ * k, d_k = |P_k P_k+1| and (a, b) = (P_i+1, P_i+L), swapped when reversed:
+ *   delta = ((|P_i P_i+L+1| + |P_j a|) + |b P_j+1|) - ((d_i + d_i+L) + d_j)
+ * in float64, every operation rounded on its own, distances as in the 2-opt (two products, one sum, a square root).  The best
+ * move is the lowest delta, ties to the lowest flat index (v n + i) n + j.  Applied: tour[:i+1] + tour[i+L+1:j+1] + seg +
+ * tour[j+1:] for j > i+L, tour[:j+1] + seg + tour[j+1:i+1] + tour[i+L+1:] for j < i.  The first 2-opt phase is the plain 2-opt
+ * and every later move shortens a tour by more than 1e-6, so no tour ends longer than difusco_tsp_two_opt_ragged leaves it.
+ * two_opt_iterations_out, or_opt_iterations_out: HOST int64 [groups], the sums of a and b; rounds_out: HOST int32 [groups], the
+ * rounds started.  DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_two_opt_ragged, a null output array and
+ * max_rounds < 1.  Blocks until every group is done. */
+int difusco_tsp_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                    int32_t* tours, int64_t max_iterations, int max_rounds, void* workspace, size_t workspace_bytes,
+                                    int64_t* two_opt_iterations_out, int64_t* or_opt_iterations_out, int32_t* rounds_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
