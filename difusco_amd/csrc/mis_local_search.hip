@@ -1,0 +1,410 @@
+// (1,2)-swap local search for MIS solutions (difusco_mis_local_search; the rule is stated in include/difusco_hip.h and restated
+// in numpy in tests/mis_local_search_emulation.py).  Not in the reference: its MIS path ends at the greedy decode.
+//
+// Works, like the decode, on the CSR of the whole call: the graphs of a batch are components, and every step below is local to
+// a component.  rank = position in the stable descending sort of the scores (rocPRIM radix sort, as in mis_decode.hip).
+//
+// All per-round work is on the device.  A control block in the workspace holds the phase and the counters; every kernel reads
+// the phase first and returns when it is not its own, so the host enqueues a fixed sequence of launches (a "group") and polls
+// the control block once per group:
+//   group  = CYCLES x cycle, then mis_ls_finish_kernel (copies the set out once the phase is DONE)
+//   cycle  = SUBROUNDS x (insert round, insert advance), then one swap round:
+//            tight, propose, conflict, apply, tight (the new set's states), swap advance
+// The phases: INSERT (sub-rounds of the insertion phase until no free node is undecided), SWAP (ready for a round), DONE.
+// A cycle whose insertion phase needs more than SUBROUNDS sub-rounds skips its swap round (still INSERT) and goes on in the
+// next cycle.  Only the one-thread advance kernels write the phase, so it is constant inside every other launch.
+//
+// Determinism: every kernel reads what earlier launches wrote and writes arrays that no other wave of its launch reads, with
+// two exceptions.  (a) An insert round reads the states of other nodes while they are being decided, as mis_round_kernel does:
+// a stale read only delays a decision by a sub-round, the decisions themselves are those of the lexicographically first
+// maximal independent set.  (b) The propose kernel marks, in mark[], the candidates of x adjacent to its first node and reads
+// the marks back in the SAME wave; candidate sets of different x are disjoint, so no other wave touches those entries.
+// The counters are integer atomic adds.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "../../include/difusco_hip.h"
+#include "kernels.h"
+
+namespace difusco {
+namespace {
+
+constexpr int LS_INSERT = 0, LS_SWAP = 1, LS_DONE = 2;
+constexpr int LS_CYCLES = 4;         // swap rounds enqueued between two host polls
+constexpr int LS_SUBROUNDS = 2;      // insertion sub-rounds enqueued in front of every swap round
+
+struct LsCtrl {                      // device; the host reads it once per group
+  int phase, bad, rounds, swaps, inserts, proposals, undecided, max_rounds;
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o, 64);
+    v = w < v ? w : v;
+  }
+  return v;
+}
+
+__global__ void mis_ls_iota_kernel(int n, unsigned* __restrict__ idx) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n) idx[v] = (unsigned)v;
+}
+
+// rank from the sorted order; the working copy of the set (anything non-zero counts as chosen); no marks yet
+__global__ void mis_ls_setup_kernel(int n, const unsigned* __restrict__ order, const int* __restrict__ solution,
+                                    int* __restrict__ rank, int* __restrict__ sol, int* __restrict__ mark) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  rank[order[p]] = p;
+  sol[p] = solution[p] != 0;
+  mark[p] = -1;
+}
+
+// The checking pass: a chosen node with a chosen neighbour sets the flag.  One wavefront per node.
+__global__ __launch_bounds__(256) void mis_ls_check_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ sol, LsCtrl* __restrict__ ctrl) {
+  const int v = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (v >= n) return;
+  if (!sol[v]) return;                                       // wave uniform
+  int hit = 0;
+  for (int e = rowptr[v] + lane; e < rowptr[v + 1]; e += 64) {
+    const int u = col[e];
+    hit |= u != v && sol[u] != 0;
+  }
+  if (__any(hit) && lane == 0) ctrl->bad = 1;
+}
+
+__global__ void mis_ls_start_kernel(LsCtrl* __restrict__ ctrl) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->phase = ctrl->bad ? LS_DONE : LS_INSERT;
+}
+
+// tight / owner / state of every node from the current set.  when: the phase it runs in; after_swaps: only in a round that
+// proposed something (the second launch of a swap round: the states the next insertion phase starts from).
+// state: 0 undecided (free), 1 in, 2 out.
+__global__ __launch_bounds__(256) void mis_ls_tight_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ sol, int* __restrict__ tight,
+                                                           int* __restrict__ owner, int* __restrict__ state,
+                                                           const LsCtrl* __restrict__ ctrl, int when, int after_swaps) {
+  const int v = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (v >= n) return;
+  if (ctrl->phase != when || (after_swaps && ctrl->proposals == 0)) return;
+  if (sol[v]) {                                              // wave uniform
+    if (lane == 0) { tight[v] = -1; owner[v] = -1; state[v] = 1; }
+    return;
+  }
+  int c = 0, o = -1;
+  for (int e = rowptr[v] + lane; e < rowptr[v + 1]; e += 64) {
+    const int u = col[e];
+    if (u != v && sol[u]) { ++c; o = max(o, u); }
+  }
+  c = wave_sum(c);
+  o = wave_max(o);
+  if (lane == 0) { tight[v] = c; owner[v] = c == 1 ? o : -1; state[v] = c > 0 ? 2 : 0; }
+}
+
+// One sub-round of the insertion phase: the rule of mis_round_kernel on the free nodes (every other node is decided).
+__global__ __launch_bounds__(256) void mis_ls_insert_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                            const int* __restrict__ rank, int* __restrict__ state,
+                                                            int* __restrict__ sol, LsCtrl* __restrict__ ctrl) {
+  const int v = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (v >= n) return;
+  if (ctrl->phase != LS_INSERT) return;
+  if (state[v] != 0) return;                                 // wave uniform
+  const int rv = rank[v];
+  int any_in = 0, any_open = 0;
+  for (int e = rowptr[v] + lane; e < rowptr[v + 1]; e += 64) {
+    const int u = col[e];
+    if (u == v) continue;
+    if (rank[u] < rv) {
+      const int su = state[u];                               // a stale read only delays the decision by a sub-round
+      any_in |= su == 1;
+      any_open |= su == 0;
+    }
+  }
+  any_in = __any(any_in);
+  any_open = __any(any_open);
+  if (lane == 0) {
+    if (any_in) state[v] = 2;
+    else if (!any_open) { state[v] = 1; sol[v] = 1; atomicAdd(&ctrl->inserts, 1); }
+    else atomicAdd(&ctrl->undecided, 1);
+  }
+}
+
+__global__ void mis_ls_insert_advance_kernel(LsCtrl* __restrict__ ctrl) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || ctrl->phase != LS_INSERT) return;
+  if (ctrl->undecided == 0) ctrl->phase = ctrl->rounds < ctrl->max_rounds ? LS_SWAP : LS_DONE;
+  ctrl->undecided = 0;
+}
+
+// The proposal of every x in the set: prop_u[x], prop_w[x], or -1.  v is in L(x) iff tight[v] == 1 && owner[v] == x.
+// The first node is the pairable candidate of the smallest rank (pairable: fewer than |L(x)| - 1 members of L(x) among its
+// neighbours); candidates are visited in rank order until one is pairable.  The second node is the member of the smallest rank
+// above the first's that is not marked as a neighbour of the first.  mark[w] == u is only ever written for w in N(u), so a mark
+// left by an earlier round still tells the truth.
+__global__ __launch_bounds__(256) void mis_ls_propose_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                             const int* __restrict__ rank, const int* __restrict__ sol,
+                                                             const int* __restrict__ tight, const int* __restrict__ owner,
+                                                             int* __restrict__ mark, int* __restrict__ prop_u,
+                                                             int* __restrict__ prop_w, LsCtrl* __restrict__ ctrl) {
+  const int x = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (x >= n) return;
+  if (ctrl->phase != LS_SWAP) return;
+  if (!sol[x]) return;                                       // wave uniform
+  const int b = rowptr[x], e = rowptr[x + 1];
+  const unsigned long long none = ~0ull;
+  int cnt = 0;
+  for (int i = b + lane; i < e; i += 64) {
+    const int v = col[i];
+    cnt += v != x && tight[v] == 1 && owner[v] == x;
+  }
+  cnt = wave_sum(cnt);
+  int pu = -1, pw = -1;
+  long long last = -1;                                       // rank of the candidate visited last
+  while (cnt >= 2) {
+    unsigned long long best = none;
+    for (int i = b + lane; i < e; i += 64) {
+      const int v = col[i];
+      if (v != x && tight[v] == 1 && owner[v] == x && rank[v] > last) {
+        const unsigned long long key = ((unsigned long long)(unsigned)rank[v] << 32) | (unsigned)v;
+        best = key < best ? key : best;
+      }
+    }
+    best = wave_min64(best);
+    if (best == none) break;                                 // every candidate visited, none pairable
+    const int u = (int)(unsigned)(best & 0xffffffffu);
+    last = (long long)(best >> 32);
+    int c = 0;
+    for (int j = rowptr[u] + lane; j < rowptr[u + 1]; j += 64) {
+      const int w = col[j];
+      if (w != u && w != x && tight[w] == 1 && owner[w] == x) {
+        ++c;
+        __hip_atomic_store(&mark[w], u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    c = wave_sum(c);
+    if (c >= cnt - 1) continue;                              // adjacent to every other candidate
+    __threadfence();                                         // this wave's marks are in memory before it reads them back
+    unsigned long long second = none;
+    for (int i = b + lane; i < e; i += 64) {
+      const int v = col[i];
+      if (v != x && v != u && tight[v] == 1 && owner[v] == x && rank[v] > last &&
+          __hip_atomic_load(&mark[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != u) {
+        const unsigned long long key = ((unsigned long long)(unsigned)rank[v] << 32) | (unsigned)v;
+        second = key < second ? key : second;
+      }
+    }
+    second = wave_min64(second);
+    if (second != none) { pu = u; pw = (int)(unsigned)(second & 0xffffffffu); }
+    break;                                                   // no second node (duplicate entries): no proposal
+  }
+  if (lane == 0) {
+    prop_u[x] = pu;
+    prop_w[x] = pw;
+    if (pu >= 0) atomicAdd(&ctrl->proposals, 1);
+  }
+}
+
+// win[x] = 1 iff x proposes and its key rank[u_x] is below the key of every conflicting proposal.  A neighbour b of u_x or w_x
+// belongs to a proposal iff it is a candidate (of y = owner[b]) and one of y's two nodes.  win = 0 for every other node.
+__global__ __launch_bounds__(256) void mis_ls_conflict_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                              const int* __restrict__ rank, const int* __restrict__ tight,
+                                                              const int* __restrict__ owner, const int* __restrict__ prop_u,
+                                                              const int* __restrict__ prop_w, int* __restrict__ win,
+                                                              const LsCtrl* __restrict__ ctrl) {
+  const int x = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (x >= n) return;
+  if (ctrl->phase != LS_SWAP || ctrl->proposals == 0) return;
+  const int pu = tight[x] == -1 ? prop_u[x] : -1;            // tight == -1: x is in the set (prop_* are this round's)
+  if (pu < 0) {                                              // wave uniform
+    if (lane == 0) win[x] = 0;
+    return;
+  }
+  const int key = rank[pu];
+  int lose = 0;
+  for (int s = 0; s < 2; ++s) {
+    const int a = s == 0 ? pu : prop_w[x];
+    for (int j = rowptr[a] + lane; j < rowptr[a + 1]; j += 64) {
+      const int q = col[j];
+      if (q == a || tight[q] != 1) continue;
+      const int y = owner[q];
+      if (y == x) continue;
+      const int uy = prop_u[y];
+      if (uy >= 0 && (uy == q || prop_w[y] == q)) lose |= rank[uy] < key;
+    }
+  }
+  lose = __any(lose);
+  if (lane == 0) win[x] = !lose;
+}
+
+// All winners at once: x leaves, u_x and w_x enter.  Membership is read from tight (the set before this round), never from
+// sol, which this launch writes; the three entries a winner writes are written by no other thread.
+__global__ void mis_ls_apply_kernel(int n, const int* __restrict__ tight, const int* __restrict__ win,
+                                    const int* __restrict__ prop_u, const int* __restrict__ prop_w, int* __restrict__ sol,
+                                    LsCtrl* __restrict__ ctrl) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  if (x >= n) return;
+  if (ctrl->phase != LS_SWAP || ctrl->proposals == 0) return;
+  if (tight[x] != -1 || !win[x]) return;
+  sol[x] = 0;
+  sol[prop_u[x]] = 1;
+  sol[prop_w[x]] = 1;
+  atomicAdd(&ctrl->swaps, 1);
+}
+
+__global__ void mis_ls_swap_advance_kernel(LsCtrl* __restrict__ ctrl) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || ctrl->phase != LS_SWAP) return;
+  if (ctrl->proposals == 0) {
+    ctrl->phase = LS_DONE;                                   // a round without a proposal ends the search, uncounted
+  } else {
+    ctrl->rounds += 1;
+    ctrl->proposals = 0;
+    ctrl->phase = LS_INSERT;
+  }
+}
+
+__global__ void mis_ls_finish_kernel(int n, const int* __restrict__ sol, int* __restrict__ solution,
+                                     const LsCtrl* __restrict__ ctrl) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  if (ctrl->phase != LS_DONE || ctrl->bad) return;
+  solution[v] = sol[v];
+}
+
+size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+struct LsCarve {
+  float* key_b;
+  unsigned *idx_a, *idx_b;
+  int *rank, *sol, *state, *tight, *owner, *mark, *prop_u, *prop_w, *win;
+  LsCtrl* ctrl;
+  void* temp;
+  size_t temp_bytes, total;
+};
+
+hipError_t ls_carve(void* base, int n, LsCarve* c) {
+  size_t t = 0;
+  hipError_t er = rocprim::radix_sort_pairs_desc(nullptr, t, (float*)nullptr, (float*)nullptr, (unsigned*)nullptr,
+                                                 (unsigned*)nullptr, (size_t)n, 0, 32, 0, false);
+  if (er != hipSuccess) return er;
+  c->temp_bytes = t;
+  size_t cur = 0;
+  auto take = [&](size_t bytes) {
+    size_t at = cur;
+    cur += up256(bytes);
+    return base ? (void*)((char*)base + at) : (void*)nullptr;
+  };
+  const size_t row = 4 * (size_t)n;
+  c->key_b = (float*)take(row);
+  c->idx_a = (unsigned*)take(row);
+  c->idx_b = (unsigned*)take(row);
+  c->rank = (int*)take(row);
+  c->sol = (int*)take(row);
+  c->state = (int*)take(row);
+  c->tight = (int*)take(row);
+  c->owner = (int*)take(row);
+  c->mark = (int*)take(row);
+  c->prop_u = (int*)take(row);
+  c->prop_w = (int*)take(row);
+  c->win = (int*)take(row);
+  c->ctrl = (LsCtrl*)take(sizeof(LsCtrl));
+  c->temp = take(t);
+  c->total = cur;
+  return hipSuccess;
+}
+
+}  // namespace
+}  // namespace difusco
+
+extern "C" {
+
+int difusco_mis_local_search_workspace_bytes(int n_nodes, int64_t n_edges, size_t* bytes) {
+  using namespace difusco;
+  if (!bytes || n_nodes < 1 || n_edges < 0) return set_error(DIFUSCO_EINVAL, "mis_local_search_workspace_bytes: bad arguments");
+  LsCarve c;
+  hipError_t er = ls_carve(nullptr, n_nodes, &c);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "rocprim temp size: %s", hipGetErrorString(er));
+  *bytes = c.total;
+  return DIFUSCO_OK;
+}
+
+int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores, int32_t* solution,
+                             int32_t max_rounds, void* workspace, size_t workspace_bytes, int32_t counters[3], void* stream) {
+  using namespace difusco;
+  if (n_nodes < 1 || !rowptr || !col || !scores || !solution || !workspace || !counters)
+    return set_error(DIFUSCO_EINVAL, "mis_local_search: null array or empty graph");
+  if (max_rounds < 0) return set_error(DIFUSCO_EINVAL, "mis_local_search: max_rounds = %d < 0", (int)max_rounds);
+  LsCarve c;
+  hipError_t er = ls_carve(workspace, n_nodes, &c);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "rocprim temp size: %s", hipGetErrorString(er));
+  if (workspace_bytes < c.total)
+    return set_error(DIFUSCO_EINVAL, "mis_local_search: workspace %zu < %zu bytes", workspace_bytes, c.total);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = n_nodes;
+  const dim3 blk(256);
+  const dim3 g1((unsigned)((n + 255) / 256));                         // one thread per node
+  const dim3 gw((unsigned)(((long long)n * 64 + 255) / 256));         // one wavefront per node
+  const dim3 one(1);
+
+  LsCtrl h;
+  std::memset(&h, 0, sizeof(h));
+  h.phase = LS_DONE;                                                   // until the start kernel has seen the check
+  h.max_rounds = max_rounds;
+  er = hipMemcpyAsync(c.ctrl, &h, sizeof(h), hipMemcpyHostToDevice, st);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_local_search control block: %s", hipGetErrorString(er));
+  hipLaunchKernelGGL(mis_ls_iota_kernel, g1, blk, 0, st, n, c.idx_a);
+  size_t tb = c.temp_bytes;
+  // descending by score; the sort is stable, so equal scores keep increasing index order (the order of difusco_mis_decode)
+  er = rocprim::radix_sort_pairs_desc(c.temp, tb, scores, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "radix_sort_pairs_desc: %s", hipGetErrorString(er));
+  hipLaunchKernelGGL(mis_ls_setup_kernel, g1, blk, 0, st, n, c.idx_b, solution, c.rank, c.sol, c.mark);
+  hipLaunchKernelGGL(mis_ls_check_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_start_kernel, one, dim3(64), 0, st, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_INSERT, 0);
+
+  // every counted round applies a swap and every unfinished sub-round decides a node, so a correct input ends long before this
+  const long long max_groups = 2LL * n + 8;
+  for (long long group = 0;; ++group) {
+    for (int cyc = 0; cyc < LS_CYCLES; ++cyc) {
+      for (int s = 0; s < LS_SUBROUNDS; ++s) {
+        hipLaunchKernelGGL(mis_ls_insert_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.state, c.sol, c.ctrl);
+        hipLaunchKernelGGL(mis_ls_insert_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+      }
+      hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 0);
+      hipLaunchKernelGGL(mis_ls_propose_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.sol, c.tight, c.owner, c.mark,
+                         c.prop_u, c.prop_w, c.ctrl);
+      hipLaunchKernelGGL(mis_ls_conflict_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.tight, c.owner, c.prop_u, c.prop_w,
+                         c.win, c.ctrl);
+      hipLaunchKernelGGL(mis_ls_apply_kernel, g1, blk, 0, st, n, c.tight, c.win, c.prop_u, c.prop_w, c.sol, c.ctrl);
+      hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 1);
+      hipLaunchKernelGGL(mis_ls_swap_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+    }
+    hipLaunchKernelGGL(mis_ls_finish_kernel, g1, blk, 0, st, n, c.sol, solution, c.ctrl);
+    er = hipMemcpyAsync(&h, c.ctrl, sizeof(h), hipMemcpyDeviceToHost, st);
+    if (er == hipSuccess) er = hipStreamSynchronize(st);                // the one host synchronisation of the group
+    if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_local_search rounds: %s", hipGetErrorString(er));
+    if (h.bad) return set_error(DIFUSCO_EINVAL, "mis_local_search: the input set is not independent (solution unchanged)");
+    if (h.phase == LS_DONE) break;
+    if (group > max_groups) return set_error(DIFUSCO_EINVAL, "mis_local_search: no progress (adjacency not symmetric?)");
+  }
+  counters[0] = h.rounds;
+  counters[1] = h.swaps;
+  counters[2] = h.inserts;
+  return DIFUSCO_OK;
+}
+
+}  // extern "C"

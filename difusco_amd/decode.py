@@ -406,3 +406,55 @@ def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, 
                                     ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(rounds),
                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
     return sol.cpu().numpy().astype(int)
+
+
+MIS_LOCAL_SEARCHES = ("none", "swap")
+
+
+def check_mis_local_search(local_search):
+    if local_search not in MIS_LOCAL_SEARCHES:
+        raise ValueError(f"MIS local search {local_search!r}: one of {MIS_LOCAL_SEARCHES}")
+    return local_search
+
+
+def mis_local_search_np(predictions, solution, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0",
+                        graph_build="host", max_rounds=1000, stats=None):
+    """(1,2)-swap local search on a MIS solution (``difusco_mis_local_search``, include/difusco_hip.h; not in the reference):
+    the arguments of ``mis_decode_np`` plus ``solution``, a 0/1 array [N] that is an independent set (e.g. what
+    ``mis_decode_np`` returned; all zeros is allowed).  Rounds of "one chosen node out, two of its neighbours in", each followed
+    by the greedy insertion of the nodes that became free, in the score order of the decode, until no such swap is left or
+    ``max_rounds`` rounds ran; never a smaller set, always independent and maximal.  Returns the 0/1 int numpy array; ``stats``
+    (a dict) receives ``rounds``, ``swaps`` and ``inserts``.  A set that is not independent raises ``DifuscoHipError``.  GPU only."""
+    from .graph import build_csr
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError("mis_local_search_np runs on the GPU only (no CPU fallback)")
+    if int(max_rounds) != max_rounds or max_rounds < 0:
+        raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 0")
+    L = _lib.lib()
+    scores = _dev(predictions, torch.float32, device).reshape(-1)
+    n = scores.shape[0]
+    sol = _dev(solution if isinstance(solution, torch.Tensor) else np.asarray(solution), torch.int32, device).reshape(-1)
+    if sol.shape[0] != n:
+        raise ValueError(f"solution holds {sol.shape[0]} entries for {n} scores")
+    if isinstance(solution, torch.Tensor):
+        sol = sol.clone()                                  # the library refines in place; the caller's tensor stays
+    if graph is None:
+        if edge_index is None:
+            coo = adj_matrix.tocoo()
+            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
+        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
+                          n, device, method=graph_build)
+    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
+    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_mis_local_search_workspace_bytes(n, int(graph.col.shape[0]), ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    counters = (ctypes.c_int32 * 3)()
+    _lib.check(L.difusco_mis_local_search(n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
+                                          ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(sol.data_ptr()), int(max_rounds),
+                                          ctypes.c_void_p(ws.data_ptr()), nbytes.value, counters,
+                                          ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
+    return sol.cpu().numpy().astype(int)

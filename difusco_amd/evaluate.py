@@ -23,7 +23,9 @@ depend on the world size, the rank an instance lands on, or what the model ran b
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
 ``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--local_search
 {2opt,2opt+oropt}`` (``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
-``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``), ``--merge_method {loop,batched}``
+``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``), ``--mis_local_search {none,swap}`` (MIS:
+``decode.mis_local_search_np`` after every decode, never a smaller set; the records gain ``decoded_costs``, the greedy sizes in
+the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -99,6 +101,9 @@ EXTENSION_ARGS = [
     ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt"),
                              help="tour refinement: 2opt (the reference's) or 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
                                   "records gain or_opt_iterations and local_search_rounds)")),
+    ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
+                                 help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
+                                      "search; records gain decoded_costs)")),
     ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
                             help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
     ("--graph_build", dict(type=str, default="host", choices=("host", "device"),
@@ -143,6 +148,8 @@ def parse_args(argv=None):
         parser.error("--ckpt_path is required (the weights to evaluate)")
     if args.local_search != "2opt" and args.two_opt_method != "exact":
         parser.error(f"--local_search {args.local_search} runs the exact 2-opt sweep: --two_opt_method {args.two_opt_method} is not built")
+    if args.mis_local_search != "none" and args.task != "mis":
+        parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     ignored = sorted(k for k in given if k in TRAINING_ONLY or (k == "save_numpy_heatmap" and args.task == "mis"))
     return args, ignored
 
@@ -258,11 +265,14 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
     return rec
 
 
-def mis_record(split: str, index: int, ex, seed: int, result) -> dict:
+def mis_record(split: str, index: int, ex, seed: int, result, stats: Optional[dict] = None) -> dict:
     sol, size, sizes = result
-    return {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.n_nodes),
-            "gt_cost": float(np.asarray(ex.labels).sum()), "solved_cost": float(size), "all_costs": [float(s) for s in sizes],
-            "seed": int(seed), "mis": np.nonzero(np.asarray(sol))[0].tolist()}
+    rec = {"split": split, "index": int(index), "source": list(ex.source), "n_nodes": int(ex.n_nodes),
+           "gt_cost": float(np.asarray(ex.labels).sum()), "solved_cost": float(size), "all_costs": [float(s) for s in sizes],
+           "seed": int(seed), "mis": np.nonzero(np.asarray(sol))[0].tolist()}
+    if stats is not None:      # --mis_local_search swap: the greedy sizes only (the call counters belong to a chunk, not an instance)
+        rec["decoded_costs"] = [float(s) for s in stats["decoded_sizes"]]
+    return rec
 
 
 def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, Optional[float]]:
@@ -284,7 +294,8 @@ def split_metrics(task: str, split: str, records: Sequence[dict]) -> Dict[str, O
 def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0, sparse_factor: int = -1,
                 parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
-                two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt") -> List[dict]:
+                two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt",
+                mis_local_search: str = "none") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -310,11 +321,14 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 if heats is not None:
                     save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
         else:
+            swap = mis_local_search != "none"
+            ls_stats = [] if swap else None
             res = solve_mis_batch(model, [(examples[i].n_nodes, examples[i].edge_index) for i in idx],
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling, seeds=seeds,
-                                  generators=gens, timings=timings, step_offset=0)
+                                  generators=gens, timings=timings, step_offset=0,
+                                  **(dict(local_search=mis_local_search, stats=ls_stats) if swap else {}))
             for k, i in enumerate(idx):
-                records.append(mis_record(split, i, examples[i], seeds[k], res[k]))
+                records.append(mis_record(split, i, examples[i], seeds[k], res[k], ls_stats[k] if swap else None))
     return records
 
 
@@ -372,7 +386,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
                                two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir,
                                two_opt_method=args.two_opt_method, merge_method=args.merge_method,
-                               local_search=args.local_search)
+                               local_search=args.local_search, mis_local_search=args.mis_local_search)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -397,6 +411,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["mixed_size_chunks"] = True
             if args.local_search != "2opt":
                 line["local_search"] = args.local_search
+            if args.mis_local_search != "none":
+                line["mis_local_search"] = args.mis_local_search
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

@@ -101,32 +101,48 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
 
 def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, generator: Optional[torch.Generator] = None,
-              timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1, *, graphed: bool = False):
+              timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1, *, graphed: bool = False,
+              local_search: str = "none", local_search_rounds: int = 1000, stats: Optional[dict] = None):
     """``MISModel.test_step`` (``difusco/pl_mis_model.py:142-206``): ``sequential_sampling`` rounds of
     ``parallel_sampling`` noise samples of ONE graph through the denoising loop (disjoint union), greedy decode of every
     sample, best = largest set.  ``edge_index``: int64 [2,E] in the dataset's layout (both directions + self loops).
     Returns (best 0/1 array, best size, sizes).  Upstream re-duplicates ``edge_index`` inside the sequential loop
     (``pl_mis_model.py:168-169``), which breaks ``parallel > 1 and sequential > 1`` there; here the duplication happens
     once, which is what that combination means.  ``graphed=True``: every sampling loop is one graph replay
-    (``MISModel.sample``), same results."""
-    from .decode import mis_decode_np
+    (``MISModel.sample``), same results.  ``local_search``: "none" (default) or "swap": every decode is followed by one
+    ``decode.mis_local_search_np`` call on the same graph (all P copies at once, at most ``local_search_rounds`` rounds): never
+    a smaller set.  ``stats`` (a dict) then receives ``decoded_sizes`` (the greedy sizes in the order of ``sizes``) and the
+    call counters ``rounds``, ``swaps``, ``inserts`` summed over the sequential rounds."""
+    from .decode import check_mis_local_search, mis_decode_np, mis_local_search_np
+    check_mis_local_search(local_search)
     dev = model.device
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index))
     ei = ei.to(dev)
     tick = _ticker(timings, dev)
     ei_rep = model.duplicate_edge_index(ei, n_nodes, dev, copies=parallel_sampling) if parallel_sampling > 1 else ei   # pl_mis_model.py:168-169
     graph = model.prepare_graph(ei_rep, n_nodes * parallel_sampling)
-    sols = []
+    sols, decoded, counters = [], [], {"rounds": 0, "swaps": 0, "inserts": 0}
     for _ in range(sequential_sampling):                                                          # :156
         t0 = time.perf_counter()
         scores = model.sample(n_nodes * parallel_sampling, ei_rep, generator=generator, graphed=graphed)   # :157-192
         tick("sampling", t0)
         t0 = time.perf_counter()
-        sols.append(mis_decode_np(scores, graph=graph, device=dev).reshape(parallel_sampling, n_nodes))   # :195-198
+        sol = mis_decode_np(scores, graph=graph, device=dev)                                      # :195-198
         tick("decode", t0)
+        if local_search == "swap":
+            t0 = time.perf_counter()
+            decoded += sol.reshape(parallel_sampling, n_nodes).sum(axis=1).tolist()
+            call = {}
+            sol = mis_local_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call)
+            for k in counters:
+                counters[k] += call[k]
+            tick("local_search", t0)
+        sols.append(sol.reshape(parallel_sampling, n_nodes))
     sol = np.concatenate(sols, axis=0)
     sizes = sol.sum(axis=1)
     best = int(np.argmax(sizes))
+    if local_search == "swap" and stats is not None:
+        stats.update(decoded_sizes=decoded, **counters)
     return sol[best], int(sizes[best]), sizes.tolist()
 
 
@@ -350,13 +366,19 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
 def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sampling: int = 1,
                     seeds: Optional[Sequence[int]] = None, generators: Optional[Sequence[torch.Generator]] = None,
                     timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None,
-                    step_offset: Optional[int] = None) -> List[tuple]:
+                    step_offset: Optional[int] = None, *, local_search: str = "none", local_search_rounds: int = 1000,
+                    stats: Optional[list] = None) -> List[tuple]:
     """``solve_mis`` of B graphs: ``instances`` = [(n_nodes, edge_index), ...].  Returns the list of what ``solve_mis`` returns
     for every graph (run with ``seed = seeds[b]``, ``generator = generators[b]``).  Up to ``instances_per_call`` graphs share
     one sampling loop over their union (``MISModel.sample_batch``) and one greedy decode of the union (``mis_decode_np``: the
-    decode never crosses a component, so every graph gets its own decode).  ``step_offset``: as in ``solve_tsp_batch``."""
-    from .decode import mis_decode_np
+    decode never crosses a component, so every graph gets its own decode).  ``step_offset``: as in ``solve_tsp_batch``.
+    ``local_search``, ``local_search_rounds``: as ``solve_mis``; one ``decode.mis_local_search_np`` call per decode on the
+    union of the chunk (the search never crosses a component and round r of the union is round r of every graph, so every graph
+    gets its solo answer).  ``stats``: a list to which one dict per instance is appended (only with "swap"): ``decoded_sizes``
+    of the instance, and the counters ``rounds``, ``swaps``, ``inserts`` of its CHUNK's calls summed over the sequential rounds."""
+    from .decode import check_mis_local_search, mis_decode_np, mis_local_search_np
     from .graph import build_csr
+    check_mis_local_search(local_search)
     instances = list(instances)
     B = len(instances)
     if B < 1:
@@ -377,6 +399,8 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
         union = torch.cat([e + int(off[g]) for g, e in enumerate(eis)], dim=1)
         graph = build_csr(union, int(off[-1]), dev, method=getattr(model, "graph_build", "host"))
         sols = [[] for _ in ns]
+        decoded = [[] for _ in ns]
+        counters = {"rounds": 0, "swaps": 0, "inserts": 0}
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             scores = model.sample_batch([n * P for n in ns], eis, seeds=None if seeds is None else seeds[c0:c1],
@@ -385,12 +409,24 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
             tick("sampling", t0)
             t0 = time.perf_counter()
             sol = mis_decode_np(torch.cat(scores), graph=graph, device=dev)
+            if local_search == "swap":
+                tick("decode", t0)
+                t0 = time.perf_counter()
+                for g, n in enumerate(ns):
+                    decoded[g] += sol[off[g]:off[g + 1]].reshape(P, n).sum(axis=1).tolist()
+                call = {}
+                sol = mis_local_search_np(torch.cat(scores), sol, graph=graph, device=dev, max_rounds=local_search_rounds,
+                                          stats=call)
+                for k in counters:
+                    counters[k] += call[k]
             for g, n in enumerate(ns):
                 sols[g].append(sol[off[g]:off[g + 1]].reshape(P, n))
-            tick("decode", t0)
+            tick("local_search" if local_search == "swap" else "decode", t0)
         for g in range(len(ns)):
             sol = np.concatenate(sols[g], axis=0)
             sizes = sol.sum(axis=1)
             best = int(np.argmax(sizes))
             results.append((sol[best], int(sizes[best]), sizes.tolist()))
+            if local_search == "swap" and stats is not None:
+                stats.append(dict(decoded_sizes=decoded[g], **counters))
     return results

@@ -410,6 +410,37 @@ int difusco_mis_decode_workspace_bytes(int n_nodes, size_t* bytes);
 int difusco_mis_decode(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores, int32_t* solution,
                        void* workspace, size_t workspace_bytes, int32_t* rounds_out, void* stream);
 
+/* ---- (1,2)-swap local search for MIS solutions (additive to ABI 13; not in the reference, whose MIS path ends at the greedy
+ * decode).  rowptr/col/scores: as difusco_mis_decode (DEVICE; the symmetric adjacency of the whole call, self loops allowed and
+ * ignored, rows may be empty).  solution: DEVICE int32 [n_nodes], in/out: an independent set (non-zero = chosen), not
+ * necessarily maximal, all zeros allowed; on return 0/1.
+ *   rank[v]   position of v in the stable descending sort of the scores - the order of difusco_mis_decode, equal scores by
+ *             increasing node id; a smaller rank is a higher priority.
+ *   tight[v]  on the current set S: the number of neighbours u != v of v in S.  A node outside S is FREE with tight = 0 and a
+ *             CANDIDATE of its one solution neighbour with tight = 1; L(x) is the set of candidates of x in S.
+ *   insertion phase  insert the lexicographically first maximal independent set, by rank, of the subgraph the free nodes
+ *             induce: a free node goes in iff all its higher-priority free neighbours stay out.
+ * One insertion phase, then rounds until a round proposes nothing (that round is not counted) or max_rounds rounds ran:
+ *   1. proposal  every x in S takes the pair (u, w), u and w in L(x), not adjacent, rank[u] < rank[w], that is smallest in
+ *                (rank[u], rank[w]); without such a pair x proposes nothing;
+ *   2. conflict  proposals x != y conflict iff a node of {u_x, w_x} is adjacent to a node of {u_y, w_y}; x is applied iff
+ *                rank[u_x] < rank[u_y] for every conflicting y (the keys are distinct: candidate sets are disjoint; the
+ *                smallest key always applies, so a counted round applies a swap and there are at most n_nodes rounds);
+ *   3. apply     all winners at once: x leaves S, u_x and w_x enter;
+ *   4. an insertion phase (the third leaf of a claw; nodes whose two solution neighbours both left).
+ * The result is independent and maximal, |S_out| = |S_in| + swaps + inserts, and with max_rounds high enough no x has a
+ * proposal left.  Every step is local to a connected component and round r of a union is round r of every component, so a
+ * call on a disjoint union gives every component the nodes its own call gives, capped or not.  Duplicate entries in a
+ * neighbour list can only make the search find fewer swaps, never a dependent set.
+ * counters: HOST int32 [3] = rounds, swaps, inserts of the whole call.  max_rounds = 0 runs the first insertion phase only.
+ * DIFUSCO_EINVAL on a null array, n_nodes < 1, max_rounds < 0, a workspace below _workspace_bytes, and on an input set that
+ * is not independent: one checking pass sets a device flag and solution is left unchanged.  All per-round work runs on the
+ * device behind a phase word in the workspace; the host polls it once per group of four rounds.  Blocks. */
+int difusco_mis_local_search_workspace_bytes(int n_nodes, int64_t n_edges, size_t* bytes);
+int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores,
+                             int32_t* solution /* in/out, device */, int32_t max_rounds, void* workspace,
+                             size_t workspace_bytes, int32_t counters[3] /* host: rounds, swaps, inserts */, void* stream);
+
 /* ---- heatmap -> tour: the greedy edge insertion the reference runs on the host right after the
  * sampling loop, difusco/utils/tsp_utils.py:89-145 (merge_tours) + utils/cython_merge/cython_merge.pyx:19-104
  * (merge_cython), restricted to the E entries of the sparse heatmap instead of the N x N densification.
