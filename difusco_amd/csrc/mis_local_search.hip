@@ -20,26 +20,37 @@
 // maximal independent set.  (b) The propose kernel marks, in mark[], the candidates of x adjacent to its first node and reads
 // the marks back in the SAME wave; candidate sets of different x are disjoint, so no other wave touches those entries.
 // The counters are integer atomic adds.
+//
+// difusco_mis_iterated_search (second half of this file) repeats that descent between seeded random kicks: the same kernels and
+// phase word, two more phases, and a kick sequence after every IT_CYCLES cycles (restated in tests/mis_iterated_search_emulation.py).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/difusco_hip.h"
+#include "common.h"
 #include "kernels.h"
 
 namespace difusco {
 namespace {
 
 constexpr int LS_INSERT = 0, LS_SWAP = 1, LS_DONE = 2;
+constexpr int LS_KICK = 3, LS_FINAL = 4;   // the iterated search only (below): a kick is being applied; the incumbent is final
 constexpr int LS_CYCLES = 4;         // swap rounds enqueued between two host polls
 constexpr int LS_SUBROUNDS = 2;      // insertion sub-rounds enqueued in front of every swap round
 
 struct LsCtrl {                      // device; the host reads it once per group
   int phase, bad, rounds, swaps, inserts, proposals, undecided, max_rounds;
+  // the iterated search only: kicks asked for and applied, 1 once the first descent is the incumbent, the round cap of ONE
+  // descent (max_rounds above is then rounds-so-far + cap), kick_size, 1 when the instance table is malformed
+  int kicks, kicks_done, started, cap, kick_size, bad_table;
 };
+
+thread_local int g_host_syncs = 0;   // host synchronisations of this thread's last search call (difusco_mis_search_host_syncs)
 
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
@@ -285,6 +296,168 @@ __global__ void mis_ls_finish_kernel(int n, const int* __restrict__ sol, int* __
   solution[v] = sol[v];
 }
 
+// ---- the iterated search (difusco_mis_iterated_search): kicks between descents ----------------------------------------------
+// After the cycles of a unit comes the kick sequence.  Its kernels run only when the descent has ended (phase DONE):
+//   keep      one block per instance: |C_b| against |I_b|, then I_b <- C_b or C_b <- I_b (the first time: I <- the descent)
+//   advance   DONE -> FINAL when every kick ran, else -> KICK
+//   draw      w_v and the kicked test of every node          (KICK)
+//   enter     the kicked nodes without a smaller kicked neighbour (KICK)
+//   evict     members next to an entered node leave, the entered nodes go in (KICK)
+//   tight     the states the next descent starts from        (KICK)
+//   advance   KICK -> INSERT: the next descent, with its own round cap  Every kernel reads what earlier launches wrote; the only words two waves of
+// one launch write are entered_flag[b], where every writer stores the same 1.
+
+// The instance of node v: the last b with rows[b] <= v.  Stays inside the table whatever the table holds.
+__device__ __forceinline__ int ls_instance_of(const int64_t* __restrict__ rows, int nb, int v) {
+  int lo = 0, hi = nb;
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (rows[mid] <= (int64_t)v) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// rows[0] = 0, rows[nb] = n, non-decreasing; anything else ends the call before a kernel walks an instance
+__global__ void mis_it_table_kernel(int n, int nb, const int64_t* __restrict__ rows, LsCtrl* __restrict__ ctrl) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > nb) return;
+  const bool bad = i == nb ? rows[nb] != (int64_t)n : (rows[i] > rows[i + 1] || (i == 0 && rows[0] != 0));
+  if (bad) { ctrl->bad_table = 1; ctrl->bad = 1; }
+}
+
+__global__ void mis_it_setup_kernel(int n, int nb, const int64_t* __restrict__ rows, int* __restrict__ inst,
+                                    int* __restrict__ entered_flag, int* __restrict__ per) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n) inst[v] = ls_instance_of(rows, nb, v);
+  if (v < nb) {
+    entered_flag[v] = 0;
+    per[4 * v] = per[4 * v + 1] = per[4 * v + 2] = per[4 * v + 3] = 0;
+  }
+}
+
+// per: entered, accepted, size_before, size_after of every instance
+__global__ __launch_bounds__(256) void mis_it_keep_kernel(const int64_t* __restrict__ rows, int* __restrict__ sol,
+                                                          int* __restrict__ inc, int* __restrict__ isize,
+                                                          int* __restrict__ entered_flag, int* __restrict__ per,
+                                                          const LsCtrl* __restrict__ ctrl) {
+  if (ctrl->phase != LS_DONE || ctrl->bad) return;
+  __shared__ int part[4];
+  __shared__ int total;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lo = (int)rows[b], hi = (int)rows[b + 1];
+  const int first = !ctrl->started;
+  const int old = first ? 0 : isize[b];                      // read by every thread before thread 0 writes it
+  int c = 0;
+  for (int v = lo + (int)threadIdx.x; v < hi; v += 256) c += sol[v] != 0;
+  c = wave_sum(c);
+  if (lane == 0) part[wave] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) total = part[0] + part[1] + part[2] + part[3];
+  __syncthreads();
+  const int cnt = total;
+  const int keep = first || cnt >= old;
+  for (int v = lo + (int)threadIdx.x; v < hi; v += 256) {
+    if (keep) inc[v] = sol[v]; else sol[v] = inc[v];
+  }
+  if (threadIdx.x == 0) {
+    if (first) per[4 * b + 2] = cnt;
+    else if (entered_flag[b]) { per[4 * b] += 1; per[4 * b + 1] += keep; }
+    entered_flag[b] = 0;
+    if (keep) isize[b] = cnt;
+    per[4 * b + 3] = keep ? cnt : old;
+  }
+}
+
+__global__ void mis_it_keep_advance_kernel(LsCtrl* __restrict__ ctrl) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || ctrl->phase != LS_DONE || ctrl->bad) return;
+  ctrl->started = 1;
+  ctrl->phase = ctrl->kicks_done >= ctrl->kicks ? LS_FINAL : LS_KICK;
+}
+
+// kw[v] = w_v when v is kicked, -1 otherwise.  sol is the incumbent here (the keep kernel made it so).
+__global__ void mis_it_draw_kernel(int n, const int64_t* __restrict__ rows, const uint64_t* __restrict__ seeds,
+                                   const uint64_t* __restrict__ offsets, const int* __restrict__ inst,
+                                   const int* __restrict__ isize, const int* __restrict__ sol, int* __restrict__ kw,
+                                   const LsCtrl* __restrict__ ctrl) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  if (ctrl->phase != LS_KICK) return;
+  int out = -1;
+  if (!sol[v]) {
+    const int b = inst[v];
+    const int64_t lo = rows[b];
+    uint32_t r[4];
+    Philox::run(seeds[b], offsets[b] + (uint64_t)ctrl->kicks_done, (uint64_t)((int64_t)v - lo), r);
+    const uint64_t w = r[0] >> 8;
+    const uint64_t m = (uint64_t)(rows[b + 1] - lo - (int64_t)isize[b]);
+    if (w * m < ((uint64_t)ctrl->kick_size << 24)) out = (int)w;     // exact: w < 2^24, m < 2^31, kick_size < 2^31
+  }
+  kw[v] = out;
+}
+
+// One wavefront per node.  ent[v] = 1 iff v is kicked and no kicked neighbour has a smaller (w, node).
+__global__ __launch_bounds__(256) void mis_it_enter_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ kw, const int* __restrict__ inst,
+                                                           int* __restrict__ ent, int* __restrict__ entered_flag,
+                                                           const LsCtrl* __restrict__ ctrl) {
+  const int v = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (v >= n) return;
+  if (ctrl->phase != LS_KICK) return;
+  const int wv = kw[v];
+  if (wv < 0) {                                              // wave uniform
+    if (lane == 0) ent[v] = 0;
+    return;
+  }
+  const unsigned long long key = ((unsigned long long)(unsigned)wv << 32) | (unsigned)v;
+  int lose = 0;
+  for (int e = rowptr[v] + lane; e < rowptr[v + 1]; e += 64) {
+    const int u = col[e];
+    const int wu = kw[u];
+    if (u != v && wu >= 0) lose |= (((unsigned long long)(unsigned)wu << 32) | (unsigned)u) < key;
+  }
+  lose = __any(lose);
+  if (lane == 0) {
+    ent[v] = !lose;
+    if (!lose) __hip_atomic_store(&entered_flag[inst[v]], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One wavefront per node.  Every wave writes sol[v] of its own node only and reads ent[], which this launch does not write.
+__global__ __launch_bounds__(256) void mis_it_evict_kernel(int n, const int* __restrict__ rowptr, const int* __restrict__ col,
+                                                           const int* __restrict__ ent, int* __restrict__ sol,
+                                                           const LsCtrl* __restrict__ ctrl) {
+  const int v = (int)(((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+  if (v >= n) return;
+  if (ctrl->phase != LS_KICK) return;
+  if (ent[v]) {                                              // wave uniform
+    if (lane == 0) sol[v] = 1;
+    return;
+  }
+  if (!sol[v]) return;                                       // wave uniform
+  int hit = 0;
+  for (int e = rowptr[v] + lane; e < rowptr[v + 1]; e += 64) {
+    const int u = col[e];
+    hit |= u != v && ent[u] != 0;
+  }
+  if (__any(hit) && lane == 0) sol[v] = 0;
+}
+
+__global__ void mis_it_kick_advance_kernel(LsCtrl* __restrict__ ctrl) {
+  if (blockIdx.x != 0 || threadIdx.x != 0 || ctrl->phase != LS_KICK) return;
+  ctrl->kicks_done += 1;
+  const long long cap = (long long)ctrl->rounds + ctrl->cap;           // the descent that starts now has its own cap
+  ctrl->max_rounds = cap > 0x7fffffffLL ? 0x7fffffff : (int)cap;
+  ctrl->phase = LS_INSERT;
+}
+
+__global__ void mis_it_finish_kernel(int n, const int* __restrict__ sol, int* __restrict__ solution,
+                                     const LsCtrl* __restrict__ ctrl) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= n) return;
+  if (ctrl->phase != LS_FINAL || ctrl->bad) return;
+  solution[v] = sol[v];
+}
+
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct LsCarve {
@@ -327,6 +500,69 @@ hipError_t ls_carve(void* base, int n, LsCarve* c) {
   return hipSuccess;
 }
 
+// What a search starts with: the control block, the ranks, the working copy of the set and the checking pass.
+hipError_t ls_enqueue_begin(const LsCarve& c, int n, const int* rowptr, const int* col, const float* scores,
+                            const int* solution, const LsCtrl& h, hipStream_t st) {
+  const dim3 blk(256), g1((unsigned)((n + 255) / 256)), gw((unsigned)(((long long)n * 64 + 255) / 256));
+  hipError_t er = hipMemcpyAsync(c.ctrl, &h, sizeof(h), hipMemcpyHostToDevice, st);
+  if (er != hipSuccess) return er;
+  hipLaunchKernelGGL(mis_ls_iota_kernel, g1, blk, 0, st, n, c.idx_a);
+  size_t tb = c.temp_bytes;
+  // descending by score; the sort is stable, so equal scores keep increasing index order (the order of difusco_mis_decode)
+  er = rocprim::radix_sort_pairs_desc(c.temp, tb, scores, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
+  if (er != hipSuccess) return er;
+  hipLaunchKernelGGL(mis_ls_setup_kernel, g1, blk, 0, st, n, c.idx_b, solution, c.rank, c.sol, c.mark);
+  hipLaunchKernelGGL(mis_ls_check_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.ctrl);
+  return hipSuccess;
+}
+
+// One cycle: SUBROUNDS x (insert round, insert advance), then one swap round.
+void ls_enqueue_cycle(const LsCarve& c, int n, const int* rowptr, const int* col, hipStream_t st) {
+  const dim3 blk(256), g1((unsigned)((n + 255) / 256)), gw((unsigned)(((long long)n * 64 + 255) / 256)), one(1);
+  for (int s = 0; s < LS_SUBROUNDS; ++s) {
+    hipLaunchKernelGGL(mis_ls_insert_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.state, c.sol, c.ctrl);
+    hipLaunchKernelGGL(mis_ls_insert_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+  }
+  hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 0);
+  hipLaunchKernelGGL(mis_ls_propose_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.sol, c.tight, c.owner, c.mark,
+                     c.prop_u, c.prop_w, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_conflict_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.tight, c.owner, c.prop_u, c.prop_w,
+                     c.win, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_apply_kernel, g1, blk, 0, st, n, c.tight, c.win, c.prop_u, c.prop_w, c.sol, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 1);
+  hipLaunchKernelGGL(mis_ls_swap_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+}
+
+constexpr int IT_CYCLES = 2;         // cycles in front of every kick sequence (a descent after a kick is short)
+constexpr int IT_UNITS = 8;          // (cycles, kick sequence) units enqueued between two host polls
+
+struct ItCarve {                     // the workspace of the iterated search: the descent's, then its own arrays
+  LsCarve ls;
+  int *inc, *kw, *ent, *inst, *isize, *entered_flag, *per;
+  size_t total;
+};
+
+hipError_t it_carve(void* base, int n, int nb, ItCarve* c) {
+  hipError_t er = ls_carve(base, n, &c->ls);
+  if (er != hipSuccess) return er;
+  size_t cur = c->ls.total;
+  auto take = [&](size_t bytes) {
+    size_t at = cur;
+    cur += up256(bytes);
+    return base ? (int*)((char*)base + at) : (int*)nullptr;
+  };
+  const size_t row = 4 * (size_t)n, irow = 4 * (size_t)nb;
+  c->inc = take(row);
+  c->kw = take(row);
+  c->ent = take(row);
+  c->inst = take(row);
+  c->isize = take(irow);
+  c->entered_flag = take(irow);
+  c->per = take(4 * irow);
+  c->total = cur;
+  return hipSuccess;
+}
+
 }  // namespace
 }  // namespace difusco
 
@@ -348,6 +584,7 @@ int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* 
   if (n_nodes < 1 || !rowptr || !col || !scores || !solution || !workspace || !counters)
     return set_error(DIFUSCO_EINVAL, "mis_local_search: null array or empty graph");
   if (max_rounds < 0) return set_error(DIFUSCO_EINVAL, "mis_local_search: max_rounds = %d < 0", (int)max_rounds);
+  g_host_syncs = 0;
   LsCarve c;
   hipError_t er = ls_carve(workspace, n_nodes, &c);
   if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "rocprim temp size: %s", hipGetErrorString(er));
@@ -364,38 +601,19 @@ int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* 
   std::memset(&h, 0, sizeof(h));
   h.phase = LS_DONE;                                                   // until the start kernel has seen the check
   h.max_rounds = max_rounds;
-  er = hipMemcpyAsync(c.ctrl, &h, sizeof(h), hipMemcpyHostToDevice, st);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_local_search control block: %s", hipGetErrorString(er));
-  hipLaunchKernelGGL(mis_ls_iota_kernel, g1, blk, 0, st, n, c.idx_a);
-  size_t tb = c.temp_bytes;
-  // descending by score; the sort is stable, so equal scores keep increasing index order (the order of difusco_mis_decode)
-  er = rocprim::radix_sort_pairs_desc(c.temp, tb, scores, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "radix_sort_pairs_desc: %s", hipGetErrorString(er));
-  hipLaunchKernelGGL(mis_ls_setup_kernel, g1, blk, 0, st, n, c.idx_b, solution, c.rank, c.sol, c.mark);
-  hipLaunchKernelGGL(mis_ls_check_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.ctrl);
+  er = ls_enqueue_begin(c, n, rowptr, col, scores, solution, h, st);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_local_search start: %s", hipGetErrorString(er));
   hipLaunchKernelGGL(mis_ls_start_kernel, one, dim3(64), 0, st, c.ctrl);
   hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_INSERT, 0);
 
   // every counted round applies a swap and every unfinished sub-round decides a node, so a correct input ends long before this
   const long long max_groups = 2LL * n + 8;
   for (long long group = 0;; ++group) {
-    for (int cyc = 0; cyc < LS_CYCLES; ++cyc) {
-      for (int s = 0; s < LS_SUBROUNDS; ++s) {
-        hipLaunchKernelGGL(mis_ls_insert_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.state, c.sol, c.ctrl);
-        hipLaunchKernelGGL(mis_ls_insert_advance_kernel, one, dim3(64), 0, st, c.ctrl);
-      }
-      hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 0);
-      hipLaunchKernelGGL(mis_ls_propose_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.sol, c.tight, c.owner, c.mark,
-                         c.prop_u, c.prop_w, c.ctrl);
-      hipLaunchKernelGGL(mis_ls_conflict_kernel, gw, blk, 0, st, n, rowptr, col, c.rank, c.tight, c.owner, c.prop_u, c.prop_w,
-                         c.win, c.ctrl);
-      hipLaunchKernelGGL(mis_ls_apply_kernel, g1, blk, 0, st, n, c.tight, c.win, c.prop_u, c.prop_w, c.sol, c.ctrl);
-      hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_SWAP, 1);
-      hipLaunchKernelGGL(mis_ls_swap_advance_kernel, one, dim3(64), 0, st, c.ctrl);
-    }
+    for (int cyc = 0; cyc < LS_CYCLES; ++cyc) ls_enqueue_cycle(c, n, rowptr, col, st);
     hipLaunchKernelGGL(mis_ls_finish_kernel, g1, blk, 0, st, n, c.sol, solution, c.ctrl);
     er = hipMemcpyAsync(&h, c.ctrl, sizeof(h), hipMemcpyDeviceToHost, st);
     if (er == hipSuccess) er = hipStreamSynchronize(st);                // the one host synchronisation of the group
+    ++g_host_syncs;
     if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_local_search rounds: %s", hipGetErrorString(er));
     if (h.bad) return set_error(DIFUSCO_EINVAL, "mis_local_search: the input set is not independent (solution unchanged)");
     if (h.phase == LS_DONE) break;
@@ -404,6 +622,99 @@ int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* 
   counters[0] = h.rounds;
   counters[1] = h.swaps;
   counters[2] = h.inserts;
+  return DIFUSCO_OK;
+}
+
+int difusco_mis_search_host_syncs(void) { return difusco::g_host_syncs; }
+
+int difusco_mis_iterated_search_workspace_bytes(int n_nodes, int64_t n_edges, int n_instances, size_t* bytes) {
+  using namespace difusco;
+  if (!bytes || n_nodes < 1 || n_edges < 0 || n_instances < 1)
+    return set_error(DIFUSCO_EINVAL, "mis_iterated_search_workspace_bytes: bad arguments");
+  ItCarve c;
+  hipError_t er = it_carve(nullptr, n_nodes, n_instances, &c);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "rocprim temp size: %s", hipGetErrorString(er));
+  *bytes = c.total;
+  return DIFUSCO_OK;
+}
+
+int difusco_mis_iterated_search(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores, int32_t* solution,
+                                int n_instances, const int64_t* instance_rows, const uint64_t* instance_seeds,
+                                const uint64_t* instance_offsets, int32_t kicks, int32_t kick_size, int32_t max_rounds,
+                                void* workspace, size_t workspace_bytes, int32_t counters[3], int32_t* per_instance, void* stream) {
+  using namespace difusco;
+  g_host_syncs = 0;
+  if (n_nodes < 1 || !rowptr || !col || !scores || !solution || !workspace || !counters || !instance_rows || !instance_seeds ||
+      !instance_offsets)
+    return set_error(DIFUSCO_EINVAL, "mis_iterated_search: null array or empty graph");
+  if (n_instances < 1) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: n_instances = %d < 1", n_instances);
+  if (max_rounds < 0) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: max_rounds = %d < 0", (int)max_rounds);
+  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: kicks = %d < 0", (int)kicks);
+  if (kick_size < 1) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: kick_size = %d < 1", (int)kick_size);
+  ItCarve w;
+  hipError_t er = it_carve(workspace, n_nodes, n_instances, &w);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "rocprim temp size: %s", hipGetErrorString(er));
+  if (workspace_bytes < w.total)
+    return set_error(DIFUSCO_EINVAL, "mis_iterated_search: workspace %zu < %zu bytes", workspace_bytes, w.total);
+  const LsCarve& c = w.ls;
+  hipStream_t st = (hipStream_t)stream;
+  const int n = n_nodes, nb = n_instances;
+  const dim3 blk(256);
+  const dim3 g1((unsigned)((n + 255) / 256));                         // one thread per node
+  const dim3 gw((unsigned)(((long long)n * 64 + 255) / 256));         // one wavefront per node
+  const dim3 gs((unsigned)(((n > nb ? n : nb) + 255) / 256));         // one thread per node and per instance
+  const dim3 gt((unsigned)(nb / 256 + 1));                            // one thread per table entry
+  const dim3 one(1);
+
+  LsCtrl h;
+  std::memset(&h, 0, sizeof(h));
+  h.phase = LS_DONE;                                                   // until the start kernel has seen the checks
+  h.max_rounds = h.cap = max_rounds;
+  h.kicks = kicks;
+  h.kick_size = kick_size;
+  er = ls_enqueue_begin(c, n, rowptr, col, scores, solution, h, st);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_iterated_search start: %s", hipGetErrorString(er));
+  hipLaunchKernelGGL(mis_it_table_kernel, gt, blk, 0, st, n, nb, instance_rows, c.ctrl);
+  hipLaunchKernelGGL(mis_it_setup_kernel, gs, blk, 0, st, n, nb, instance_rows, w.inst, w.entered_flag, w.per);
+  hipLaunchKernelGGL(mis_ls_start_kernel, one, dim3(64), 0, st, c.ctrl);
+  hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl, LS_INSERT, 0);
+
+  std::vector<int32_t> per(4 * (size_t)nb);
+  // every descent ends within 2 n + 8 groups (difusco_mis_local_search), and there are kicks + 1 of them
+  const long long max_groups = (2LL * n + 8) * ((long long)kicks + 1);
+  for (long long group = 0;; ++group) {
+    for (int unit = 0; unit < IT_UNITS; ++unit) {
+      for (int cyc = 0; cyc < IT_CYCLES; ++cyc) ls_enqueue_cycle(c, n, rowptr, col, st);
+      hipLaunchKernelGGL(mis_it_keep_kernel, dim3((unsigned)nb), blk, 0, st, instance_rows, c.sol, w.inc, w.isize, w.entered_flag,
+                         w.per, c.ctrl);
+      hipLaunchKernelGGL(mis_it_keep_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+      if (kicks > 0) {
+        hipLaunchKernelGGL(mis_it_draw_kernel, g1, blk, 0, st, n, instance_rows, instance_seeds, instance_offsets, w.inst,
+                           w.isize, c.sol, w.kw, c.ctrl);
+        hipLaunchKernelGGL(mis_it_enter_kernel, gw, blk, 0, st, n, rowptr, col, w.kw, w.inst, w.ent, w.entered_flag, c.ctrl);
+        hipLaunchKernelGGL(mis_it_evict_kernel, gw, blk, 0, st, n, rowptr, col, w.ent, c.sol, c.ctrl);
+        hipLaunchKernelGGL(mis_ls_tight_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.tight, c.owner, c.state, c.ctrl,
+                           LS_KICK, 0);                                // the states the next descent starts from
+        hipLaunchKernelGGL(mis_it_kick_advance_kernel, one, dim3(64), 0, st, c.ctrl);
+      }
+    }
+    hipLaunchKernelGGL(mis_it_finish_kernel, g1, blk, 0, st, n, c.sol, solution, c.ctrl);
+    er = hipMemcpyAsync(&h, c.ctrl, sizeof(h), hipMemcpyDeviceToHost, st);
+    if (er == hipSuccess) er = hipMemcpyAsync(per.data(), w.per, per.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (er == hipSuccess) er = hipStreamSynchronize(st);                // the one host synchronisation of the group
+    ++g_host_syncs;
+    if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "mis_iterated_search rounds: %s", hipGetErrorString(er));
+    if (h.bad_table)
+      return set_error(DIFUSCO_EINVAL, "mis_iterated_search: instance_rows must start at 0, end at n_nodes and not decrease "
+                                       "(solution unchanged)");
+    if (h.bad) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: the input set is not independent (solution unchanged)");
+    if (h.phase == LS_FINAL) break;
+    if (group > max_groups) return set_error(DIFUSCO_EINVAL, "mis_iterated_search: no progress (adjacency not symmetric?)");
+  }
+  counters[0] = h.rounds;
+  counters[1] = h.swaps;
+  counters[2] = h.inserts;
+  if (per_instance) std::memcpy(per_instance, per.data(), per.size() * sizeof(int32_t));
   return DIFUSCO_OK;
 }
 

@@ -458,3 +458,82 @@ def mis_local_search_np(predictions, solution, adj_matrix=None, *, graph=None, e
     if stats is not None:
         stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
     return sol.cpu().numpy().astype(int)
+
+
+MIS_KICK_OFFSET = 1 << 62        # first Philox offset of the kick streams: far above the step counters the sampling draws at
+
+
+def check_mis_kicks(local_search, kicks, kick_size):
+    """``kicks`` / ``kick_size`` of ``solve_mis`` and the runner: kicks iterate the swap search, so they need it."""
+    if int(kicks) != kicks or kicks < 0:
+        raise ValueError(f"local_search_kicks = {kicks!r}: an integer >= 0")
+    if int(kick_size) != kick_size or kick_size < 1:
+        raise ValueError(f"local_search_kick_size = {kick_size!r}: an integer >= 1")
+    if kicks > 0 and local_search != "swap":
+        raise ValueError(f"local_search_kicks = {kicks} iterates the swap search: it needs local_search='swap', not {local_search!r}")
+    return int(kicks), int(kick_size)
+
+
+def mis_iterated_search_np(predictions, solution, adj_matrix=None, *, graph=None, edge_index=None, instance_rows=None, seeds=None,
+                           offsets=None, kicks, kick_size=4, max_rounds=1000, device="cuda:0", graph_build="host", stats=None):
+    """The swap search of ``mis_local_search_np`` iterated with seeded random kicks (``difusco_mis_iterated_search``,
+    include/difusco_hip.h; not in the reference): after the descent, ``kicks`` times: about ``kick_size`` random nodes of every
+    instance are forced in, their neighbours leave, the descent runs again and every instance keeps the result unless it is
+    smaller.  ``instance_rows`` [B + 1]: the node offsets of the instances of the call (default: one instance); no edge may
+    join two instances.  ``seeds`` / ``offsets`` [B]: the Philox key and first offset of every instance (default 0; kick t
+    draws at ``offsets[b] + t``); an instance gets the same answer alone or in any union.  ``kicks=0`` is
+    ``mis_local_search_np``.  Returns the 0/1 int numpy array; ``stats`` (a dict) receives ``rounds``, ``swaps``, ``inserts``
+    (all descents), ``host_syncs`` and the per-instance lists ``entered``, ``accepted``, ``size_before``, ``size_after``.
+    A set that is not independent or a malformed table raises ``DifuscoHipError``.  GPU only."""
+    from .graph import build_csr
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError("mis_iterated_search_np runs on the GPU only (no CPU fallback)")
+    if int(max_rounds) != max_rounds or max_rounds < 0:
+        raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 0")
+    kicks, kick_size = check_mis_kicks("swap", kicks, kick_size)
+    L = _lib.lib()
+    scores = _dev(predictions, torch.float32, device).reshape(-1)
+    n = scores.shape[0]
+    sol = _dev(solution if isinstance(solution, torch.Tensor) else np.asarray(solution), torch.int32, device).reshape(-1)
+    if sol.shape[0] != n:
+        raise ValueError(f"solution holds {sol.shape[0]} entries for {n} scores")
+    if isinstance(solution, torch.Tensor):
+        sol = sol.clone()                                  # the library refines in place; the caller's tensor stays
+    rows = np.array([0, n], dtype=np.int64) if instance_rows is None else np.asarray(instance_rows, dtype=np.int64).reshape(-1)
+    B = len(rows) - 1
+    if B < 1:
+        raise ValueError("instance_rows must hold n_instances + 1 >= 2 offsets")
+    mask = (1 << 64) - 1
+    table = []
+    for name, v in (("seeds", seeds), ("offsets", offsets)):
+        v = [0] * B if v is None else [int(x) & mask for x in v]
+        if len(v) != B:
+            raise ValueError(f"{name}: {len(v)} entries for {B} instances")
+        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
+    d_rows = torch.from_numpy(rows).to(device)
+    if graph is None:
+        if edge_index is None:
+            coo = adj_matrix.tocoo()
+            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
+        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
+                          n, device, method=graph_build)
+    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
+    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_mis_iterated_search_workspace_bytes(n, int(graph.col.shape[0]), B, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    counters = (ctypes.c_int32 * 3)()
+    per = (ctypes.c_int32 * (4 * B))()
+    _lib.check(L.difusco_mis_iterated_search(
+        n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
+        ctypes.c_void_p(sol.data_ptr()), B, ctypes.c_void_p(d_rows.data_ptr()), ctypes.c_void_p(table[0].data_ptr()),
+        ctypes.c_void_p(table[1].data_ptr()), kicks, kick_size, int(max_rounds), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+        counters, per, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
+        stats["host_syncs"] = int(L.difusco_mis_search_host_syncs())
+        p = np.array(per[:], dtype=np.int64).reshape(B, 4)
+        for k, name in enumerate(("entered", "accepted", "size_before", "size_after")):
+            stats[name] = p[:, k].tolist()
+    return sol.cpu().numpy().astype(int)

@@ -25,7 +25,10 @@ Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``defaul
 {2opt,2opt+oropt}`` (``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
 ``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``), ``--mis_local_search {none,swap}`` (MIS:
 ``decode.mis_local_search_np`` after every decode, never a smaller set; the records gain ``decoded_costs``, the greedy sizes in
-the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--merge_method {loop,batched}``
+the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--mis_local_search_kicks N`` /
+``--mis_local_search_kick_size K`` (N > 0 only with ``--mis_local_search swap``: the search iterated with N seeded kicks,
+``decode.mis_iterated_search_np``, keyed by the instance seed; the records gain ``swap_costs``, ``kicks_entered``,
+``kicks_accepted`` and the two settings, the header the two settings), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -104,6 +107,10 @@ EXTENSION_ARGS = [
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
+    ("--mis_local_search_kicks", dict(type=int, default=0,
+                                       help="MIS: iterate the swap search with this many seeded random kicks (needs "
+                                            "--mis_local_search swap; 0: one descent)")),
+    ("--mis_local_search_kick_size", dict(type=int, default=4, help="MIS: nodes forced in per kick and instance, on average")),
     ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
                             help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
     ("--graph_build", dict(type=str, default="host", choices=("host", "device"),
@@ -150,6 +157,10 @@ def parse_args(argv=None):
         parser.error(f"--local_search {args.local_search} runs the exact 2-opt sweep: --two_opt_method {args.two_opt_method} is not built")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
+    if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
+        parser.error("--mis_local_search_kicks must be >= 0 and --mis_local_search_kick_size >= 1")
+    if args.mis_local_search_kicks > 0 and args.mis_local_search != "swap":
+        parser.error(f"--mis_local_search_kicks {args.mis_local_search_kicks} iterates the swap search: pass --mis_local_search swap")
     ignored = sorted(k for k in given if k in TRAINING_ONLY or (k == "save_numpy_heatmap" and args.task == "mis"))
     return args, ignored
 
@@ -272,6 +283,10 @@ def mis_record(split: str, index: int, ex, seed: int, result, stats: Optional[di
            "seed": int(seed), "mis": np.nonzero(np.asarray(sol))[0].tolist()}
     if stats is not None:      # --mis_local_search swap: the greedy sizes only (the call counters belong to a chunk, not an instance)
         rec["decoded_costs"] = [float(s) for s in stats["decoded_sizes"]]
+        if "swap_sizes" in stats:      # --mis_local_search_kicks N > 0: the sizes after the first descent and the kick counters
+            rec["swap_costs"] = [float(s) for s in stats["swap_sizes"]]
+            rec["kicks_entered"] = [int(v) for v in stats["kicks_entered"]]
+            rec["kicks_accepted"] = [int(v) for v in stats["kicks_accepted"]]
     return rec
 
 
@@ -295,7 +310,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 parallel_sampling: int = 1, sequential_sampling: int = 1, two_opt_iterations: int = 1000,
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
                 two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt",
-                mis_local_search: str = "none") -> List[dict]:
+                mis_local_search: str = "none", mis_local_search_kicks: int = 0,
+                mis_local_search_kick_size: int = 4) -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -326,9 +342,14 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
             res = solve_mis_batch(model, [(examples[i].n_nodes, examples[i].edge_index) for i in idx],
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling, seeds=seeds,
                                   generators=gens, timings=timings, step_offset=0,
-                                  **(dict(local_search=mis_local_search, stats=ls_stats) if swap else {}))
+                                  **(dict(local_search=mis_local_search, stats=ls_stats) if swap else {}),
+                                  **(dict(local_search_kicks=mis_local_search_kicks,
+                                          local_search_kick_size=mis_local_search_kick_size) if mis_local_search_kicks > 0 else {}))
             for k, i in enumerate(idx):
-                records.append(mis_record(split, i, examples[i], seeds[k], res[k], ls_stats[k] if swap else None))
+                rec = mis_record(split, i, examples[i], seeds[k], res[k], ls_stats[k] if swap else None)
+                if mis_local_search_kicks > 0:
+                    rec.update(mis_local_search_kicks=mis_local_search_kicks, mis_local_search_kick_size=mis_local_search_kick_size)
+                records.append(rec)
     return records
 
 
@@ -386,7 +407,9 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                sparse_factor=args.sparse_factor, parallel_sampling=P, sequential_sampling=S,
                                two_opt_iterations=args.two_opt_iterations, timings=timings, heatmap_dir=heatmap_dir,
                                two_opt_method=args.two_opt_method, merge_method=args.merge_method,
-                               local_search=args.local_search, mis_local_search=args.mis_local_search)
+                               local_search=args.local_search, mis_local_search=args.mis_local_search,
+                               mis_local_search_kicks=args.mis_local_search_kicks,
+                               mis_local_search_kick_size=args.mis_local_search_kick_size)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -413,6 +436,9 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["local_search"] = args.local_search
             if args.mis_local_search != "none":
                 line["mis_local_search"] = args.mis_local_search
+            if args.mis_local_search_kicks > 0:
+                line["mis_local_search_kicks"] = args.mis_local_search_kicks
+                line["mis_local_search_kick_size"] = args.mis_local_search_kick_size
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

@@ -102,7 +102,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
 def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, generator: Optional[torch.Generator] = None,
               timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1, *, graphed: bool = False,
-              local_search: str = "none", local_search_rounds: int = 1000, stats: Optional[dict] = None):
+              local_search: str = "none", local_search_rounds: int = 1000, stats: Optional[dict] = None,
+              local_search_kicks: int = 0, local_search_kick_size: int = 4):
     """``MISModel.test_step`` (``difusco/pl_mis_model.py:142-206``): ``sequential_sampling`` rounds of
     ``parallel_sampling`` noise samples of ONE graph through the denoising loop (disjoint union), greedy decode of every
     sample, best = largest set.  ``edge_index``: int64 [2,E] in the dataset's layout (both directions + self loops).
@@ -112,9 +113,15 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     (``MISModel.sample``), same results.  ``local_search``: "none" (default) or "swap": every decode is followed by one
     ``decode.mis_local_search_np`` call on the same graph (all P copies at once, at most ``local_search_rounds`` rounds): never
     a smaller set.  ``stats`` (a dict) then receives ``decoded_sizes`` (the greedy sizes in the order of ``sizes``) and the
-    call counters ``rounds``, ``swaps``, ``inserts`` summed over the sequential rounds."""
-    from .decode import check_mis_local_search, mis_decode_np, mis_local_search_np
+    call counters ``rounds``, ``swaps``, ``inserts`` summed over the sequential rounds.  ``local_search_kicks`` > 0 (only with
+    "swap", else ``ValueError``): the search is iterated with that many seeded kicks of about ``local_search_kick_size`` nodes
+    (``decode.mis_iterated_search_np``); copy p of sequential round r is its own instance of the call, keyed by the model's
+    seed at Philox offset ``2^62 + (r P + p) 2^32``.  ``stats`` then also receives ``swap_sizes`` (the sizes after
+    the first descent), ``kicks_entered`` and ``kicks_accepted``, in the order of ``sizes``.  0 is the plain swap search."""
+    from .decode import check_mis_kicks, check_mis_local_search, mis_decode_np, mis_iterated_search_np, mis_local_search_np
     check_mis_local_search(local_search)
+    kicks, kick_size = check_mis_kicks(local_search, local_search_kicks, local_search_kick_size)
+    kick_stats = {"swap_sizes": [], "kicks_entered": [], "kicks_accepted": []}
     dev = model.device
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index))
     ei = ei.to(dev)
@@ -122,7 +129,7 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     ei_rep = model.duplicate_edge_index(ei, n_nodes, dev, copies=parallel_sampling) if parallel_sampling > 1 else ei   # pl_mis_model.py:168-169
     graph = model.prepare_graph(ei_rep, n_nodes * parallel_sampling)
     sols, decoded, counters = [], [], {"rounds": 0, "swaps": 0, "inserts": 0}
-    for _ in range(sequential_sampling):                                                          # :156
+    for r in range(sequential_sampling):                                                          # :156
         t0 = time.perf_counter()
         scores = model.sample(n_nodes * parallel_sampling, ei_rep, generator=generator, graphed=graphed)   # :157-192
         tick("sampling", t0)
@@ -133,7 +140,14 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
             t0 = time.perf_counter()
             decoded += sol.reshape(parallel_sampling, n_nodes).sum(axis=1).tolist()
             call = {}
-            sol = mis_local_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call)
+            if kicks > 0:
+                P = parallel_sampling
+                sol = mis_iterated_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call,
+                                             kicks=kicks, kick_size=kick_size, instance_rows=[n_nodes * p for p in range(P + 1)],
+                                             seeds=[model.seed] * P, offsets=_kick_offsets(r, P))
+                _kick_stats(kick_stats, call, 0, P)
+            else:
+                sol = mis_local_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call)
             for k in counters:
                 counters[k] += call[k]
             tick("local_search", t0)
@@ -142,8 +156,21 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     sizes = sol.sum(axis=1)
     best = int(np.argmax(sizes))
     if local_search == "swap" and stats is not None:
-        stats.update(decoded_sizes=decoded, **counters)
+        stats.update(decoded_sizes=decoded, **counters, **(kick_stats if kicks > 0 else {}))
     return sol[best], int(sizes[best]), sizes.tolist()
+
+
+def _kick_offsets(r: int, P: int):
+    """Philox offsets of the kick streams of the P copies of sequential round ``r``: copy p of the round is the (r P + p)-th
+    copy of its instance and owns the 2^32 offsets from ``2^62 + (r P + p) 2^32``; the sampling draws at small step counters
+    under the same key, so the streams cannot meet."""
+    from .decode import MIS_KICK_OFFSET
+    return [MIS_KICK_OFFSET + ((r * P + p) << 32) for p in range(P)]
+
+
+def _kick_stats(out: dict, call: dict, first: int, P: int):
+    for k, src in (("swap_sizes", "size_before"), ("kicks_entered", "entered"), ("kicks_accepted", "accepted")):
+        out[k] += call[src][first:first + P]
 
 
 def _chunks(B: int, per_call: Optional[int]):
@@ -367,7 +394,7 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
                     seeds: Optional[Sequence[int]] = None, generators: Optional[Sequence[torch.Generator]] = None,
                     timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None,
                     step_offset: Optional[int] = None, *, local_search: str = "none", local_search_rounds: int = 1000,
-                    stats: Optional[list] = None) -> List[tuple]:
+                    stats: Optional[list] = None, local_search_kicks: int = 0, local_search_kick_size: int = 4) -> List[tuple]:
     """``solve_mis`` of B graphs: ``instances`` = [(n_nodes, edge_index), ...].  Returns the list of what ``solve_mis`` returns
     for every graph (run with ``seed = seeds[b]``, ``generator = generators[b]``).  Up to ``instances_per_call`` graphs share
     one sampling loop over their union (``MISModel.sample_batch``) and one greedy decode of the union (``mis_decode_np``: the
@@ -375,10 +402,15 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
     ``local_search``, ``local_search_rounds``: as ``solve_mis``; one ``decode.mis_local_search_np`` call per decode on the
     union of the chunk (the search never crosses a component and round r of the union is round r of every graph, so every graph
     gets its solo answer).  ``stats``: a list to which one dict per instance is appended (only with "swap"): ``decoded_sizes``
-    of the instance, and the counters ``rounds``, ``swaps``, ``inserts`` of its CHUNK's calls summed over the sequential rounds."""
-    from .decode import check_mis_local_search, mis_decode_np, mis_local_search_np
+    of the instance, and the counters ``rounds``, ``swaps``, ``inserts`` of its CHUNK's calls summed over the sequential rounds.
+    ``local_search_kicks``, ``local_search_kick_size``: as ``solve_mis``; every one of the P copies of an instance is its own
+    row of the call's instance table, keyed by the instance's sampling seed (``seeds[b]`` as ``sample_batch`` resolves it) at
+    offset ``2^62 + (r P + p) 2^32``, so the records do not depend on the chunking; the per-instance dicts then also hold
+    ``swap_sizes``, ``kicks_entered`` and ``kicks_accepted``."""
+    from .decode import check_mis_kicks, check_mis_local_search, mis_decode_np, mis_iterated_search_np, mis_local_search_np
     from .graph import build_csr
     check_mis_local_search(local_search)
+    kicks, kick_size = check_mis_kicks(local_search, local_search_kicks, local_search_kick_size)
     instances = list(instances)
     B = len(instances)
     if B < 1:
@@ -401,6 +433,9 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
         sols = [[] for _ in ns]
         decoded = [[] for _ in ns]
         counters = {"rounds": 0, "swaps": 0, "inserts": 0}
+        kick_stats = [{"swap_sizes": [], "kicks_entered": [], "kicks_accepted": []} for _ in ns]
+        # the Philox keys of the chunk's instances, resolved the way sample_batch resolves them
+        keys = [int(v) & (2 ** 63 - 1) for v in ([model.seed] * len(ns) if seeds is None else seeds[c0:c1])]
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             scores = model.sample_batch([n * P for n in ns], eis, seeds=None if seeds is None else seeds[c0:c1],
@@ -415,8 +450,16 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
                 for g, n in enumerate(ns):
                     decoded[g] += sol[off[g]:off[g + 1]].reshape(P, n).sum(axis=1).tolist()
                 call = {}
-                sol = mis_local_search_np(torch.cat(scores), sol, graph=graph, device=dev, max_rounds=local_search_rounds,
-                                          stats=call)
+                if kicks > 0:
+                    sol = mis_iterated_search_np(
+                        torch.cat(scores), sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call, kicks=kicks,
+                        kick_size=kick_size, instance_rows=[int(off[g]) + n * p for g, n in enumerate(ns) for p in range(P)] + [int(off[-1])],
+                        seeds=[k for k in keys for _ in range(P)], offsets=_kick_offsets(r, P) * len(ns))
+                    for g in range(len(ns)):
+                        _kick_stats(kick_stats[g], call, g * P, P)
+                else:
+                    sol = mis_local_search_np(torch.cat(scores), sol, graph=graph, device=dev, max_rounds=local_search_rounds,
+                                              stats=call)
                 for k in counters:
                     counters[k] += call[k]
             for g, n in enumerate(ns):
@@ -428,5 +471,5 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
             best = int(np.argmax(sizes))
             results.append((sol[best], int(sizes[best]), sizes.tolist()))
             if local_search == "swap" and stats is not None:
-                stats.append(dict(decoded_sizes=decoded[g], **counters))
+                stats.append(dict(decoded_sizes=decoded[g], **counters, **(kick_stats[g] if kicks > 0 else {})))
     return results

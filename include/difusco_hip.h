@@ -441,6 +441,47 @@ int difusco_mis_local_search(int n_nodes, const int32_t* rowptr, const int32_t* 
                              int32_t* solution /* in/out, device */, int32_t max_rounds, void* workspace,
                              size_t workspace_bytes, int32_t counters[3] /* host: rounds, swaps, inserts */, void* stream);
 
+/* ---- iterated (1,2)-swap search for MIS solutions: seeded random kicks between descents (additive to ABI 13; not in the
+ * reference).  Graph, scores, solution and max_rounds: as difusco_mis_local_search.  THE DESCENT below is that search exactly:
+ * one insertion phase, then swap rounds until a round proposes nothing or max_rounds rounds ran; the ranks come from `scores`.
+ * The instance table (DEVICE, the types of difusco_step_args): instance_rows int64 [n_instances + 1], non-decreasing node
+ * offsets from 0 to n_nodes (empty instances allowed); instance_seeds, instance_offsets uint64 [n_instances].  No edge joins two
+ * instances: the caller guarantees it, it is not checked.  kicks >= 0, kick_size >= 1.
+ *   1. The descent on the input set gives the incumbent I.
+ *   2. For t = 0 .. kicks - 1, synchronously over the whole call:
+ *      draw     node v of instance b, local index r = v - instance_rows[b], draws
+ *               w_v = (word 0 of Philox4x32-10(key instance_seeds[b], offset instance_offsets[b] + t, index r)) >> 8,
+ *               the project's 24-bit uniform kept as an integer;
+ *      kicked   m_b = the number of nodes of b outside I; v is kicked iff v is outside I and w_v * m_b < kick_size * 2^24,
+ *               evaluated exactly in uint64 (the left side stays below 2^55): about kick_size nodes of every instance;
+ *      entered  a kicked v enters iff no kicked neighbour u != v has (w_u, u) < (w_v, v); entered nodes are pairwise
+ *               non-adjacent by construction;
+ *      evict    C = I minus every member adjacent to an entered node, plus the entered nodes (self loops are ignored);
+ *      descend  the descent on C (its leading insertion phase re-fills around the evicted nodes);
+ *      keep     per instance: if |C_b| >= |I_b| then I_b <- C_b (plateau moves are kept), otherwise I_b stays.
+ *   3. solution <- I.
+ * kicks = 0 returns exactly what difusco_mis_local_search returns, set and counters alike.  The result is independent and
+ * maximal, and |out_b| >= the swap descent's |S_b| for every instance.  Every step is local to an instance and step t of a
+ * union is step t of each instance, so a call on a union gives every instance exactly what its own call gives with the same
+ * seed and offset, capped by max_rounds or not.
+ * counters: HOST int32 [3] = rounds, swaps, inserts summed over all descents, the restored ones included.  per_instance: HOST
+ * int32 [4 * n_instances], may be NULL; for instance b: [4b] entered = the kicks in which at least one node of b entered,
+ * [4b + 1] accepted = those of them that were kept, [4b + 2] size_before = |I_b| after step 1, [4b + 3] size_after.
+ * DIFUSCO_EINVAL on a null array, n_nodes < 1, n_instances < 1, max_rounds < 0, kicks < 0, kick_size < 1, a workspace below
+ * _workspace_bytes, a malformed table (checked on the device) and an input set that is not independent; solution is then
+ * left unchanged.  The kick loop runs on the device behind the phase word of the descent (two more phases); the host enqueues
+ * groups of 8 x (2 rounds of the descent, one kick) launches and polls once per group, so a call makes at most `kicks` more
+ * host synchronisations than the kicks = 0 call unless the descents after the kicks average more than 16 rounds.  Blocks.
+ * difusco_mis_search_host_syncs: the host synchronisations of the calling thread's last difusco_mis_local_search or
+ * difusco_mis_iterated_search call. */
+int difusco_mis_iterated_search_workspace_bytes(int n_nodes, int64_t n_edges, int n_instances, size_t* bytes);
+int difusco_mis_iterated_search(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores,
+                                int32_t* solution /* in/out, device */, int n_instances, const int64_t* instance_rows,
+                                const uint64_t* instance_seeds, const uint64_t* instance_offsets, int32_t kicks,
+                                int32_t kick_size, int32_t max_rounds, void* workspace, size_t workspace_bytes,
+                                int32_t counters[3] /* host */, int32_t* per_instance /* host, optional */, void* stream);
+int difusco_mis_search_host_syncs(void);
+
 /* ---- heatmap -> tour: the greedy edge insertion the reference runs on the host right after the
  * sampling loop, difusco/utils/tsp_utils.py:89-145 (merge_tours) + utils/cython_merge/cython_merge.pyx:19-104
  * (merge_cython), restricted to the E entries of the sparse heatmap instead of the N x N densification.
