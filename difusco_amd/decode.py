@@ -276,7 +276,7 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
 
 
-LOCAL_SEARCHES = ("2opt", "2opt+oropt")
+LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt")
 
 
 def check_local_search(local_search, two_opt_method="exact"):
@@ -377,6 +377,82 @@ def batched_local_search_ragged(points_list, tours_list, max_iterations=1000, de
     if stats is not None:
         stats["or_opt_iterations"], stats["rounds"] = orr, rounds
     return out, two
+
+
+def _multi_two_opt_checked(who, pts, trs, max_iterations, select_rounds, device):
+    """The argument checks of the three multi-move 2-opt functions (before any library call)."""
+    if int(select_rounds) != select_rounds or select_rounds < 1:
+        raise ValueError(f"select_rounds = {select_rounds!r}: an integer >= 1")
+    return _local_search_checked(who, pts, trs, max_iterations, 1, device)
+
+
+def _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device):
+    """One ``difusco_tsp_multi_two_opt_ragged`` call on checked arguments.  Returns (int64 tours per group, sweeps, moves [G]
+    int64)."""
+    G = len(pts)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_multi_two_opt_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
+                                                                  ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    sweeps, moves = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+    _lib.check(L.difusco_tsp_multi_two_opt_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
+                                                  ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), int(select_rounds),
+                                                  ctypes.c_void_p(ws.data_ptr()), nbytes.value, sweeps.ctypes.data, moves.ctypes.data,
+                                                  ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], sweeps, moves
+
+
+def batched_multi_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
+    """Multi-move 2-opt of the tours of ONE instance, the arguments of ``batched_two_opt_torch``: every sweep of all pairs applies
+    a set of improving 2-opt moves with pairwise disjoint position ranges, chosen in at most ``select_rounds`` rounds (the rule:
+    ``difusco_tsp_multi_two_opt_ragged``, include/difusco_hip.h; GPU only; not the reference's one move per sweep, so another
+    2-opt optimum).  Every tour runs on its own; at most ``max_iterations`` sweeps.  Returns ``(tour int64 numpy [B, N+1],
+    sweeps)``; ``stats`` (a dict) receives ``moves``, the moves applied over all tours."""
+    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
+    device = _multi_two_opt_checked("batched_multi_two_opt_torch", pts, trs, max_iterations, select_rounds, device)
+    out, sweeps, moves = _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device)
+    if stats is not None:
+        stats["moves"] = int(moves[0])
+    return out[0], int(sweeps[0])
+
+
+def batched_multi_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
+    """``batched_multi_two_opt_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points`` float64
+    [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_multi_two_opt_torch`` call returns.
+    Returns ``(tours int64 numpy [G * P, N + 1], sweeps int64 numpy [G])``; ``stats`` receives ``moves`` (int64 [G])."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts_l = [np.ascontiguousarray(p) for p in pts]
+    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
+    device = _multi_two_opt_checked("batched_multi_two_opt_grouped", pts_l, trs, max_iterations, select_rounds, device)
+    out, sweeps, moves = _multi_two_opt_run(pts_l, trs, max_iterations, select_rounds, device)
+    if stats is not None:
+        stats["moves"] = moves
+    return np.concatenate(out, axis=0), sweeps
+
+
+def batched_multi_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
+    """``batched_multi_two_opt_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.  Returns
+    ``(list of int64 numpy [P_g, n_g + 1], sweeps int64 numpy [G])``; ``stats``: as ``batched_multi_two_opt_grouped``."""
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    device = _multi_two_opt_checked("batched_multi_two_opt_ragged", pts, trs, max_iterations, select_rounds, device)
+    out, sweeps, moves = _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device)
+    if stats is not None:
+        stats["moves"] = moves
+    return out, sweeps
 
 
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):

@@ -604,6 +604,34 @@ int difusco_tsp_local_search_ragged(int groups, const int32_t* group_n, const in
                                     int32_t* tours, int64_t max_iterations, int max_rounds, void* workspace, size_t workspace_bytes,
                                     int64_t* two_opt_iterations_out, int64_t* or_opt_iterations_out, int32_t* rounds_out, void* stream);
 
+/* Multi-move 2-opt (additive to ABI 13; not in the reference, which applies one move per sweep): the arrays, conventions and
+ * limits of difusco_tsp_two_opt_ragged.  Every TOUR runs on its own.  With P_k the point at position k of the closed tour
+ * (P_n = P_0) and d_k = |P_k P_k+1|, one SWEEP of a tour of n nodes is:
+ *   1. Row proposals.  Row i = 0 .. n-3 evaluates change(i, j) = ((|P_i P_j| + |P_i+1 P_j+1|) - d_i) - d_j for i+2 <= j <= n-1 in
+ *      float64, every operation rounded on its own, distances as two products, one sum, a square root: the changes of
+ *      difusco_tsp_two_opt, bit for bit.  The row keeps its lowest change, ties to the lowest j, and proposes (i, j_i) if that
+ *      change is < -1e-6.  The proposal's key is (change, i), ordered lexicographically (keys are distinct); its range is the
+ *      half-open position interval [i, j_i + 1).
+ *   2. Selection, in at most select_rounds rounds.  In a round a live proposal wins if its key is lower than the key of every
+ *      other live proposal whose range intersects its own.  After the round the winners leave the live set, and every live
+ *      proposal whose range intersects a winner's range is dropped for this sweep.  Selection ends early when nothing is live.
+ *      With select_rounds unbounded this is the greedy choice in key order.
+ *   3. Apply.  Every winner reverses tour[i+1 .. j_i]; the ranges are disjoint, so the order does not matter.  Positions 0 and n
+ *      never move.
+ *   4. Stop test.  A tour with no proposal is done and costs no further work.  A sweep counts for a group if one of its tours
+ *      moved.  A group stops when all its tours are done or after max_iterations counted sweeps; with max_iterations = 0 no
+ *      sweep counts and nothing is applied.
+ * So: the best pair of the exact 2-opt (lowest change, lowest flat index i n + j) is always a winner of round 1; every counted
+ * sweep shortens every moved tour by more than 1e-6 per move; a tour that stops before the cap has no improving 2-opt move left;
+ * a tour's result does not depend on which other tours or groups share the call.
+ * sweeps_out, moves_out: HOST int64 [groups], the counted sweeps and the moves applied over all tours of the group.
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_two_opt_ragged, a null output array and select_rounds < 1.
+ * Blocks until every group is done. */
+int difusco_tsp_multi_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_multi_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                     int32_t* tours, int64_t max_iterations, int select_rounds, void* workspace,
+                                     size_t workspace_bytes, int64_t* sweeps_out, int64_t* moves_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
