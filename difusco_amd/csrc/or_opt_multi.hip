@@ -1,0 +1,454 @@
+// Multi-move local search (difusco_tsp_multi_local_search_ragged): per tour, rounds of a multi-move 2-opt phase and a multi-move
+// Or-opt phase.  A sweep of either phase applies a set of improving moves whose position ranges are pairwise disjoint.  The rule
+// is stated in include/difusco_hip.h and restated in numpy in tests/multi_local_search_emulation.py; a 2-opt change is best_tile's
+// (two_opt_common.h) and an Or-opt delta is or_opt_tile's (or_opt.hip), bit for bit.
+//
+// One sweep is three launches, whatever the phases of the tours:
+//   mls_prep_kernel       tp / dlen of every tour that is still running (prep_entry);
+//   mls_row_best_kernel   one block per (row tile of 16, tour), the loop of the tour's phase.  2-opt: row_best_tile
+//                         (multi_move_common.h), the loop of two_opt_multi.hip.  Or-opt: or_row_best_tile, the loop of or_opt_tile -
+//                         a thread keeps 4 columns of every 1024-column chunk in registers, walks the rows of the tile upwards and
+//                         carries |P_j P_i+2|, |P_j P_i+3| (and the two from P_j+1) to the next row, two square roots per (i, j)
+//                         for all five variants; the row-only terms are computed once per tile in LDS - with 16 running bests
+//                         (delta, v n + j), one per row, across all chunks and one block reduction per row at the end.  A tile's
+//                         block walks all its column chunks, so nothing is combined between blocks;
+//   mls_select_kernel     one block of 1024 threads per tour: the selection rounds (select_disjoint, multi_move_common.h) on
+//                         (key, range), the moves of the phase - a wave reverses one winner's stretch, or copies one winner's
+//                         stretch to a buffer of the tour's own and writes it back shifted -, the switch of phase and round, the
+//                         stop tests and the counters.  The last tour of a group to finish counts the group as stopped; the
+//                         host enqueues sweeps and polls the counter of stopped groups.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/difusco_hip.h"
+#include "kernels.h"
+#include "multi_move_common.h"
+#include "two_opt_common.h"
+
+namespace difusco {
+namespace {
+
+constexpr int LMAX = 3;                    // longest segment
+
+__device__ __forceinline__ int variant_len(int v) { return (v + 3) >> 1; }      // 1, 2, 2, 3, 3
+__device__ __forceinline__ bool variant_rev(int v) { return v == 2 || v == 4; }
+
+enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2 };
+
+struct MlTour {            // offsets in elements of the array they index
+  int n, nblk_two, nblk_or, group;
+  long long points;        // the group's first coordinate in `points` (doubles)
+  long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
+  long long cols;          //                       in dlen, rowv, rowj, live and winners (n per tour)
+  long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
+};
+
+struct MlTourState {       // device-resident loop state of a tour, zero at the start of a call
+  int phase, round;        // round: zero-based
+  int or_moved, pad;       // the Or-opt phase of this round has applied a move
+  long long sweeps, two_opt_sweeps, or_opt_sweeps, two_opt_moves, or_opt_moves;   // sweeps: in which the tour moved
+};
+
+struct MlGroup {           // tours of the group, and how many of them are done (zero at the start of a call)
+  int count, done;
+};
+
+struct MlState {
+  int done;                // groups that have stopped
+  int pad;
+};
+
+__global__ void mls_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const MlTour* __restrict__ desc,
+                                double2* __restrict__ tp, double* __restrict__ dlen, const MlTourState* __restrict__ ts) {
+  const MlTour d = desc[blockIdx.y];
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > d.n || ts[blockIdx.y].phase == kDone) return;
+  prep_entry(points + d.points, tours + d.closed, d.n, k, tp + d.closed, dlen + d.cols);
+}
+
+// one block of the Or-opt row-best sweep: rows i0 .. i0 + TI - 1 of the tour (P = its tp, D = its dlen, n nodes) against every
+// column.  Row i <= n - 2 gets its lowest delta in rowv[i], ties to the lowest v and then the lowest j; rowj[i] = v n + j of
+// that candidate, or -1 if the delta is not below the threshold.
+__device__ __forceinline__ void or_row_best_tile(const double2* __restrict__ P, const double* __restrict__ D, int n, int i0,
+                                                 double* __restrict__ rowv, int* __restrict__ rowj) {
+  __shared__ double2 pr[TI + LMAX + 1];    // P_i0 .. P_i0+TI+3, the index clipped to n
+  __shared__ double closing[LMAX][TI];     // |P_i P_i+L+1|
+  __shared__ double removed[LMAX][TI];     // d_i + d_i+L
+  __shared__ double redv[4][TI];
+  __shared__ int redc[4][TI];
+  for (int t = threadIdx.x; t < TI + LMAX + 1; t += blockDim.x) pr[t] = P[i0 + t < n ? i0 + t : n];
+  for (int t = threadIdx.x; t < LMAX * TI; t += blockDim.x) {
+    const int r = t % TI, L = t / TI + 1, i = i0 + r;
+    double c = 0.0, d = 0.0;
+    if (i <= n - 1 - L) {
+      const double2 p = P[i], q = P[i + L + 1];
+      c = dist2d(p.x - q.x, p.y - q.y);
+      d = __dadd_rn(D[i], D[i + L]);
+    }
+    closing[L - 1][r] = c;
+    removed[L - 1][r] = d;
+  }
+  __syncthreads();
+  double bv[TI];
+  int bc[TI];                              // v n + j: the order of (v, j)
+#pragma unroll
+  for (int r = 0; r < TI; ++r) bv[r] = 0.0, bc[r] = INT_MAX;
+  for (int jbase = 0; jbase < n; jbase += 256 * JPT) {
+    double2 pj[JPT], pj1[JPT];
+    double dj[JPT], e1[JPT], e2[JPT], e3[JPT], f1[JPT], f2[JPT], f3[JPT];   // e_k = |P_j P_i+k|, f_k = |P_j+1 P_i+k|
+    int jj[JPT];
+#pragma unroll
+    for (int u = 0; u < JPT; ++u) {
+      const int j = jbase + u * 256 + threadIdx.x, jc = j < n ? j : n - 1;
+      jj[u] = j;
+      pj[u] = P[jc];
+      pj1[u] = P[jc + 1];
+      dj[u] = D[jc];
+      e1[u] = dist2d(pj[u].x - pr[1].x, pj[u].y - pr[1].y);
+      e2[u] = dist2d(pj[u].x - pr[2].x, pj[u].y - pr[2].y);
+      e3[u] = dist2d(pj[u].x - pr[3].x, pj[u].y - pr[3].y);
+      f1[u] = dist2d(pj1[u].x - pr[1].x, pj1[u].y - pr[1].y);
+      f2[u] = dist2d(pj1[u].x - pr[2].x, pj1[u].y - pr[2].y);
+      f3[u] = dist2d(pj1[u].x - pr[3].x, pj1[u].y - pr[3].y);
+    }
+#pragma unroll
+    for (int r = 0; r < TI; ++r) {
+      const int i = i0 + r;
+      const double c1 = closing[0][r], c2 = closing[1][r], c3 = closing[2][r];
+      const double r1 = removed[0][r], r2 = removed[1][r], r3 = removed[2][r];
+      const double2 next = pr[r + LMAX + 1];                    // P_i+4, for the row after this one
+      const bool row1 = i <= n - 2, row2 = i <= n - 3, row3 = i <= n - 4;
+#pragma unroll
+      for (int u = 0; u < JPT; ++u) {
+        const int j = jj[u];
+        // delta = ((|P_i P_i+L+1| + |P_j a|) + |b P_j+1|) - ((d_i + d_i+L) + d_j), every operation rounded on its own
+        const double rem1 = __dadd_rn(r1, dj[u]), rem2 = __dadd_rn(r2, dj[u]), rem3 = __dadd_rn(r3, dj[u]);
+        const double d0 = __dsub_rn(__dadd_rn(__dadd_rn(c1, e1[u]), f1[u]), rem1);
+        const double d1 = __dsub_rn(__dadd_rn(__dadd_rn(c2, e1[u]), f2[u]), rem2);
+        const double d2 = __dsub_rn(__dadd_rn(__dadd_rn(c2, e2[u]), f1[u]), rem2);
+        const double d3 = __dsub_rn(__dadd_rn(__dadd_rn(c3, e1[u]), f3[u]), rem3);
+        const double d4 = __dsub_rn(__dadd_rn(__dadd_rn(c3, e3[u]), f1[u]), rem3);
+        const bool in = j < n, left = j < i;
+        const bool ok1 = in && row1 && (left || j > i + 1), ok2 = in && row2 && (left || j > i + 2),
+                   ok3 = in && row3 && (left || j > i + 3);
+        // the lowest delta of the pair's variants, the lowest v on a tie
+        double m = ok1 ? d0 : INFINITY;
+        int v = 0;
+        if (ok2 && d1 < m) m = d1, v = 1;
+        if (ok2 && d2 < m) m = d2, v = 2;
+        if (ok3 && d3 < m) m = d3, v = 3;
+        if (ok3 && d4 < m) m = d4, v = 4;
+        const int code = v * n + j;
+        if (better_col(m, code, bv[r], bc[r])) bv[r] = m, bc[r] = code;
+        e1[u] = e2[u];
+        e2[u] = e3[u];
+        e3[u] = dist2d(pj[u].x - next.x, pj[u].y - next.y);
+        f1[u] = f2[u];
+        f2[u] = f3[u];
+        f3[u] = dist2d(pj1[u].x - next.x, pj1[u].y - next.y);
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int r = 0; r < TI; ++r) {
+    double v = bv[r];
+    int c = bc[r];
+    for (int off = 32; off > 0; off >>= 1) {
+      const double ov = __shfl_down(v, off);
+      const int oc = __shfl_down(c, off);
+      if (better_col(ov, oc, v, c)) v = ov, c = oc;
+    }
+    if (lane == 0) redv[wave][r] = v, redc[wave][r] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x < TI && i0 + (int)threadIdx.x <= n - 2) {
+    const int r = threadIdx.x;
+    double v = redv[0][r];
+    int c = redc[0][r];
+    for (int w = 1; w < 4; ++w)
+      if (better_col(redv[w][r], redc[w][r], v, c)) v = redv[w][r], c = redc[w][r];
+    rowv[i0 + r] = v;
+    rowj[i0 + r] = v < kThreshold ? c : -1;                      // below the threshold c is the code of a candidate
+  }
+}
+
+__global__ __launch_bounds__(256) void mls_row_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
+                                                           const MlTour* __restrict__ desc, double* __restrict__ rowv,
+                                                           int* __restrict__ rowj, const MlTourState* __restrict__ ts) {
+  const MlTour d = desc[blockIdx.y];
+  const int phase = ts[blockIdx.y].phase;                        // uniform over the block
+  if (phase == kDone || (int)blockIdx.x >= (phase == kTwoOpt ? d.nblk_two : d.nblk_or)) return;
+  const int i0 = blockIdx.x * TI;
+  if (phase == kTwoOpt)
+    row_best_tile(tp + d.closed, dlen + d.cols, d.n, i0, rowv + d.cols, rowj + d.cols);
+  else
+    or_row_best_tile(tp + d.closed, dlen + d.cols, d.n, i0, rowv + d.cols, rowj + d.cols);
+}
+
+// the range of a proposal of either phase.  2-opt (i, j = rowj[i]): [i, j + 1).  Or-opt (rowj[i] = v n + j): [min(i, j), hi + 1)
+// with hi = j for j > i + L and i + L for j < i - from the first position of the lowest of the three edges the move touches to
+// the first position of the highest.  One type for both, so that the selection is instantiated once.
+struct PhaseRange {
+  const int* __restrict__ rowj;
+  int n;
+  bool or_opt;
+  __device__ __forceinline__ bool proposes(int i) const { return rowj[i] >= 0; }
+  __device__ __forceinline__ void operator()(int i, int* a, int* b) const {
+    const int c = rowj[i], j = or_opt ? c % n : c, L = or_opt ? variant_len(c / n) : 0;
+    *a = j < i ? j : i;
+    *b = (j < i ? i + L : j) + 1;
+  }
+};
+
+// the Or-opt moves of the winners: the stretch between a segment and its insertion edge shifts by L places over the segment, so
+// a wave copies the rewritten positions lo .. hi of one winner to `stage` (n + 1 entries of the tour's own), and after a barrier
+// writes them back from there (apply_or_opt_move of or_opt.hip, a winner per wave).  The stretches are disjoint.
+__device__ __forceinline__ void or_opt_winners(int* __restrict__ tour, int* __restrict__ stage, const int* __restrict__ winners,
+                                               const int* __restrict__ rowj, int n, int total) {
+  const int lane = threadIdx.x & 63;
+  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
+    const int i = winners[w], j = rowj[i] % n, L = variant_len(rowj[i] / n);
+    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;  // 1 <= lo <= hi <= n - 1
+    for (int k = lo + lane; k <= hi; k += 64) stage[k] = tour[k];
+  }
+  __syncthreads();
+  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
+    const int i = winners[w], j = rowj[i] % n, v = rowj[i] / n, L = variant_len(v);
+    const bool rev = variant_rev(v);
+    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;
+    for (int k = lo + lane; k <= hi; k += 64) {
+      int src;
+      if (j > i) {                                               // tour[:i+1] + tour[i+L+1 : j+1] + seg + tour[j+1:]
+        const int s = k - (j - L + 1);
+        src = s < 0 ? k + L : (rev ? i + L - s : i + 1 + s);
+      } else {                                                   // tour[:j+1] + seg + tour[j+1 : i+1] + tour[i+L+1:]
+        const int s = k - (j + 1);
+        src = s < L ? (rev ? i + L - s : i + 1 + s) : k - L;
+      }
+      tour[k] = stage[src];
+    }
+  }
+}
+
+// thread 0 of a tour that is done: the last tour of its group to finish counts the group as stopped
+__device__ __forceinline__ void report_done(MlGroup* g, MlState* st) {
+  if (atomicAdd(&g->done, 1) == g->count - 1) atomicAdd(&st->done, 1);
+}
+
+__global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
+    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
+    int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
+    MlState* st, MlGroup* grp, MlTourState* ts) {
+  const int t = blockIdx.x;
+  const int phase = ts[t].phase;                                 // written by thread 0 of this block at its end only
+  if (phase == kDone) return;
+  const MlTour d = desc[t];
+  const int n = d.n;
+  const int* rowj = rowj_all + d.cols;
+  int* winners = winners_all + d.cols;
+  __shared__ int nwin;
+  const int total = select_disjoint(PhaseRange{rowj, n, phase == kOrOpt}, phase == kTwoOpt ? n - 2 : n - 1, n,
+                                    rowv_all + d.cols, live_all + d.cols, winners, tabv_all + d.table, tabi_all + d.table,
+                                    marks_all + d.closed, cum_all + d.closed, select_rounds, &nwin);
+  MlTourState* s = ts + t;                                       // thread 0 alone writes it
+  if (total == 0) {                                              // no proposal: the phase ends
+    if (threadIdx.x == 0) {
+      if (phase == kTwoOpt) {
+        s->phase = kOrOpt;
+        s->or_moved = 0;
+      } else if (!s->or_moved || s->round + 1 >= max_rounds) {
+        s->phase = kDone;
+        report_done(grp + d.group, st);
+      } else {
+        s->phase = kTwoOpt;
+        s->round += 1;
+      }
+    }
+    return;
+  }
+  if (phase == kTwoOpt)
+    reverse_winners(tours + d.closed, winners, rowj, total);
+  else
+    or_opt_winners(tours + d.closed, (int*)(cum_all + d.closed), winners, rowj, n, total);   // cum is free after the selection
+  if (threadIdx.x == 0) {
+    s->sweeps += 1;
+    if (phase == kTwoOpt) {
+      s->two_opt_sweeps += 1;
+      s->two_opt_moves += total;
+    } else {
+      s->or_opt_sweeps += 1;
+      s->or_opt_moves += total;
+      s->or_moved = 1;
+    }
+    if (s->sweeps >= max_iterations) {
+      s->phase = kDone;
+      report_done(grp + d.group, st);
+    }
+  }
+}
+
+struct MlLayout {          // byte offsets
+  size_t desc, tp, dlen, rowv, rowj, live, winners, tabv, tabi, marks, cum, grp, ts, st, total;
+  int tours, nmax, nblk_max;
+};
+
+constexpr int kMaxTours = 65535;                   // a grid dimension; the limits of difusco_tsp_two_opt_ragged
+constexpr int kMaxNodes = 65535 * TI;
+
+// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
+int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, MlLayout* L,
+               std::vector<MlTour>* tab, std::vector<MlGroup>* gtab) {
+  if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
+  if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
+  long long T = 0;
+  for (int g = 0; g < groups; ++g) {
+    if (group_n[g] < 4) return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, needs n >= 4", who, g, group_n[g]);
+    if (group_n[g] > kMaxNodes)
+      return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, at most %d nodes", who, g, group_n[g], kMaxNodes);
+    if (group_tours[g] < 1) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d tours, needs at least 1", who, g, group_tours[g]);
+    T += group_tours[g];
+    if (T > kMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kMaxTours);
+  }
+  size_t points = 0, closed = 0, cols = 0, cells = 0;
+  L->nmax = L->nblk_max = 0;
+  for (int g = 0; g < groups; ++g) {
+    const int n = group_n[g];
+    const int nblk_two = (n - 2 + TI - 1) / TI, nblk_or = (n - 1 + TI - 1) / TI;   // rows 0 .. n - 3 and 0 .. n - 2
+    L->nmax = n > L->nmax ? n : L->nmax;
+    L->nblk_max = nblk_or > L->nblk_max ? nblk_or : L->nblk_max;
+    if (gtab) gtab->push_back(MlGroup{group_tours[g], 0});
+    for (int p = 0; p < group_tours[g]; ++p) {
+      if (tab) tab->push_back(MlTour{n, nblk_two, nblk_or, g, (long long)points, (long long)closed, (long long)cols, (long long)cells});
+      closed += (size_t)n + 1;
+      cols += (size_t)n;
+      cells += (size_t)table_levels(n) * ((size_t)n + 1);
+    }
+    points += 2 * (size_t)n;
+  }
+  L->tours = (int)T;
+  size_t off = 0;
+  auto take = [&off](size_t bytes) {
+    const size_t at = off;
+    off += up256(bytes);
+    return at;
+  };
+  L->desc = take(sizeof(MlTour) * T);
+  L->tp = take(sizeof(double2) * closed);
+  L->dlen = take(sizeof(double) * cols);
+  L->rowv = take(sizeof(double) * cols);
+  L->rowj = take(sizeof(int) * cols);
+  L->live = take(sizeof(int) * cols);
+  L->winners = take(sizeof(int) * cols);
+  L->tabv = take(sizeof(unsigned long long) * cells);
+  L->tabi = take(sizeof(int) * cells);
+  L->marks = take(sizeof(int2) * closed);
+  L->cum = take(sizeof(int2) * closed);
+  L->grp = take(sizeof(MlGroup) * groups);
+  L->ts = take(sizeof(MlTourState) * T);                         // ts .. st are cleared by one memset
+  L->st = take(sizeof(MlState));
+  L->total = off;
+  return DIFUSCO_OK;
+}
+
+}  // namespace
+}  // namespace difusco
+
+extern "C" {
+
+int difusco_tsp_multi_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                          size_t* bytes) {
+  using namespace difusco;
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "multi_local_search_ragged_workspace_bytes: bytes is null");
+  MlLayout lay;
+  const int rc = mls_layout("multi_local_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
+  if (rc == DIFUSCO_OK) *bytes = lay.total;
+  return rc;
+}
+
+int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                          int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace,
+                                          size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
+                                          int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream) {
+  using namespace difusco;
+  MlLayout lay;
+  std::vector<MlTour> tab;
+  std::vector<MlGroup> gtab;
+  const int rc = mls_layout("tsp_multi_local_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
+      !or_opt_moves_out || max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: needs non-null device arrays, the five host output arrays "
+                                     "[groups] and max_iterations >= 0");
+  if (max_rounds < 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
+  if (select_rounds < 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
+  if (workspace_bytes < lay.total)
+    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: workspace %zu < %zu bytes", workspace_bytes, lay.total);
+  for (int g = 0; g < groups; ++g) {
+    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
+    rounds_out[g] = 1;                                           // every tour starts round 1
+  }
+  if (max_iterations == 0) return DIFUSCO_OK;                    // no sweep may move a tour: nothing is applied
+  char* w = (char*)workspace;
+  MlTour* desc = (MlTour*)(w + lay.desc);
+  double2* tp = (double2*)(w + lay.tp);
+  double* dlen = (double*)(w + lay.dlen);
+  double* rowv = (double*)(w + lay.rowv);
+  int* rowj = (int*)(w + lay.rowj);
+  int* live = (int*)(w + lay.live);
+  int* winners = (int*)(w + lay.winners);
+  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
+  int* tabi = (int*)(w + lay.tabi);
+  int2* marks = (int2*)(w + lay.marks);
+  int2* cum = (int2*)(w + lay.cum);
+  MlGroup* grp = (MlGroup*)(w + lay.grp);
+  MlTourState* ts = (MlTourState*)(w + lay.ts);
+  MlState* st = (MlState*)(w + lay.st);
+  hipStream_t s = (hipStream_t)stream;
+  const int T = lay.tours;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(ts, 0, lay.total - lay.ts, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_local_search_ragged setup: %s", hipGetErrorString(er));
+  // a launch sequence either moves a tour (at most max_iterations per tour) or ends one of its phases (two per round)
+  const long long ends = 2LL * max_rounds;
+  const long long limit = max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends;
+  MlState host{0, 0};
+  const int poll = 4;
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
+  for (long long it = 0; it < limit; ++it) {
+    hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
+    hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
+    hipLaunchKernelGGL(mls_select_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners, tabv,
+                       tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "multi_local_search state: %s", hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  std::vector<MlTourState> states(T);
+  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_local_search_ragged counters: %s", hipGetErrorString(er));
+  for (int b = 0; b < T; ++b) {
+    const int g = tab[b].group;
+    const MlTourState& x = states[b];
+    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
+    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
+    if (x.round + 1 > rounds_out[g]) rounds_out[g] = x.round + 1;
+    two_opt_moves_out[g] += x.two_opt_moves;
+    or_opt_moves_out[g] += x.or_opt_moves;
+  }
+  return DIFUSCO_OK;
+}
+
+}  // extern "C"

@@ -276,7 +276,7 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
 
 
-LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt")
+LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt")
 
 
 def check_local_search(local_search, two_opt_method="exact"):
@@ -453,6 +453,85 @@ def batched_multi_two_opt_ragged(points_list, tours_list, max_iterations=1000, d
     if stats is not None:
         stats["moves"] = moves
     return out, sweeps
+
+
+def _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device):
+    """The argument checks of the three multi-move local-search functions (before any library call)."""
+    if int(select_rounds) != select_rounds or select_rounds < 1:
+        raise ValueError(f"select_rounds = {select_rounds!r}: an integer >= 1")
+    return _local_search_checked(who, pts, trs, max_iterations, max_rounds, device)
+
+
+def _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device):
+    """One ``difusco_tsp_multi_local_search_ragged`` call on checked arguments.  Returns (int64 tours per group, the stats dict
+    of ``batched_multi_local_search_grouped``)."""
+    G = len(pts)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_multi_local_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
+                                                                       ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
+           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
+           "or_opt_moves": np.zeros(G, dtype=np.int64)}
+    _lib.check(L.difusco_tsp_multi_local_search_ragged(
+        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
+        int(max_iterations), int(max_rounds), int(select_rounds), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
+        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data,
+        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+
+
+def batched_multi_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4):
+    """Multi-move 2-opt + Or-opt local search of the tours of ONE instance, the arguments of ``batched_two_opt_torch``: every
+    tour runs rounds of a multi-move 2-opt phase (the sweeps of ``batched_multi_two_opt_torch``) and a multi-move Or-opt phase
+    (every sweep moves a set of segments of 1-3 cities, forwards or reversed, with pairwise disjoint position ranges) until an
+    Or-opt phase applies nothing, ``max_rounds`` rounds ran or the tour moved in ``max_iterations`` sweeps (the rule:
+    ``difusco_tsp_multi_local_search_ragged``, include/difusco_hip.h; GPU only).  No tour ends longer than the multi-move 2-opt
+    leaves it.  Returns ``(tour int64 numpy [B, N+1], stats)``: ``stats`` holds ``two_opt_sweeps``, ``or_opt_sweeps``, ``rounds``
+    (the maxima over the tours) and ``two_opt_moves``, ``or_opt_moves`` (the sums over the tours), ints."""
+    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
+    device = _multi_local_search_checked("batched_multi_local_search_torch", pts, trs, max_iterations, max_rounds, select_rounds,
+                                         device)
+    out, stats = _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device)
+    return out[0], {k: int(v[0]) for k, v in stats.items()}
+
+
+def batched_multi_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4):
+    """``batched_multi_local_search_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points``
+    float64 [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_multi_local_search_torch`` call
+    returns.  Returns ``(tours int64 numpy [G * P, N + 1], stats)``; the entries of ``stats`` are numpy arrays [G]."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts_l = [np.ascontiguousarray(p) for p in pts]
+    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
+    device = _multi_local_search_checked("batched_multi_local_search_grouped", pts_l, trs, max_iterations, max_rounds,
+                                         select_rounds, device)
+    out, stats = _multi_local_search_run(pts_l, trs, max_iterations, max_rounds, select_rounds, device)
+    return np.concatenate(out, axis=0), stats
+
+
+def batched_multi_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
+                                      select_rounds=4):
+    """``batched_multi_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.
+    Returns ``(list of int64 numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_multi_local_search_grouped``."""
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    device = _multi_local_search_checked("batched_multi_local_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds,
+                                         device)
+    return _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device)
 
 
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):

@@ -22,10 +22,12 @@ depend on the world size, the rank an instance lands on, or what the model ran b
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
 ``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--local_search
-{2opt,2opt+oropt,multi2opt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
+{2opt,2opt+oropt,multi2opt,multi2opt+oropt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
 ``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``; ``multi2opt``,
 ``decode.batched_multi_two_opt_grouped``: every sweep applies all disjoint improving 2-opt moves it selects, ``2opt_iterations``
-counts sweeps and the records gain ``two_opt_moves``), ``--mis_local_search {none,swap}`` (MIS:
+counts sweeps and the records gain ``two_opt_moves``; ``multi2opt+oropt``, ``decode.batched_multi_local_search_grouped``: rounds
+of multi-move 2-opt and multi-move Or-opt sweeps, ``2opt_iterations`` and ``or_opt_iterations`` count sweeps and the records gain
+``two_opt_moves``, ``or_opt_moves`` and ``local_search_rounds``), ``--mis_local_search {none,swap}`` (MIS:
 ``decode.mis_local_search_np`` after every decode, never a smaller set; the records gain ``decoded_costs``, the greedy sizes in
 the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--mis_local_search_kicks N`` /
 ``--mis_local_search_kick_size K`` (N > 0 only with ``--mis_local_search swap``: the search iterated with N seeded kicks,
@@ -103,11 +105,13 @@ EXTENSION_ARGS = [
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
     ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
-    ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt"),
+    ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt"),
                              help="tour refinement: 2opt (the reference's), 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
                                   "records gain or_opt_iterations and local_search_rounds) or multi2opt (every sweep applies all "
                                   "disjoint improving 2-opt moves it selects; 2opt_iterations counts sweeps, records gain "
-                                  "two_opt_moves)")),
+                                  "two_opt_moves) or multi2opt+oropt (rounds of multi-move 2-opt and multi-move Or-opt "
+                                  "sweeps; 2opt_iterations and or_opt_iterations count sweeps, records gain two_opt_moves, "
+                                  "or_opt_moves and local_search_rounds)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -274,7 +278,7 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
            "gt_cost": tsp_gt_cost(ex.points, ex.tour), "solved_cost": float(cost), "all_costs": [float(c) for c in costs],
            "merged_costs": [float(c) for c in info["merged_costs"]], "2opt_iterations": int(info["two_opt_iterations"]),
            "merge_iterations": float(info["merge_iterations"]), "seed": int(seed), "tour": [int(v) for v in tour]}
-    for k in ("or_opt_iterations", "local_search_rounds", "two_opt_moves"):      # --local_search 2opt+oropt / multi2opt
+    for k in ("or_opt_iterations", "local_search_rounds", "two_opt_moves", "or_opt_moves"):      # --local_search other than 2opt
         if k in info:
             rec[k] = int(info[k])
     return rec

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from .decode import (check_local_search, check_merge_method, check_two_opt_method, batched_local_search_grouped,
-                     batched_local_search_ragged, batched_local_search_torch, batched_multi_two_opt_grouped,
+                     batched_local_search_ragged, batched_local_search_torch, batched_multi_local_search_grouped,
+                     batched_multi_local_search_ragged, batched_multi_local_search_torch, batched_multi_two_opt_grouped,
                      batched_multi_two_opt_ragged, batched_multi_two_opt_torch, batched_two_opt_grouped, batched_two_opt_ragged,
                      batched_two_opt_torch, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
@@ -50,7 +51,11 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     (default) or "2opt+oropt" (``decode.batched_local_search_torch`` with ``max_iterations=two_opt_iterations``: never a longer
     tour; info gains ``or_opt_iterations`` and ``local_search_rounds`` of the last round; exact sweep only) or "multi2opt"
     (``decode.batched_multi_two_opt_torch``: every sweep applies all disjoint improving moves it selects, another 2-opt optimum;
-    ``two_opt_iterations`` of info is the sweep count and info gains ``two_opt_moves``, both of the last round; exact sweep only)."""
+    ``two_opt_iterations`` of info is the sweep count and info gains ``two_opt_moves``, both of the last round; exact sweep only)
+    or "multi2opt+oropt" (``decode.batched_multi_local_search_torch`` with ``max_iterations=two_opt_iterations``: rounds of
+    multi-move 2-opt and multi-move Or-opt sweeps, never a longer tour than "multi2opt"; ``two_opt_iterations`` of info is the
+    2-opt sweep count, info gains ``two_opt_moves``, ``or_opt_iterations`` (the Or-opt sweeps), ``or_opt_moves`` and
+    ``local_search_rounds``, all of the last round; exact sweep only)."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     dev = model.device
@@ -91,6 +96,10 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
         elif local_search == "multi2opt":
             solved, ns = batched_multi_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),
                                                      max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+        elif local_search == "multi2opt+oropt":
+            solved, ls_stats = batched_multi_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
+                                                                max_iterations=two_opt_iterations, device=dev)
+            ns = ls_stats["two_opt_sweeps"]
         else:
             solved, ns = batched_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
                                                     max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
@@ -103,6 +112,9 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     info = {"merge_iterations": merge_iterations, "two_opt_iterations": ns, "merged_costs": merged_costs}
     if local_search == "multi2opt":
         info.update(two_opt_moves=ls_stats["moves"])
+    elif local_search == "multi2opt+oropt":
+        info.update(two_opt_moves=ls_stats["two_opt_moves"], or_opt_iterations=ls_stats["or_opt_sweeps"],
+                    or_opt_moves=ls_stats["or_opt_moves"], local_search_rounds=ls_stats["rounds"])
     elif local_search != "2opt":
         info.update(or_opt_iterations=ls_stats["or_opt_iterations"], local_search_rounds=ls_stats["rounds"])
     return solved[best].tolist(), costs[best], costs, info
@@ -289,6 +301,10 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             elif local_search == "multi2opt":
                 solved, ns = batched_multi_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt":
+                solved, ls_stats = batched_multi_local_search_grouped(
+                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations, device=dev)
+                ns = ls_stats["two_opt_sweeps"]
             else:
                 solved, ns = batched_local_search_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
                                                           max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
@@ -303,6 +319,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]), "merged_costs": merged_costs[g]}
             if local_search == "multi2opt":
                 info.update(two_opt_moves=int(ls_stats["moves"][g]))
+            elif local_search == "multi2opt+oropt":
+                info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
+                            or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             elif local_search != "2opt":
                 info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             results.append((sol[best].tolist(), costs[best], costs, info))
@@ -386,6 +405,10 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             elif local_search == "multi2opt":
                 solved, its = batched_multi_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt":
+                solved, ls_stats = batched_multi_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
+                                                                     max_iterations=two_opt_iterations, device=dev)
+                its = ls_stats["two_opt_sweeps"]
             else:
                 solved, its = batched_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                           max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
@@ -400,6 +423,9 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]), "merged_costs": merged_costs[g]}
             if local_search == "multi2opt":
                 info.update(two_opt_moves=int(ls_stats["moves"][g]))
+            elif local_search == "multi2opt+oropt":
+                info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
+                            or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             elif local_search != "2opt":
                 info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             results.append((sol[best].tolist(), costs[best], costs, info))

@@ -632,6 +632,43 @@ int difusco_tsp_multi_two_opt_ragged(int groups, const int32_t* group_n, const i
                                      int32_t* tours, int64_t max_iterations, int select_rounds, void* workspace,
                                      size_t workspace_bytes, int64_t* sweeps_out, int64_t* moves_out, void* stream);
 
+/* Multi-move local search, 2-opt + Or-opt (additive to ABI 13; not in the reference): the arrays, conventions and limits of
+ * difusco_tsp_two_opt_ragged, the notation of the two comments above: the tour is closed (tour[n] == tour[0]), P_k is the point at
+ * position k, d_k = |P_k P_k+1|, everything is float64 with every operation rounded on its own, a distance is two products, one
+ * sum and a square root, the threshold is -1e-6, positions 0 and n never move.  Every TOUR runs on its own and keeps its own
+ * phase, round and counters.  A tour runs ROUNDS of two phases:
+ *   2-opt phase   the sweeps of difusco_tsp_multi_two_opt_ragged, exactly - steps 1-3 of its comment with the same
+ *                 select_rounds -, until a sweep has no proposal;
+ *   Or-opt phase  sweeps of three steps, until a sweep has no proposal:
+ *     1. Row proposals.  Row i = 0 .. n-2 evaluates the candidates (v, i, j) of difusco_tsp_local_search_ragged that start at i:
+ *        (L, reversed) = variant v of [(1,no), (2,no), (2,yes), (3,no), (3,yes)] with i <= n-1-L, 0 <= j <= n-1, j outside
+ *        [i, i+L]; each with that comment's delta, bit for bit.  The row keeps its lowest delta, ties to the lowest v and then
+ *        the lowest j (the flat-index order (v n + i) n + j within one row), and proposes if that delta is < -1e-6.  The key is
+ *        (delta, i) (keys are distinct); the range is the half-open position interval [min(i, j), hi + 1) with hi = j for
+ *        j > i+L and hi = i+L for j < i: from the first position of the lowest of the three edges the move touches to the first
+ *        position of the highest, the convention of the 2-opt range [i, j+1).
+ *     2. Selection.  Step 2 of the multi-move 2-opt, verbatim, over these keys and ranges.
+ *     3. Apply.  Every winner applies its move as difusco_tsp_local_search_ragged defines it.  Only positions inside its range are
+ *        rewritten and the winners' ranges are disjoint, so the order does not matter.
+ * Stopping.  A tour is done after a round whose Or-opt phase applied nothing, after max_rounds rounds, or when it has moved in
+ * max_iterations sweeps, both kinds counted together (with max_iterations = 0 nothing is applied).  The cap is per tour, so a
+ * tour's result never depends on which other tours or groups share the call.  A done tour costs no further work; a group is done
+ * when all its tours are.
+ * So: the first 2-opt phase is the multi-move 2-opt - a tour on which the first Or-opt phase proposes nothing ends exactly as
+ * difusco_tsp_multi_two_opt_ragged (without a binding cap) leaves it; every move shortens its tour by more than 1e-6, and no tour
+ * ends longer than the multi-move 2-opt leaves it; a tour that stops below both caps has no improving 2-opt move and no improving
+ * Or-opt move left.
+ * Outputs, HOST arrays [groups]: two_opt_sweeps_out, or_opt_sweeps_out (int64) and rounds_out (int32) are the maxima over the
+ * group's tours of the tour's own counts - the sweeps in which it moved, by kind, and the rounds it started (every tour starts
+ * round 1); two_opt_moves_out, or_opt_moves_out (int64) are the sums over the group's tours of the moves applied.
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_two_opt_ragged, a null output array, max_rounds < 1 and
+ * select_rounds < 1.  Blocks until every group is done. */
+int difusco_tsp_multi_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                          int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace,
+                                          size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
+                                          int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
