@@ -17,12 +17,17 @@
 //                         stretch to a buffer of the tour's own and writes it back shifted -, the switch of phase and round, the
 //                         stop tests and the counters.  The last tour of a group to finish counts the group as stopped; the
 //                         host enqueues sweeps and polls the counter of stopped groups.
+// The iterated search (difusco_tsp_iterated_search_ragged) launches the same three and a fourth after them:
+//   mls_keep_kick_kernel  one block of 1024 threads per tour whose descent has just ended: the length of the tour in one fixed
+//                         association, the comparison with the tour's incumbent, the copy one way or the other, and either the
+//                         next seeded kick (segment swaps read from the incumbent) with a reset of the descent state, or the end.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <vector>
 
 #include "../../include/difusco_hip.h"
+#include "common.h"
 #include "kernels.h"
 #include "multi_move_common.h"
 #include "two_opt_common.h"
@@ -35,7 +40,7 @@ constexpr int LMAX = 3;                    // longest segment
 __device__ __forceinline__ int variant_len(int v) { return (v + 3) >> 1; }      // 1, 2, 2, 3, 3
 __device__ __forceinline__ bool variant_rev(int v) { return v == 2 || v == 4; }
 
-enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2 };
+enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2, kKeep = 3 };   // kKeep: the iterated search only
 
 struct MlTour {            // offsets in elements of the array they index
   int n, nblk_two, nblk_or, group;
@@ -238,7 +243,10 @@ __device__ __forceinline__ void report_done(MlGroup* g, MlState* st) {
   if (atomicAdd(&g->done, 1) == g->count - 1) atomicAdd(&st->done, 1);
 }
 
-__global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
+// the select step of one tour (the block).  kIterated: where the descent ends, the tour goes to the keep / kick step of the
+// iterated search (mls_keep_kick_kernel) instead of being done.
+template <bool kIterated>
+__device__ __forceinline__ void mls_select_tour(
     int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
@@ -261,8 +269,12 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
         s->phase = kOrOpt;
         s->or_moved = 0;
       } else if (!s->or_moved || s->round + 1 >= max_rounds) {
-        s->phase = kDone;
-        report_done(grp + d.group, st);
+        if constexpr (kIterated) {
+          s->phase = kKeep;
+        } else {
+          s->phase = kDone;
+          report_done(grp + d.group, st);
+        }
       } else {
         s->phase = kTwoOpt;
         s->round += 1;
@@ -285,6 +297,144 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
       s->or_moved = 1;
     }
     if (s->sweeps >= max_iterations) {
+      if constexpr (kIterated) {
+        s->phase = kKeep;
+      } else {
+        s->phase = kDone;
+        report_done(grp + d.group, st);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
+    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
+    int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
+    MlState* st, MlGroup* grp, MlTourState* ts) {
+  mls_select_tour<false>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                         max_iterations, max_rounds, select_rounds, st, grp, ts);
+}
+
+// ---- the iterated search (difusco_tsp_iterated_search_ragged): descents of the search above with seeded segment kicks between
+// them.  The rule is stated in include/difusco_hip.h and restated in numpy in tests/tsp_iterated_search_emulation.py.
+
+__global__ __launch_bounds__(kSelectThreads) void mls_select_iterated_kernel(
+    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
+    int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
+    MlState* st, MlGroup* grp, MlTourState* ts) {
+  mls_select_tour<true>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                        max_iterations, max_rounds, select_rounds, st, grp, ts);
+}
+
+constexpr int kMaxKickSize = 64;           // the draws of a kick: one wave decides which are kept
+constexpr int kLenParts = kSelectThreads;  // strided partial sums of a tour length
+
+struct MlIter {            // device-resident state of a tour of the iterated search, zero at the start of a call
+  int kick, have;          // kicks drawn so far; the tour has an incumbent
+  int kept, improved;      // kicks whose descent ended not longer / strictly shorter than the incumbent
+  long long swapped;       // segment pairs swapped over all kicks
+  int max_round, pad;      // the highest zero-based round of any descent
+  double first_length, length;   // of the first descent's result, of the incumbent
+};
+
+// The length of the closed tour in the fixed association: thread r sums d_r, d_r+1024, .. in rising k from 0.0, then a halving
+// tree over the 1024 partial sums (part[r] += part[r + h], h = 512 .. 1).  d_k is prep_entry's.  The result in every thread.
+__device__ __forceinline__ double tour_length(const double* __restrict__ points, const int* __restrict__ tour, int n,
+                                              double* part) {
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < n; k += kLenParts) {
+    const int c = tour[k], c1 = tour[k + 1];
+    acc = __dadd_rn(acc, dist2d(points[2 * c] - points[2 * c1], points[2 * c + 1] - points[2 * c1 + 1]));
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = kLenParts / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] = __dadd_rn(part[threadIdx.x], part[threadIdx.x + h]);
+    __syncthreads();
+  }
+  const double len = part[0];
+  __syncthreads();
+  return len;
+}
+
+// One block per tour, a no-op unless the tour's descent has just ended (phase kKeep).  Keep: the length of the descended tour C
+// against the incumbent I (`inc`, n + 1 entries of the tour's own); I <- C if it is not longer (or there is no incumbent yet),
+// else C <- I.  Kick, if kicks remain: the draws of kick t, the disjointness filter in rising c by wave 0, the kept draws swap
+// their two adjacent segments in C reading I - a wave per draw -, and the descent state is reset.  Else the tour is done; C = I.
+__global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
+    const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const MlTour* __restrict__ desc,
+    const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets, int kicks, int kick_size,
+    int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters) {
+  const int t = blockIdx.x;
+  if (ts[t].phase != kKeep) return;                              // written by thread 0 of this block at its end only
+  const MlTour d = desc[t];
+  const int n = d.n;
+  int* tour = tours + d.closed;
+  int* inc = inc_all + d.closed;
+  MlIter* it = iters + t;                                        // thread 0 alone writes it, at the end
+  __shared__ double part[kLenParts];
+  __shared__ int ka[kMaxKickSize], kl1[kMaxKickSize], kb[kMaxKickSize], kkeep[kMaxKickSize];
+  const int have = it->have, kick = it->kick;                    // read before the barriers of tour_length
+  const double inc_len = it->length;
+  const double len = tour_length(points + d.points, tour, n, part);
+  const bool take = !have || len <= inc_len;                     // uniform over the block
+  if (take)
+    for (int k = threadIdx.x; k <= n; k += kSelectThreads) inc[k] = tour[k];
+  else
+    for (int k = threadIdx.x; k <= n; k += kSelectThreads) tour[k] = inc[k];
+  const bool more = kick < kicks;
+  int nkept = 0;
+  if (more) {
+    if (threadIdx.x < 64) {
+      const int c = threadIdx.x;
+      const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
+      int a = 0, b = 0, l1 = 0, keep = 0;
+      if (c < kick_size) {
+        uint32_t w[4];
+        Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
+        l1 = 1 + (int)(w[1] % lc);
+        const int l2 = 1 + (int)(w[2] % lc);
+        a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
+        b = a + l1 + l2;
+        keep = 1;
+      }
+      for (int e = 0; e < kick_size; ++e) {                      // lane e's flag is final when e comes up
+        const int ae = __shfl(a, e), be = __shfl(b, e), ke = __shfl(keep, e);
+        if (c > e && ke && a < be && ae < b) keep = 0;
+      }
+      ka[c] = a, kl1[c] = l1, kb[c] = b, kkeep[c] = keep;
+    }
+    __syncthreads();                                             // and the copy above is complete
+    const int lane = threadIdx.x & 63;
+    for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
+      if (!kkeep[c]) continue;
+      const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
+      for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (more)
+      for (int c = 0; c < kick_size; ++c) nkept += kkeep[c];
+    MlTourState* s = ts + t;
+    if (!have) {
+      it->have = 1;
+      it->first_length = len;
+    } else if (take) {
+      it->kept += 1;
+      if (len < inc_len) it->improved += 1;
+    }
+    if (take) it->length = len;
+    if (s->round > it->max_round) it->max_round = s->round;
+    if (more) {
+      it->kick = kick + 1;
+      it->swapped += nkept;
+      s->phase = no_descent ? kKeep : kTwoOpt;
+      s->round = 0;
+      s->or_moved = 0;
+      s->sweeps = 0;
+    } else {
       s->phase = kDone;
       report_done(grp + d.group, st);
     }
@@ -352,6 +502,20 @@ int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_
   L->st = take(sizeof(MlState));
   L->total = off;
   return DIFUSCO_OK;
+}
+
+struct MlIterLayout {      // byte offsets behind the layout of the descent
+  size_t inc, iters, total;
+};
+
+thread_local int g_host_syncs = 0;   // host synchronisations of this thread's last iterated call (difusco_tsp_search_host_syncs)
+
+void mls_iter_layout(const MlLayout& lay, int groups, const int32_t* group_n, const int32_t* group_tours, MlIterLayout* I) {
+  size_t closed = 0;
+  for (int g = 0; g < groups; ++g) closed += ((size_t)group_n[g] + 1) * (size_t)group_tours[g];
+  I->inc = lay.total;
+  I->iters = I->inc + up256(sizeof(int) * closed);
+  I->total = I->iters + up256(sizeof(MlIter) * (size_t)lay.tours);
 }
 
 }  // namespace
@@ -447,6 +611,140 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
     if (x.round + 1 > rounds_out[g]) rounds_out[g] = x.round + 1;
     two_opt_moves_out[g] += x.two_opt_moves;
     or_opt_moves_out[g] += x.or_opt_moves;
+  }
+  return DIFUSCO_OK;
+}
+
+int difusco_tsp_iterated_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                       size_t* bytes) {
+  using namespace difusco;
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged_workspace_bytes: bytes is null");
+  MlLayout lay;
+  const int rc = mls_layout("tsp_iterated_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
+  if (rc != DIFUSCO_OK) return rc;
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  *bytes = il.total;
+  return DIFUSCO_OK;
+}
+
+int difusco_tsp_search_host_syncs(void) { return difusco::g_host_syncs; }
+
+int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                       int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                       int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                       void* workspace, size_t workspace_bytes, int64_t* two_opt_sweeps_out,
+                                       int64_t* or_opt_sweeps_out, int32_t* rounds_out, int64_t* two_opt_moves_out,
+                                       int64_t* or_opt_moves_out, int32_t* kicks_kept_out, int32_t* kicks_improved_out,
+                                       int64_t* segments_swapped_out, double* first_length_out, double* final_length_out,
+                                       void* stream) {
+  using namespace difusco;
+  g_host_syncs = 0;
+  MlLayout lay;
+  std::vector<MlTour> tab;
+  std::vector<MlGroup> gtab;
+  const int rc = mls_layout("tsp_iterated_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
+      !or_opt_moves_out || max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: needs non-null device arrays, the five host output arrays "
+                                     "[groups] and max_iterations >= 0");
+  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
+      !final_length_out)
+    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: needs the device arrays tour_seeds / tour_offsets and the five "
+                                     "host output arrays [tours]");
+  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
+  if (select_rounds < 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
+  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: kicks = %d < 0", (int)kicks);
+  if (kick_size < 1 || kick_size > kMaxKickSize)
+    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
+  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: span = %d < 1", (int)span);
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  if (workspace_bytes < il.total)
+    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: workspace %zu < %zu bytes", workspace_bytes, il.total);
+  char* w = (char*)workspace;
+  MlTour* desc = (MlTour*)(w + lay.desc);
+  double2* tp = (double2*)(w + lay.tp);
+  double* dlen = (double*)(w + lay.dlen);
+  double* rowv = (double*)(w + lay.rowv);
+  int* rowj = (int*)(w + lay.rowj);
+  int* live = (int*)(w + lay.live);
+  int* winners = (int*)(w + lay.winners);
+  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
+  int* tabi = (int*)(w + lay.tabi);
+  int2* marks = (int2*)(w + lay.marks);
+  int2* cum = (int2*)(w + lay.cum);
+  MlGroup* grp = (MlGroup*)(w + lay.grp);
+  MlTourState* ts = (MlTourState*)(w + lay.ts);
+  MlState* st = (MlState*)(w + lay.st);
+  int* inc = (int*)(w + il.inc);
+  MlIter* iters = (MlIter*)(w + il.iters);
+  hipStream_t s = (hipStream_t)stream;
+  const int T = lay.tours;
+  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
+  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
+  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
+  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search_ragged setup: %s", hipGetErrorString(er));
+  // a launch sequence either moves a tour (at most max_iterations per descent), ends one of its phases (two per round) - the
+  // last of them runs the keep / kick step -, or, with no descent, is one keep / kick step: the bound per descent, kicks + 1 times
+  const long long ends = 2LL * max_rounds;
+  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
+  const long long limit = per > INT64_MAX / ((long long)kicks + 1) ? INT64_MAX : per * ((long long)kicks + 1);
+  MlState host{0, 0};
+  const int poll = 8;
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
+  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
+  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
+  for (long long it = 0; it < limit; ++it) {
+    if (!no_descent) {
+      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
+      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
+      hipLaunchKernelGGL(mls_select_iterated_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
+                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
+    }
+    hipLaunchKernelGGL(mls_keep_kick_kernel, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
+                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters);
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      ++g_host_syncs;
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search state: %s", hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  std::vector<MlIter> its(T);
+  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search_ragged counters: %s", hipGetErrorString(er));
+  for (int g = 0; g < groups; ++g) {
+    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
+    rounds_out[g] = 1;                                           // every descent starts round 1
+  }
+  for (int b = 0; b < T; ++b) {
+    const int g = tab[b].group;
+    const MlTourState& x = states[b];
+    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
+    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
+    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
+    two_opt_moves_out[g] += x.two_opt_moves;
+    or_opt_moves_out[g] += x.or_opt_moves;
+    kicks_kept_out[b] = its[b].kept;
+    kicks_improved_out[b] = its[b].improved;
+    segments_swapped_out[b] = its[b].swapped;
+    first_length_out[b] = its[b].first_length;
+    final_length_out[b] = its[b].length;
   }
   return DIFUSCO_OK;
 }

@@ -534,6 +534,121 @@ def batched_multi_local_search_ragged(points_list, tours_list, max_iterations=10
     return _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device)
 
 
+TSP_KICK_SIZE, TSP_KICK_SPAN = 16, 30     # the pair of scripts/tsp_iterated_search_table.py
+
+
+def check_tsp_kicks(local_search, kicks, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN):
+    """``kicks`` / ``kick_size`` / ``span`` of ``solve_tsp`` and the runner: kicks iterate the multi-move local search, so they
+    need it."""
+    if int(kicks) != kicks or kicks < 0:
+        raise ValueError(f"local_search_kicks = {kicks!r}: an integer >= 0")
+    if int(kick_size) != kick_size or not 1 <= kick_size <= 64:
+        raise ValueError(f"local_search_kick_size = {kick_size!r}: an integer in 1 .. 64")
+    if int(span) != span or not 1 <= span < 2 ** 31:
+        raise ValueError(f"local_search_kick_span = {span!r}: an integer >= 1")
+    if kicks > 0 and local_search != "multi2opt+oropt":
+        raise ValueError(f"local_search_kicks = {kicks} iterates the multi-move local search: it needs "
+                         f"local_search='multi2opt+oropt', not {local_search!r}")
+    return int(kicks), int(kick_size), int(span)
+
+
+TSP_KICK_STATS = ("kicks_kept", "kicks_improved", "segments_swapped", "first_length", "final_length")
+
+
+def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
+                         stats):
+    """The checks of the three iterated-search functions (before any library call) and one
+    ``difusco_tsp_iterated_search_ragged`` call.  Returns (int64 tours per group, the stats dict of
+    ``batched_multi_local_search_grouped``); ``stats`` receives the per-tour arrays and ``host_syncs``."""
+    if int(kicks) != kicks or kicks < 0 or kicks >= 2 ** 31:
+        raise ValueError(f"kicks = {kicks!r}: an integer >= 0")
+    _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
+    device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
+    T = sum(t.shape[0] for t in trs)
+    mask = (1 << 64) - 1
+    table = []
+    for name, v in (("seeds", seeds), ("offsets", offsets)):
+        v = [0] * T if v is None else [int(x) & mask for x in v]
+        if len(v) != T:
+            raise ValueError(f"{name}: {len(v)} entries for {T} tours")
+        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
+    G = len(pts)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_iterated_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
+                                                                    ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
+           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
+           "or_opt_moves": np.zeros(G, dtype=np.int64)}
+    per = {"kicks_kept": np.zeros(T, dtype=np.int32), "kicks_improved": np.zeros(T, dtype=np.int32),
+           "segments_swapped": np.zeros(T, dtype=np.int64), "first_length": np.zeros(T, dtype=np.float64),
+           "final_length": np.zeros(T, dtype=np.float64)}
+    _lib.check(L.difusco_tsp_iterated_search_ragged(
+        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
+        int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
+        ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
+        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_KICK_STATS),
+        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats.update(per, host_syncs=int(L.difusco_tsp_search_host_syncs()))
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+
+
+def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
+                                  kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None):
+    """``batched_multi_local_search_torch`` iterated with seeded segment kicks (the rule: ``difusco_tsp_iterated_search_ragged``,
+    include/difusco_hip.h; GPU only; not in the reference): after its descent every tour, ``kicks`` times, swaps up to
+    ``kick_size`` disjoint pairs of adjacent random segments of at most ``span`` cities each, descends again (the caps are per
+    descent) and keeps the result unless it is longer.  ``seeds`` / ``offsets`` [B]: the Philox key and first offset of every
+    tour (default 0; kick t draws at ``offsets[b] + t``); a tour gets the same answer alone or in any call.  ``kicks=0`` is
+    ``batched_multi_local_search_torch``.  Returns ``(tour int64 numpy [B, N+1], stats)`` as that function (sweeps and moves
+    summed over a tour's descents, ``rounds`` the most rounds of a descent); ``stats`` (a dict) receives the per-tour numpy
+    arrays [B] ``kicks_kept``, ``kicks_improved``, ``segments_swapped``, ``first_length``, ``final_length`` and ``host_syncs``."""
+    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
+    out, st = _iterated_search_run("batched_iterated_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device,
+                                   kicks, kick_size, span, seeds, offsets, stats)
+    return out[0], {k: int(v[0]) for k, v in st.items()}
+
+
+def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
+                                    kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None):
+    """``batched_iterated_search_torch`` of G instances at once, the arguments of ``batched_multi_local_search_grouped``;
+    ``seeds`` / ``offsets`` [G * P] in the order of ``tours``.  Every tour gets what its own call returns.  Returns ``(tours int64
+    numpy [G * P, N + 1], stats)``; the entries of the returned stats are numpy arrays [G], the per-tour arrays [G * P]."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts_l = [np.ascontiguousarray(p) for p in pts]
+    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
+    out, st = _iterated_search_run("batched_iterated_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds,
+                                   device, kicks, kick_size, span, seeds, offsets, stats)
+    return np.concatenate(out, axis=0), st
+
+
+def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
+                                   select_rounds=4, kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None,
+                                   offsets=None, stats=None):
+    """``batched_iterated_search_torch`` of G instances of ANY sizes at once, the arguments of
+    ``batched_multi_local_search_ragged``; ``seeds`` / ``offsets``: one per tour, group after group.  Returns ``(list of int64
+    numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_iterated_search_grouped``."""
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    return _iterated_search_run("batched_iterated_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device,
+                                kicks, kick_size, span, seeds, offsets, stats)
+
+
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).

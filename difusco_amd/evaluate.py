@@ -32,7 +32,11 @@ of multi-move 2-opt and multi-move Or-opt sweeps, ``2opt_iterations`` and ``or_o
 the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--mis_local_search_kicks N`` /
 ``--mis_local_search_kick_size K`` (N > 0 only with ``--mis_local_search swap``: the search iterated with N seeded kicks,
 ``decode.mis_iterated_search_np``, keyed by the instance seed; the records gain ``swap_costs``, ``kicks_entered``,
-``kicks_accepted`` and the two settings, the header the two settings), ``--merge_method {loop,batched}``
+``kicks_accepted`` and the two settings, the header the two settings), ``--tsp_local_search_kicks N`` /
+``--tsp_local_search_kick_size K`` / ``--tsp_local_search_kick_span S`` (N > 0 only with ``--local_search multi2opt+oropt``: that
+search iterated with N seeded segment kicks, ``decode.batched_iterated_search_grouped``, every tour keyed by its instance seed;
+the records gain ``kicks_improved``, one count per copy in the order of the last round, and the three settings, the header
+the three settings), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -100,6 +104,7 @@ REFERENCE_ARGS = [
 TRAINING_ONLY = ("training_split", "training_split_label_dir", "batch_size", "num_epochs", "learning_rate", "weight_decay",
                  "lr_scheduler", "num_workers", "use_activation_checkpoint", "project_name", "wandb_entity",
                  "wandb_logger_name", "resume_id", "resume_weight_only")
+TSP_KICK_SIZE, TSP_KICK_SPAN = 16, 30     # decode.TSP_KICK_SIZE / TSP_KICK_SPAN (this module parses without torch)
 EXTENSION_ARGS = [
     ("--seed", dict(type=int, default=0, help="base of the per-instance seeds (instance_seed)")),
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
@@ -112,6 +117,11 @@ EXTENSION_ARGS = [
                                   "two_opt_moves) or multi2opt+oropt (rounds of multi-move 2-opt and multi-move Or-opt "
                                   "sweeps; 2opt_iterations and or_opt_iterations count sweeps, records gain two_opt_moves, "
                                   "or_opt_moves and local_search_rounds)")),
+    ("--tsp_local_search_kicks", dict(type=int, default=0,
+                                       help="TSP: iterate the multi-move local search with this many seeded segment kicks "
+                                            "(needs --local_search multi2opt+oropt; 0: one descent)")),
+    ("--tsp_local_search_kick_size", dict(type=int, default=TSP_KICK_SIZE, help="TSP: segment swaps drawn per kick (1 .. 64)")),
+    ("--tsp_local_search_kick_span", dict(type=int, default=TSP_KICK_SPAN, help="TSP: longest segment of a swap, in cities")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -163,6 +173,14 @@ def parse_args(argv=None):
         parser.error("--ckpt_path is required (the weights to evaluate)")
     if args.local_search != "2opt" and args.two_opt_method != "exact":
         parser.error(f"--local_search {args.local_search} runs the exact 2-opt sweep: --two_opt_method {args.two_opt_method} is not built")
+    if args.tsp_local_search_kicks < 0 or not 1 <= args.tsp_local_search_kick_size <= 64 or args.tsp_local_search_kick_span < 1:
+        parser.error("--tsp_local_search_kicks must be >= 0, --tsp_local_search_kick_size in 1 .. 64 and "
+                     "--tsp_local_search_kick_span >= 1")
+    if args.tsp_local_search_kicks > 0 and args.local_search != "multi2opt+oropt":
+        parser.error(f"--tsp_local_search_kicks {args.tsp_local_search_kicks} iterates the multi-move local search: pass "
+                     "--local_search multi2opt+oropt")
+    if args.tsp_local_search_kicks > 0 and args.task != "tsp":
+        parser.error(f"--tsp_local_search_kicks {args.tsp_local_search_kicks} refines TSP tours: not with --task {args.task}")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -281,6 +299,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
     for k in ("or_opt_iterations", "local_search_rounds", "two_opt_moves", "or_opt_moves"):      # --local_search other than 2opt
         if k in info:
             rec[k] = int(info[k])
+    if "local_search_kicks_improved" in info:      # --tsp_local_search_kicks N > 0
+        rec["kicks_improved"] = [int(v) for v in info["local_search_kicks_improved"]]
     return rec
 
 
@@ -319,7 +339,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
                 two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt",
                 mis_local_search: str = "none", mis_local_search_kicks: int = 0,
-                mis_local_search_kick_size: int = 4) -> List[dict]:
+                mis_local_search_kick_size: int = 4, tsp_local_search_kicks: int = 0,
+                tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN) -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -339,9 +360,16 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   parallel_sampling=parallel_sampling, sequential_sampling=sequential_sampling,
                                   two_opt_iterations=two_opt_iterations, seeds=seeds, generators=gens, timings=timings,
                                   step_offset=0, heatmaps=heats, two_opt_method=two_opt_method,
-                                  merge_method=merge_method, local_search=local_search)
+                                  merge_method=merge_method, local_search=local_search,
+                                  **(dict(local_search_kicks=tsp_local_search_kicks,
+                                          local_search_kick_size=tsp_local_search_kick_size,
+                                          local_search_kick_span=tsp_local_search_kick_span) if tsp_local_search_kicks > 0 else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
+                if tsp_local_search_kicks > 0:
+                    records[-1].update(tsp_local_search_kicks=tsp_local_search_kicks,
+                                       tsp_local_search_kick_size=tsp_local_search_kick_size,
+                                       tsp_local_search_kick_span=tsp_local_search_kick_span)
                 if heats is not None:
                     save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
         else:
@@ -417,7 +445,10 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                two_opt_method=args.two_opt_method, merge_method=args.merge_method,
                                local_search=args.local_search, mis_local_search=args.mis_local_search,
                                mis_local_search_kicks=args.mis_local_search_kicks,
-                               mis_local_search_kick_size=args.mis_local_search_kick_size)
+                               mis_local_search_kick_size=args.mis_local_search_kick_size,
+                               tsp_local_search_kicks=args.tsp_local_search_kicks,
+                               tsp_local_search_kick_size=args.tsp_local_search_kick_size,
+                               tsp_local_search_kick_span=args.tsp_local_search_kick_span)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -444,6 +475,10 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["local_search"] = args.local_search
             if args.mis_local_search != "none":
                 line["mis_local_search"] = args.mis_local_search
+            if args.tsp_local_search_kicks > 0:
+                line["tsp_local_search_kicks"] = args.tsp_local_search_kicks
+                line["tsp_local_search_kick_size"] = args.tsp_local_search_kick_size
+                line["tsp_local_search_kick_span"] = args.tsp_local_search_kick_span
             if args.mis_local_search_kicks > 0:
                 line["mis_local_search_kicks"] = args.mis_local_search_kicks
                 line["mis_local_search_kick_size"] = args.mis_local_search_kick_size

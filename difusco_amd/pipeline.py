@@ -16,7 +16,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import (check_local_search, check_merge_method, check_two_opt_method, batched_local_search_grouped,
+from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_kicks,
+                     check_two_opt_method, batched_local_search_grouped,
+                     batched_iterated_search_grouped, batched_iterated_search_ragged, batched_iterated_search_torch,
                      batched_local_search_ragged, batched_local_search_torch, batched_multi_local_search_grouped,
                      batched_multi_local_search_ragged, batched_multi_local_search_torch, batched_multi_two_opt_grouped,
                      batched_multi_two_opt_ragged, batched_multi_two_opt_torch, batched_two_opt_grouped, batched_two_opt_ragged,
@@ -41,7 +43,8 @@ def _ticker(timings, dev):
 def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: int = 1, two_opt_iterations: int = 1000,
               generator: Optional[torch.Generator] = None, timings: Optional[Dict[str, float]] = None,
               sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact",
-              local_search: str = "2opt"):
+              local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
+              local_search_kick_span: int = TSP_KICK_SPAN):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -55,9 +58,15 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     or "multi2opt+oropt" (``decode.batched_multi_local_search_torch`` with ``max_iterations=two_opt_iterations``: rounds of
     multi-move 2-opt and multi-move Or-opt sweeps, never a longer tour than "multi2opt"; ``two_opt_iterations`` of info is the
     2-opt sweep count, info gains ``two_opt_moves``, ``or_opt_iterations`` (the Or-opt sweeps), ``or_opt_moves`` and
-    ``local_search_rounds``, all of the last round; exact sweep only)."""
+    ``local_search_rounds``, all of the last round; exact sweep only).  ``local_search_kicks`` > 0 (only with
+    "multi2opt+oropt", else ``ValueError``): that search iterated with that many seeded kicks of up to
+    ``local_search_kick_size`` segment swaps within ``local_search_kick_span`` cities (``decode.batched_iterated_search_torch``;
+    never a longer tour); copy p of sequential round r is its own tour, keyed by the model's seed at the Philox offset
+    ``2^62 + (r P + p) 2^32``; info gains ``local_search_kicks_improved`` of the last round (a list, one per copy).  0 is the
+    plain search."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
+    kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -80,8 +89,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
     stacked, merged_costs = [], []
     merge_iterations, ns = 0.0, 0
-    ls_stats = {}
-    for _ in range(sequential_sampling):                                                    # :185
+    ls_stats, kick_stats = {}, {}
+    for r in range(sequential_sampling):                                                    # :185
         t0 = time.perf_counter()
         heat = model.sample(pts_rep, ei_rep, generator=generator, graphed=graphed)          # :186-222, on the device
         tick("sampling", t0)
@@ -96,6 +105,12 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
         elif local_search == "multi2opt":
             solved, ns = batched_multi_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),
                                                      max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+        elif local_search == "multi2opt+oropt" and kicks > 0:
+            solved, ls_stats = batched_iterated_search_torch(
+                np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
+                kick_size=kick_size, span=kick_span, seeds=[_kick_key(model.seed)] * parallel_sampling,
+                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats)
+            ns = ls_stats["two_opt_sweeps"]
         elif local_search == "multi2opt+oropt":
             solved, ls_stats = batched_multi_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
                                                                 max_iterations=two_opt_iterations, device=dev)
@@ -115,6 +130,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     elif local_search == "multi2opt+oropt":
         info.update(two_opt_moves=ls_stats["two_opt_moves"], or_opt_iterations=ls_stats["or_opt_sweeps"],
                     or_opt_moves=ls_stats["or_opt_moves"], local_search_rounds=ls_stats["rounds"])
+        if kicks > 0:
+            info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"]])
     elif local_search != "2opt":
         info.update(or_opt_iterations=ls_stats["or_opt_iterations"], local_search_rounds=ls_stats["rounds"])
     return solved[best].tolist(), costs[best], costs, info
@@ -188,6 +205,11 @@ def _kick_offsets(r: int, P: int):
     return [MIS_KICK_OFFSET + ((r * P + p) << 32) for p in range(P)]
 
 
+def _kick_key(seed) -> int:
+    """A sampling seed as the Philox key of a kick stream: the way ``sample_batch`` resolves it."""
+    return int(seed) & (2 ** 63 - 1)
+
+
 def _kick_stats(out: dict, call: dict, first: int, P: int):
     for k, src in (("swap_sizes", "size_before"), ("kicks_entered", "entered"), ("kicks_accepted", "accepted")):
         out[k] += call[src][first:first + P]
@@ -219,7 +241,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     generators: Optional[Sequence[torch.Generator]] = None, timings: Optional[Dict[str, float]] = None,
                     instances_per_call: Optional[int] = None, step_offset: Optional[int] = None,
                     heatmaps: Optional[list] = None, *, two_opt_method: str = "exact",
-                    merge_method: str = "loop", local_search: str = "2opt") -> List[tuple]:
+                    merge_method: str = "loop", local_search: str = "2opt", local_search_kicks: int = 0,
+                    local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN) -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -232,14 +255,17 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     its ``sequential_sampling`` heatmaps, each shaped like ``TSPModel.sample``'s output (what ``test_step`` saves with
     ``--save_numpy_heatmap``); None (default) copies nothing.  ``two_opt_method``: as ``solve_tsp``.  ``merge_method``:
     ``"loop"`` (default) merges instance by instance (``decode.merge_tours``), ``"batched"`` merges the chunk in one library
-    call (``decode.merge_tours_batch``): the same tours and counters.  ``local_search``: as ``solve_tsp``, per instance."""
+    call (``decode.merge_tours_batch``): the same tours and counters.  ``local_search``: as ``solve_tsp``, per instance.
+    ``local_search_kicks``, ``local_search_kick_size``, ``local_search_kick_span``: as ``solve_tsp``; every one of the P copies of
+    an instance is its own tour, keyed by the instance's seed, so an instance gets what its solo call gets."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
+    kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
-                               merge_method, local_search)
+                               merge_method, local_search, kicks, kick_size, kick_span)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -272,7 +298,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         ns = np.zeros(G, dtype=np.int64)
-        ls_stats = {}
+        ls_stats, kick_stats = {}, {}
+        # the Philox keys of the chunk's instances, resolved the way sample_batch resolves them
+        keys = [_kick_key(v) for v in ([model.seed] * G if seeds is None else seeds_c)]
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
@@ -301,6 +329,12 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             elif local_search == "multi2opt":
                 solved, ns = batched_multi_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt" and kicks > 0:
+                solved, ls_stats = batched_iterated_search_grouped(
+                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
+                    device=dev, kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats)
+                ns = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt":
                 solved, ls_stats = batched_multi_local_search_grouped(
                     np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations, device=dev)
@@ -322,6 +356,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             elif local_search == "multi2opt+oropt":
                 info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+                if kicks > 0:
+                    info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
             elif local_search != "2opt":
                 info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             results.append((sol[best].tolist(), costs[best], costs, info))
@@ -332,7 +368,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
                     instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop",
-                    local_search="2opt") -> List[tuple]:
+                    local_search="2opt", kicks=0, kick_size=TSP_KICK_SIZE, kick_span=TSP_KICK_SPAN) -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
     check_local_search(local_search, two_opt_method)
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
@@ -376,7 +412,8 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         its = np.zeros(G, dtype=np.int64)
-        ls_stats = {}
+        ls_stats, kick_stats = {}, {}
+        keys = [_kick_key(v) for v in ([model.seed] * G if seeds is None else seeds_c)]
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
             heats = model.sample_batch(pts_rep, ei_rep, seeds=seeds_c, generators=gens_c,
@@ -405,6 +442,12 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             elif local_search == "multi2opt":
                 solved, its = batched_multi_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt" and kicks > 0:
+                solved, ls_stats = batched_iterated_search_ragged(
+                    np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
+                    kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats)
+                its = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt":
                 solved, ls_stats = batched_multi_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                                      max_iterations=two_opt_iterations, device=dev)
@@ -426,6 +469,8 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             elif local_search == "multi2opt+oropt":
                 info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+                if kicks > 0:
+                    info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
             elif local_search != "2opt":
                 info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
             results.append((sol[best].tolist(), costs[best], costs, info))

@@ -669,6 +669,54 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
                                           size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
                                           int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream);
 
+/* Iterated multi-move local search: seeded segment kicks between descents (additive to ABI 13; not in the reference): the
+ * arrays, conventions and limits of difusco_tsp_multi_local_search_ragged, plus kicks >= 0, kick_size in 1 .. 64, span >= 1 and
+ * tour_seeds / tour_offsets: DEVICE uint64 [T], T = the tours of the call in tour order (group after group): the Philox key and
+ * the first Philox offset of every tour (the types of difusco_step_args' instance table).  Every TOUR runs on its own, with its
+ * own kick counter, incumbent and counters; nothing a tour does depends on what shares the call.
+ *   1. First descent.  The incumbent I is the search of difusco_tsp_multi_local_search_ragged on the input tour with
+ *      max_iterations, max_rounds and select_rounds.  The caps are per descent.
+ *   2. Kick t = 0 .. kicks-1, drawn from I.  Lc = min(span, (n-1)/2) (integer division; >= 1 since n >= 4).  Draw
+ *      c = 0 .. kick_size-1 takes the words w0, w1, w2 of Philox4x32-10 with key seed, counter (c, offset + t) - the offset
+ *      modulo 2^64 - and sets, in unsigned 32-bit arithmetic, l1 = 1 + w1 % Lc, l2 = 1 + w2 % Lc, a = 1 + w0 % (n - l1 - l2),
+ *      b = a + l1 + l2; so 1 <= a and b <= n: positions 0 and n never move.  Draw c is KEPT iff [a, b) intersects the range of no
+ *      kept draw with a lower c, decided in rising c (adjacent ranges do not intersect).  Every kept draw swaps its two adjacent
+ *      segments: C[a .. b) = I[a+l1 .. b) ++ I[a .. a+l1), the local double bridge; C = I elsewhere.  The ranges are disjoint and
+ *      are read from I, so the order does not matter.
+ *   3. Descent of C as in step 1, with fresh caps and round counter.
+ *   4. Keep.  len(X) = sum of d_k over the positions k = 0 .. n-1 of the closed tour, d_k = |P_k P_k+1| as above (the
+ *      coordinates of position k minus those of position k+1, two products, one sum, one square root), in ONE association:
+ *      s_r = the sum of d_r, d_r+1024, d_r+2048, .. in rising k starting from 0.0, r = 0 .. 1023 (0.0 where r >= n); then for
+ *      h = 512, 256, .. 1: s_r = s_r + s_r+h for r < h; len = s_0.  I <- C iff len(C) <= len(I) (a plateau result is kept).
+ *      len(I) is computed once, when I changes.
+ *   5. The output tour is I after the last kick.
+ * So: the result is a permutation closed on tour[0]; its len is never above that of the kicks = 0 result under the same caps;
+ * the same (seed, offset) gives a tour the same result in a solo, a grouped and a ragged call; different seeds give different
+ * kicks.  kicks = 0 returns what difusco_tsp_multi_local_search_ragged returns, tours and counters alike.  With
+ * max_iterations = 0 no descent moves a tour and the call is the keeps and kicks alone.
+ * Outputs.  The five HOST arrays [groups] of difusco_tsp_multi_local_search_ragged: a tour's sweeps and moves are summed over
+ * all its descents and then combined over the group's tours as there (maxima of the sweeps, sums of the moves); rounds_out is
+ * the maximum over the group's tours and their descents of the rounds a descent started.  HOST arrays [T] per tour: kicks_kept_out
+ * (int32; kicks whose descent ended not longer than the incumbent), kicks_improved_out (int32; strictly shorter),
+ * segments_swapped_out (int64; kept draws over all kicks), first_length_out and final_length_out (float64; len of the first
+ * descent's result and of the output tour).
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_multi_local_search_ragged, a null new array, kicks < 0,
+ * kick_size outside 1 .. 64 and span < 1; a refused call leaves `tours` untouched.  The kick loop runs on the device behind the
+ * phase word of the descent: the host enqueues launch sequences (the three launches of a sweep and the keep / kick step) and
+ * polls the counter of stopped groups every 8.  Blocks until every group is done.
+ * difusco_tsp_search_host_syncs: the host synchronisations of the calling thread's last difusco_tsp_iterated_search_ragged
+ * call. */
+int difusco_tsp_iterated_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                       int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                       int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                       void* workspace, size_t workspace_bytes, int64_t* two_opt_sweeps_out,
+                                       int64_t* or_opt_sweeps_out, int32_t* rounds_out, int64_t* two_opt_moves_out,
+                                       int64_t* or_opt_moves_out, int32_t* kicks_kept_out, int32_t* kicks_improved_out,
+                                       int64_t* segments_swapped_out, double* first_length_out, double* final_length_out,
+                                       void* stream);
+int difusco_tsp_search_host_syncs(void);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
