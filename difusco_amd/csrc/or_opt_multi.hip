@@ -21,6 +21,8 @@
 //   mls_keep_kick_kernel  one block of 1024 threads per tour whose descent has just ended: the length of the tour in one fixed
 //                         association, the comparison with the tour's incumbent, the copy one way or the other, and either the
 //                         next seeded kick (segment swaps read from the incumbent) with a reset of the descent state, or the end.
+// The focused search (difusco_tsp_focused_search_ragged) launches the first two as they are and three of its own
+// (or_opt_focused.h, included behind the kernels here): after a kick a tour's sweeps evaluate only candidates next to a marked edge.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -521,6 +523,8 @@ void mls_iter_layout(const MlLayout& lay, int groups, const int32_t* group_n, co
 }  // namespace
 }  // namespace difusco
 
+#include "or_opt_focused.h"   // the focused search: the kernels and the layout behind the ones above
+
 extern "C" {
 
 int difusco_tsp_multi_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
@@ -745,6 +749,160 @@ int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const
     segments_swapped_out[b] = its[b].swapped;
     first_length_out[b] = its[b].first_length;
     final_length_out[b] = its[b].length;
+  }
+  return DIFUSCO_OK;
+}
+
+int difusco_tsp_focused_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                      size_t* bytes) {
+  using namespace difusco;
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged_workspace_bytes: bytes is null");
+  MlLayout lay;
+  const int rc = mls_layout("tsp_focused_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
+  if (rc != DIFUSCO_OK) return rc;
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  MlFocusLayout fl;
+  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
+  *bytes = fl.total;
+  return DIFUSCO_OK;
+}
+
+int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                      int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                      int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                      int32_t compact_select_max, void* workspace, size_t workspace_bytes,
+                                      int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out,
+                                      int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int32_t* kicks_kept_out,
+                                      int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
+                                      double* final_length_out, int32_t* closing_sweeps_out, void* stream) {
+  using namespace difusco;
+  g_host_syncs = 0;
+  MlLayout lay;
+  std::vector<MlTour> tab;
+  std::vector<MlGroup> gtab;
+  const int rc = mls_layout("tsp_focused_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
+      !or_opt_moves_out || max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: needs non-null device arrays, the five host output arrays "
+                                     "[groups] and max_iterations >= 0");
+  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
+      !final_length_out || !closing_sweeps_out)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: needs the device arrays tour_seeds / tour_offsets and the six "
+                                     "host output arrays [tours]");
+  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
+  if (select_rounds < 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
+  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: kicks = %d < 0", (int)kicks);
+  if (kick_size < 1 || kick_size > kMaxKickSize)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
+  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: span = %d < 1", (int)span);
+  if (compact_select_max < 0 || compact_select_max > kCompactMax)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: compact_select_max = %d, needs 0 .. %d", (int)compact_select_max,
+                     kCompactMax);
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  MlFocusLayout fl;
+  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
+  if (workspace_bytes < fl.total)
+    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: workspace %zu < %zu bytes", workspace_bytes, fl.total);
+  char* w = (char*)workspace;
+  MlTour* desc = (MlTour*)(w + lay.desc);
+  double2* tp = (double2*)(w + lay.tp);
+  double* dlen = (double*)(w + lay.dlen);
+  double* rowv = (double*)(w + lay.rowv);
+  int* rowj = (int*)(w + lay.rowj);
+  int* live = (int*)(w + lay.live);
+  int* winners = (int*)(w + lay.winners);
+  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
+  int* tabi = (int*)(w + lay.tabi);
+  int2* marks = (int2*)(w + lay.marks);
+  int2* cum = (int2*)(w + lay.cum);
+  MlGroup* grp = (MlGroup*)(w + lay.grp);
+  MlTourState* ts = (MlTourState*)(w + lay.ts);
+  MlState* st = (MlState*)(w + lay.st);
+  int* inc = (int*)(w + il.inc);
+  MlIter* iters = (MlIter*)(w + il.iters);
+  int* smark = (int*)(w + fl.smark);
+  int* tmark = (int*)(w + fl.tmark);
+  int* arows = (int*)(w + fl.arows);
+  int* acols = (int*)(w + fl.acols);
+  MlFocus* foc = (MlFocus*)(w + fl.foc);
+  MlTourState* full = (MlTourState*)(w + fl.full);
+  hipStream_t s = (hipStream_t)stream;
+  const int T = lay.tours;
+  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
+  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
+  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
+  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
+  if (er == hipSuccess) er = hipMemsetAsync(foc, 0, sizeof(MlFocus) * T, s);    // every tour starts in its first, full descent
+  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(full, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search_ragged setup: %s", hipGetErrorString(er));
+  // the bound per descent of the iterated search; a tour runs its first descent, one per kick and the closing one
+  const long long ends = 2LL * max_rounds;
+  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
+  const long long limit = per > INT64_MAX / ((long long)kicks + 2) ? INT64_MAX : per * ((long long)kicks + 2);
+  MlState host{0, 0};
+  const int poll = 8;
+  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
+  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
+  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
+  for (long long it = 0; it < limit; ++it) {
+    if (!no_descent) {
+      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
+      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, full);
+      hipLaunchKernelGGL(mls_focused_row_best_kernel, focus_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts, foc, arows,
+                         acols, marks, split);
+      hipLaunchKernelGGL(mls_select_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
+                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, (int)compact_select_max, st,
+                         grp, ts, full, foc, smark, tmark, arows, acols);
+    }
+    hipLaunchKernelGGL(mls_keep_kick_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
+                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark, tmark,
+                       arows, acols);
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      ++g_host_syncs;
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search state: %s", hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  std::vector<MlIter> its(T);
+  std::vector<MlFocus> focs(T);
+  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(focs.data(), foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search_ragged counters: %s", hipGetErrorString(er));
+  for (int g = 0; g < groups; ++g) {
+    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
+    rounds_out[g] = 1;                                           // every descent starts round 1
+  }
+  for (int b = 0; b < T; ++b) {
+    const int g = tab[b].group;
+    const MlTourState& x = states[b];
+    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
+    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
+    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
+    two_opt_moves_out[g] += x.two_opt_moves;
+    or_opt_moves_out[g] += x.or_opt_moves;
+    kicks_kept_out[b] = its[b].kept;
+    kicks_improved_out[b] = its[b].improved;
+    segments_swapped_out[b] = its[b].swapped;
+    first_length_out[b] = its[b].first_length;
+    final_length_out[b] = its[b].length;
+    closing_sweeps_out[b] = focs[b].closing_sweeps;
   }
   return DIFUSCO_OK;
 }

@@ -555,13 +555,32 @@ def check_tsp_kicks(local_search, kicks, kick_size=TSP_KICK_SIZE, span=TSP_KICK_
 TSP_KICK_STATS = ("kicks_kept", "kicks_improved", "segments_swapped", "first_length", "final_length")
 
 
+TSP_DESCENTS = ("full", "focused")
+TSP_COMPACT_SELECT_MAX = 1024             # proposals the focused search selects one per thread (difusco_tsp_focused_search_ragged)
+
+
+def check_tsp_descent(descent, kicks=None):
+    """``descent`` of the iterated search; for ``solve_tsp`` and the runner (``kicks`` given) the focused descents follow
+    kicks, so they need some."""
+    if descent not in TSP_DESCENTS:
+        raise ValueError(f"local_search_descent = {descent!r}: one of {TSP_DESCENTS}")
+    if kicks is not None and descent == "focused" and not kicks > 0:
+        raise ValueError("local_search_descent = 'focused' restricts the descents after the kicks of the multi-move local "
+                         "search: it needs local_search_kicks > 0")
+    return descent
+
+
 def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
-                         stats):
+                         stats, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
     """The checks of the three iterated-search functions (before any library call) and one
-    ``difusco_tsp_iterated_search_ragged`` call.  Returns (int64 tours per group, the stats dict of
-    ``batched_multi_local_search_grouped``); ``stats`` receives the per-tour arrays and ``host_syncs``."""
+    ``difusco_tsp_iterated_search_ragged`` call - ``descent="focused"``: one ``difusco_tsp_focused_search_ragged`` call.
+    Returns (int64 tours per group, the stats dict of ``batched_multi_local_search_grouped``); ``stats`` receives the per-tour
+    arrays and ``host_syncs``."""
     if int(kicks) != kicks or kicks < 0 or kicks >= 2 ** 31:
         raise ValueError(f"kicks = {kicks!r}: an integer >= 0")
+    focused = check_tsp_descent(descent) == "focused"
+    if int(compact_select_max) != compact_select_max or not 0 <= compact_select_max <= TSP_COMPACT_SELECT_MAX:
+        raise ValueError(f"compact_select_max = {compact_select_max!r}: an integer in 0 .. {TSP_COMPACT_SELECT_MAX}")
     _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
     device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
     T = sum(t.shape[0] for t in trs)
@@ -577,8 +596,8 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
     group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
     L = _lib.lib()
     nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_iterated_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
-                                                                    ctypes.byref(nbytes)))
+    size_fn = L.difusco_tsp_focused_search_ragged_workspace_bytes if focused else L.difusco_tsp_iterated_search_ragged_workspace_bytes
+    _lib.check(size_fn(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.byref(nbytes)))
     d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
     d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
@@ -588,13 +607,19 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
     per = {"kicks_kept": np.zeros(T, dtype=np.int32), "kicks_improved": np.zeros(T, dtype=np.int32),
            "segments_swapped": np.zeros(T, dtype=np.int64), "first_length": np.zeros(T, dtype=np.float64),
            "final_length": np.zeros(T, dtype=np.float64)}
-    _lib.check(L.difusco_tsp_iterated_search_ragged(
-        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
-        int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
-        ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
-        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_KICK_STATS),
-        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    head = (G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
+            int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
+            ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()))
+    tail = (ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+            out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
+            out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_KICK_STATS))
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    if focused:
+        per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
+        _lib.check(L.difusco_tsp_focused_search_ragged(*head, int(compact_select_max), *tail, per["closing_sweeps"].ctypes.data,
+                                                       stream))
+    else:
+        _lib.check(L.difusco_tsp_iterated_search_ragged(*head, *tail, stream))
     if stats is not None:
         stats.update(per, host_syncs=int(L.difusco_tsp_search_host_syncs()))
     flat = d_tours.cpu().numpy().astype(np.int64)
@@ -603,7 +628,8 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
 
 
 def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
-                                  kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None):
+                                  kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None,
+                                  descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
     """``batched_multi_local_search_torch`` iterated with seeded segment kicks (the rule: ``difusco_tsp_iterated_search_ragged``,
     include/difusco_hip.h; GPU only; not in the reference): after its descent every tour, ``kicks`` times, swaps up to
     ``kick_size`` disjoint pairs of adjacent random segments of at most ``span`` cities each, descends again (the caps are per
@@ -611,15 +637,20 @@ def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cud
     tour (default 0; kick t draws at ``offsets[b] + t``); a tour gets the same answer alone or in any call.  ``kicks=0`` is
     ``batched_multi_local_search_torch``.  Returns ``(tour int64 numpy [B, N+1], stats)`` as that function (sweeps and moves
     summed over a tour's descents, ``rounds`` the most rounds of a descent); ``stats`` (a dict) receives the per-tour numpy
-    arrays [B] ``kicks_kept``, ``kicks_improved``, ``segments_swapped``, ``first_length``, ``final_length`` and ``host_syncs``."""
+    arrays [B] ``kicks_kept``, ``kicks_improved``, ``segments_swapped``, ``first_length``, ``final_length`` and ``host_syncs``.
+    ``descent="focused"`` (the rule: ``difusco_tsp_focused_search_ragged``): a descent after a kick evaluates only the candidates
+    next to an edge that the kick or a move since has touched, and one full descent closes the call; ``stats`` gains
+    ``closing_sweeps`` [B], the sweeps in which that descent still moved (0: the focused descents missed nothing).
+    ``compact_select_max`` (0 .. 1024) changes the cost of a focused sweep's selection alone, never its result."""
     pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
     out, st = _iterated_search_run("batched_iterated_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                   kicks, kick_size, span, seeds, offsets, stats)
+                                   kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
     return out[0], {k: int(v[0]) for k, v in st.items()}
 
 
 def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
-                                    kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None):
+                                    kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None,
+                                    descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
     """``batched_iterated_search_torch`` of G instances at once, the arguments of ``batched_multi_local_search_grouped``;
     ``seeds`` / ``offsets`` [G * P] in the order of ``tours``.  Every tour gets what its own call returns.  Returns ``(tours int64
     numpy [G * P, N + 1], stats)``; the entries of the returned stats are numpy arrays [G], the per-tour arrays [G * P]."""
@@ -633,20 +664,20 @@ def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="
     pts_l = [np.ascontiguousarray(p) for p in pts]
     trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
     out, st = _iterated_search_run("batched_iterated_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds,
-                                   device, kicks, kick_size, span, seeds, offsets, stats)
+                                   device, kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
     return np.concatenate(out, axis=0), st
 
 
 def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
                                    select_rounds=4, kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None,
-                                   offsets=None, stats=None):
+                                   offsets=None, stats=None, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
     """``batched_iterated_search_torch`` of G instances of ANY sizes at once, the arguments of
     ``batched_multi_local_search_ragged``; ``seeds`` / ``offsets``: one per tour, group after group.  Returns ``(list of int64
     numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_iterated_search_grouped``."""
     pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
     trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
     return _iterated_search_run("batched_iterated_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                kicks, kick_size, span, seeds, offsets, stats)
+                                kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
 
 
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):

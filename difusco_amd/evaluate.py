@@ -36,7 +36,10 @@ the order of ``all_costs``, the header ``mis_local_search``; refused with ``--ta
 ``--tsp_local_search_kick_size K`` / ``--tsp_local_search_kick_span S`` (N > 0 only with ``--local_search multi2opt+oropt``: that
 search iterated with N seeded segment kicks, ``decode.batched_iterated_search_grouped``, every tour keyed by its instance seed;
 the records gain ``kicks_improved``, one count per copy in the order of the last round, and the three settings, the header
-the three settings), ``--merge_method {loop,batched}``
+the three settings), ``--tsp_local_search_descent {full,focused}`` (focused only with ``--tsp_local_search_kicks N`` > 0: the
+descents after the kicks evaluate only the candidates next to a touched edge and one full descent closes the search,
+``descent="focused"`` of ``decode.batched_iterated_search_grouped``, keyed as the kicks are; only when it is ``focused`` the
+records gain the setting and ``closing_sweeps``, one count per copy, and the header the setting), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -122,6 +125,10 @@ EXTENSION_ARGS = [
                                             "(needs --local_search multi2opt+oropt; 0: one descent)")),
     ("--tsp_local_search_kick_size", dict(type=int, default=TSP_KICK_SIZE, help="TSP: segment swaps drawn per kick (1 .. 64)")),
     ("--tsp_local_search_kick_span", dict(type=int, default=TSP_KICK_SPAN, help="TSP: longest segment of a swap, in cities")),
+    ("--tsp_local_search_descent", dict(type=str, default="full", choices=("full", "focused"),
+                                         help="TSP: the descents after the kicks: full (every pair of the tour) or focused (only "
+                                              "the candidates next to an edge a kick or a move touched, and one full descent at "
+                                              "the end; needs --tsp_local_search_kicks N > 0)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -181,6 +188,9 @@ def parse_args(argv=None):
                      "--local_search multi2opt+oropt")
     if args.tsp_local_search_kicks > 0 and args.task != "tsp":
         parser.error(f"--tsp_local_search_kicks {args.tsp_local_search_kicks} refines TSP tours: not with --task {args.task}")
+    if args.tsp_local_search_descent == "focused" and not args.tsp_local_search_kicks > 0:
+        parser.error("--tsp_local_search_descent focused restricts the descents after the kicks of the multi-move local search: "
+                     "pass --tsp_local_search_kicks N > 0")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -301,6 +311,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
             rec[k] = int(info[k])
     if "local_search_kicks_improved" in info:      # --tsp_local_search_kicks N > 0
         rec["kicks_improved"] = [int(v) for v in info["local_search_kicks_improved"]]
+    if "local_search_closing_sweeps" in info:      # --tsp_local_search_descent focused
+        rec["closing_sweeps"] = [int(v) for v in info["local_search_closing_sweeps"]]
     return rec
 
 
@@ -340,7 +352,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt",
                 mis_local_search: str = "none", mis_local_search_kicks: int = 0,
                 mis_local_search_kick_size: int = 4, tsp_local_search_kicks: int = 0,
-                tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN) -> List[dict]:
+                tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
+                tsp_local_search_descent: str = "full") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -363,13 +376,16 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   merge_method=merge_method, local_search=local_search,
                                   **(dict(local_search_kicks=tsp_local_search_kicks,
                                           local_search_kick_size=tsp_local_search_kick_size,
-                                          local_search_kick_span=tsp_local_search_kick_span) if tsp_local_search_kicks > 0 else {}))
+                                          local_search_kick_span=tsp_local_search_kick_span) if tsp_local_search_kicks > 0 else {}),
+                                  **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if tsp_local_search_kicks > 0:
                     records[-1].update(tsp_local_search_kicks=tsp_local_search_kicks,
                                        tsp_local_search_kick_size=tsp_local_search_kick_size,
                                        tsp_local_search_kick_span=tsp_local_search_kick_span)
+                if tsp_local_search_descent == "focused":
+                    records[-1].update(tsp_local_search_descent="focused")
                 if heats is not None:
                     save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
         else:
@@ -448,7 +464,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                mis_local_search_kick_size=args.mis_local_search_kick_size,
                                tsp_local_search_kicks=args.tsp_local_search_kicks,
                                tsp_local_search_kick_size=args.tsp_local_search_kick_size,
-                               tsp_local_search_kick_span=args.tsp_local_search_kick_span)
+                               tsp_local_search_kick_span=args.tsp_local_search_kick_span,
+                               tsp_local_search_descent=args.tsp_local_search_descent)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -479,6 +496,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["tsp_local_search_kicks"] = args.tsp_local_search_kicks
                 line["tsp_local_search_kick_size"] = args.tsp_local_search_kick_size
                 line["tsp_local_search_kick_span"] = args.tsp_local_search_kick_span
+            if args.tsp_local_search_descent == "focused":
+                line["tsp_local_search_descent"] = "focused"
             if args.mis_local_search_kicks > 0:
                 line["mis_local_search_kicks"] = args.mis_local_search_kicks
                 line["mis_local_search_kick_size"] = args.mis_local_search_kick_size

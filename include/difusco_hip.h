@@ -717,6 +717,52 @@ int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const
                                        void* stream);
 int difusco_tsp_search_host_syncs(void);
 
+/* Iterated multi-move local search with FOCUSED descents after the kicks (additive to ABI 13; not in the reference): the
+ * arrays, conventions, limits and rule of difusco_tsp_iterated_search_ragged except for the points below.  Every TOUR runs on
+ * its own.
+ *   First descent.  The full search of difusco_tsp_multi_local_search_ragged, exactly as there.
+ *   Marks.  A tour keeps two sets of CITIES, S (current) and T (touched since the kick).  Position k = 0 .. n-1 of the tour is
+ *     ACTIVE iff tour[k] and tour[k+1] are both in S: the edge k -> k+1 is suspect.
+ *   After kick t.  T is set to the cities that C holds at positions a-1, a, a+l2-1, a+l2, b-1 and b of every kept draw: the six
+ *     end cities of the three edges a kept draw creates.
+ *   Descent after a kick.  The rounds, phases, caps and stop tests of difusco_tsp_multi_local_search_ragged (max_iterations and
+ *     max_rounds per descent, select_rounds as there).  Each phase begins with S := T.  A sweep evaluates only these candidates:
+ *       2-opt   (i, j) iff position i or position j is active;
+ *       Or-opt  (v, i, j) iff row i is ROW-ACTIVE - one of the positions i .. i+3, clipped to n-1, is active - or position j is
+ *               active.
+ *     Within the evaluated candidates everything is that comment's, bit for bit: the changes and deltas, the row's lowest value
+ *     with ties to the lowest j (or the lowest v, then j), the threshold -1e-6, the key (value, i), the ranges, the selection
+ *     and the apply.  A row without an evaluated candidate does not propose.
+ *   Marks after a sweep, with the tour as it was before the apply.  S := the cities at the ends of the removed edges of EVERY
+ *     proposal of the sweep, winner or not - 2-opt: positions i, i+1, j, j+1; Or-opt: i, i+1, i+L, i+L+1, j, j+1.  T := T + the
+ *     same cities of the winners only.
+ *   Closing descent, only when kicks > 0 and max_iterations > 0.  After the keep of the last kick one FULL descent of the
+ *     incumbent follows, with fresh caps.  Its result replaces the incumbent iff its len is not larger (the keep rule and the
+ *     len of step 4 there); it counts in neither kicks_kept_out nor kicks_improved_out.  The output is the incumbent after that.
+ * So: the output is a permutation closed on tour[0]; its len is never above first_length_out; where no cap binds it has no
+ * improving 2-opt or Or-opt move left; the same (seed, offset) gives a tour the same result in a solo, a grouped and a ragged
+ * call; kicks = 0 returns what difusco_tsp_multi_local_search_ragged returns, tours and counters alike.
+ * compact_select_max, 0 .. 1024: a sweep of a focused descent with at most this many proposals is selected by one thread per
+ * proposal, every proposal against all (step 2 of the multi-move 2-opt read literally, O(m^2 / 1024) per round); a sweep with
+ * more, and every sweep with 0, by the selection of the full descents.  The winners are the same: the argument changes the cost
+ * alone.  closing_sweeps_out: HOST int32 [T], the sweeps in which the tour's closing descent moved it; 0: the focused descents
+ * missed nothing.  The other outputs are those of difusco_tsp_iterated_search_ragged; the group counters sum all descents, the
+ * closing one included.
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_iterated_search_ragged, compact_select_max out of range
+ * and a null closing_sweeps_out; a refused call leaves `tours` untouched.  The host enqueues launch sequences (five launches:
+ * the three of a sweep, the focused row-best and the keep / kick step) and polls the counter of stopped groups every 8; at most
+ * (the bound of a descent) x (kicks + 2) sequences.  Blocks until every group is done.  difusco_tsp_search_host_syncs also
+ * reports this call. */
+int difusco_tsp_focused_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                      int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                      int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                      int32_t compact_select_max, void* workspace, size_t workspace_bytes,
+                                      int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out,
+                                      int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int32_t* kicks_kept_out,
+                                      int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
+                                      double* final_length_out, int32_t* closing_sweeps_out, void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
