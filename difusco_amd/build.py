@@ -22,6 +22,7 @@ SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip"
 PROF_SOURCES = SOURCES + ["edge_layer_abl.hip", "stage_lab.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "edge_layer_common.h"), os.path.join(CSRC, "edge_layer_kernel.h"),
            os.path.join(CSRC, "two_opt_common.h"), os.path.join(CSRC, "multi_move_common.h"), os.path.join(CSRC, "or_opt_focused.h"),
+           os.path.join(CSRC, "or_opt_heat.h"),
            os.path.join(os.path.dirname(PKG), "include", "difusco_hip.h")]
 
 

@@ -367,13 +367,14 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_focused_kernel(
 
 // mls_keep_kick_kernel for the focused search.  After a kick: T := the cities the kicked tour holds at a-1, a, a+l2-1, a+l2, b-1
 // and b of every kept draw, S := T, the lists of the first 2-opt sweep, and the tour is focused.  After the keep of the last
-// kick (kicks > 0): the closing full descent of the incumbent starts; at its keep the tour is done.
+// kick (kicks > 0): the closing full descent of the incumbent starts; at its keep the tour is done.  kHeat: as there.
+template <bool kHeat>
 __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
     const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const MlTour* __restrict__ desc,
     const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets, int kicks, int kick_size,
     int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters, MlTourState* full, MlFocus* foc,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, int* __restrict__ smark_all, int* __restrict__ tmark_all,
-    int* __restrict__ arows_all, int* __restrict__ acols_all) {
+    int* __restrict__ arows_all, int* __restrict__ acols_all, HeatArgs<kHeat> hx) {
   const int t = blockIdx.x;
   if (ts[t].phase != kKeep) return;                              // written by thread 0 of this block at its end only
   const MlTour d = desc[t];
@@ -398,6 +399,11 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
   const bool close_next = !closing && !more && kicks > 0 && !no_descent;
   int nkept = 0;
   if (more) {
+    if constexpr (kHeat) {
+      __syncthreads();                                           // the copy above is complete
+      const MlHeatTour h = hx.tab[t];
+      heat_prefix(inc, n, hx.row_ptr + h.rows, hx.col + h.edges, hx.q + h.heat, hx.W + d.closed, (unsigned long long*)part);
+    }
     if (threadIdx.x < 64) {
       const int c = threadIdx.x;
       const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
@@ -407,7 +413,10 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
         Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
         l1 = 1 + (int)(w[1] % lc);
         const int l2 = 1 + (int)(w[2] % lc);
-        a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
+        if constexpr (kHeat)
+          a = heat_pick(hx.W + d.closed, n - l1 - l2, w[0], w[3]);
+        else
+          a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
         b = a + l1 + l2;
         keep = 1;
       }

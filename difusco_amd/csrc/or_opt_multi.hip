@@ -23,6 +23,8 @@
 //                         next seeded kick (segment swaps read from the incumbent) with a reset of the descent state, or the end.
 // The focused search (difusco_tsp_focused_search_ragged) launches the first two as they are and three of its own
 // (or_opt_focused.h, included behind the kernels here): after a kick a tour's sweeps evaluate only candidates next to a marked edge.
+// The guided search (difusco_tsp_guided_search_ragged) is either of the two with the keep / kick kernel's `kHeat` instantiation:
+// the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -333,6 +335,14 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_iterated_kernel(
 constexpr int kMaxKickSize = 64;           // the draws of a kick: one wave decides which are kept
 constexpr int kLenParts = kSelectThreads;  // strided partial sums of a tour length
 
+}  // namespace
+}  // namespace difusco
+
+#include "or_opt_heat.h"      // the heat-biased draws of the guided search
+
+namespace difusco {
+namespace {
+
 struct MlIter {            // device-resident state of a tour of the iterated search, zero at the start of a call
   int kick, have;          // kicks drawn so far; the tour has an incumbent
   int kept, improved;      // kicks whose descent ended not longer / strictly shorter than the incumbent
@@ -365,10 +375,12 @@ __device__ __forceinline__ double tour_length(const double* __restrict__ points,
 // against the incumbent I (`inc`, n + 1 entries of the tour's own); I <- C if it is not longer (or there is no incumbent yet),
 // else C <- I.  Kick, if kicks remain: the draws of kick t, the disjointness filter in rising c by wave 0, the kept draws swap
 // their two adjacent segments in C reading I - a wave per draw -, and the descent state is reset.  Else the tour is done; C = I.
+// kHeat: `a` of a draw comes from the running weights of I (heat_prefix, heat_pick), computed behind the keep copy.
+template <bool kHeat>
 __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
     const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const MlTour* __restrict__ desc,
     const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets, int kicks, int kick_size,
-    int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters) {
+    int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters, HeatArgs<kHeat> hx) {
   const int t = blockIdx.x;
   if (ts[t].phase != kKeep) return;                              // written by thread 0 of this block at its end only
   const MlTour d = desc[t];
@@ -389,6 +401,11 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
   const bool more = kick < kicks;
   int nkept = 0;
   if (more) {
+    if constexpr (kHeat) {
+      __syncthreads();                                           // the copy above is complete
+      const MlHeatTour h = hx.tab[t];
+      heat_prefix(inc, n, hx.row_ptr + h.rows, hx.col + h.edges, hx.q + h.heat, hx.W + d.closed, (unsigned long long*)part);
+    }
     if (threadIdx.x < 64) {
       const int c = threadIdx.x;
       const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
@@ -398,7 +415,10 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
         Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
         l1 = 1 + (int)(w[1] % lc);
         const int l2 = 1 + (int)(w[2] % lc);
-        a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
+        if constexpr (kHeat)
+          a = heat_pick(hx.W + d.closed, n - l1 - l2, w[0], w[3]);
+        else
+          a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
         b = a + l1 + l2;
         keep = 1;
       }
@@ -716,8 +736,8 @@ int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const
       hipLaunchKernelGGL(mls_select_iterated_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
                          tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
     }
-    hipLaunchKernelGGL(mls_keep_kick_kernel, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
-                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters);
+    hipLaunchKernelGGL(mls_keep_kick_kernel<false>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
+                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, HeatArgs<false>{});
     if ((it + 1) % poll == 0 || it + 1 == limit) {
       er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
       if (er == hipSuccess) er = hipStreamSynchronize(s);
@@ -866,9 +886,9 @@ int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const 
                          tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, (int)compact_select_max, st,
                          grp, ts, full, foc, smark, tmark, arows, acols);
     }
-    hipLaunchKernelGGL(mls_keep_kick_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
-                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark, tmark,
-                       arows, acols);
+    hipLaunchKernelGGL(mls_keep_kick_focused_kernel<false>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds,
+                       offsets, (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark,
+                       tmark, arows, acols, HeatArgs<false>{});
     if ((it + 1) % poll == 0 || it + 1 == limit) {
       er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
       if (er == hipSuccess) er = hipStreamSynchronize(s);
@@ -903,6 +923,228 @@ int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const 
     first_length_out[b] = its[b].first_length;
     final_length_out[b] = its[b].length;
     closing_sweeps_out[b] = focs[b].closing_sweeps;
+  }
+  return DIFUSCO_OK;
+}
+
+int difusco_tsp_guided_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                     const int32_t* group_edges, size_t* bytes) {
+  using namespace difusco;
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: bytes is null");
+  MlLayout lay;
+  const int rc = mls_layout("tsp_guided_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!group_edges) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: group_edges is null");
+  for (int g = 0; g < groups; ++g)
+    if (group_edges[g] < 0)
+      return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: group %d has %d edges", g, (int)group_edges[g]);
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  MlFocusLayout fl;
+  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);   // one size for both descents
+  MlHeatLayout hl;
+  mls_heat_layout(fl.total, lay.tours, groups, group_n, group_tours, group_edges, &hl);
+  *bytes = hl.total;
+  return DIFUSCO_OK;
+}
+
+// the launch sequences of difusco_tsp_iterated_search_ragged (descent 0) or difusco_tsp_focused_search_ragged (descent 1) with the
+// kHeat keep / kick kernel; the graph check rides in front of the setup synchronisation, so the host polls are theirs
+int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                     int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                     int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                     int32_t compact_select_max, int32_t descent, const int32_t* group_edges,
+                                     const int32_t* row_ptr, const int32_t* col, const float* heat, void* workspace,
+                                     size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
+                                     int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out,
+                                     int32_t* kicks_kept_out, int32_t* kicks_improved_out, int64_t* segments_swapped_out,
+                                     double* first_length_out, double* final_length_out, int32_t* closing_sweeps_out,
+                                     void* stream) {
+  using namespace difusco;
+  g_host_syncs = 0;
+  MlLayout lay;
+  std::vector<MlTour> tab;
+  std::vector<MlGroup> gtab;
+  const int rc = mls_layout("tsp_guided_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (descent != 0 && descent != 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: descent = %d, needs 0 (full) or 1 (focused)", (int)descent);
+  const bool focused = descent == 1;
+  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
+      !or_opt_moves_out || max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs non-null device arrays, the five host output arrays "
+                                     "[groups] and max_iterations >= 0");
+  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
+      !final_length_out || (focused && !closing_sweeps_out))
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs the device arrays tour_seeds / tour_offsets and the host "
+                                     "output arrays [tours] (closing_sweeps_out when the descent is focused)");
+  if (!group_edges || !row_ptr || !col || !heat)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs group_edges and the device arrays row_ptr / col / heat");
+  for (int g = 0; g < groups; ++g)
+    if (group_edges[g] < 0)
+      return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: group %d has %d edges", g, (int)group_edges[g]);
+  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
+  if (select_rounds < 1)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
+  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: kicks = %d < 0", (int)kicks);
+  if (kick_size < 1 || kick_size > kMaxKickSize)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
+  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: span = %d < 1", (int)span);
+  if (focused && (compact_select_max < 0 || compact_select_max > kCompactMax))
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: compact_select_max = %d, needs 0 .. %d", (int)compact_select_max,
+                     kCompactMax);
+  MlIterLayout il;
+  mls_iter_layout(lay, groups, group_n, group_tours, &il);
+  MlFocusLayout fl;
+  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
+  MlHeatLayout hl;
+  mls_heat_layout(fl.total, lay.tours, groups, group_n, group_tours, group_edges, &hl);
+  if (workspace_bytes < hl.total)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: workspace %zu < %zu bytes", workspace_bytes, hl.total);
+  // the graph tables: a group's first row_ptr / col entry, a tour's first heat entry
+  std::vector<MlHeatTour> htab;
+  std::vector<MlHeatGroup> hgrp;
+  int emax = 0;
+  {
+    long long rows = 0, edges = 0, cells = 0;
+    for (int g = 0; g < groups; ++g) {
+      hgrp.push_back(MlHeatGroup{group_n[g], group_edges[g], rows, edges});
+      for (int p = 0; p < group_tours[g]; ++p) {
+        htab.push_back(MlHeatTour{rows, edges, cells, group_n[g], group_edges[g]});
+        cells += group_edges[g];
+      }
+      rows += (long long)group_n[g] + 1;
+      edges += group_edges[g];
+      emax = group_edges[g] > emax ? group_edges[g] : emax;
+    }
+  }
+  char* w = (char*)workspace;
+  MlTour* desc = (MlTour*)(w + lay.desc);
+  double2* tp = (double2*)(w + lay.tp);
+  double* dlen = (double*)(w + lay.dlen);
+  double* rowv = (double*)(w + lay.rowv);
+  int* rowj = (int*)(w + lay.rowj);
+  int* live = (int*)(w + lay.live);
+  int* winners = (int*)(w + lay.winners);
+  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
+  int* tabi = (int*)(w + lay.tabi);
+  int2* marks = (int2*)(w + lay.marks);
+  int2* cum = (int2*)(w + lay.cum);
+  MlGroup* grp = (MlGroup*)(w + lay.grp);
+  MlTourState* ts = (MlTourState*)(w + lay.ts);
+  MlState* st = (MlState*)(w + lay.st);
+  int* inc = (int*)(w + il.inc);
+  MlIter* iters = (MlIter*)(w + il.iters);
+  int* smark = (int*)(w + fl.smark);
+  int* tmark = (int*)(w + fl.tmark);
+  int* arows = (int*)(w + fl.arows);
+  int* acols = (int*)(w + fl.acols);
+  MlFocus* foc = (MlFocus*)(w + fl.foc);
+  MlTourState* full = (MlTourState*)(w + fl.full);
+  MlHeatTour* d_htab = (MlHeatTour*)(w + hl.tab);
+  MlHeatGroup* d_hgrp = (MlHeatGroup*)(w + hl.groups);
+  int* d_bad = (int*)(w + hl.bad);
+  unsigned short* qtab = (unsigned short*)(w + hl.q);
+  HeatArgs<true> hx{row_ptr, col, qtab, d_htab, (unsigned long long*)(w + hl.W)};
+  hipStream_t s = (hipStream_t)stream;
+  const int T = lay.tours;
+  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
+  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
+  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
+  int bad = 0;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(d_htab, htab.data(), sizeof(MlHeatTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(d_hgrp, hgrp.data(), sizeof(MlHeatGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(d_bad, 0, sizeof(int), s);
+  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
+  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
+  if (er == hipSuccess) er = hipMemsetAsync(foc, 0, sizeof(MlFocus) * T, s);    // every tour starts in its first, full descent
+  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(full, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) {
+    const long long longest = (long long)lay.nmax + 1 > emax ? (long long)lay.nmax + 1 : emax;
+    hipLaunchKernelGGL(heat_graph_check_kernel, dim3((unsigned)((longest + 255) / 256), groups), dim3(256), 0, s, row_ptr, col,
+                       d_hgrp, d_bad);
+    er = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
+  }
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search_ragged setup: %s", hipGetErrorString(er));
+  if (bad)
+    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: a group's graph is not a CSR over its cities (row_ptr[0] = 0, "
+                                     "row_ptr rising to row_ptr[n] = edges, 0 <= col < n)");
+  if (emax > 0)                                                  // the q table of every tour, once per call, in stream order
+    hipLaunchKernelGGL(heat_table_kernel, dim3((unsigned)(((long long)emax + 255) / 256), T), dim3(256), 0, s, row_ptr, col, heat,
+                       d_htab, qtab);
+  // the bounds of the two entries: a tour runs its first descent, one per kick and, focused, the closing one
+  const long long ends = 2LL * max_rounds;
+  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
+  const long long descents = (long long)kicks + (focused ? 2 : 1);
+  const long long limit = per > INT64_MAX / descents ? INT64_MAX : per * descents;
+  MlState host{0, 0};
+  const int poll = 8;
+  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
+  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
+  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
+  for (long long it = 0; it < limit; ++it) {
+    if (!no_descent && focused) {
+      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
+      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, full);
+      hipLaunchKernelGGL(mls_focused_row_best_kernel, focus_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts, foc, arows,
+                         acols, marks, split);
+      hipLaunchKernelGGL(mls_select_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
+                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, (int)compact_select_max, st,
+                         grp, ts, full, foc, smark, tmark, arows, acols);
+    } else if (!no_descent) {
+      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
+      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
+      hipLaunchKernelGGL(mls_select_iterated_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
+                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
+    }
+    if (focused)
+      hipLaunchKernelGGL(mls_keep_kick_focused_kernel<true>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds,
+                         offsets, (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark,
+                         tmark, arows, acols, hx);
+    else
+      hipLaunchKernelGGL(mls_keep_kick_kernel<true>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
+                         (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, hx);
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      ++g_host_syncs;
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search state: %s", hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  std::vector<MlIter> its(T);
+  std::vector<MlFocus> focs(T);
+  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(focs.data(), foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search_ragged counters: %s", hipGetErrorString(er));
+  for (int g = 0; g < groups; ++g) {
+    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
+    rounds_out[g] = 1;                                           // every descent starts round 1
+  }
+  for (int b = 0; b < T; ++b) {
+    const int g = tab[b].group;
+    const MlTourState& x = states[b];
+    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
+    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
+    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
+    two_opt_moves_out[g] += x.two_opt_moves;
+    or_opt_moves_out[g] += x.or_opt_moves;
+    kicks_kept_out[b] = its[b].kept;
+    kicks_improved_out[b] = its[b].improved;
+    segments_swapped_out[b] = its[b].swapped;
+    first_length_out[b] = its[b].first_length;
+    final_length_out[b] = its[b].length;
+    if (closing_sweeps_out) closing_sweeps_out[b] = focused ? focs[b].closing_sweeps : 0;
   }
   return DIFUSCO_OK;
 }

@@ -570,19 +570,96 @@ def check_tsp_descent(descent, kicks=None):
     return descent
 
 
+TSP_KICK_BIASES = ("uniform", "heat")
+
+
+def check_tsp_kick_bias(kick_bias, kicks=None):
+    """``kick_bias`` of the iterated search; for ``solve_tsp`` and the runner (``kicks`` given) the bias is one of the kicks, so
+    it needs some."""
+    if kick_bias not in TSP_KICK_BIASES:
+        raise ValueError(f"local_search_kick_bias = {kick_bias!r}: one of {TSP_KICK_BIASES}")
+    if kicks is not None and kick_bias == "heat" and not kicks > 0:
+        raise ValueError("local_search_kick_bias = 'heat' draws the kicks of the multi-move local search from the heatmap: it "
+                         "needs local_search_kicks > 0")
+    return kick_bias
+
+
+def _heat_graph(who, pts, trs, heat, edge_index, device):
+    """The candidate graphs and heat of a guided call, on the device: per group ``heat[g]`` ([P_g, E_g] with ``edge_index[g]``
+    [2, E_g]; [P_g, n_g, n_g] with ``edge_index=None``: the complete graph, entry (i, j) at i n + j as ``merge_tours`` lists it),
+    numpy arrays or tensors (a device tensor never visits the host).  Edges that are not sorted by row are sorted (stable), the
+    heat alike.  Returns (group_edges int32 numpy [G], row_ptr int32, col int32, heat float32 device tensors).  Every shape is
+    checked here, before any library call."""
+    G = len(pts)
+    heat = list(heat)
+    if len(heat) != G:
+        raise ValueError(f"{who}: {len(heat)} heat arrays for {G} groups")
+    dense = edge_index is None
+    if not dense:
+        edge_index = list(edge_index)
+        if len(edge_index) != G or any(e is None for e in edge_index):
+            raise ValueError(f"{who}: sparse heat needs one edge_index [2, E] per group ({G}); dense heat takes edge_index=None")
+    rps, cols, hs, ne = [], [], [], []
+    for g in range(G):
+        n, P = pts[g].shape[0], trs[g].shape[0]
+        h = _dev(heat[g], torch.float32, device)
+        if dense:
+            if h.numel() != P * n * n:
+                raise ValueError(f"{who}: heat[{g}] holds {h.numel()} values, a dense heatmap of {P} tours has [{P}, {n}, {n}]")
+            if n * n >= 2 ** 31:
+                raise ValueError(f"{who}: a dense heatmap of n = {n} has more than 2^31 - 1 edges")
+            idx = torch.arange(n, dtype=torch.int32, device=device)
+            rp, cl, E = torch.arange(0, n * n + 1, n, dtype=torch.int32, device=device), idx.repeat(n), n * n
+        else:
+            ei = _dev(edge_index[g], torch.int64, device)
+            if ei.ndim != 2 or ei.shape[0] != 2:
+                raise ValueError(f"{who}: edge_index[{g}] must be [2, E], got {list(ei.shape)}")
+            E = int(ei.shape[1])
+            if h.numel() != P * E:
+                raise ValueError(f"{who}: heat[{g}] holds {h.numel()} values for {P} tours of {E} edges")
+            if E >= 2 ** 31:
+                raise ValueError(f"{who}: edge_index[{g}] has more than 2^31 - 1 edges")
+            row, cl = ei[0], ei[1]
+            h = h.reshape(P, E)
+            if E > 0:
+                if int(row.min()) < 0 or int(row.max()) >= n or int(cl.min()) < 0 or int(cl.max()) >= n:
+                    raise ValueError(f"{who}: edge_index[{g}] names a city outside 0 .. {n - 1}")
+                if not bool((row[1:] >= row[:-1]).all()):
+                    order = torch.sort(row, stable=True).indices
+                    row, cl, h = row[order], cl[order], h[:, order]
+            counts = torch.bincount(row, minlength=n)
+            rp = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(counts, 0)]).to(torch.int32)
+            cl = cl.to(torch.int32)
+        rps.append(rp)
+        cols.append(cl)
+        hs.append(h.reshape(-1))
+        ne.append(E)
+    pad = lambda t, dt: t if t.numel() else torch.zeros(1, dtype=dt, device=device)      # never a null pointer
+    return (np.array(ne, dtype=np.int32), torch.cat(rps).contiguous(), pad(torch.cat(cols).contiguous(), torch.int32),
+            pad(torch.cat(hs).contiguous(), torch.float32))
+
+
 def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
-                         stats, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
+                         stats, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX, kick_bias="uniform", heat=None,
+                         edge_index=None):
     """The checks of the three iterated-search functions (before any library call) and one
-    ``difusco_tsp_iterated_search_ragged`` call - ``descent="focused"``: one ``difusco_tsp_focused_search_ragged`` call.
+    ``difusco_tsp_iterated_search_ragged`` call - ``descent="focused"``: one ``difusco_tsp_focused_search_ragged`` call;
+    ``kick_bias="heat"``: one ``difusco_tsp_guided_search_ragged`` call, either descent.
     Returns (int64 tours per group, the stats dict of ``batched_multi_local_search_grouped``); ``stats`` receives the per-tour
     arrays and ``host_syncs``."""
     if int(kicks) != kicks or kicks < 0 or kicks >= 2 ** 31:
         raise ValueError(f"kicks = {kicks!r}: an integer >= 0")
     focused = check_tsp_descent(descent) == "focused"
+    guided = check_tsp_kick_bias(kick_bias) == "heat"
+    if guided and heat is None:
+        raise ValueError(f"{who}: kick_bias='heat' needs heat= (and edge_index= unless the heat is dense)")
+    if not guided and (heat is not None or edge_index is not None):
+        raise ValueError(f"{who}: heat= / edge_index= are read only with kick_bias='heat'")
     if int(compact_select_max) != compact_select_max or not 0 <= compact_select_max <= TSP_COMPACT_SELECT_MAX:
         raise ValueError(f"compact_select_max = {compact_select_max!r}: an integer in 0 .. {TSP_COMPACT_SELECT_MAX}")
     _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
     device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
+    graph = _heat_graph(who, pts, trs, heat, edge_index, device) if guided else None
     T = sum(t.shape[0] for t in trs)
     mask = (1 << 64) - 1
     table = []
@@ -597,7 +674,11 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
     L = _lib.lib()
     nbytes = ctypes.c_size_t()
     size_fn = L.difusco_tsp_focused_search_ragged_workspace_bytes if focused else L.difusco_tsp_iterated_search_ragged_workspace_bytes
-    _lib.check(size_fn(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.byref(nbytes)))
+    if guided:
+        _lib.check(L.difusco_tsp_guided_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
+                                                                      graph[0].ctypes.data, ctypes.byref(nbytes)))
+    else:
+        _lib.check(size_fn(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.byref(nbytes)))
     d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
     d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
@@ -614,7 +695,15 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
             out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
             out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_KICK_STATS))
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    if focused:
+    if guided:
+        group_edges, row_ptr, col, d_heat = graph
+        if focused:
+            per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
+        _lib.check(L.difusco_tsp_guided_search_ragged(
+            *head, int(compact_select_max), int(focused), group_edges.ctypes.data, ctypes.c_void_p(row_ptr.data_ptr()),
+            ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(d_heat.data_ptr()), *tail,
+            per["closing_sweeps"].ctypes.data if focused else None, stream))
+    elif focused:
         per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
         _lib.check(L.difusco_tsp_focused_search_ragged(*head, int(compact_select_max), *tail, per["closing_sweeps"].ctypes.data,
                                                        stream))
@@ -629,7 +718,8 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
 
 def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
                                   kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None,
-                                  descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
+                                  descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX, kick_bias="uniform", heat=None,
+                                  edge_index=None):
     """``batched_multi_local_search_torch`` iterated with seeded segment kicks (the rule: ``difusco_tsp_iterated_search_ragged``,
     include/difusco_hip.h; GPU only; not in the reference): after its descent every tour, ``kicks`` times, swaps up to
     ``kick_size`` disjoint pairs of adjacent random segments of at most ``span`` cities each, descends again (the caps are per
@@ -641,19 +731,30 @@ def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cud
     ``descent="focused"`` (the rule: ``difusco_tsp_focused_search_ragged``): a descent after a kick evaluates only the candidates
     next to an edge that the kick or a move since has touched, and one full descent closes the call; ``stats`` gains
     ``closing_sweeps`` [B], the sweeps in which that descent still moved (0: the focused descents missed nothing).
-    ``compact_select_max`` (0 .. 1024) changes the cost of a focused sweep's selection alone, never its result."""
+    ``compact_select_max`` (0 .. 1024) changes the cost of a focused sweep's selection alone, never its result.
+    ``kick_bias``: ``"uniform"`` (default: the cuts of a kick fall anywhere alike) or ``"heat"`` (the rule:
+    ``difusco_tsp_guided_search_ragged``): the first cut of every draw falls on a tour edge with a probability that rises as the
+    heat of that edge falls, either descent.  It reads ``heat`` and ``edge_index`` in the shapes ``merge_tours`` takes - sparse:
+    ``heat`` [B, E] (or [B * E]), one row per tour, in the edge order of ``edge_index`` [2, E]; dense: ``heat`` [B, N, N] with
+    ``edge_index=None`` -, numpy arrays or device tensors; edges not sorted by their first row are sorted (stable).  An edge
+    absent from the graph counts as heat 0.  ``ValueError`` before any library call: ``"heat"`` without ``heat``, shapes that do
+    not match, ``heat`` with ``"uniform"``, an unknown ``kick_bias``.  Constant heat does not reproduce ``"uniform"``."""
     pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
     out, st = _iterated_search_run("batched_iterated_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                   kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
+                                   kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias,
+                                   None if heat is None else [heat], None if edge_index is None else [edge_index])
     return out[0], {k: int(v[0]) for k, v in st.items()}
 
 
 def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
                                     kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None,
-                                    descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
+                                    descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX, kick_bias="uniform", heat=None,
+                                    edge_index=None):
     """``batched_iterated_search_torch`` of G instances at once, the arguments of ``batched_multi_local_search_grouped``;
     ``seeds`` / ``offsets`` [G * P] in the order of ``tours``.  Every tour gets what its own call returns.  Returns ``(tours int64
-    numpy [G * P, N + 1], stats)``; the entries of the returned stats are numpy arrays [G], the per-tour arrays [G * P]."""
+    numpy [G * P, N + 1], stats)``; the entries of the returned stats are numpy arrays [G], the per-tour arrays [G * P].
+    ``kick_bias="heat"``: ``heat`` and ``edge_index`` are lists with one entry per instance, as ``merge_tours_batch`` takes them
+    (``heat[g]`` [P, E_g] with ``edge_index[g]`` [2, E_g]; [P, N, N] with ``edge_index=None``)."""
     pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
     if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
         raise ValueError("points must be [groups, N, 2]")
@@ -664,20 +765,24 @@ def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="
     pts_l = [np.ascontiguousarray(p) for p in pts]
     trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
     out, st = _iterated_search_run("batched_iterated_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds,
-                                   device, kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
+                                   device, kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias,
+                                   heat, edge_index)
     return np.concatenate(out, axis=0), st
 
 
 def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
                                    select_rounds=4, kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None,
-                                   offsets=None, stats=None, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX):
+                                   offsets=None, stats=None, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX,
+                                   kick_bias="uniform", heat=None, edge_index=None):
     """``batched_iterated_search_torch`` of G instances of ANY sizes at once, the arguments of
     ``batched_multi_local_search_ragged``; ``seeds`` / ``offsets``: one per tour, group after group.  Returns ``(list of int64
-    numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_iterated_search_grouped``."""
+    numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_iterated_search_grouped``.  ``kick_bias``, ``heat``, ``edge_index``:
+    as there."""
     pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
     trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
     return _iterated_search_run("batched_iterated_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max)
+                                kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias, heat,
+                                edge_index)
 
 
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):

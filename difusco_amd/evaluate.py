@@ -39,7 +39,11 @@ the records gain ``kicks_improved``, one count per copy in the order of the last
 the three settings), ``--tsp_local_search_descent {full,focused}`` (focused only with ``--tsp_local_search_kicks N`` > 0: the
 descents after the kicks evaluate only the candidates next to a touched edge and one full descent closes the search,
 ``descent="focused"`` of ``decode.batched_iterated_search_grouped``, keyed as the kicks are; only when it is ``focused`` the
-records gain the setting and ``closing_sweeps``, one count per copy, and the header the setting), ``--merge_method {loop,batched}``
+records gain the setting and ``closing_sweeps``, one count per copy, and the header the setting),
+``--tsp_local_search_kick_bias {uniform,heat}`` (heat only with ``--tsp_local_search_kicks N`` > 0 and ``--task tsp``: the first cut
+of every draw of a kick falls on a tour edge with a probability that rises as the heat of that edge falls,
+``kick_bias="heat"`` of ``decode.batched_iterated_search_grouped`` on each sample's own heatmap; only when it is ``heat`` the
+records and the header gain the setting), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -129,6 +133,10 @@ EXTENSION_ARGS = [
                                          help="TSP: the descents after the kicks: full (every pair of the tour) or focused (only "
                                               "the candidates next to an edge a kick or a move touched, and one full descent at "
                                               "the end; needs --tsp_local_search_kicks N > 0)")),
+    ("--tsp_local_search_kick_bias", dict(type=str, default="uniform", choices=("uniform", "heat"),
+                                           help="TSP: where the first cut of a kick's draws falls: uniform (anywhere alike) or "
+                                                "heat (on a tour edge with a probability that rises as the sampled heat of the "
+                                                "edge falls; needs --tsp_local_search_kicks N > 0)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -191,6 +199,11 @@ def parse_args(argv=None):
     if args.tsp_local_search_descent == "focused" and not args.tsp_local_search_kicks > 0:
         parser.error("--tsp_local_search_descent focused restricts the descents after the kicks of the multi-move local search: "
                      "pass --tsp_local_search_kicks N > 0")
+    if args.tsp_local_search_kick_bias == "heat" and not args.tsp_local_search_kicks > 0:
+        parser.error("--tsp_local_search_kick_bias heat draws the kicks of the multi-move local search from the heatmap: pass "
+                     "--tsp_local_search_kicks N > 0")
+    if args.tsp_local_search_kick_bias == "heat" and args.task != "tsp":
+        parser.error(f"--tsp_local_search_kick_bias heat biases the kicks of TSP tours: not with --task {args.task}")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -353,7 +366,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 mis_local_search: str = "none", mis_local_search_kicks: int = 0,
                 mis_local_search_kick_size: int = 4, tsp_local_search_kicks: int = 0,
                 tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
-                tsp_local_search_descent: str = "full") -> List[dict]:
+                tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -377,7 +390,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   **(dict(local_search_kicks=tsp_local_search_kicks,
                                           local_search_kick_size=tsp_local_search_kick_size,
                                           local_search_kick_span=tsp_local_search_kick_span) if tsp_local_search_kicks > 0 else {}),
-                                  **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}))
+                                  **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
+                                  **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if tsp_local_search_kicks > 0:
@@ -386,6 +400,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                        tsp_local_search_kick_span=tsp_local_search_kick_span)
                 if tsp_local_search_descent == "focused":
                     records[-1].update(tsp_local_search_descent="focused")
+                if tsp_local_search_kick_bias == "heat":
+                    records[-1].update(tsp_local_search_kick_bias="heat")
                 if heats is not None:
                     save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
         else:
@@ -465,7 +481,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_kicks=args.tsp_local_search_kicks,
                                tsp_local_search_kick_size=args.tsp_local_search_kick_size,
                                tsp_local_search_kick_span=args.tsp_local_search_kick_span,
-                               tsp_local_search_descent=args.tsp_local_search_descent)
+                               tsp_local_search_descent=args.tsp_local_search_descent,
+                               tsp_local_search_kick_bias=args.tsp_local_search_kick_bias)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -498,6 +515,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["tsp_local_search_kick_span"] = args.tsp_local_search_kick_span
             if args.tsp_local_search_descent == "focused":
                 line["tsp_local_search_descent"] = "focused"
+            if args.tsp_local_search_kick_bias == "heat":
+                line["tsp_local_search_kick_bias"] = "heat"
             if args.mis_local_search_kicks > 0:
                 line["mis_local_search_kicks"] = args.mis_local_search_kicks
                 line["mis_local_search_kick_size"] = args.mis_local_search_kick_size

@@ -16,8 +16,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kicks,
-                     check_two_opt_method, batched_local_search_grouped,
+from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
+                     check_tsp_kicks, check_two_opt_method, batched_local_search_grouped,
                      batched_iterated_search_grouped, batched_iterated_search_ragged, batched_iterated_search_torch,
                      batched_local_search_ragged, batched_local_search_torch, batched_multi_local_search_grouped,
                      batched_multi_local_search_ragged, batched_multi_local_search_torch, batched_multi_two_opt_grouped,
@@ -44,7 +44,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               generator: Optional[torch.Generator] = None, timings: Optional[Dict[str, float]] = None,
               sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact",
               local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
-              local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full"):
+              local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
+              local_search_kick_bias: str = "uniform"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -66,11 +67,16 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     plain search.  ``local_search_descent``: "full" (default) or "focused" (only with ``local_search_kicks`` > 0, else
     ``ValueError``): the descents after the kicks evaluate only the candidates next to a touched edge and one full descent
     closes the search (``descent="focused"`` of ``decode.batched_iterated_search_torch``); info gains
-    ``local_search_closing_sweeps`` of the last round (a list, one per copy)."""
+    ``local_search_closing_sweeps`` of the last round (a list, one per copy).  ``local_search_kick_bias``: "uniform" (default)
+    or "heat" (only with ``local_search_kicks`` > 0, else ``ValueError``): the first cut of every draw of a kick falls on a tour
+    edge with a probability that rises as the heat of that edge falls (``kick_bias="heat"`` of
+    ``decode.batched_iterated_search_torch``); copy p reads its own heatmap of its sequential round, the tensor the merge
+    received, still on the device; info gains ``local_search_kick_bias`` ("heat"; the uniform records stay as they were)."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
+    kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -113,7 +119,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
             solved, ls_stats = batched_iterated_search_torch(
                 np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
                 kick_size=kick_size, span=kick_span, seeds=[_kick_key(model.seed)] * parallel_sampling,
-                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats, descent=descent)
+                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats, descent=descent,
+                **(dict(kick_bias="heat", heat=heat, edge_index=edge_index) if kick_bias == "heat" else {}))
             ns = ls_stats["two_opt_sweeps"]
         elif local_search == "multi2opt+oropt":
             solved, ls_stats = batched_multi_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
@@ -136,6 +143,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
                     or_opt_moves=ls_stats["or_opt_moves"], local_search_rounds=ls_stats["rounds"])
         if kicks > 0:
             info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"]])
+            if kick_bias == "heat":
+                info.update(local_search_kick_bias="heat")
             if descent == "focused":
                 info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"]])
     elif local_search != "2opt":
@@ -249,7 +258,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     heatmaps: Optional[list] = None, *, two_opt_method: str = "exact",
                     merge_method: str = "loop", local_search: str = "2opt", local_search_kicks: int = 0,
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
-                    local_search_descent: str = "full") -> List[tuple]:
+                    local_search_descent: str = "full", local_search_kick_bias: str = "uniform") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -265,16 +274,18 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     call (``decode.merge_tours_batch``): the same tours and counters.  ``local_search``: as ``solve_tsp``, per instance.
     ``local_search_kicks``, ``local_search_kick_size``, ``local_search_kick_span``: as ``solve_tsp``; every one of the P copies of
     an instance is its own tour, keyed by the instance's seed, so an instance gets what its solo call gets.
-    ``local_search_descent``: as ``solve_tsp``."""
+    ``local_search_descent``, ``local_search_kick_bias``: as ``solve_tsp``; "heat" passes every instance's own heatmaps of the
+    round (the tensors the merge received, on the device) and its own graph."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
+    kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
-                               merge_method, local_search, kicks, kick_size, kick_span, descent)
+                               merge_method, local_search, kicks, kick_size, kick_span, descent, kick_bias)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -342,7 +353,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                 solved, ls_stats = batched_iterated_search_grouped(
                     np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
                     device=dev, kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent)
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent,
+                    **(dict(kick_bias="heat", heat=heats, edge_index=eis if sparse else None) if kick_bias == "heat" else {}))
                 ns = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt":
                 solved, ls_stats = batched_multi_local_search_grouped(
@@ -367,6 +379,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
                 if kicks > 0:
                     info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
+                    if kick_bias == "heat":
+                        info.update(local_search_kick_bias="heat")
                     if descent == "focused":
                         info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"][g * P:(g + 1) * P]])
             elif local_search != "2opt":
@@ -380,7 +394,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
                     instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop",
                     local_search="2opt", kicks=0, kick_size=TSP_KICK_SIZE, kick_span=TSP_KICK_SPAN,
-                    descent="full") -> List[tuple]:
+                    descent="full", kick_bias="uniform") -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
     check_local_search(local_search, two_opt_method)
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
@@ -458,7 +472,8 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
                 solved, ls_stats = batched_iterated_search_ragged(
                     np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
                     kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent)
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent,
+                    **(dict(kick_bias="heat", heat=heats, edge_index=eis if sparse else None) if kick_bias == "heat" else {}))
                 its = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt":
                 solved, ls_stats = batched_multi_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
@@ -483,6 +498,8 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
                 if kicks > 0:
                     info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
+                    if kick_bias == "heat":
+                        info.update(local_search_kick_bias="heat")
                     if descent == "focused":
                         info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"][g * P:(g + 1) * P]])
             elif local_search != "2opt":

@@ -763,6 +763,54 @@ int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const 
                                       int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
                                       double* final_length_out, int32_t* closing_sweeps_out, void* stream);
 
+/* Iterated multi-move local search with HEAT-BIASED kicks (additive to ABI 13; not in the reference): the arrays, conventions,
+ * limits and rule of difusco_tsp_iterated_search_ragged (descent = 0) or of difusco_tsp_focused_search_ragged (descent = 1;
+ * compact_select_max is read only then) except for how draw c of kick t gets `a`.  Every TOUR runs on its own.
+ *   Inputs.  Group g carries a directed candidate graph in CSR over its n_g cities: row_ptr int32 [n_g + 1] and col int32 [E_g],
+ *     E_g = group_edges[g] (HOST [groups]).  Rows may have any degree, 0 included; duplicate (u, v) entries and self edges are
+ *     allowed.  Every tour of the group has one heat float32 [E_g] in that edge order.  DEVICE arrays: row_ptr, the groups'
+ *     arrays one after the other (sum of n_g + 1 entries); col (sum of E_g); heat (sum of P_g E_g), tour after tour in the
+ *     call's tour order.
+ *   Quantised heat.  q(e) = (uint32) rint(clamp(heat_e, 0, 1) * 65535.0f): the product in float32, rint to nearest even, the
+ *     clamp fminf(fmaxf(h, 0.0f), 1.0f), so a NaN counts as 0.  q(u, v) = the largest q(e) over the entries e of row u with
+ *     col[e] == v, 0 if there is none.
+ *   Weights, from the incumbent I when kick t is drawn.  Position k = 0 .. n-1 has w_k = 65536 - max(q(I[k], I[k+1]),
+ *     q(I[k+1], I[k])), an integer in 1 .. 65536: no position is ever impossible.  W_0 = 0, W_k+1 = W_k + w_k, in uint64.
+ *   Draw c.  The words w0 .. w3 of the same Philox call (key seed, counter (c, offset + t)); l1 and l2 from w1 and w2 as there;
+ *     M = n - l1 - l2; r = ((uint64) w0 << 32 | w3) mod W_M; p the position with W_p <= r < W_p+1; a = p + 1, so 1 <= a <= M,
+ *     the range of the uniform rule.  A cut falls after position p with a probability that rises as the heat of the tour edge
+ *     there falls.
+ *   Everything else - the kept-draw filter, the segment swap, the marks of a focused descent (they follow from a, l1, l2), the
+ *     descents, the keep rule, the counters and outputs - is unchanged.
+ * So: the output is a permutation closed on tour[0], never longer than first_length_out; the same (seed, offset, heat) gives a
+ * tour the same result in a solo, a grouped and a ragged call; kicks = 0 returns what difusco_tsp_multi_local_search_ragged
+ * returns, whatever the heat.  Constant heat is NOT the uniform rule: it takes r mod W_M where that one takes w0 mod M, so the
+ * two entries above and this one give different tours on the same seed.
+ * closing_sweeps_out may be null when descent = 0 (where it is given it receives zeros).  The workspace size does not depend
+ * on descent.  DIFUSCO_EINVAL before any GPU work on the conditions of the entry it extends, a null group_edges / row_ptr /
+ * col / heat, group_edges[g] < 0 and descent outside {0, 1}.  Before the search starts one small kernel checks every group's
+ * row_ptr (row_ptr[0] = 0, rising, row_ptr[n_g] = E_g) and col (0 <= col < n_g) on the device; its flag comes back with the
+ * setup synchronisation, and a bad graph is DIFUSCO_EINVAL instead of a read out of bounds.  A refused call leaves `tours`
+ * untouched.  The launch sequences, grid sizes and host polls are those of the entry it extends, with the heat instantiation
+ * of the keep / kick kernel: behind the keep copy the tour's block computes w_k (two row scans per position) and W in n + 1
+ * uint64 words of the workspace, and one lane per draw searches W_0 .. W_M.  Behind the check one more kernel writes q by
+ * (tour, entry) once per call, 16 bits each in the workspace (hence group_edges in _workspace_bytes), with duplicates resolved:
+ * the first entry of a pair (u, v) in row u holds q(u, v), so a row scan ends at its first match - a few reads where rows list
+ * near cities first, as k-NN rows do.  That pass costs E_g x (degree) reads per tour and call.  difusco_tsp_search_host_syncs
+ * also reports this call. */
+int difusco_tsp_guided_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                     const int32_t* group_edges, size_t* bytes);
+int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                     int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                     int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                     int32_t compact_select_max, int32_t descent, const int32_t* group_edges,
+                                     const int32_t* row_ptr, const int32_t* col, const float* heat, void* workspace,
+                                     size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
+                                     int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out,
+                                     int32_t* kicks_kept_out, int32_t* kicks_improved_out, int64_t* segments_swapped_out,
+                                     double* first_length_out, double* final_length_out, int32_t* closing_sweeps_out,
+                                     void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
