@@ -1,6 +1,8 @@
 // The focused search (difusco_tsp_focused_search_ragged): the iterated search of or_opt_multi.hip whose descents after a kick
 // evaluate only candidates next to a marked edge.  Included by or_opt_multi.hip behind its kernels, whose types and device
-// functions it uses; the rule is stated in include/difusco_hip.h and restated in numpy in tests/tsp_focused_search_emulation.py.
+// functions it uses (the kick itself is kick_draws / kick_swaps there), and in front of its host side, which lays out the focus
+// state and launches the kernels here (mls_layout, mls_run); the rule is stated in include/difusco_hip.h and restated in numpy in
+// tests/tsp_focused_search_emulation.py.
 //
 // A tour is in one of three modes: kFull (its first descent), kFocused (a descent after a kick) and kClosing (the full descent
 // that closes the call).  A launch sequence is five launches, whatever the modes of the tours:
@@ -404,36 +406,10 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
       const MlHeatTour h = hx.tab[t];
       heat_prefix(inc, n, hx.row_ptr + h.rows, hx.col + h.edges, hx.q + h.heat, hx.W + d.closed, (unsigned long long*)part);
     }
-    if (threadIdx.x < 64) {
-      const int c = threadIdx.x;
-      const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
-      int a = 0, b = 0, l1 = 0, keep = 0;
-      if (c < kick_size) {
-        uint32_t w[4];
-        Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
-        l1 = 1 + (int)(w[1] % lc);
-        const int l2 = 1 + (int)(w[2] % lc);
-        if constexpr (kHeat)
-          a = heat_pick(hx.W + d.closed, n - l1 - l2, w[0], w[3]);
-        else
-          a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
-        b = a + l1 + l2;
-        keep = 1;
-      }
-      for (int e = 0; e < kick_size; ++e) {                      // lane e's flag is final when e comes up
-        const int ae = __shfl(a, e), be = __shfl(b, e), ke = __shfl(keep, e);
-        if (c > e && ke && a < be && ae < b) keep = 0;
-      }
-      ka[c] = a, kl1[c] = l1, kb[c] = b, kkeep[c] = keep;
-    }
+    if (threadIdx.x < 64) kick_draws<kHeat>(seeds, offsets, t, kick, kick_size, span, n, d.closed, hx, ka, kl1, kb, kkeep);
     for (int c = threadIdx.x; c < n; c += kSelectThreads) tmark[c] = 0;
     __syncthreads();                                             // and the copy above is complete
-    const int lane = threadIdx.x & 63;
-    for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
-      if (!kkeep[c]) continue;
-      const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
-      for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
-    }
+    kick_swaps(tour, inc, kick_size, ka, kl1, kb, kkeep);
     __syncthreads();
     if ((int)threadIdx.x < kick_size && kkeep[threadIdx.x]) {    // 1 <= a, b <= n
       const int a = ka[threadIdx.x], b = kb[threadIdx.x], l2 = b - a - kl1[threadIdx.x];
@@ -477,29 +453,6 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
       report_done(grp + d.group, st);
     }
   }
-}
-
-struct MlFocusLayout {     // byte offsets behind the layout of the iterated search
-  size_t smark, tmark, arows, acols, foc, full, total;
-};
-
-void mls_focus_layout(const MlLayout& lay, const MlIterLayout& il, int groups, const int32_t* group_n, const int32_t* group_tours,
-                      MlFocusLayout* F) {
-  size_t cols = 0;
-  for (int g = 0; g < groups; ++g) cols += (size_t)group_n[g] * (size_t)group_tours[g];
-  size_t off = il.total;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += up256(bytes);
-    return at;
-  };
-  F->smark = take(sizeof(int) * cols);
-  F->tmark = take(sizeof(int) * cols);
-  F->arows = take(sizeof(int) * cols);
-  F->acols = take(sizeof(int) * cols);
-  F->foc = take(sizeof(MlFocus) * (size_t)lay.tours);
-  F->full = take(sizeof(MlTourState) * (size_t)lay.tours);
-  F->total = off;
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // Heat-biased kicks (difusco_tsp_guided_search_ragged): the first cut of every draw of a kick falls on position p of the incumbent
 // with a probability proportional to w_p = 65536 - (the quantised heat of the tour edge at p).  Included by or_opt_multi.hip in
-// front of its keep / kick kernels, which are templates on `kHeat` and call heat_prefix / heat_pick here; the rule is stated in
+// front of its keep / kick kernels: they are templates on `kHeat` and call heat_prefix, their draws (kick_draws) heat_pick,
+// and its host side lays out the tables and launches the two kernels here (mls_layout, mls_run); the rule is stated in
 // include/difusco_hip.h and restated in numpy in tests/tsp_heat_kick_emulation.py.  All of it is integer arithmetic.
 //
 //   heat_graph_check_kernel  once per call, before the search: row_ptr and col of every group are what the row scans rely on;
@@ -144,31 +145,6 @@ __device__ __forceinline__ int heat_pick(const unsigned long long* __restrict__ 
       hi = mid;
   }
   return lo + 1;
-}
-
-struct MlHeatLayout {      // byte offsets behind the layout of the focused search
-  size_t W, q, tab, groups, bad, total;
-};
-
-void mls_heat_layout(size_t base, int tours, int groups, const int32_t* group_n, const int32_t* group_tours,
-                     const int32_t* group_edges, MlHeatLayout* H) {
-  size_t closed = 0, cells = 0;
-  for (int g = 0; g < groups; ++g) {
-    closed += ((size_t)group_n[g] + 1) * (size_t)group_tours[g];
-    cells += (size_t)group_edges[g] * (size_t)group_tours[g];
-  }
-  size_t off = base;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += up256(bytes);
-    return at;
-  };
-  H->W = take(sizeof(unsigned long long) * closed);
-  H->q = take(sizeof(unsigned short) * cells);
-  H->tab = take(sizeof(MlHeatTour) * (size_t)tours);
-  H->groups = take(sizeof(MlHeatGroup) * (size_t)groups);
-  H->bad = take(sizeof(int));
-  H->total = off;
 }
 
 }  // namespace

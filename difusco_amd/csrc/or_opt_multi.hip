@@ -24,7 +24,14 @@
 // The focused search (difusco_tsp_focused_search_ragged) launches the first two as they are and three of its own
 // (or_opt_focused.h, included behind the kernels here): after a kick a tour's sweeps evaluate only candidates next to a marked edge.
 // The guided search (difusco_tsp_guided_search_ragged) is either of the two with the keep / kick kernel's `kHeat` instantiation:
-// the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).
+// the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).  Both keep / kick kernels draw and apply a
+// kick with kick_draws and kick_swaps here.
+//
+// The host side of all four entries is at the end of this file, once: mls_layout describes the workspace - the sections of the
+// descent and, as the entry needs them, the iterated state, the focus state and the heat tables - and builds the host tables,
+// MlPtrs holds the sections as typed pointers, and mls_run(MlCall) checks the arguments, sets the state up, enqueues launch
+// sequences under their bound, polls, reads the state back and reduces it to the outputs.  The entries fill an MlCall: its mode
+// (one descent, iterated, iterated with focused descents), whether the kicks are drawn by heat, the arguments and the outputs.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -338,7 +345,8 @@ constexpr int kLenParts = kSelectThreads;  // strided partial sums of a tour len
 }  // namespace
 }  // namespace difusco
 
-#include "or_opt_heat.h"      // the heat-biased draws of the guided search
+#include "or_opt_heat.h"      // the heat-biased draws of the guided search: its kernels stand here, between the select and the
+                              // keep / kick kernels
 
 namespace difusco {
 namespace {
@@ -369,6 +377,46 @@ __device__ __forceinline__ double tour_length(const double* __restrict__ points,
   const double len = part[0];
   __syncthreads();
   return len;
+}
+
+// Wave 0: the draws of kick `kick` of tour t, one lane per draw c < kick_size - two segment lengths l1, l2 of at most `span`
+// cities and the first cut a (kHeat: by the running weights of the incumbent, heat_pick), so that the draw swaps [a, a + l1) and
+// [a + l1, b), b = a + l1 + l2 - and the disjointness filter in rising c: a draw is kept unless it meets a kept draw before it.
+template <bool kHeat>
+__device__ __forceinline__ void kick_draws(const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets,
+                                           int t, int kick, int kick_size, int span, int n, long long closed, HeatArgs<kHeat> hx,
+                                           int* ka, int* kl1, int* kb, int* kkeep) {
+  const int c = threadIdx.x;
+  const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
+  int a = 0, b = 0, l1 = 0, keep = 0;
+  if (c < kick_size) {
+    uint32_t w[4];
+    Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
+    l1 = 1 + (int)(w[1] % lc);
+    const int l2 = 1 + (int)(w[2] % lc);
+    if constexpr (kHeat)
+      a = heat_pick(hx.W + closed, n - l1 - l2, w[0], w[3]);
+    else
+      a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
+    b = a + l1 + l2;
+    keep = 1;
+  }
+  for (int e = 0; e < kick_size; ++e) {                          // lane e's flag is final when e comes up
+    const int ae = __shfl(a, e), be = __shfl(b, e), ke = __shfl(keep, e);
+    if (c > e && ke && a < be && ae < b) keep = 0;
+  }
+  ka[c] = a, kl1[c] = l1, kb[c] = b, kkeep[c] = keep;
+}
+
+// the kept draws swap their two adjacent segments in `tour` reading the incumbent `inc`, a wave per draw
+__device__ __forceinline__ void kick_swaps(int* __restrict__ tour, const int* __restrict__ inc, int kick_size, const int* ka,
+                                           const int* kl1, const int* kb, const int* kkeep) {
+  const int lane = threadIdx.x & 63;
+  for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
+    if (!kkeep[c]) continue;
+    const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
+    for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
+  }
 }
 
 // One block per tour, a no-op unless the tour's descent has just ended (phase kKeep).  Keep: the length of the descended tour C
@@ -406,35 +454,9 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
       const MlHeatTour h = hx.tab[t];
       heat_prefix(inc, n, hx.row_ptr + h.rows, hx.col + h.edges, hx.q + h.heat, hx.W + d.closed, (unsigned long long*)part);
     }
-    if (threadIdx.x < 64) {
-      const int c = threadIdx.x;
-      const unsigned lc = (unsigned)span < (unsigned)(n - 1) / 2 ? (unsigned)span : (unsigned)(n - 1) / 2;
-      int a = 0, b = 0, l1 = 0, keep = 0;
-      if (c < kick_size) {
-        uint32_t w[4];
-        Philox::run(seeds[t], offsets[t] + (unsigned long long)kick, (uint64_t)c, w);
-        l1 = 1 + (int)(w[1] % lc);
-        const int l2 = 1 + (int)(w[2] % lc);
-        if constexpr (kHeat)
-          a = heat_pick(hx.W + d.closed, n - l1 - l2, w[0], w[3]);
-        else
-          a = 1 + (int)(w[0] % (unsigned)(n - l1 - l2));
-        b = a + l1 + l2;
-        keep = 1;
-      }
-      for (int e = 0; e < kick_size; ++e) {                      // lane e's flag is final when e comes up
-        const int ae = __shfl(a, e), be = __shfl(b, e), ke = __shfl(keep, e);
-        if (c > e && ke && a < be && ae < b) keep = 0;
-      }
-      ka[c] = a, kl1[c] = l1, kb[c] = b, kkeep[c] = keep;
-    }
+    if (threadIdx.x < 64) kick_draws<kHeat>(seeds, offsets, t, kick, kick_size, span, n, d.closed, hx, ka, kl1, kb, kkeep);
     __syncthreads();                                             // and the copy above is complete
-    const int lane = threadIdx.x & 63;
-    for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
-      if (!kkeep[c]) continue;
-      const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
-      for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
-    }
+    kick_swaps(tour, inc, kick_size, ka, kl1, kb, kkeep);
   }
   if (threadIdx.x == 0) {
     if (more)
@@ -463,17 +485,41 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
   }
 }
 
-struct MlLayout {          // byte offsets
-  size_t desc, tp, dlen, rowv, rowj, live, winners, tabv, tabi, marks, cum, grp, ts, st, total;
-  int tours, nmax, nblk_max;
+}  // namespace
+}  // namespace difusco
+
+#include "or_opt_focused.h"   // the focused search: its kernels, which use the types and device functions above
+
+// ---- the host side: one workspace description (mls_layout, MlPtrs) and one driver (mls_run) behind the four entries
+
+namespace difusco {
+namespace {
+
+enum MlPart : unsigned { kIterPart = 1, kFocusPart = 2, kHeatPart = 4 };   // the optional parts of a workspace
+
+struct MlLayout {          // byte offsets; the optional parts follow the descent's in this order, an absent one is empty
+  size_t desc, tp, dlen, rowv, rowj, live, winners, tabv, tabi, marks, cum, grp, ts, st;
+  size_t inc, iters;                             // kIterPart: the incumbents and MlIter
+  size_t smark, tmark, arows, acols, foc, full;  // kFocusPart
+  size_t W, q, htab, hgrp, bad;                  // kHeatPart
+  size_t total;
+  int tours, nmax, nblk_max, emax;               // emax: the most edges of a group
+};
+
+struct MlTables {          // the host tables of a call
+  std::vector<MlTour> tours;
+  std::vector<MlGroup> groups;
+  std::vector<MlHeatTour> heat_tours;            // kHeatPart: a group's first row_ptr / col entry, a tour's first heat entry
+  std::vector<MlHeatGroup> heat_groups;
 };
 
 constexpr int kMaxTours = 65535;                   // a grid dimension; the limits of difusco_tsp_two_opt_ragged
 constexpr int kMaxNodes = 65535 * TI;
 
-// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
-int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, MlLayout* L,
-               std::vector<MlTour>* tab, std::vector<MlGroup>* gtab) {
+// checks the group arrays (group_edges with kHeatPart) and lays out the workspace of a call that needs `parts`; `tabs`
+// (optional) receives the tables
+int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts,
+               const int32_t* group_edges, MlLayout* L, MlTables* tabs) {
   if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
   if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
   long long T = 0;
@@ -485,76 +531,345 @@ int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_
     T += group_tours[g];
     if (T > kMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kMaxTours);
   }
-  size_t points = 0, closed = 0, cols = 0, cells = 0;
-  L->nmax = L->nblk_max = 0;
+  const bool heat = parts & kHeatPart;
+  if (heat && !group_edges) return set_error(DIFUSCO_EINVAL, "%s: group_edges is null", who);
+  for (int g = 0; heat && g < groups; ++g)
+    if (group_edges[g] < 0) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d edges", who, g, (int)group_edges[g]);
+  size_t points = 0, closed = 0, cols = 0, cells = 0, rows = 0, edges = 0, heats = 0;
+  *L = MlLayout{};
   for (int g = 0; g < groups; ++g) {
-    const int n = group_n[g];
+    const int n = group_n[g], E = heat ? group_edges[g] : 0;
     const int nblk_two = (n - 2 + TI - 1) / TI, nblk_or = (n - 1 + TI - 1) / TI;   // rows 0 .. n - 3 and 0 .. n - 2
     L->nmax = n > L->nmax ? n : L->nmax;
     L->nblk_max = nblk_or > L->nblk_max ? nblk_or : L->nblk_max;
-    if (gtab) gtab->push_back(MlGroup{group_tours[g], 0});
+    L->emax = E > L->emax ? E : L->emax;
+    if (tabs) tabs->groups.push_back(MlGroup{group_tours[g], 0});
+    if (tabs && heat) tabs->heat_groups.push_back(MlHeatGroup{n, E, (long long)rows, (long long)edges});
     for (int p = 0; p < group_tours[g]; ++p) {
-      if (tab) tab->push_back(MlTour{n, nblk_two, nblk_or, g, (long long)points, (long long)closed, (long long)cols, (long long)cells});
+      if (tabs)
+        tabs->tours.push_back(MlTour{n, nblk_two, nblk_or, g, (long long)points, (long long)closed, (long long)cols, (long long)cells});
+      if (tabs && heat) tabs->heat_tours.push_back(MlHeatTour{(long long)rows, (long long)edges, (long long)heats, n, E});
       closed += (size_t)n + 1;
       cols += (size_t)n;
       cells += (size_t)table_levels(n) * ((size_t)n + 1);
+      heats += (size_t)E;
     }
     points += 2 * (size_t)n;
+    rows += (size_t)n + 1;
+    edges += (size_t)E;
   }
   L->tours = (int)T;
   size_t off = 0;
-  auto take = [&off](size_t bytes) {
+  auto take = [&off](bool present, size_t bytes) {
     const size_t at = off;
-    off += up256(bytes);
+    if (present) off += up256(bytes);
     return at;
   };
-  L->desc = take(sizeof(MlTour) * T);
-  L->tp = take(sizeof(double2) * closed);
-  L->dlen = take(sizeof(double) * cols);
-  L->rowv = take(sizeof(double) * cols);
-  L->rowj = take(sizeof(int) * cols);
-  L->live = take(sizeof(int) * cols);
-  L->winners = take(sizeof(int) * cols);
-  L->tabv = take(sizeof(unsigned long long) * cells);
-  L->tabi = take(sizeof(int) * cells);
-  L->marks = take(sizeof(int2) * closed);
-  L->cum = take(sizeof(int2) * closed);
-  L->grp = take(sizeof(MlGroup) * groups);
-  L->ts = take(sizeof(MlTourState) * T);                         // ts .. st are cleared by one memset
-  L->st = take(sizeof(MlState));
+  L->desc = take(true, sizeof(MlTour) * T);
+  L->tp = take(true, sizeof(double2) * closed);
+  L->dlen = take(true, sizeof(double) * cols);
+  L->rowv = take(true, sizeof(double) * cols);
+  L->rowj = take(true, sizeof(int) * cols);
+  L->live = take(true, sizeof(int) * cols);
+  L->winners = take(true, sizeof(int) * cols);
+  L->tabv = take(true, sizeof(unsigned long long) * cells);
+  L->tabi = take(true, sizeof(int) * cells);
+  L->marks = take(true, sizeof(int2) * closed);
+  L->cum = take(true, sizeof(int2) * closed);
+  L->grp = take(true, sizeof(MlGroup) * groups);
+  L->ts = take(true, sizeof(MlTourState) * T);
+  L->st = take(true, sizeof(MlState));
+  const bool iter = parts & kIterPart, focus = parts & kFocusPart;
+  L->inc = take(iter, sizeof(int) * closed);
+  L->iters = take(iter, sizeof(MlIter) * T);
+  L->smark = take(focus, sizeof(int) * cols);
+  L->tmark = take(focus, sizeof(int) * cols);
+  L->arows = take(focus, sizeof(int) * cols);
+  L->acols = take(focus, sizeof(int) * cols);
+  L->foc = take(focus, sizeof(MlFocus) * T);
+  L->full = take(focus, sizeof(MlTourState) * T);
+  L->W = take(heat, sizeof(unsigned long long) * closed);
+  L->q = take(heat, sizeof(unsigned short) * heats);
+  L->htab = take(heat, sizeof(MlHeatTour) * T);
+  L->hgrp = take(heat, sizeof(MlHeatGroup) * groups);
+  L->bad = take(heat, sizeof(int));
   L->total = off;
   return DIFUSCO_OK;
 }
 
-struct MlIterLayout {      // byte offsets behind the layout of the descent
-  size_t inc, iters, total;
+// the four `_workspace_bytes` entries
+int mls_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts,
+                        const int32_t* group_edges, size_t* bytes) {
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "%s: bytes is null", who);
+  MlLayout lay;
+  const int rc = mls_layout(who, groups, group_n, group_tours, parts, group_edges, &lay, nullptr);
+  if (rc == DIFUSCO_OK) *bytes = lay.total;
+  return rc;
+}
+
+struct MlPtrs {            // the sections of a workspace; those of a part the layout does not hold are never read
+  MlTour* desc;
+  double2* tp;
+  double *dlen, *rowv;
+  int *rowj, *live, *winners;
+  unsigned long long* tabv;
+  int* tabi;
+  int2 *marks, *cum;
+  MlGroup* grp;
+  MlTourState* ts;
+  MlState* st;
+  int* inc;
+  MlIter* iters;
+  int *smark, *tmark, *arows, *acols;
+  MlFocus* foc;
+  MlTourState* full;
+  unsigned long long* W;
+  unsigned short* q;
+  MlHeatTour* htab;
+  MlHeatGroup* hgrp;
+  int* bad;
+  MlPtrs(void* workspace, const MlLayout& L) {
+    char* w = (char*)workspace;
+    desc = (MlTour*)(w + L.desc), tp = (double2*)(w + L.tp), dlen = (double*)(w + L.dlen), rowv = (double*)(w + L.rowv);
+    rowj = (int*)(w + L.rowj), live = (int*)(w + L.live), winners = (int*)(w + L.winners);
+    tabv = (unsigned long long*)(w + L.tabv), tabi = (int*)(w + L.tabi), marks = (int2*)(w + L.marks), cum = (int2*)(w + L.cum);
+    grp = (MlGroup*)(w + L.grp), ts = (MlTourState*)(w + L.ts), st = (MlState*)(w + L.st);
+    inc = (int*)(w + L.inc), iters = (MlIter*)(w + L.iters);
+    smark = (int*)(w + L.smark), tmark = (int*)(w + L.tmark), arows = (int*)(w + L.arows), acols = (int*)(w + L.acols);
+    foc = (MlFocus*)(w + L.foc), full = (MlTourState*)(w + L.full);
+    W = (unsigned long long*)(w + L.W), q = (unsigned short*)(w + L.q), htab = (MlHeatTour*)(w + L.htab);
+    hgrp = (MlHeatGroup*)(w + L.hgrp), bad = (int*)(w + L.bad);
+  }
 };
 
 thread_local int g_host_syncs = 0;   // host synchronisations of this thread's last iterated call (difusco_tsp_search_host_syncs)
 
-void mls_iter_layout(const MlLayout& lay, int groups, const int32_t* group_n, const int32_t* group_tours, MlIterLayout* I) {
-  size_t closed = 0;
-  for (int g = 0; g < groups; ++g) closed += ((size_t)group_n[g] + 1) * (size_t)group_tours[g];
-  I->inc = lay.total;
-  I->iters = I->inc + up256(sizeof(int) * closed);
-  I->total = I->iters + up256(sizeof(MlIter) * (size_t)lay.tours);
+enum MlMode : int { kPlain = 0, kIterFull = 1, kIterFocused = 2 };   // one descent; descents and kicks; focused descents after kicks
+
+struct MlCall {            // a call of one of the four entries
+  const char* who;         // the entry, in front of every message
+  MlMode mode;
+  bool heat;               // the kicks are drawn by heat (the guided entry)
+  unsigned parts;          // what the entry's workspace holds: the guided entry reserves the focus part for both descents
+  const char* tour_outputs;   // how the entry's refusal names its per-tour output arrays
+  int groups;
+  const int32_t *group_n, *group_tours;
+  const double* points;
+  int32_t* tours;
+  int64_t max_iterations;
+  int max_rounds, select_rounds;
+  int32_t kicks, kick_size, span;                // from here to `heat_values`: the iterated modes
+  const uint64_t *tour_seeds, *tour_offsets;
+  int32_t compact_select_max;                    // kIterFocused
+  const int32_t *group_edges, *row_ptr, *col;    // heat
+  const float* heat_values;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t *two_opt_sweeps_out, *or_opt_sweeps_out;
+  int32_t* rounds_out;
+  int64_t *two_opt_moves_out, *or_opt_moves_out;
+  int32_t *kicks_kept_out, *kicks_improved_out;  // the per-tour outputs: the iterated modes
+  int64_t* segments_swapped_out;
+  double *first_length_out, *final_length_out;
+  int32_t* closing_sweeps_out;                   // kIterFocused; with heat and a full descent optional, written as 0
+  void* stream;
+};
+
+// the keep / kick step of every tour: the kernel of the descent, its instantiation of the draws
+template <bool kHeat>
+void mls_launch_keep_kick(const MlCall& c, const MlPtrs& p, int T, int no_descent, HeatArgs<kHeat> hx) {
+  hipStream_t s = (hipStream_t)c.stream;
+  const unsigned long long* seeds = (const unsigned long long*)c.tour_seeds;
+  const unsigned long long* offsets = (const unsigned long long*)c.tour_offsets;
+  if (c.mode == kIterFocused)
+    hipLaunchKernelGGL(mls_keep_kick_focused_kernel<kHeat>, dim3(T), dim3(kSelectThreads), 0, s, c.points, c.tours, p.inc, p.desc,
+                       seeds, offsets, (int)c.kicks, (int)c.kick_size, (int)c.span, no_descent, p.st, p.grp, p.ts, p.iters, p.full,
+                       p.foc, p.marks, p.cum, p.smark, p.tmark, p.arows, p.acols, hx);
+  else
+    hipLaunchKernelGGL(mls_keep_kick_kernel<kHeat>, dim3(T), dim3(kSelectThreads), 0, s, c.points, c.tours, p.inc, p.desc, seeds,
+                       offsets, (int)c.kicks, (int)c.kick_size, (int)c.span, no_descent, p.st, p.grp, p.ts, p.iters, hx);
+}
+
+// The four entries.  Checks the arguments, sets the device state up, enqueues launch sequences - a sweep of every tour that is
+// still descending and, in the iterated modes, the keep / kick step - until every group has stopped, and reduces the tours'
+// counters to the outputs.
+int mls_run(const MlCall& c) {
+  const bool plain = c.mode == kPlain, focused = c.mode == kIterFocused;
+  const int groups = c.groups;
+  if (!plain) g_host_syncs = 0;
+  MlLayout lay;
+  MlTables tabs;
+  const int rc = mls_layout(c.who, groups, c.group_n, c.group_tours, c.parts, c.group_edges, &lay, &tabs);
+  if (rc != DIFUSCO_OK) return rc;
+  if (!c.points || !c.tours || !c.workspace || !c.two_opt_sweeps_out || !c.or_opt_sweeps_out || !c.rounds_out ||
+      !c.two_opt_moves_out || !c.or_opt_moves_out || c.max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "%s: needs non-null device arrays, the five host output arrays [groups] and "
+                                     "max_iterations >= 0", c.who);
+  if (!plain && (!c.tour_seeds || !c.tour_offsets || !c.kicks_kept_out || !c.kicks_improved_out || !c.segments_swapped_out ||
+                 !c.first_length_out || !c.final_length_out || (focused && !c.closing_sweeps_out)))
+    return set_error(DIFUSCO_EINVAL, "%s: needs the device arrays tour_seeds / tour_offsets and %s", c.who, c.tour_outputs);
+  if (c.max_rounds < 1) return set_error(DIFUSCO_EINVAL, "%s: max_rounds = %d, needs at least 1", c.who, c.max_rounds);
+  if (c.select_rounds < 1) return set_error(DIFUSCO_EINVAL, "%s: select_rounds = %d, needs at least 1", c.who, c.select_rounds);
+  if (!plain) {
+    if (c.kicks < 0) return set_error(DIFUSCO_EINVAL, "%s: kicks = %d < 0", c.who, (int)c.kicks);
+    if (c.kick_size < 1 || c.kick_size > kMaxKickSize)
+      return set_error(DIFUSCO_EINVAL, "%s: kick_size = %d, needs 1 .. %d", c.who, (int)c.kick_size, kMaxKickSize);
+    if (c.span < 1) return set_error(DIFUSCO_EINVAL, "%s: span = %d < 1", c.who, (int)c.span);
+  }
+  if (focused && (c.compact_select_max < 0 || c.compact_select_max > kCompactMax))
+    return set_error(DIFUSCO_EINVAL, "%s: compact_select_max = %d, needs 0 .. %d", c.who, (int)c.compact_select_max, kCompactMax);
+  if (c.workspace_bytes < lay.total)
+    return set_error(DIFUSCO_EINVAL, "%s: workspace %zu < %zu bytes", c.who, c.workspace_bytes, lay.total);
+  for (int g = 0; g < groups; ++g) {
+    c.two_opt_sweeps_out[g] = c.or_opt_sweeps_out[g] = c.two_opt_moves_out[g] = c.or_opt_moves_out[g] = 0;
+    c.rounds_out[g] = 1;                                         // every descent starts round 1
+  }
+  // no sweep may move a tour.  One descent: nothing is applied; the iterated modes: a call of keeps and kicks only
+  const int no_descent = c.max_iterations == 0;
+  if (plain && no_descent) return DIFUSCO_OK;
+  const MlPtrs p(c.workspace, lay);
+  const HeatArgs<true> hx{c.row_ptr, c.col, p.q, p.htab, p.W};
+  hipStream_t s = (hipStream_t)c.stream;
+  const int T = lay.tours;
+  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
+  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
+  int bad = 0;
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(p.desc, tabs.tours.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(p.grp, tabs.groups.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
+  if (plain) {
+    if (er == hipSuccess) er = hipMemsetAsync(p.ts, 0, lay.total - lay.ts, s);   // ts .. st, the end of this workspace
+  } else {
+    if (er == hipSuccess) er = hipMemsetAsync(p.st, 0, sizeof(MlState), s);
+    if (er == hipSuccess) er = hipMemsetAsync(p.iters, 0, sizeof(MlIter) * T, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(p.ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  }
+  if (focused) {                                                 // every tour starts in its first, full descent
+    if (er == hipSuccess) er = hipMemsetAsync(p.foc, 0, sizeof(MlFocus) * T, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(p.full, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
+  }
+  if (c.heat) {              // the graph tables and the check of the graphs, in front of the setup synchronisation
+    if (er == hipSuccess) er = hipMemcpyAsync(p.htab, tabs.heat_tours.data(), sizeof(MlHeatTour) * T, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess)
+      er = hipMemcpyAsync(p.hgrp, tabs.heat_groups.data(), sizeof(MlHeatGroup) * groups, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemsetAsync(p.bad, 0, sizeof(int), s);
+    if (er == hipSuccess) {
+      const long long longest = (long long)lay.nmax + 1 > lay.emax ? (long long)lay.nmax + 1 : lay.emax;
+      hipLaunchKernelGGL(heat_graph_check_kernel, dim3((unsigned)((longest + 255) / 256), groups), dim3(256), 0, s, c.row_ptr, c.col,
+                         p.hgrp, p.bad);
+      er = hipMemcpyAsync(&bad, p.bad, sizeof(int), hipMemcpyDeviceToHost, s);
+    }
+  }
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (!plain) ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s setup: %s", c.who, hipGetErrorString(er));
+  if (bad)
+    return set_error(DIFUSCO_EINVAL, "%s: a group's graph is not a CSR over its cities (row_ptr[0] = 0, row_ptr rising to "
+                                     "row_ptr[n] = edges, 0 <= col < n)", c.who);
+  if (c.heat && lay.emax > 0)                                    // the q table of every tour, once per call, in stream order
+    hipLaunchKernelGGL(heat_table_kernel, dim3((unsigned)(((long long)lay.emax + 255) / 256), T), dim3(256), 0, s, c.row_ptr, c.col,
+                       c.heat_values, p.htab, p.q);
+  // A launch sequence either moves a tour (at most max_iterations per descent), ends one of its phases (two per round) - in the
+  // iterated modes the last of them runs the keep / kick step -, or, with no descent, is one keep / kick step: the bound per
+  // descent.  A tour runs its first descent, one per kick and, focused, the closing one.
+  const long long ends = 2LL * c.max_rounds;
+  const long long per = no_descent ? 1 : (c.max_iterations > INT64_MAX - ends ? INT64_MAX : c.max_iterations + ends);
+  const long long descents = plain ? 1 : (long long)c.kicks + (focused ? 2 : 1);
+  const long long limit = per > INT64_MAX / descents ? INT64_MAX : per * descents;
+  MlState host{0, 0};
+  const int poll = plain ? 4 : 8;
+  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
+  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
+  const long long cap = (long long)c.max_iterations;
+  const auto select_kernel = plain ? mls_select_kernel : mls_select_iterated_kernel;
+  for (long long it = 0; it < limit; ++it) {
+    if (!no_descent) {
+      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, c.points, c.tours, p.desc, p.tp, p.dlen, p.ts);
+      // a focused tour reads kDone in `full`: the full sweep skips it, the focused one takes it
+      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, focused ? p.full : p.ts);
+      if (focused) {
+        hipLaunchKernelGGL(mls_focused_row_best_kernel, focus_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, p.ts,
+                           p.foc, p.arows, p.acols, p.marks, split);
+        hipLaunchKernelGGL(mls_select_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, c.tours, p.desc, p.rowv, p.rowj, p.live,
+                           p.winners, p.tabv, p.tabi, p.marks, p.cum, cap, c.max_rounds, c.select_rounds, (int)c.compact_select_max,
+                           p.st, p.grp, p.ts, p.full, p.foc, p.smark, p.tmark, p.arows, p.acols);
+      } else {
+        hipLaunchKernelGGL(select_kernel, dim3(T), dim3(kSelectThreads), 0, s, c.tours,
+                           p.desc, p.rowv, p.rowj, p.live, p.winners, p.tabv, p.tabi, p.marks, p.cum, cap, c.max_rounds,
+                           c.select_rounds, p.st, p.grp, p.ts);
+      }
+    }
+    if (!plain && c.heat) mls_launch_keep_kick<true>(c, p, T, no_descent, hx);
+    if (!plain && !c.heat) mls_launch_keep_kick<false>(c, p, T, no_descent, HeatArgs<false>{});
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      er = hipMemcpyAsync(&host, p.st, sizeof(host), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      if (!plain) ++g_host_syncs;
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(er));
+      if (host.done >= groups) break;
+    }
+  }
+  std::vector<MlIter> its(plain ? 0 : T);
+  std::vector<MlFocus> focs(focused ? T : 0);
+  er = hipMemcpyAsync(states.data(), p.ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (!plain && er == hipSuccess) er = hipMemcpyAsync(its.data(), p.iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
+  if (focused && er == hipSuccess) er = hipMemcpyAsync(focs.data(), p.foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (!plain) ++g_host_syncs;
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s counters: %s", c.who, hipGetErrorString(er));
+  for (int b = 0; b < T; ++b) {
+    const int g = tabs.tours[b].group;
+    const MlTourState& x = states[b];
+    const int rounds = (plain ? x.round : its[b].max_round) + 1;
+    if (x.two_opt_sweeps > c.two_opt_sweeps_out[g]) c.two_opt_sweeps_out[g] = x.two_opt_sweeps;
+    if (x.or_opt_sweeps > c.or_opt_sweeps_out[g]) c.or_opt_sweeps_out[g] = x.or_opt_sweeps;
+    if (rounds > c.rounds_out[g]) c.rounds_out[g] = rounds;
+    c.two_opt_moves_out[g] += x.two_opt_moves;
+    c.or_opt_moves_out[g] += x.or_opt_moves;
+    if (plain) continue;
+    c.kicks_kept_out[b] = its[b].kept;
+    c.kicks_improved_out[b] = its[b].improved;
+    c.segments_swapped_out[b] = its[b].swapped;
+    c.first_length_out[b] = its[b].first_length;
+    c.final_length_out[b] = its[b].length;
+    if (c.closing_sweeps_out) c.closing_sweeps_out[b] = focused ? focs[b].closing_sweeps : 0;
+  }
+  return DIFUSCO_OK;
+}
+
+// the arguments the three iterated entries share, as they pass them
+int mls_iterated_entry(const char* who, MlMode mode, bool heat, unsigned parts, const char* tour_outputs, int groups,
+                       const int32_t* group_n, const int32_t* group_tours, const double* points, int32_t* tours,
+                       int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks, int32_t kick_size, int32_t span,
+                       const uint64_t* tour_seeds, const uint64_t* tour_offsets, int32_t compact_select_max,
+                       const int32_t* group_edges, const int32_t* row_ptr, const int32_t* col, const float* heat_values,
+                       void* workspace, size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
+                       int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int32_t* kicks_kept_out,
+                       int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
+                       double* final_length_out, int32_t* closing_sweeps_out, void* stream) {
+  MlCall c{};
+  c.who = who, c.mode = mode, c.heat = heat, c.parts = parts, c.tour_outputs = tour_outputs;
+  c.groups = groups, c.group_n = group_n, c.group_tours = group_tours, c.points = points, c.tours = tours;
+  c.max_iterations = max_iterations, c.max_rounds = max_rounds, c.select_rounds = select_rounds;
+  c.kicks = kicks, c.kick_size = kick_size, c.span = span, c.tour_seeds = tour_seeds, c.tour_offsets = tour_offsets;
+  c.compact_select_max = compact_select_max;
+  c.group_edges = group_edges, c.row_ptr = row_ptr, c.col = col, c.heat_values = heat_values;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+  c.two_opt_sweeps_out = two_opt_sweeps_out, c.or_opt_sweeps_out = or_opt_sweeps_out, c.rounds_out = rounds_out;
+  c.two_opt_moves_out = two_opt_moves_out, c.or_opt_moves_out = or_opt_moves_out;
+  c.kicks_kept_out = kicks_kept_out, c.kicks_improved_out = kicks_improved_out, c.segments_swapped_out = segments_swapped_out;
+  c.first_length_out = first_length_out, c.final_length_out = final_length_out, c.closing_sweeps_out = closing_sweeps_out;
+  return mls_run(c);
 }
 
 }  // namespace
 }  // namespace difusco
 
-#include "or_opt_focused.h"   // the focused search: the kernels and the layout behind the ones above
-
 extern "C" {
 
 int difusco_tsp_multi_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
                                                           size_t* bytes) {
-  using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "multi_local_search_ragged_workspace_bytes: bytes is null");
-  MlLayout lay;
-  const int rc = mls_layout("multi_local_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
-  if (rc == DIFUSCO_OK) *bytes = lay.total;
-  return rc;
+  return difusco::mls_workspace_bytes("multi_local_search_ragged_workspace_bytes", groups, group_n, group_tours, 0, nullptr, bytes);
 }
 
 int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
@@ -562,97 +877,37 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
                                           size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
                                           int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream) {
   using namespace difusco;
-  MlLayout lay;
-  std::vector<MlTour> tab;
-  std::vector<MlGroup> gtab;
-  const int rc = mls_layout("tsp_multi_local_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
-  if (rc != DIFUSCO_OK) return rc;
-  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
-      !or_opt_moves_out || max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: needs non-null device arrays, the five host output arrays "
-                                     "[groups] and max_iterations >= 0");
-  if (max_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
-  if (select_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
-  if (workspace_bytes < lay.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_local_search_ragged: workspace %zu < %zu bytes", workspace_bytes, lay.total);
-  for (int g = 0; g < groups; ++g) {
-    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
-    rounds_out[g] = 1;                                           // every tour starts round 1
-  }
-  if (max_iterations == 0) return DIFUSCO_OK;                    // no sweep may move a tour: nothing is applied
-  char* w = (char*)workspace;
-  MlTour* desc = (MlTour*)(w + lay.desc);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  double* rowv = (double*)(w + lay.rowv);
-  int* rowj = (int*)(w + lay.rowj);
-  int* live = (int*)(w + lay.live);
-  int* winners = (int*)(w + lay.winners);
-  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
-  int* tabi = (int*)(w + lay.tabi);
-  int2* marks = (int2*)(w + lay.marks);
-  int2* cum = (int2*)(w + lay.cum);
-  MlGroup* grp = (MlGroup*)(w + lay.grp);
-  MlTourState* ts = (MlTourState*)(w + lay.ts);
-  MlState* st = (MlState*)(w + lay.st);
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(ts, 0, lay.total - lay.ts, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_local_search_ragged setup: %s", hipGetErrorString(er));
-  // a launch sequence either moves a tour (at most max_iterations per tour) or ends one of its phases (two per round)
-  const long long ends = 2LL * max_rounds;
-  const long long limit = max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends;
-  MlState host{0, 0};
-  const int poll = 4;
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
-  for (long long it = 0; it < limit; ++it) {
-    hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
-    hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
-    hipLaunchKernelGGL(mls_select_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners, tabv,
-                       tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "multi_local_search state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  std::vector<MlTourState> states(T);
-  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_local_search_ragged counters: %s", hipGetErrorString(er));
-  for (int b = 0; b < T; ++b) {
-    const int g = tab[b].group;
-    const MlTourState& x = states[b];
-    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
-    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
-    if (x.round + 1 > rounds_out[g]) rounds_out[g] = x.round + 1;
-    two_opt_moves_out[g] += x.two_opt_moves;
-    or_opt_moves_out[g] += x.or_opt_moves;
-  }
-  return DIFUSCO_OK;
+  MlCall c{};
+  c.who = "tsp_multi_local_search_ragged", c.mode = kPlain, c.parts = 0;
+  c.groups = groups, c.group_n = group_n, c.group_tours = group_tours, c.points = points, c.tours = tours;
+  c.max_iterations = max_iterations, c.max_rounds = max_rounds, c.select_rounds = select_rounds;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+  c.two_opt_sweeps_out = two_opt_sweeps_out, c.or_opt_sweeps_out = or_opt_sweeps_out, c.rounds_out = rounds_out;
+  c.two_opt_moves_out = two_opt_moves_out, c.or_opt_moves_out = or_opt_moves_out;
+  return mls_run(c);
 }
 
 int difusco_tsp_iterated_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
                                                        size_t* bytes) {
   using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged_workspace_bytes: bytes is null");
-  MlLayout lay;
-  const int rc = mls_layout("tsp_iterated_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
-  if (rc != DIFUSCO_OK) return rc;
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  *bytes = il.total;
-  return DIFUSCO_OK;
+  return mls_workspace_bytes("tsp_iterated_search_ragged_workspace_bytes", groups, group_n, group_tours, kIterPart, nullptr, bytes);
 }
 
 int difusco_tsp_search_host_syncs(void) { return difusco::g_host_syncs; }
+
+int difusco_tsp_focused_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                      size_t* bytes) {
+  using namespace difusco;
+  return mls_workspace_bytes("tsp_focused_search_ragged_workspace_bytes", groups, group_n, group_tours, kIterPart | kFocusPart,
+                             nullptr, bytes);
+}
+
+int difusco_tsp_guided_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                     const int32_t* group_edges, size_t* bytes) {
+  using namespace difusco;
+  return mls_workspace_bytes("tsp_guided_search_ragged_workspace_bytes", groups, group_n, group_tours,
+                             kIterPart | kFocusPart | kHeatPart, group_edges, bytes);   // one size for both descents
+}
 
 int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
                                        int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
@@ -663,129 +918,11 @@ int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const
                                        int64_t* segments_swapped_out, double* first_length_out, double* final_length_out,
                                        void* stream) {
   using namespace difusco;
-  g_host_syncs = 0;
-  MlLayout lay;
-  std::vector<MlTour> tab;
-  std::vector<MlGroup> gtab;
-  const int rc = mls_layout("tsp_iterated_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
-  if (rc != DIFUSCO_OK) return rc;
-  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
-      !or_opt_moves_out || max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: needs non-null device arrays, the five host output arrays "
-                                     "[groups] and max_iterations >= 0");
-  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
-      !final_length_out)
-    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: needs the device arrays tour_seeds / tour_offsets and the five "
-                                     "host output arrays [tours]");
-  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
-  if (select_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
-  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: kicks = %d < 0", (int)kicks);
-  if (kick_size < 1 || kick_size > kMaxKickSize)
-    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
-  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: span = %d < 1", (int)span);
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  if (workspace_bytes < il.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_iterated_search_ragged: workspace %zu < %zu bytes", workspace_bytes, il.total);
-  char* w = (char*)workspace;
-  MlTour* desc = (MlTour*)(w + lay.desc);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  double* rowv = (double*)(w + lay.rowv);
-  int* rowj = (int*)(w + lay.rowj);
-  int* live = (int*)(w + lay.live);
-  int* winners = (int*)(w + lay.winners);
-  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
-  int* tabi = (int*)(w + lay.tabi);
-  int2* marks = (int2*)(w + lay.marks);
-  int2* cum = (int2*)(w + lay.cum);
-  MlGroup* grp = (MlGroup*)(w + lay.grp);
-  MlTourState* ts = (MlTourState*)(w + lay.ts);
-  MlState* st = (MlState*)(w + lay.st);
-  int* inc = (int*)(w + il.inc);
-  MlIter* iters = (MlIter*)(w + il.iters);
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
-  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
-  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
-  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search_ragged setup: %s", hipGetErrorString(er));
-  // a launch sequence either moves a tour (at most max_iterations per descent), ends one of its phases (two per round) - the
-  // last of them runs the keep / kick step -, or, with no descent, is one keep / kick step: the bound per descent, kicks + 1 times
-  const long long ends = 2LL * max_rounds;
-  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
-  const long long limit = per > INT64_MAX / ((long long)kicks + 1) ? INT64_MAX : per * ((long long)kicks + 1);
-  MlState host{0, 0};
-  const int poll = 8;
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
-  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
-  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
-  for (long long it = 0; it < limit; ++it) {
-    if (!no_descent) {
-      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
-      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
-      hipLaunchKernelGGL(mls_select_iterated_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
-                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
-    }
-    hipLaunchKernelGGL(mls_keep_kick_kernel<false>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
-                       (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, HeatArgs<false>{});
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      ++g_host_syncs;
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  std::vector<MlIter> its(T);
-  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_iterated_search_ragged counters: %s", hipGetErrorString(er));
-  for (int g = 0; g < groups; ++g) {
-    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
-    rounds_out[g] = 1;                                           // every descent starts round 1
-  }
-  for (int b = 0; b < T; ++b) {
-    const int g = tab[b].group;
-    const MlTourState& x = states[b];
-    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
-    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
-    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
-    two_opt_moves_out[g] += x.two_opt_moves;
-    or_opt_moves_out[g] += x.or_opt_moves;
-    kicks_kept_out[b] = its[b].kept;
-    kicks_improved_out[b] = its[b].improved;
-    segments_swapped_out[b] = its[b].swapped;
-    first_length_out[b] = its[b].first_length;
-    final_length_out[b] = its[b].length;
-  }
-  return DIFUSCO_OK;
-}
-
-int difusco_tsp_focused_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
-                                                      size_t* bytes) {
-  using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged_workspace_bytes: bytes is null");
-  MlLayout lay;
-  const int rc = mls_layout("tsp_focused_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
-  if (rc != DIFUSCO_OK) return rc;
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  MlFocusLayout fl;
-  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
-  *bytes = fl.total;
-  return DIFUSCO_OK;
+  return mls_iterated_entry("tsp_iterated_search_ragged", kIterFull, false, kIterPart, "the five host output arrays [tours]", groups,
+                            group_n, group_tours, points, tours, max_iterations, max_rounds, select_rounds, kicks, kick_size, span,
+                            tour_seeds, tour_offsets, 0, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                            two_opt_sweeps_out, or_opt_sweeps_out, rounds_out, two_opt_moves_out, or_opt_moves_out, kicks_kept_out,
+                            kicks_improved_out, segments_swapped_out, first_length_out, final_length_out, nullptr, stream);
 }
 
 int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
@@ -797,159 +934,15 @@ int difusco_tsp_focused_search_ragged(int groups, const int32_t* group_n, const 
                                       int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
                                       double* final_length_out, int32_t* closing_sweeps_out, void* stream) {
   using namespace difusco;
-  g_host_syncs = 0;
-  MlLayout lay;
-  std::vector<MlTour> tab;
-  std::vector<MlGroup> gtab;
-  const int rc = mls_layout("tsp_focused_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
-  if (rc != DIFUSCO_OK) return rc;
-  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
-      !or_opt_moves_out || max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: needs non-null device arrays, the five host output arrays "
-                                     "[groups] and max_iterations >= 0");
-  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
-      !final_length_out || !closing_sweeps_out)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: needs the device arrays tour_seeds / tour_offsets and the six "
-                                     "host output arrays [tours]");
-  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
-  if (select_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
-  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: kicks = %d < 0", (int)kicks);
-  if (kick_size < 1 || kick_size > kMaxKickSize)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
-  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: span = %d < 1", (int)span);
-  if (compact_select_max < 0 || compact_select_max > kCompactMax)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: compact_select_max = %d, needs 0 .. %d", (int)compact_select_max,
-                     kCompactMax);
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  MlFocusLayout fl;
-  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
-  if (workspace_bytes < fl.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_focused_search_ragged: workspace %zu < %zu bytes", workspace_bytes, fl.total);
-  char* w = (char*)workspace;
-  MlTour* desc = (MlTour*)(w + lay.desc);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  double* rowv = (double*)(w + lay.rowv);
-  int* rowj = (int*)(w + lay.rowj);
-  int* live = (int*)(w + lay.live);
-  int* winners = (int*)(w + lay.winners);
-  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
-  int* tabi = (int*)(w + lay.tabi);
-  int2* marks = (int2*)(w + lay.marks);
-  int2* cum = (int2*)(w + lay.cum);
-  MlGroup* grp = (MlGroup*)(w + lay.grp);
-  MlTourState* ts = (MlTourState*)(w + lay.ts);
-  MlState* st = (MlState*)(w + lay.st);
-  int* inc = (int*)(w + il.inc);
-  MlIter* iters = (MlIter*)(w + il.iters);
-  int* smark = (int*)(w + fl.smark);
-  int* tmark = (int*)(w + fl.tmark);
-  int* arows = (int*)(w + fl.arows);
-  int* acols = (int*)(w + fl.acols);
-  MlFocus* foc = (MlFocus*)(w + fl.foc);
-  MlTourState* full = (MlTourState*)(w + fl.full);
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
-  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
-  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
-  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
-  if (er == hipSuccess) er = hipMemsetAsync(foc, 0, sizeof(MlFocus) * T, s);    // every tour starts in its first, full descent
-  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(full, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search_ragged setup: %s", hipGetErrorString(er));
-  // the bound per descent of the iterated search; a tour runs its first descent, one per kick and the closing one
-  const long long ends = 2LL * max_rounds;
-  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
-  const long long limit = per > INT64_MAX / ((long long)kicks + 2) ? INT64_MAX : per * ((long long)kicks + 2);
-  MlState host{0, 0};
-  const int poll = 8;
-  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
-  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
-  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
-  for (long long it = 0; it < limit; ++it) {
-    if (!no_descent) {
-      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
-      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, full);
-      hipLaunchKernelGGL(mls_focused_row_best_kernel, focus_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts, foc, arows,
-                         acols, marks, split);
-      hipLaunchKernelGGL(mls_select_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
-                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, (int)compact_select_max, st,
-                         grp, ts, full, foc, smark, tmark, arows, acols);
-    }
-    hipLaunchKernelGGL(mls_keep_kick_focused_kernel<false>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds,
-                       offsets, (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark,
-                       tmark, arows, acols, HeatArgs<false>{});
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      ++g_host_syncs;
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  std::vector<MlIter> its(T);
-  std::vector<MlFocus> focs(T);
-  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(focs.data(), foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_focused_search_ragged counters: %s", hipGetErrorString(er));
-  for (int g = 0; g < groups; ++g) {
-    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
-    rounds_out[g] = 1;                                           // every descent starts round 1
-  }
-  for (int b = 0; b < T; ++b) {
-    const int g = tab[b].group;
-    const MlTourState& x = states[b];
-    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
-    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
-    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
-    two_opt_moves_out[g] += x.two_opt_moves;
-    or_opt_moves_out[g] += x.or_opt_moves;
-    kicks_kept_out[b] = its[b].kept;
-    kicks_improved_out[b] = its[b].improved;
-    segments_swapped_out[b] = its[b].swapped;
-    first_length_out[b] = its[b].first_length;
-    final_length_out[b] = its[b].length;
-    closing_sweeps_out[b] = focs[b].closing_sweeps;
-  }
-  return DIFUSCO_OK;
+  return mls_iterated_entry("tsp_focused_search_ragged", kIterFocused, false, kIterPart | kFocusPart,
+                            "the six host output arrays [tours]", groups, group_n, group_tours, points, tours, max_iterations,
+                            max_rounds, select_rounds, kicks, kick_size, span, tour_seeds, tour_offsets, compact_select_max, nullptr,
+                            nullptr, nullptr, nullptr, workspace, workspace_bytes, two_opt_sweeps_out, or_opt_sweeps_out, rounds_out,
+                            two_opt_moves_out, or_opt_moves_out, kicks_kept_out, kicks_improved_out, segments_swapped_out,
+                            first_length_out, final_length_out, closing_sweeps_out, stream);
 }
 
-int difusco_tsp_guided_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
-                                                     const int32_t* group_edges, size_t* bytes) {
-  using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: bytes is null");
-  MlLayout lay;
-  const int rc = mls_layout("tsp_guided_search_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
-  if (rc != DIFUSCO_OK) return rc;
-  if (!group_edges) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: group_edges is null");
-  for (int g = 0; g < groups; ++g)
-    if (group_edges[g] < 0)
-      return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged_workspace_bytes: group %d has %d edges", g, (int)group_edges[g]);
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  MlFocusLayout fl;
-  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);   // one size for both descents
-  MlHeatLayout hl;
-  mls_heat_layout(fl.total, lay.tours, groups, group_n, group_tours, group_edges, &hl);
-  *bytes = hl.total;
-  return DIFUSCO_OK;
-}
-
-// the launch sequences of difusco_tsp_iterated_search_ragged (descent 0) or difusco_tsp_focused_search_ragged (descent 1) with the
-// kHeat keep / kick kernel; the graph check rides in front of the setup synchronisation, so the host polls are theirs
+// either of the two above with heat-drawn kicks; the workspace holds the focus part for both descents
 int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
                                      int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
                                      int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
@@ -961,192 +954,17 @@ int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const i
                                      double* first_length_out, double* final_length_out, int32_t* closing_sweeps_out,
                                      void* stream) {
   using namespace difusco;
-  g_host_syncs = 0;
-  MlLayout lay;
-  std::vector<MlTour> tab;
-  std::vector<MlGroup> gtab;
-  const int rc = mls_layout("tsp_guided_search_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
-  if (rc != DIFUSCO_OK) return rc;
   if (descent != 0 && descent != 1)
     return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: descent = %d, needs 0 (full) or 1 (focused)", (int)descent);
-  const bool focused = descent == 1;
-  if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
-      !or_opt_moves_out || max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs non-null device arrays, the five host output arrays "
-                                     "[groups] and max_iterations >= 0");
-  if (!tour_seeds || !tour_offsets || !kicks_kept_out || !kicks_improved_out || !segments_swapped_out || !first_length_out ||
-      !final_length_out || (focused && !closing_sweeps_out))
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs the device arrays tour_seeds / tour_offsets and the host "
-                                     "output arrays [tours] (closing_sweeps_out when the descent is focused)");
   if (!group_edges || !row_ptr || !col || !heat)
     return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: needs group_edges and the device arrays row_ptr / col / heat");
-  for (int g = 0; g < groups; ++g)
-    if (group_edges[g] < 0)
-      return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: group %d has %d edges", g, (int)group_edges[g]);
-  if (max_rounds < 1) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: max_rounds = %d, needs at least 1", max_rounds);
-  if (select_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: select_rounds = %d, needs at least 1", select_rounds);
-  if (kicks < 0) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: kicks = %d < 0", (int)kicks);
-  if (kick_size < 1 || kick_size > kMaxKickSize)
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: kick_size = %d, needs 1 .. %d", (int)kick_size, kMaxKickSize);
-  if (span < 1) return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: span = %d < 1", (int)span);
-  if (focused && (compact_select_max < 0 || compact_select_max > kCompactMax))
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: compact_select_max = %d, needs 0 .. %d", (int)compact_select_max,
-                     kCompactMax);
-  MlIterLayout il;
-  mls_iter_layout(lay, groups, group_n, group_tours, &il);
-  MlFocusLayout fl;
-  mls_focus_layout(lay, il, groups, group_n, group_tours, &fl);
-  MlHeatLayout hl;
-  mls_heat_layout(fl.total, lay.tours, groups, group_n, group_tours, group_edges, &hl);
-  if (workspace_bytes < hl.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: workspace %zu < %zu bytes", workspace_bytes, hl.total);
-  // the graph tables: a group's first row_ptr / col entry, a tour's first heat entry
-  std::vector<MlHeatTour> htab;
-  std::vector<MlHeatGroup> hgrp;
-  int emax = 0;
-  {
-    long long rows = 0, edges = 0, cells = 0;
-    for (int g = 0; g < groups; ++g) {
-      hgrp.push_back(MlHeatGroup{group_n[g], group_edges[g], rows, edges});
-      for (int p = 0; p < group_tours[g]; ++p) {
-        htab.push_back(MlHeatTour{rows, edges, cells, group_n[g], group_edges[g]});
-        cells += group_edges[g];
-      }
-      rows += (long long)group_n[g] + 1;
-      edges += group_edges[g];
-      emax = group_edges[g] > emax ? group_edges[g] : emax;
-    }
-  }
-  char* w = (char*)workspace;
-  MlTour* desc = (MlTour*)(w + lay.desc);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  double* rowv = (double*)(w + lay.rowv);
-  int* rowj = (int*)(w + lay.rowj);
-  int* live = (int*)(w + lay.live);
-  int* winners = (int*)(w + lay.winners);
-  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
-  int* tabi = (int*)(w + lay.tabi);
-  int2* marks = (int2*)(w + lay.marks);
-  int2* cum = (int2*)(w + lay.cum);
-  MlGroup* grp = (MlGroup*)(w + lay.grp);
-  MlTourState* ts = (MlTourState*)(w + lay.ts);
-  MlState* st = (MlState*)(w + lay.st);
-  int* inc = (int*)(w + il.inc);
-  MlIter* iters = (MlIter*)(w + il.iters);
-  int* smark = (int*)(w + fl.smark);
-  int* tmark = (int*)(w + fl.tmark);
-  int* arows = (int*)(w + fl.arows);
-  int* acols = (int*)(w + fl.acols);
-  MlFocus* foc = (MlFocus*)(w + fl.foc);
-  MlTourState* full = (MlTourState*)(w + fl.full);
-  MlHeatTour* d_htab = (MlHeatTour*)(w + hl.tab);
-  MlHeatGroup* d_hgrp = (MlHeatGroup*)(w + hl.groups);
-  int* d_bad = (int*)(w + hl.bad);
-  unsigned short* qtab = (unsigned short*)(w + hl.q);
-  HeatArgs<true> hx{row_ptr, col, qtab, d_htab, (unsigned long long*)(w + hl.W)};
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  const int no_descent = max_iterations == 0;                    // no sweep may move a tour: a call of keeps and kicks only
-  std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
-  for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
-  int bad = 0;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(d_htab, htab.data(), sizeof(MlHeatTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(d_hgrp, hgrp.data(), sizeof(MlHeatGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(d_bad, 0, sizeof(int), s);
-  if (er == hipSuccess) er = hipMemsetAsync(st, 0, sizeof(MlState), s);
-  if (er == hipSuccess) er = hipMemsetAsync(iters, 0, sizeof(MlIter) * T, s);
-  if (er == hipSuccess) er = hipMemsetAsync(foc, 0, sizeof(MlFocus) * T, s);    // every tour starts in its first, full descent
-  if (er == hipSuccess) er = hipMemcpyAsync(ts, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(full, states.data(), sizeof(MlTourState) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) {
-    const long long longest = (long long)lay.nmax + 1 > emax ? (long long)lay.nmax + 1 : emax;
-    hipLaunchKernelGGL(heat_graph_check_kernel, dim3((unsigned)((longest + 255) / 256), groups), dim3(256), 0, s, row_ptr, col,
-                       d_hgrp, d_bad);
-    er = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s);
-  }
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search_ragged setup: %s", hipGetErrorString(er));
-  if (bad)
-    return set_error(DIFUSCO_EINVAL, "tsp_guided_search_ragged: a group's graph is not a CSR over its cities (row_ptr[0] = 0, "
-                                     "row_ptr rising to row_ptr[n] = edges, 0 <= col < n)");
-  if (emax > 0)                                                  // the q table of every tour, once per call, in stream order
-    hipLaunchKernelGGL(heat_table_kernel, dim3((unsigned)(((long long)emax + 255) / 256), T), dim3(256), 0, s, row_ptr, col, heat,
-                       d_htab, qtab);
-  // the bounds of the two entries: a tour runs its first descent, one per kick and, focused, the closing one
-  const long long ends = 2LL * max_rounds;
-  const long long per = no_descent ? 1 : (max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends);
-  const long long descents = (long long)kicks + (focused ? 2 : 1);
-  const long long limit = per > INT64_MAX / descents ? INT64_MAX : per * descents;
-  MlState host{0, 0};
-  const int poll = 8;
-  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
-  const unsigned long long* seeds = (const unsigned long long*)tour_seeds;
-  const unsigned long long* offsets = (const unsigned long long*)tour_offsets;
-  for (long long it = 0; it < limit; ++it) {
-    if (!no_descent && focused) {
-      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
-      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, full);
-      hipLaunchKernelGGL(mls_focused_row_best_kernel, focus_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts, foc, arows,
-                         acols, marks, split);
-      hipLaunchKernelGGL(mls_select_focused_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
-                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, (int)compact_select_max, st,
-                         grp, ts, full, foc, smark, tmark, arows, acols);
-    } else if (!no_descent) {
-      hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, ts);
-      hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, ts);
-      hipLaunchKernelGGL(mls_select_iterated_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners,
-                         tabv, tabi, marks, cum, (long long)max_iterations, max_rounds, select_rounds, st, grp, ts);
-    }
-    if (focused)
-      hipLaunchKernelGGL(mls_keep_kick_focused_kernel<true>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds,
-                         offsets, (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, full, foc, marks, cum, smark,
-                         tmark, arows, acols, hx);
-    else
-      hipLaunchKernelGGL(mls_keep_kick_kernel<true>, dim3(T), dim3(kSelectThreads), 0, s, points, tours, inc, desc, seeds, offsets,
-                         (int)kicks, (int)kick_size, (int)span, no_descent, st, grp, ts, iters, hx);
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      ++g_host_syncs;
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  std::vector<MlIter> its(T);
-  std::vector<MlFocus> focs(T);
-  er = hipMemcpyAsync(states.data(), ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(its.data(), iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(focs.data(), foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  ++g_host_syncs;
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_guided_search_ragged counters: %s", hipGetErrorString(er));
-  for (int g = 0; g < groups; ++g) {
-    two_opt_sweeps_out[g] = or_opt_sweeps_out[g] = two_opt_moves_out[g] = or_opt_moves_out[g] = 0;
-    rounds_out[g] = 1;                                           // every descent starts round 1
-  }
-  for (int b = 0; b < T; ++b) {
-    const int g = tab[b].group;
-    const MlTourState& x = states[b];
-    if (x.two_opt_sweeps > two_opt_sweeps_out[g]) two_opt_sweeps_out[g] = x.two_opt_sweeps;
-    if (x.or_opt_sweeps > or_opt_sweeps_out[g]) or_opt_sweeps_out[g] = x.or_opt_sweeps;
-    if (its[b].max_round + 1 > rounds_out[g]) rounds_out[g] = its[b].max_round + 1;
-    two_opt_moves_out[g] += x.two_opt_moves;
-    or_opt_moves_out[g] += x.or_opt_moves;
-    kicks_kept_out[b] = its[b].kept;
-    kicks_improved_out[b] = its[b].improved;
-    segments_swapped_out[b] = its[b].swapped;
-    first_length_out[b] = its[b].first_length;
-    final_length_out[b] = its[b].length;
-    if (closing_sweeps_out) closing_sweeps_out[b] = focused ? focs[b].closing_sweeps : 0;
-  }
-  return DIFUSCO_OK;
+  return mls_iterated_entry("tsp_guided_search_ragged", descent == 1 ? kIterFocused : kIterFull, true,
+                            kIterPart | kFocusPart | kHeatPart,
+                            "the host output arrays [tours] (closing_sweeps_out when the descent is focused)", groups, group_n,
+                            group_tours, points, tours, max_iterations, max_rounds, select_rounds, kicks, kick_size, span, tour_seeds,
+                            tour_offsets, compact_select_max, group_edges, row_ptr, col, heat, workspace, workspace_bytes,
+                            two_opt_sweeps_out, or_opt_sweeps_out, rounds_out, two_opt_moves_out, or_opt_moves_out, kicks_kept_out,
+                            kicks_improved_out, segments_swapped_out, first_length_out, final_length_out, closing_sweeps_out, stream);
 }
 
 }  // extern "C"
