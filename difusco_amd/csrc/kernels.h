@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstddef>
+#include <cstdint>
 
 namespace difusco {
 
@@ -31,6 +33,14 @@ int set_error(int code, const char* fmt, ...);
 __host__ __device__ inline long long edge_tiled_offset(long long s, int f) {
   return (s >> 5) * 8192 + (long long)(f >> 4) * 512 + ((f >> 3) & 1) * 256 + ((((f >> 2) & 1) * 32) + (s & 31)) * 4 + (f & 3);
 }
+
+// the descent of difusco_tsp_multi_local_search_ragged with messages that name `who` and, optionally, the sweeps in which every
+// tour moved (HOST int64 [tours]); or_opt_multi.hip, used by the window search of tsp_window_search.hip
+int mls_descent_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int mls_descent(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace, size_t workspace_bytes,
+                int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out, int64_t* two_opt_moves_out,
+                int64_t* or_opt_moves_out, int64_t* tour_sweeps_out, void* stream);
 
 hipError_t linear_rows(const float* x, const float* w, const float* bias, const float* residual, float* y,
                        long long m, int k, int n_out, long long ldy, hipStream_t stream);

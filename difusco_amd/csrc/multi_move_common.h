@@ -319,6 +319,91 @@ __device__ __forceinline__ void reverse_winners(int* __restrict__ tour, const in
   }
 }
 
+// ---- what the searches of or_opt_multi.hip and tsp_window_search.hip share beyond the selection: the Or-opt variants, the range
+// of a proposal of either phase, the Or-opt apply, the fixed-association tour length and the segment swaps of a kick
+
+__device__ __forceinline__ int variant_len(int v) { return (v + 3) >> 1; }      // 1, 2, 2, 3, 3
+__device__ __forceinline__ bool variant_rev(int v) { return v == 2 || v == 4; }
+
+// the range of a proposal of either phase.  2-opt (i, j = rowj[i]): [i, j + 1).  Or-opt (rowj[i] = v n + j): [min(i, j), hi + 1)
+// with hi = j for j > i + L and i + L for j < i - from the first position of the lowest of the three edges the move touches to
+// the first position of the highest.  One type for both, so that the selection is instantiated once.
+struct PhaseRange {
+  const int* __restrict__ rowj;
+  int n;
+  bool or_opt;
+  __device__ __forceinline__ bool proposes(int i) const { return rowj[i] >= 0; }
+  __device__ __forceinline__ void operator()(int i, int* a, int* b) const {
+    const int c = rowj[i], j = or_opt ? c % n : c, L = or_opt ? variant_len(c / n) : 0;
+    *a = j < i ? j : i;
+    *b = (j < i ? i + L : j) + 1;
+  }
+};
+
+// the Or-opt moves of the winners: the stretch between a segment and its insertion edge shifts by L places over the segment, so
+// a wave copies the rewritten positions lo .. hi of one winner to `stage` (n + 1 entries of the tour's own), and after a barrier
+// writes them back from there (apply_or_opt_move of or_opt.hip, a winner per wave).  The stretches are disjoint.
+__device__ __forceinline__ void or_opt_winners(int* __restrict__ tour, int* __restrict__ stage, const int* __restrict__ winners,
+                                               const int* __restrict__ rowj, int n, int total) {
+  const int lane = threadIdx.x & 63;
+  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
+    const int i = winners[w], j = rowj[i] % n, L = variant_len(rowj[i] / n);
+    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;  // 1 <= lo <= hi <= n - 1
+    for (int k = lo + lane; k <= hi; k += 64) stage[k] = tour[k];
+  }
+  __syncthreads();
+  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
+    const int i = winners[w], j = rowj[i] % n, v = rowj[i] / n, L = variant_len(v);
+    const bool rev = variant_rev(v);
+    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;
+    for (int k = lo + lane; k <= hi; k += 64) {
+      int src;
+      if (j > i) {                                               // tour[:i+1] + tour[i+L+1 : j+1] + seg + tour[j+1:]
+        const int s = k - (j - L + 1);
+        src = s < 0 ? k + L : (rev ? i + L - s : i + 1 + s);
+      } else {                                                   // tour[:j+1] + seg + tour[j+1 : i+1] + tour[i+L+1:]
+        const int s = k - (j + 1);
+        src = s < L ? (rev ? i + L - s : i + 1 + s) : k - L;
+      }
+      tour[k] = stage[src];
+    }
+  }
+}
+
+constexpr int kMaxKickSize = 64;           // the draws of a kick: one wave decides which are kept
+constexpr int kLenParts = kSelectThreads;  // strided partial sums of a tour length
+
+// The length of the closed tour in the fixed association: thread r sums d_r, d_r+1024, .. in rising k from 0.0, then a halving
+// tree over the 1024 partial sums (part[r] += part[r + h], h = 512 .. 1).  d_k is prep_entry's.  The result in every thread.
+__device__ __forceinline__ double tour_length(const double* __restrict__ points, const int* __restrict__ tour, int n,
+                                              double* part) {
+  double acc = 0.0;
+  for (int k = threadIdx.x; k < n; k += kLenParts) {
+    const int c = tour[k], c1 = tour[k + 1];
+    acc = __dadd_rn(acc, dist2d(points[2 * c] - points[2 * c1], points[2 * c + 1] - points[2 * c1 + 1]));
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = kLenParts / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] = __dadd_rn(part[threadIdx.x], part[threadIdx.x + h]);
+    __syncthreads();
+  }
+  const double len = part[0];
+  __syncthreads();
+  return len;
+}
+
+// the kept draws swap their two adjacent segments in `tour` reading the incumbent `inc`, a wave per draw
+__device__ __forceinline__ void kick_swaps(int* __restrict__ tour, const int* __restrict__ inc, int kick_size, const int* ka,
+                                           const int* kl1, const int* kb, const int* kkeep) {
+  const int lane = threadIdx.x & 63;
+  for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
+    if (!kkeep[c]) continue;
+    const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
+    for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
+  }
+}
+
 int table_levels(int n) {                          // floor(log2(n + 1)) + 1
   int l = 0;
   while ((2LL << l) <= (long long)n + 1) ++l;

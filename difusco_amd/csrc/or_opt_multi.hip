@@ -24,8 +24,9 @@
 // The focused search (difusco_tsp_focused_search_ragged) launches the first two as they are and three of its own
 // (or_opt_focused.h, included behind the kernels here): after a kick a tour's sweeps evaluate only candidates next to a marked edge.
 // The guided search (difusco_tsp_guided_search_ragged) is either of the two with the keep / kick kernel's `kHeat` instantiation:
-// the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).  Both keep / kick kernels draw and apply a
-// kick with kick_draws and kick_swaps here.
+// the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).  Both keep / kick kernels draw a kick
+// with kick_draws here and apply it with kick_swaps (multi_move_common.h, which also holds what the window search of
+// tsp_window_search.hip shares with this file: PhaseRange, or_opt_winners, tour_length).
 //
 // The host side of all four entries is at the end of this file, once: mls_layout describes the workspace - the sections of the
 // descent and, as the entry needs them, the iterated state, the focus state and the heat tables - and builds the host tables,
@@ -47,9 +48,6 @@ namespace difusco {
 namespace {
 
 constexpr int LMAX = 3;                    // longest segment
-
-__device__ __forceinline__ int variant_len(int v) { return (v + 3) >> 1; }      // 1, 2, 2, 3, 3
-__device__ __forceinline__ bool variant_rev(int v) { return v == 2 || v == 4; }
 
 enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2, kKeep = 3 };   // kKeep: the iterated search only
 
@@ -204,51 +202,6 @@ __global__ __launch_bounds__(256) void mls_row_best_kernel(const double2* __rest
     or_row_best_tile(tp + d.closed, dlen + d.cols, d.n, i0, rowv + d.cols, rowj + d.cols);
 }
 
-// the range of a proposal of either phase.  2-opt (i, j = rowj[i]): [i, j + 1).  Or-opt (rowj[i] = v n + j): [min(i, j), hi + 1)
-// with hi = j for j > i + L and i + L for j < i - from the first position of the lowest of the three edges the move touches to
-// the first position of the highest.  One type for both, so that the selection is instantiated once.
-struct PhaseRange {
-  const int* __restrict__ rowj;
-  int n;
-  bool or_opt;
-  __device__ __forceinline__ bool proposes(int i) const { return rowj[i] >= 0; }
-  __device__ __forceinline__ void operator()(int i, int* a, int* b) const {
-    const int c = rowj[i], j = or_opt ? c % n : c, L = or_opt ? variant_len(c / n) : 0;
-    *a = j < i ? j : i;
-    *b = (j < i ? i + L : j) + 1;
-  }
-};
-
-// the Or-opt moves of the winners: the stretch between a segment and its insertion edge shifts by L places over the segment, so
-// a wave copies the rewritten positions lo .. hi of one winner to `stage` (n + 1 entries of the tour's own), and after a barrier
-// writes them back from there (apply_or_opt_move of or_opt.hip, a winner per wave).  The stretches are disjoint.
-__device__ __forceinline__ void or_opt_winners(int* __restrict__ tour, int* __restrict__ stage, const int* __restrict__ winners,
-                                               const int* __restrict__ rowj, int n, int total) {
-  const int lane = threadIdx.x & 63;
-  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
-    const int i = winners[w], j = rowj[i] % n, L = variant_len(rowj[i] / n);
-    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;  // 1 <= lo <= hi <= n - 1
-    for (int k = lo + lane; k <= hi; k += 64) stage[k] = tour[k];
-  }
-  __syncthreads();
-  for (int w = threadIdx.x >> 6; w < total; w += kSelectThreads / 64) {
-    const int i = winners[w], j = rowj[i] % n, v = rowj[i] / n, L = variant_len(v);
-    const bool rev = variant_rev(v);
-    const int lo = (j < i ? j : i) + 1, hi = j < i ? i + L : j;
-    for (int k = lo + lane; k <= hi; k += 64) {
-      int src;
-      if (j > i) {                                               // tour[:i+1] + tour[i+L+1 : j+1] + seg + tour[j+1:]
-        const int s = k - (j - L + 1);
-        src = s < 0 ? k + L : (rev ? i + L - s : i + 1 + s);
-      } else {                                                   // tour[:j+1] + seg + tour[j+1 : i+1] + tour[i+L+1:]
-        const int s = k - (j + 1);
-        src = s < L ? (rev ? i + L - s : i + 1 + s) : k - L;
-      }
-      tour[k] = stage[src];
-    }
-  }
-}
-
 // thread 0 of a tour that is done: the last tour of its group to finish counts the group as stopped
 __device__ __forceinline__ void report_done(MlGroup* g, MlState* st) {
   if (atomicAdd(&g->done, 1) == g->count - 1) atomicAdd(&st->done, 1);
@@ -339,9 +292,6 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_iterated_kernel(
                         max_iterations, max_rounds, select_rounds, st, grp, ts);
 }
 
-constexpr int kMaxKickSize = 64;           // the draws of a kick: one wave decides which are kept
-constexpr int kLenParts = kSelectThreads;  // strided partial sums of a tour length
-
 }  // namespace
 }  // namespace difusco
 
@@ -358,26 +308,6 @@ struct MlIter {            // device-resident state of a tour of the iterated se
   int max_round, pad;      // the highest zero-based round of any descent
   double first_length, length;   // of the first descent's result, of the incumbent
 };
-
-// The length of the closed tour in the fixed association: thread r sums d_r, d_r+1024, .. in rising k from 0.0, then a halving
-// tree over the 1024 partial sums (part[r] += part[r + h], h = 512 .. 1).  d_k is prep_entry's.  The result in every thread.
-__device__ __forceinline__ double tour_length(const double* __restrict__ points, const int* __restrict__ tour, int n,
-                                              double* part) {
-  double acc = 0.0;
-  for (int k = threadIdx.x; k < n; k += kLenParts) {
-    const int c = tour[k], c1 = tour[k + 1];
-    acc = __dadd_rn(acc, dist2d(points[2 * c] - points[2 * c1], points[2 * c + 1] - points[2 * c1 + 1]));
-  }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int h = kLenParts / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) part[threadIdx.x] = __dadd_rn(part[threadIdx.x], part[threadIdx.x + h]);
-    __syncthreads();
-  }
-  const double len = part[0];
-  __syncthreads();
-  return len;
-}
 
 // Wave 0: the draws of kick `kick` of tour t, one lane per draw c < kick_size - two segment lengths l1, l2 of at most `span`
 // cities and the first cut a (kHeat: by the running weights of the incumbent, heat_pick), so that the draw swaps [a, a + l1) and
@@ -406,17 +336,6 @@ __device__ __forceinline__ void kick_draws(const unsigned long long* __restrict_
     if (c > e && ke && a < be && ae < b) keep = 0;
   }
   ka[c] = a, kl1[c] = l1, kb[c] = b, kkeep[c] = keep;
-}
-
-// the kept draws swap their two adjacent segments in `tour` reading the incumbent `inc`, a wave per draw
-__device__ __forceinline__ void kick_swaps(int* __restrict__ tour, const int* __restrict__ inc, int kick_size, const int* ka,
-                                           const int* kl1, const int* kb, const int* kkeep) {
-  const int lane = threadIdx.x & 63;
-  for (int c = threadIdx.x >> 6; c < kick_size; c += kSelectThreads / 64) {
-    if (!kkeep[c]) continue;
-    const int a = ka[c], b = kb[c], l1 = kl1[c], l2 = b - a - l1;
-    for (int k = a + lane; k < b; k += 64) tour[k] = inc[k < a + l2 ? k + l1 : k - l2];
-  }
 }
 
 // One block per tour, a no-op unless the tour's descent has just ended (phase kKeep).  Keep: the length of the descended tour C
@@ -672,6 +591,7 @@ struct MlCall {            // a call of one of the four entries
   int64_t* segments_swapped_out;
   double *first_length_out, *final_length_out;
   int32_t* closing_sweeps_out;                   // kIterFocused; with heat and a full descent optional, written as 0
+  int64_t* tour_sweeps_out;                      // optional, [tours]: the sweeps in which the tour moved (the window search)
   void* stream;
 };
 
@@ -826,6 +746,7 @@ int mls_run(const MlCall& c) {
     if (rounds > c.rounds_out[g]) c.rounds_out[g] = rounds;
     c.two_opt_moves_out[g] += x.two_opt_moves;
     c.or_opt_moves_out[g] += x.or_opt_moves;
+    if (c.tour_sweeps_out) c.tour_sweeps_out[b] = x.sweeps;
     if (plain) continue;
     c.kicks_kept_out[b] = its[b].kept;
     c.kicks_improved_out[b] = its[b].improved;
@@ -863,6 +784,27 @@ int mls_iterated_entry(const char* who, MlMode mode, bool heat, unsigned parts, 
 }
 
 }  // namespace
+
+// the descent of difusco_tsp_multi_local_search_ragged for the window search (tsp_window_search.hip, declared in kernels.h): the
+// messages name `who`, and tour_sweeps_out (HOST [tours], optional) receives the sweeps in which every tour moved
+int mls_descent_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes) {
+  return mls_workspace_bytes(who, groups, group_n, group_tours, 0, nullptr, bytes);
+}
+
+int mls_descent(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace, size_t workspace_bytes,
+                int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out, int64_t* two_opt_moves_out,
+                int64_t* or_opt_moves_out, int64_t* tour_sweeps_out, void* stream) {
+  MlCall c{};
+  c.who = who, c.mode = kPlain, c.parts = 0;
+  c.groups = groups, c.group_n = group_n, c.group_tours = group_tours, c.points = points, c.tours = tours;
+  c.max_iterations = max_iterations, c.max_rounds = max_rounds, c.select_rounds = select_rounds;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+  c.two_opt_sweeps_out = two_opt_sweeps_out, c.or_opt_sweeps_out = or_opt_sweeps_out, c.rounds_out = rounds_out;
+  c.two_opt_moves_out = two_opt_moves_out, c.or_opt_moves_out = or_opt_moves_out, c.tour_sweeps_out = tour_sweeps_out;
+  return mls_run(c);
+}
+
 }  // namespace difusco
 
 extern "C" {
@@ -876,15 +818,9 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
                                           int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace,
                                           size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
                                           int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream) {
-  using namespace difusco;
-  MlCall c{};
-  c.who = "tsp_multi_local_search_ragged", c.mode = kPlain, c.parts = 0;
-  c.groups = groups, c.group_n = group_n, c.group_tours = group_tours, c.points = points, c.tours = tours;
-  c.max_iterations = max_iterations, c.max_rounds = max_rounds, c.select_rounds = select_rounds;
-  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
-  c.two_opt_sweeps_out = two_opt_sweeps_out, c.or_opt_sweeps_out = or_opt_sweeps_out, c.rounds_out = rounds_out;
-  c.two_opt_moves_out = two_opt_moves_out, c.or_opt_moves_out = or_opt_moves_out;
-  return mls_run(c);
+  return difusco::mls_descent("tsp_multi_local_search_ragged", groups, group_n, group_tours, points, tours, max_iterations, max_rounds,
+                              select_rounds, workspace, workspace_bytes, two_opt_sweeps_out, or_opt_sweeps_out, rounds_out,
+                              two_opt_moves_out, or_opt_moves_out, nullptr, stream);
 }
 
 int difusco_tsp_iterated_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,

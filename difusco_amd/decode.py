@@ -785,6 +785,144 @@ def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000,
                                 edge_index)
 
 
+TSP_WINDOW_MIN, TSP_WINDOW_MAX, TSP_WINDOW_MAX_KICKS = 16, 1024, 1024
+# the recommended window mode: the lowest row of scripts/tsp_window_search_table.py
+TSP_WINDOW, TSP_WINDOW_KICK_SIZE, TSP_WINDOW_KICK_SPAN = 128, 8, 30
+TSP_WINDOW_STATS = ("kicks_kept", "kicks_improved", "segments_swapped", "first_length", "final_length", "passes_kept",
+                    "windows_searched", "window_sweeps", "window_moves", "closing_sweeps")
+
+
+def check_tsp_window(local_search, window, passes=1, kicks=0, descent="full", kick_bias="uniform"):
+    """``window`` / ``passes`` of ``solve_tsp`` and the runner.  ``window = 0``: the mode is off (``passes`` must be 1 then).
+    ``window > 0`` runs the windowed iterated search (``batched_window_search_torch``): it needs
+    ``local_search='multi2opt+oropt'``, reads ``kicks`` as the kicks per window and pass, and combines with neither focused
+    descents nor heat-biased kicks."""
+    if int(window) != window or not (window == 0 or TSP_WINDOW_MIN <= window <= TSP_WINDOW_MAX):
+        raise ValueError(f"local_search_window = {window!r}: 0 (off) or an integer in {TSP_WINDOW_MIN} .. {TSP_WINDOW_MAX}")
+    if int(passes) != passes or passes < 1 or passes >= 2 ** 31:
+        raise ValueError(f"local_search_passes = {passes!r}: an integer >= 1")
+    if window == 0:
+        if passes != 1:
+            raise ValueError(f"local_search_passes = {passes} counts the passes of the windowed search: it needs local_search_window > 0")
+        return 0, 1
+    if local_search != "multi2opt+oropt":
+        raise ValueError(f"local_search_window = {window} runs the multi-move local search on tour windows: it needs "
+                         f"local_search='multi2opt+oropt', not {local_search!r}")
+    if kicks > TSP_WINDOW_MAX_KICKS:
+        raise ValueError(f"local_search_kicks = {kicks} with local_search_window > 0 is per window and pass: at most "
+                         f"{TSP_WINDOW_MAX_KICKS}")
+    if descent != "full":
+        raise ValueError(f"local_search_window = {window} does not combine with local_search_descent = {descent!r}")
+    if kick_bias != "uniform":
+        raise ValueError(f"local_search_window = {window} does not combine with local_search_kick_bias = {kick_bias!r}")
+    return int(window), int(passes)
+
+
+def _window_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
+                       stats, window, passes):
+    """The checks of the three windowed-search functions (before any library call) and one ``difusco_tsp_window_search_ragged``
+    call.  Returns (int64 tours per group, the stats dict of ``batched_multi_local_search_grouped``); ``stats`` receives the
+    per-tour arrays."""
+    if int(kicks) != kicks or not 0 <= kicks <= TSP_WINDOW_MAX_KICKS:
+        raise ValueError(f"kicks = {kicks!r}: an integer in 0 .. {TSP_WINDOW_MAX_KICKS}")
+    if int(window) != window or not TSP_WINDOW_MIN <= window <= TSP_WINDOW_MAX:
+        raise ValueError(f"window = {window!r}: an integer in {TSP_WINDOW_MIN} .. {TSP_WINDOW_MAX}")
+    if int(passes) != passes or passes < 1 or passes >= 2 ** 31:
+        raise ValueError(f"passes = {passes!r}: an integer >= 1")
+    _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
+    device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
+    for p in pts:
+        if int(passes) * (-(-p.shape[0] // int(window)) + 1) * max(int(kicks), 1) >= 2 ** 32:
+            raise ValueError(f"{who}: passes = {passes} with {-(-p.shape[0] // int(window)) + 1} windows and {kicks} kicks each "
+                             "needs 2^32 or more Philox offsets per tour")
+    T = sum(t.shape[0] for t in trs)
+    mask = (1 << 64) - 1
+    table = []
+    for name, v in (("seeds", seeds), ("offsets", offsets)):
+        v = [0] * T if v is None else [int(x) & mask for x in v]
+        if len(v) != T:
+            raise ValueError(f"{name}: {len(v)} entries for {T} tours")
+        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
+    G = len(pts)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t()
+    _lib.check(L.difusco_tsp_window_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data, int(window),
+                                                                  ctypes.byref(nbytes)))
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
+           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
+           "or_opt_moves": np.zeros(G, dtype=np.int64)}
+    i32s, f64s = ("kicks_kept", "kicks_improved", "passes_kept", "windows_searched", "closing_sweeps"), ("first_length", "final_length")
+    per = {k: np.zeros(T, dtype=np.int32 if k in i32s else np.float64 if k in f64s else np.int64) for k in TSP_WINDOW_STATS}
+    _lib.check(L.difusco_tsp_window_search_ragged(
+        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
+        int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
+        ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()), int(window), int(passes),
+        ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
+        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_WINDOW_STATS),
+        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats.update(per)
+    flat = d_tours.cpu().numpy().astype(np.int64)
+    cuts = np.cumsum([t.size for t in trs])[:-1]
+    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+
+
+def batched_window_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
+                                kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None, window,
+                                passes=1):
+    """The iterated search of ``batched_iterated_search_torch`` on the WINDOWS of every tour, all windows of a pass at once (the
+    rule: ``difusco_tsp_window_search_ragged``, include/difusco_hip.h; GPU only; not in the reference): after its descent every
+    tour runs ``passes`` passes; a pass cuts the tour every ``window`` positions (16 .. 1024; odd passes shifted by half a
+    window), runs ``kicks`` kicks (0 .. 1024, per window and pass) of the iterated search on every window as an open path whose
+    ends stay, one GPU block per window with no host poll, and keeps the result unless the tour got longer; one full descent
+    closes the call.  ``seeds`` / ``offsets`` [B]: as there; window w of pass r draws at ``offsets[b] + (r C + w) kicks``,
+    ``C = ceil(N / window) + 1``.  A tour gets the same answer alone or in any call.  Returns ``(tour int64 numpy [B, N+1],
+    stats)``, the stats of ``batched_multi_local_search_torch`` over the first and the closing descent; ``stats`` (a dict)
+    receives the per-tour numpy arrays [B] ``first_length``, ``final_length``, ``passes_kept``, ``windows_searched``,
+    ``kicks_kept``, ``kicks_improved``, ``segments_swapped``, ``window_sweeps``, ``window_moves`` and ``closing_sweeps``."""
+    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
+    out, st = _window_search_run("batched_window_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device, kicks,
+                                 kick_size, span, seeds, offsets, stats, window, passes)
+    return out[0], {k: int(v[0]) for k, v in st.items()}
+
+
+def batched_window_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
+                                  kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None, window,
+                                  passes=1):
+    """``batched_window_search_torch`` of G instances at once, the arguments of ``batched_iterated_search_grouped``.  Every tour
+    gets what its own call returns.  Returns ``(tours int64 numpy [G * P, N + 1], stats)``; the entries of the returned stats
+    are numpy arrays [G], the per-tour arrays [G * P]."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    P = t.shape[0] // G
+    pts_l = [np.ascontiguousarray(p) for p in pts]
+    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
+    out, st = _window_search_run("batched_window_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds, device,
+                                 kicks, kick_size, span, seeds, offsets, stats, window, passes)
+    return np.concatenate(out, axis=0), st
+
+
+def batched_window_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
+                                 kicks=0, kick_size=TSP_KICK_SIZE, span=TSP_KICK_SPAN, seeds=None, offsets=None, stats=None,
+                                 window, passes=1):
+    """``batched_window_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_iterated_search_ragged``.
+    Returns ``(list of int64 numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_window_search_grouped``."""
+    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
+    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    return _window_search_run("batched_window_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device, kicks,
+                              kick_size, span, seeds, offsets, stats, window, passes)
+
+
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).

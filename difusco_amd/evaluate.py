@@ -43,7 +43,11 @@ records gain the setting and ``closing_sweeps``, one count per copy, and the hea
 ``--tsp_local_search_kick_bias {uniform,heat}`` (heat only with ``--tsp_local_search_kicks N`` > 0 and ``--task tsp``: the first cut
 of every draw of a kick falls on a tour edge with a probability that rises as the heat of that edge falls,
 ``kick_bias="heat"`` of ``decode.batched_iterated_search_grouped`` on each sample's own heatmap; only when it is ``heat`` the
-records and the header gain the setting), ``--merge_method {loop,batched}``
+records and the header gain the setting), ``--tsp_local_search_window W`` / ``--tsp_local_search_passes R`` (W > 0 only with
+``--local_search multi2opt+oropt``, a full descent and uniform kicks: the windowed iterated search,
+``decode.batched_window_search_grouped``, R passes over windows of W positions with ``--tsp_local_search_kicks`` kicks (>= 0) per
+window and pass, keyed as the kicks are; the records gain ``kicks_improved``, ``passes_kept`` and ``closing_sweeps``, one count per
+copy, and with the header the two settings and the three kick settings), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -137,6 +141,13 @@ EXTENSION_ARGS = [
                                            help="TSP: where the first cut of a kick's draws falls: uniform (anywhere alike) or "
                                                 "heat (on a tour edge with a probability that rises as the sampled heat of the "
                                                 "edge falls; needs --tsp_local_search_kicks N > 0)")),
+    ("--tsp_local_search_window", dict(type=int, default=0,
+                                        help="TSP: W > 0 runs the iterated search on windows of W tour positions (16 .. 1024), one "
+                                             "GPU block per window, --tsp_local_search_kicks kicks (>= 0) per window and pass (needs "
+                                             "--local_search multi2opt+oropt, a full descent and uniform kicks; 0: off)")),
+    ("--tsp_local_search_passes", dict(type=int, default=1,
+                                        help="TSP: passes of the windowed search, odd ones shifted by half a window (needs "
+                                             "--tsp_local_search_window W > 0)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -204,6 +215,22 @@ def parse_args(argv=None):
                      "--tsp_local_search_kicks N > 0")
     if args.tsp_local_search_kick_bias == "heat" and args.task != "tsp":
         parser.error(f"--tsp_local_search_kick_bias heat biases the kicks of TSP tours: not with --task {args.task}")
+    W, R = args.tsp_local_search_window, args.tsp_local_search_passes
+    if not (W == 0 or 16 <= W <= 1024) or R < 1:
+        parser.error("--tsp_local_search_window must be 0 (off) or in 16 .. 1024 and --tsp_local_search_passes >= 1")
+    if W == 0 and R != 1:
+        parser.error(f"--tsp_local_search_passes {R} counts the passes of the windowed search: pass --tsp_local_search_window W > 0")
+    if W > 0 and args.local_search != "multi2opt+oropt":
+        parser.error(f"--tsp_local_search_window {W} runs the multi-move local search on tour windows: pass "
+                     "--local_search multi2opt+oropt")
+    if W > 0 and args.tsp_local_search_kicks > 1024:
+        parser.error(f"--tsp_local_search_kicks {args.tsp_local_search_kicks} with --tsp_local_search_window is per window and "
+                     "pass: at most 1024")
+    if W > 0 and (args.tsp_local_search_descent != "full" or args.tsp_local_search_kick_bias != "uniform"):
+        parser.error(f"--tsp_local_search_window {W} combines with neither --tsp_local_search_descent focused nor "
+                     "--tsp_local_search_kick_bias heat")
+    if args.tsp_local_search_window > 0 and args.task != "tsp":
+        parser.error(f"--tsp_local_search_window {args.tsp_local_search_window} refines TSP tours: not with --task {args.task}")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -326,6 +353,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
         rec["kicks_improved"] = [int(v) for v in info["local_search_kicks_improved"]]
     if "local_search_closing_sweeps" in info:      # --tsp_local_search_descent focused
         rec["closing_sweeps"] = [int(v) for v in info["local_search_closing_sweeps"]]
+    if "local_search_passes_kept" in info:         # --tsp_local_search_window W > 0
+        rec["passes_kept"] = [int(v) for v in info["local_search_passes_kept"]]
     return rec
 
 
@@ -366,7 +395,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 mis_local_search: str = "none", mis_local_search_kicks: int = 0,
                 mis_local_search_kick_size: int = 4, tsp_local_search_kicks: int = 0,
                 tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
-                tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform") -> List[dict]:
+                tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
+                tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1) -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -389,12 +419,18 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   merge_method=merge_method, local_search=local_search,
                                   **(dict(local_search_kicks=tsp_local_search_kicks,
                                           local_search_kick_size=tsp_local_search_kick_size,
-                                          local_search_kick_span=tsp_local_search_kick_span) if tsp_local_search_kicks > 0 else {}),
+                                          local_search_kick_span=tsp_local_search_kick_span)
+                                     if tsp_local_search_kicks > 0 or tsp_local_search_window > 0 else {}),
+                                  **(dict(local_search_window=tsp_local_search_window, local_search_passes=tsp_local_search_passes)
+                                     if tsp_local_search_window > 0 else {}),
                                   **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
                                   **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
-                if tsp_local_search_kicks > 0:
+                if tsp_local_search_window > 0:
+                    records[-1].update(tsp_local_search_window=tsp_local_search_window,
+                                       tsp_local_search_passes=tsp_local_search_passes)
+                if tsp_local_search_kicks > 0 or tsp_local_search_window > 0:
                     records[-1].update(tsp_local_search_kicks=tsp_local_search_kicks,
                                        tsp_local_search_kick_size=tsp_local_search_kick_size,
                                        tsp_local_search_kick_span=tsp_local_search_kick_span)
@@ -482,7 +518,9 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_kick_size=args.tsp_local_search_kick_size,
                                tsp_local_search_kick_span=args.tsp_local_search_kick_span,
                                tsp_local_search_descent=args.tsp_local_search_descent,
-                               tsp_local_search_kick_bias=args.tsp_local_search_kick_bias)
+                               tsp_local_search_kick_bias=args.tsp_local_search_kick_bias,
+                               tsp_local_search_window=args.tsp_local_search_window,
+                               tsp_local_search_passes=args.tsp_local_search_passes)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -509,7 +547,10 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["local_search"] = args.local_search
             if args.mis_local_search != "none":
                 line["mis_local_search"] = args.mis_local_search
-            if args.tsp_local_search_kicks > 0:
+            if args.tsp_local_search_window > 0:
+                line["tsp_local_search_window"] = args.tsp_local_search_window
+                line["tsp_local_search_passes"] = args.tsp_local_search_passes
+            if args.tsp_local_search_kicks > 0 or args.tsp_local_search_window > 0:
                 line["tsp_local_search_kicks"] = args.tsp_local_search_kicks
                 line["tsp_local_search_kick_size"] = args.tsp_local_search_kick_size
                 line["tsp_local_search_kick_span"] = args.tsp_local_search_kick_span

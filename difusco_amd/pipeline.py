@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
-                     check_tsp_kicks, check_two_opt_method, batched_local_search_grouped,
+                     check_tsp_kicks, check_tsp_window, check_two_opt_method, batched_local_search_grouped,
+                     batched_window_search_grouped, batched_window_search_ragged, batched_window_search_torch,
                      batched_iterated_search_grouped, batched_iterated_search_ragged, batched_iterated_search_torch,
                      batched_local_search_ragged, batched_local_search_torch, batched_multi_local_search_grouped,
                      batched_multi_local_search_ragged, batched_multi_local_search_torch, batched_multi_two_opt_grouped,
@@ -45,7 +46,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact",
               local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
               local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
-              local_search_kick_bias: str = "uniform"):
+              local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -71,12 +72,19 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     or "heat" (only with ``local_search_kicks`` > 0, else ``ValueError``): the first cut of every draw of a kick falls on a tour
     edge with a probability that rises as the heat of that edge falls (``kick_bias="heat"`` of
     ``decode.batched_iterated_search_torch``); copy p reads its own heatmap of its sequential round, the tensor the merge
-    received, still on the device; info gains ``local_search_kick_bias`` ("heat"; the uniform records stay as they were)."""
+    received, still on the device; info gains ``local_search_kick_bias`` ("heat"; the uniform records stay as they were).
+    ``local_search_window`` = W > 0 (only with "multi2opt+oropt", a full descent and uniform kicks, else ``ValueError``; 0, the
+    default, changes nothing): the windowed iterated search (``decode.batched_window_search_torch``) with
+    ``local_search_passes`` passes over windows of W positions and ``local_search_kicks`` kicks (>= 0) per window and pass, of
+    ``local_search_kick_size`` and ``local_search_kick_span``; the copies are keyed as above; info gains
+    ``local_search_window``, ``local_search_passes`` and, of the last round, one per copy, ``local_search_kicks_improved``,
+    ``local_search_passes_kept`` and ``local_search_closing_sweeps``."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
+    window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -115,6 +123,12 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
         elif local_search == "multi2opt":
             solved, ns = batched_multi_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),
                                                      max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+        elif local_search == "multi2opt+oropt" and window > 0:
+            solved, ls_stats = batched_window_search_torch(
+                np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
+                kick_size=kick_size, span=kick_span, seeds=[_kick_key(model.seed)] * parallel_sampling,
+                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats, window=window, passes=passes)
+            ns = ls_stats["two_opt_sweeps"]
         elif local_search == "multi2opt+oropt" and kicks > 0:
             solved, ls_stats = batched_iterated_search_torch(
                 np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
@@ -141,7 +155,9 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     elif local_search == "multi2opt+oropt":
         info.update(two_opt_moves=ls_stats["two_opt_moves"], or_opt_iterations=ls_stats["or_opt_sweeps"],
                     or_opt_moves=ls_stats["or_opt_moves"], local_search_rounds=ls_stats["rounds"])
-        if kicks > 0:
+        if window > 0:
+            info.update(_window_info(kick_stats, window, passes, 0, parallel_sampling))
+        elif kicks > 0:
             info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"]])
             if kick_bias == "heat":
                 info.update(local_search_kick_bias="heat")
@@ -225,6 +241,13 @@ def _kick_key(seed) -> int:
     return int(seed) & (2 ** 63 - 1)
 
 
+def _window_info(stats: dict, window: int, passes: int, first: int, P: int) -> dict:
+    """What info gains in window mode: the settings and the per-copy arrays of the copies first .. first + P - 1."""
+    cut = lambda k: [int(v) for v in stats[k][first:first + P]]
+    return dict(local_search_window=window, local_search_passes=passes, local_search_kicks_improved=cut("kicks_improved"),
+                local_search_passes_kept=cut("passes_kept"), local_search_closing_sweeps=cut("closing_sweeps"))
+
+
 def _kick_stats(out: dict, call: dict, first: int, P: int):
     for k, src in (("swap_sizes", "size_before"), ("kicks_entered", "entered"), ("kicks_accepted", "accepted")):
         out[k] += call[src][first:first + P]
@@ -258,7 +281,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     heatmaps: Optional[list] = None, *, two_opt_method: str = "exact",
                     merge_method: str = "loop", local_search: str = "2opt", local_search_kicks: int = 0,
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
-                    local_search_descent: str = "full", local_search_kick_bias: str = "uniform") -> List[tuple]:
+                    local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
+                    local_search_passes: int = 1) -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -275,17 +299,19 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     ``local_search_kicks``, ``local_search_kick_size``, ``local_search_kick_span``: as ``solve_tsp``; every one of the P copies of
     an instance is its own tour, keyed by the instance's seed, so an instance gets what its solo call gets.
     ``local_search_descent``, ``local_search_kick_bias``: as ``solve_tsp``; "heat" passes every instance's own heatmaps of the
-    round (the tensors the merge received, on the device) and its own graph."""
+    round (the tensors the merge received, on the device) and its own graph.  ``local_search_window``,
+    ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
+    window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
-                               merge_method, local_search, kicks, kick_size, kick_span, descent, kick_bias)
+                               merge_method, local_search, kicks, kick_size, kick_span, descent, kick_bias, window, passes)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -349,6 +375,12 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             elif local_search == "multi2opt":
                 solved, ns = batched_multi_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt" and window > 0:
+                solved, ls_stats = batched_window_search_grouped(
+                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
+                    device=dev, kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, window=window, passes=passes)
+                ns = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt" and kicks > 0:
                 solved, ls_stats = batched_iterated_search_grouped(
                     np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
@@ -377,7 +409,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             elif local_search == "multi2opt+oropt":
                 info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
-                if kicks > 0:
+                if window > 0:
+                    info.update(_window_info(kick_stats, window, passes, g * P, P))
+                elif kicks > 0:
                     info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
                     if kick_bias == "heat":
                         info.update(local_search_kick_bias="heat")
@@ -394,7 +428,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
                     instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop",
                     local_search="2opt", kicks=0, kick_size=TSP_KICK_SIZE, kick_span=TSP_KICK_SPAN,
-                    descent="full", kick_bias="uniform") -> List[tuple]:
+                    descent="full", kick_bias="uniform", window=0, passes=1) -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
     check_local_search(local_search, two_opt_method)
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
@@ -468,6 +502,12 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             elif local_search == "multi2opt":
                 solved, its = batched_multi_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                            max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            elif local_search == "multi2opt+oropt" and window > 0:
+                solved, ls_stats = batched_window_search_ragged(
+                    np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
+                    kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
+                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, window=window, passes=passes)
+                its = ls_stats["two_opt_sweeps"]
             elif local_search == "multi2opt+oropt" and kicks > 0:
                 solved, ls_stats = batched_iterated_search_ragged(
                     np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
@@ -496,7 +536,9 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             elif local_search == "multi2opt+oropt":
                 info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
                             or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
-                if kicks > 0:
+                if window > 0:
+                    info.update(_window_info(kick_stats, window, passes, g * P, P))
+                elif kicks > 0:
                     info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
                     if kick_bias == "heat":
                         info.update(local_search_kick_bias="heat")

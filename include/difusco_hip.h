@@ -811,6 +811,57 @@ int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const i
                                      double* first_length_out, double* final_length_out, int32_t* closing_sweeps_out,
                                      void* stream);
 
+/* WINDOWED iterated multi-move local search: one block per tour window (additive to ABI 13; not in the reference): the arrays,
+ * conventions and limits of difusco_tsp_iterated_search_ragged, plus window = W in 16 .. 1024, passes = R >= 1 and kicks = K in
+ * 0 .. 1024 per window and pass.  Every TOUR runs on its own; its result never depends on what shares the call.
+ *   1. First descent.  The search of difusco_tsp_multi_local_search_ragged on the input tour, exactly: T_-1.
+ *   2. Pass r = 0 .. R-1, on T_r-1.  o_r = 0 for even r and W/2 (integer division) for odd r.  The cuts are 0, n and every
+ *      o_r + w W with 0 < o_r + w W < n, in rising order c_0 < .. < c_M.  Window w is the open path Q_k = T_r-1[c_w + k],
+ *      k = 0 .. m, m = c_w+1 - c_w <= W.  A window with m < 8 is copied unchanged.  Every other window is searched by steps 1-5
+ *      of difusco_tsp_iterated_search_ragged's rule, verbatim, with n := m and P_k := the coordinates of Q_k for k = 0 .. m (so
+ *      P_m is Q_m, not P_0): a first descent of the path, K kicks, each drawn from the incumbent, descended with fresh caps and
+ *      kept iff not longer.  Positions 0 and m never move - no move and no draw of that rule touches them -, so the cities on
+ *      the cuts stay.  The caps are those of the call (max_iterations, max_rounds, select_rounds, kick_size, span); the len of
+ *      step 4 is that association with n := m; the Philox key is the tour's seed and the first Philox offset is the tour's
+ *      offset + (r C + w) K modulo 2^64, C = ceil(n / W) + 1.  The candidate X is the concatenation of the window results.
+ *      T_r = X iff len(X) <= len(T_r-1), the tour-level len of step 4 there; otherwise T_r = T_r-1.  (A change inside a window
+ *      changes only edges of that window, so X is never longer up to the rounding of the window sums; the pass-level keep makes
+ *      "never longer" an exact float64 statement.)
+ *   3. Closing.  One full descent of T_R-1 as in step 1, kept iff its len is not larger.
+ *   4. The output is that tour.
+ * So: the output is a permutation closed on tour[0] with final_length_out <= first_length_out exactly; where no cap binds it has
+ * no improving 2-opt or Or-opt move left; the same (seed, offset) gives a tour the same result in a solo, a grouped and a ragged
+ * call; for n <= W and R = 1 the tour, both lengths and the kick counters are those of difusco_tsp_iterated_search_ragged with
+ * kicks = K (the cuts are 0 and n, the path is the closed tour and the offset is the tour's own) where no cap binds.
+ * Outputs.  The five HOST arrays [groups] cover the first and the closing descent: each descent's values, combined over the
+ * group's tours as difusco_tsp_multi_local_search_ragged does, are added (rounds_out: the larger of the two).  HOST arrays [T]
+ * per tour: first_length_out, final_length_out (float64; len of T_-1 and of the output); passes_kept_out (int32; passes with
+ * T_r = X); windows_searched_out (int32; windows with m >= 8, over all passes); kicks_kept_out, kicks_improved_out (int32) and
+ * segments_swapped_out (int64) as in difusco_tsp_iterated_search_ragged, summed over windows and passes, kept pass or not;
+ * window_sweeps_out, window_moves_out (int64; the sweeps in which a window moved and the moves applied, both kinds together,
+ * summed likewise); closing_sweeps_out (int32; the sweeps in which the closing descent moved the tour).
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_iterated_search_ragged, a null new array, window outside
+ * 16 .. 1024, passes < 1, kicks outside 0 .. 1024 and a tour with R C max(K, 1) >= 2^32 (the Philox offsets of two tours keyed
+ * 2^32 apart could meet); a refused call leaves `tours` untouched.  _workspace_bytes takes `window`: the workspace holds the
+ * descents' workspace, one candidate per tour and the window tables of the even and the odd passes.  Launches: the first and
+ * the closing descent are those of difusco_tsp_multi_local_search_ragged; between them the host enqueues 2 R launches with no
+ * synchronisation - per pass one block of 1024 threads per window, which keeps the window's coordinates, paths, edge lengths,
+ * row bests and selection lists in 54 KB of LDS and runs all its descents, kicks and keeps there (at most (K + 1) x
+ * (max_iterations + 2 max_rounds) sweeps; no block waits on another), and one block per tour for the pass-level len and keep.
+ * Blocks until every tour is done. */
+int difusco_tsp_window_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int32_t window,
+                                                     size_t* bytes);
+int difusco_tsp_window_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                     int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, int32_t kicks,
+                                     int32_t kick_size, int32_t span, const uint64_t* tour_seeds, const uint64_t* tour_offsets,
+                                     int32_t window, int32_t passes, void* workspace, size_t workspace_bytes,
+                                     int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out,
+                                     int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int32_t* kicks_kept_out,
+                                     int32_t* kicks_improved_out, int64_t* segments_swapped_out, double* first_length_out,
+                                     double* final_length_out, int32_t* passes_kept_out, int32_t* windows_searched_out,
+                                     int64_t* window_sweeps_out, int64_t* window_moves_out, int32_t* closing_sweeps_out,
+                                     void* stream);
+
 /* ---- MCTS heatmap rows: the numeric part of tsp_mcts/convert_numpy_to_txt.py:18-47, whose text output
  * (first line N, then N rows of N "%.6f" numbers) tsp_mcts/code/include/TSP_IO.h:461-492 reads.  From the SPARSE heatmap:
  * row/col/heat [n_edges] DEVICE, any order, no duplicate (row, col); points DEVICE float32 [n_nodes,2]; float32 arithmetic
