@@ -34,6 +34,16 @@ __host__ __device__ inline long long edge_tiled_offset(long long s, int f) {
   return (s >> 5) * 8192 + (long long)(f >> 4) * 512 + ((f >> 3) & 1) * 256 + ((((f >> 2) & 1) * 32) + (s & 31)) * 4 + (f & 3);
 }
 
+// The sort key of the MIS visiting order (mis_decode.hip, mis_local_search.hip): sorting these keys in DEscending order, stably, is
+// numpy's argsort(-score, kind="stable") - decreasing score, -0.0 and +0.0 one value, every NaN (either sign, any payload) after
+// everything else including -inf, ties by increasing index.  `bits` is the float's bit pattern.  Non-NaN floats map monotonically
+// onto 0x007FFFFF (-inf) .. 0xFF800000 (+inf); NaN maps to 0.
+__host__ __device__ inline unsigned mis_sort_key(unsigned bits) {
+  if ((bits & 0x7fffffffu) > 0x7f800000u) return 0u;      // NaN
+  if (bits == 0x80000000u) bits = 0u;                     // -0.0 is +0.0
+  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+
 // the descent of difusco_tsp_multi_local_search_ragged with messages that name `who` and, optionally, the sweeps in which every
 // tour moved (HOST int64 [tours]); or_opt_multi.hip, used by the window search of tsp_window_search.hip
 int mls_descent_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);

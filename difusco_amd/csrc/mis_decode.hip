@@ -5,10 +5,16 @@
 // the lexicographically first maximal independent set of that order.  That set has a parallel characterisation -
 // a node is IN iff all its higher-priority neighbours are OUT, and OUT iff one of them is IN - so it is computed
 // in rounds over all nodes at once (a node decides as soon as its higher-priority neighbours have); the number of
-// rounds is the longest priority-decreasing dependency chain, a few dozen on Erdos-Renyi graphs.
-//   1. rank: stable radix sort (rocPRIM) of (-score, index) - ties keep index order (numpy's argsort is unstable
-//      there; fixtures are tie-free);
-//   2. rounds of mis_round_kernel until no node is undecided (device-side counter, polled every few rounds).
+// rounds is at most the longest priority-decreasing dependency chain (a node may see a decision of its own round), a few
+// dozen on Erdos-Renyi graphs.
+//   1. rank: stable descending radix sort (rocPRIM) of (mis_sort_key(score), index) - numpy's argsort(-score, kind="stable"):
+//      -0.0 and +0.0 are one value, every NaN ranks after -inf, ties keep index order (the reference's own argsort is
+//      unstable there).  The key is the project's, so none of this rests on how a library orders float bit patterns;
+//   2. rounds of mis_round_kernel until no node is undecided (device-side counter, polled every fourth round).
+// Rounds: with level(v) = 1 + max level(u) over the neighbours u != v that rank before v (1 without one), a node of level l
+// has decided by the end of round l (a stale read delays a decision to that round at most), and the loop stops after the first
+// group of four rounds whose last one leaves nobody undecided: 4 <= rounds <= 4 * ceil(Lmax / 4).
+// A node reads its OWN row where the reference writes through the taker's row: the two agree on symmetric adjacencies only.
 // Works on the CSR of the (symmetric, self loops allowed) adjacency of the whole call; graphs of a batch are
 // independent components, so one call decodes all of them.
 #include <hip/hip_runtime.h>
@@ -24,9 +30,11 @@
 namespace difusco {
 namespace {
 
-__global__ void mis_iota_kernel(int n, unsigned* __restrict__ idx) {
+__global__ void mis_key_kernel(int n, const float* __restrict__ scores, unsigned* __restrict__ key, unsigned* __restrict__ idx) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v < n) idx[v] = (unsigned)v;
+  if (v >= n) return;
+  key[v] = mis_sort_key(__float_as_uint(scores[v]));
+  idx[v] = (unsigned)v;
 }
 
 __global__ void mis_rank_kernel(int n, const unsigned* __restrict__ order, int* __restrict__ rank, int* __restrict__ state) {
@@ -71,8 +79,7 @@ __global__ void mis_finish_kernel(int n, const int* __restrict__ state, int* __r
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct MisCarve {
-  float *key_a, *key_b;
-  unsigned *idx_a, *idx_b, *counter;
+  unsigned *key_a, *key_b, *idx_a, *idx_b, *counter;
   int *rank, *state;
   void* temp;
   size_t temp_bytes, total;
@@ -80,7 +87,7 @@ struct MisCarve {
 
 hipError_t mis_carve(void* base, int n, MisCarve* c) {
   size_t t = 0;
-  hipError_t er = rocprim::radix_sort_pairs_desc(nullptr, t, (float*)nullptr, (float*)nullptr, (unsigned*)nullptr,
+  hipError_t er = rocprim::radix_sort_pairs_desc(nullptr, t, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
                                                  (unsigned*)nullptr, (size_t)n, 0, 32, 0, false);
   if (er != hipSuccess) return er;
   c->temp_bytes = t;
@@ -90,8 +97,8 @@ hipError_t mis_carve(void* base, int n, MisCarve* c) {
     cur += up256(bytes);
     return base ? (void*)((char*)base + at) : (void*)nullptr;
   };
-  c->key_a = (float*)take(4 * (size_t)n);
-  c->key_b = (float*)take(4 * (size_t)n);
+  c->key_a = (unsigned*)take(4 * (size_t)n);
+  c->key_b = (unsigned*)take(4 * (size_t)n);
   c->idx_a = (unsigned*)take(4 * (size_t)n);
   c->idx_b = (unsigned*)take(4 * (size_t)n);
   c->rank = (int*)take(4 * (size_t)n);
@@ -129,10 +136,10 @@ int difusco_mis_decode(int n_nodes, const int32_t* rowptr, const int32_t* col, c
   hipStream_t st = (hipStream_t)stream;
   const int n = n_nodes;
   const unsigned g1 = (unsigned)((n + 255) / 256);
-  hipLaunchKernelGGL(mis_iota_kernel, dim3(g1), dim3(256), 0, st, n, c.idx_a);
+  hipLaunchKernelGGL(mis_key_kernel, dim3(g1), dim3(256), 0, st, n, scores, c.key_a, c.idx_a);
   size_t tb = c.temp_bytes;
-  // descending by score; the sort is stable, so equal scores keep increasing index order
-  er = rocprim::radix_sort_pairs_desc(c.temp, tb, scores, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
+  // descending by key; the sort is stable, so equal keys keep increasing index order
+  er = rocprim::radix_sort_pairs_desc(c.temp, tb, c.key_a, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
   if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "radix_sort_pairs_desc: %s", hipGetErrorString(er));
   hipLaunchKernelGGL(mis_rank_kernel, dim3(g1), dim3(256), 0, st, n, c.idx_b, c.rank, c.state);
   const unsigned gw = (unsigned)(((long long)n * 64 + 255) / 256);

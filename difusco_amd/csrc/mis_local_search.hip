@@ -71,9 +71,12 @@ __device__ __forceinline__ unsigned long long wave_min64(unsigned long long v) {
   return v;
 }
 
-__global__ void mis_ls_iota_kernel(int n, unsigned* __restrict__ idx) {
+// the sort key of difusco_mis_decode (mis_sort_key, kernels.h) beside the index
+__global__ void mis_ls_key_kernel(int n, const float* __restrict__ scores, unsigned* __restrict__ key, unsigned* __restrict__ idx) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v < n) idx[v] = (unsigned)v;
+  if (v >= n) return;
+  key[v] = mis_sort_key(__float_as_uint(scores[v]));
+  idx[v] = (unsigned)v;
 }
 
 // rank from the sorted order; the working copy of the set (anything non-zero counts as chosen); no marks yet
@@ -461,8 +464,7 @@ __global__ void mis_it_finish_kernel(int n, const int* __restrict__ sol, int* __
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 struct LsCarve {
-  float* key_b;
-  unsigned *idx_a, *idx_b;
+  unsigned *key_b, *idx_a, *idx_b;
   int *rank, *sol, *state, *tight, *owner, *mark, *prop_u, *prop_w, *win;
   LsCtrl* ctrl;
   void* temp;
@@ -471,7 +473,7 @@ struct LsCarve {
 
 hipError_t ls_carve(void* base, int n, LsCarve* c) {
   size_t t = 0;
-  hipError_t er = rocprim::radix_sort_pairs_desc(nullptr, t, (float*)nullptr, (float*)nullptr, (unsigned*)nullptr,
+  hipError_t er = rocprim::radix_sort_pairs_desc(nullptr, t, (unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr,
                                                  (unsigned*)nullptr, (size_t)n, 0, 32, 0, false);
   if (er != hipSuccess) return er;
   c->temp_bytes = t;
@@ -482,7 +484,7 @@ hipError_t ls_carve(void* base, int n, LsCarve* c) {
     return base ? (void*)((char*)base + at) : (void*)nullptr;
   };
   const size_t row = 4 * (size_t)n;
-  c->key_b = (float*)take(row);
+  c->key_b = (unsigned*)take(row);
   c->idx_a = (unsigned*)take(row);
   c->idx_b = (unsigned*)take(row);
   c->rank = (int*)take(row);
@@ -506,10 +508,11 @@ hipError_t ls_enqueue_begin(const LsCarve& c, int n, const int* rowptr, const in
   const dim3 blk(256), g1((unsigned)((n + 255) / 256)), gw((unsigned)(((long long)n * 64 + 255) / 256));
   hipError_t er = hipMemcpyAsync(c.ctrl, &h, sizeof(h), hipMemcpyHostToDevice, st);
   if (er != hipSuccess) return er;
-  hipLaunchKernelGGL(mis_ls_iota_kernel, g1, blk, 0, st, n, c.idx_a);
+  unsigned* key_a = (unsigned*)c.prop_u;      // free until the first proposal, which comes after the sort
+  hipLaunchKernelGGL(mis_ls_key_kernel, g1, blk, 0, st, n, scores, key_a, c.idx_a);
   size_t tb = c.temp_bytes;
-  // descending by score; the sort is stable, so equal scores keep increasing index order (the order of difusco_mis_decode)
-  er = rocprim::radix_sort_pairs_desc(c.temp, tb, scores, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
+  // descending by key; the sort is stable, so equal keys keep increasing index order (the order of difusco_mis_decode)
+  er = rocprim::radix_sort_pairs_desc(c.temp, tb, key_a, c.key_b, c.idx_a, c.idx_b, (size_t)n, 0, 32, st, false);
   if (er != hipSuccess) return er;
   hipLaunchKernelGGL(mis_ls_setup_kernel, g1, blk, 0, st, n, c.idx_b, solution, c.rank, c.sol, c.mark);
   hipLaunchKernelGGL(mis_ls_check_kernel, gw, blk, 0, st, n, rowptr, col, c.sol, c.ctrl);

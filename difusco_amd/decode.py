@@ -923,12 +923,16 @@ def batched_window_search_ragged(points_list, tours_list, max_iterations=1000, d
                               kick_size, span, seeds, offsets, stats, window, passes)
 
 
-def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host"):
+def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host", stats=None):
     """Drop-in for ``mis_decode_np`` of the reference (``difusco/utils/mis_utils.py:3-18``): ``predictions`` [N] node
     scores (numpy or tensor), ``adj_matrix`` a scipy sparse adjacency (as built at ``pl_mis_model.py:152-154``).
     Returns the 0/1 int numpy array.  Instead of a scipy matrix the caller may pass the ``CsrGraph`` of the denoise
     steps (``graph=``, no host round trip) or the ``edge_index`` the adjacency was built from (``graph_build``: the method of
-    ``graph.build_csr`` for it).  GPU only."""
+    ``graph.build_csr`` for it).  The nodes are visited as by ``np.argsort(-scores, kind="stable")`` on the scores AFTER their
+    cast to float32: decreasing score, -0.0 and +0.0 equal, NaN after everything else, equal scores by increasing node id - so
+    float64 scores that collapse to one float32 value are a tie by id.  The adjacency must be symmetric (self loops and
+    duplicate entries are allowed, a graph without any entry gives all ones).  ``stats`` (a dict) receives ``rounds``, the
+    parallel rounds the decode ran.  GPU only."""
     from .graph import build_csr
     device = torch.device(device)
     L = _lib.lib()
@@ -944,11 +948,15 @@ def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, 
     _lib.check(L.difusco_mis_decode_workspace_bytes(n, ctypes.byref(nbytes)))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
     sol = torch.empty(n, dtype=torch.int32, device=device)
+    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
+    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
     rounds = ctypes.c_int32()
-    _lib.check(L.difusco_mis_decode(n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(graph.col.data_ptr()),
+    _lib.check(L.difusco_mis_decode(n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
                                     ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(sol.data_ptr()),
                                     ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(rounds),
                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    if stats is not None:
+        stats["rounds"] = int(rounds.value)
     return sol.cpu().numpy().astype(int)
 
 

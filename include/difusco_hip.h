@@ -405,7 +405,18 @@ int difusco_knn_graph(int n_nodes, int k, const double* points, int64_t node_off
  * the symmetric adjacency of the whole call (self loops allowed, as in co_datasets/mis_dataset.py:43-48; the
  * graphs of a batch are independent components); scores: DEVICE float32 [n_nodes] (the final x_t, + 1e-6 or
  * * 0.5 + 0.5 applied); solution: DEVICE int32 [n_nodes], 1 = in the independent set.  Visiting order = decreasing
- * score, equal scores by increasing node id.  *rounds_out (HOST, optional) = parallel rounds used.  Blocks. */
+ * score, equal scores by increasing node id.  *rounds_out (HOST, optional) = parallel rounds used.  Blocks.
+ *   order     numpy's argsort(-scores, kind="stable"): -0.0 and +0.0 are one value, every NaN (either sign, any payload)
+ *             ranks after everything else including -inf, equal scores and the NaNs among themselves by increasing node id.
+ *             The library sorts a key of its own (mis_sort_key, csrc/kernels.h), not the float bit patterns.
+ *   rounds    level(v) = 1 + max level(u) over the neighbours u != v that rank before v, 1 without one; a node of level l has
+ *             decided by the end of round l, and the host polls after every fourth round, so
+ *             4 <= *rounds_out <= 4 * ceil(max level / 4) and *rounds_out % 4 == 0.
+ *   symmetry  the adjacency must be symmetric: a node reads its OWN row for the neighbours that can exclude it, where the
+ *             reference excludes through the row of the node it takes.  Not checked.  Self entries are skipped, duplicate
+ *             entries change nothing, rows may be empty.
+ *   col       must not be null even when no row has an entry (it is not read then): a caller without entries passes any
+ *             device address, as the Python wrappers do.  The same holds for the two MIS searches below. */
 int difusco_mis_decode_workspace_bytes(int n_nodes, size_t* bytes);
 int difusco_mis_decode(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores, int32_t* solution,
                        void* workspace, size_t workspace_bytes, int32_t* rounds_out, void* stream);

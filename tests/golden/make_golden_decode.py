@@ -136,6 +136,46 @@ def mis_fixtures():
         print(name, "set size", int(sol.sum()))
 
 
+def save_npz_fixed(path, arrays):
+    """np.savez_compressed with a fixed member date, so that the same arrays give the same bytes on every run."""
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as zf:
+        for key, value in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asanyarray(value), allow_pickle=False)
+
+
+def mis_zoo_fixtures():
+    """mis_decode_np of the reference (imported unmodified) on every structure of tests/mis_decode_cases.py up to n = 4097 with
+    the ``distinct`` scores: tie-free, so the reference's unstable argsort has one answer.  One file, three arrays per case
+    (``<case>__edge_index`` int32, ``<case>__predictions`` float32, ``<case>__solution`` int8).  The matrix gets an explicit
+    shape: scipy cannot infer one from no entries, and would infer too small a one where the last nodes have empty rows."""
+    import scipy.sparse
+    sys.path.insert(0, os.path.dirname(HERE))
+    import mis_decode_cases as Z
+    spec = importlib.util.spec_from_file_location("ref_mis_utils", os.path.join(REF, "utils", "mis_utils.py"))
+    mu = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mu)
+    arrays = {"provenance": np.array("reference: utils/mis_utils.mis_decode_np on tests/mis_decode_cases.FIXTURE_STRUCTURES")}
+    for name in Z.FIXTURE_STRUCTURES:
+        n, ei = Z.STRUCTURES[name]
+        pred = Z.make_scores("distinct", n, seed=sum(map(ord, name)))
+        assert pred.dtype == np.float32 and len(np.unique(pred)) == n
+        adj = scipy.sparse.coo_matrix((np.ones(ei.shape[1], dtype=np.int64), (ei[0], ei[1])), shape=(n, n))
+        sol = mu.mis_decode_np(pred, adj)
+        arrays[f"{name}__edge_index"] = ei.astype(np.int32)
+        arrays[f"{name}__predictions"] = pred
+        arrays[f"{name}__solution"] = sol.astype(np.int8)
+        print(name, "n", n, "E", ei.shape[1], "set size", int(sol.sum()))
+    save_npz_fixed(os.path.join(HERE, "mis_decode_zoo.npz"), arrays)
+
+
 if __name__ == "__main__":
+    if "--mis-zoo" in sys.argv:      # only the zoo file; every other fixture stays as recorded
+        mis_zoo_fixtures()
+        sys.exit(0)
     mis_fixtures()
+    mis_zoo_fixtures()
     main()

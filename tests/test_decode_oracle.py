@@ -92,7 +92,8 @@ def test_two_opt_oracle_matches_reference_fixture(path):
     assert np.array_equal(out, z["tours_out"])
 
 
-MIS = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "mis_decode_*.npz")))
+# one graph per file; mis_decode_zoo.npz holds many cases under other keys and is read by tests/test_mis_decode_host.py
+MIS = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), "golden", "mis_decode_*.npz")) if not p.endswith("_zoo.npz"))
 
 
 @pytest.mark.parametrize("path", MIS, ids=[os.path.basename(p)[11:-4] for p in MIS])

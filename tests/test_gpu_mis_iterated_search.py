@@ -80,6 +80,20 @@ def test_empty_rows_isolated_nodes_self_loops_and_one_node(dev):
             assert sol.tolist() == [1] and per.tolist() == [[0, 0, 1, 1]]
 
 
+def test_a_graph_without_any_entry(dev):
+    """No col array at all: every node ends in the set, with 0 swaps, from the empty set and from a partial one; the kicks find
+    every node in the set already."""
+    none = np.zeros((2, 0), dtype=np.int64)
+    sc = np.array([.5, 0, -0.0, 1, .5, 0, .25], dtype=np.float32)
+    for start in (np.zeros(7, dtype=int), np.array([0, 1, 0, 0, 1, 0, 0])):
+        from difusco_amd.decode import mis_iterated_search_np
+        stats = {}
+        mis_iterated_search_np(sc, start, edge_index=none, device=dev, seeds=[3], kicks=4, kick_size=2, stats=stats)
+        assert stats["swaps"] == 0 and stats["inserts"] == 7 - int(start.sum())
+        sol, per, _ = _same(dev, 7, none, sc, start, seeds=[3], kicks=4, kick_size=2)
+        assert sol.tolist() == [1] * 7 and per[0, 2:].tolist() == [7, 7]
+
+
 def test_duplicate_neighbour_entries(dev):
     """Every entry twice.  The descent counts a doubled member twice (a node next to it is never a candidate), so only graphs on
     which that changes nothing can equal the restatement: in K4 the candidates of the member are pairwise adjacent either way,

@@ -91,6 +91,28 @@ def test_isolated_nodes_self_loops_and_one_node(dev):
         assert _same(dev, 1, loops, np.array([.3], dtype=np.float32), np.ones(1, dtype=int)).tolist() == [1]
 
 
+def test_a_graph_without_any_entry(dev):
+    """No col array at all: every node ends in the set, with 0 swaps, from the empty set and from a partial one."""
+    from difusco_amd.decode import mis_local_search_np
+    none = np.zeros((2, 0), dtype=np.int64)
+    sc = np.array([.5, 0, -0.0, 1, .5, 0, .25], dtype=np.float32)
+    for start in (np.zeros(7, dtype=int), np.array([0, 1, 0, 0, 1, 0, 0])):
+        stats = {}
+        got = mis_local_search_np(sc, start, edge_index=none, device=dev, stats=stats)
+        assert got.tolist() == [1] * 7 and stats["swaps"] == 0 and stats["inserts"] == 7 - int(start.sum())
+        _same(dev, 7, none, sc, start)
+
+
+def test_nan_scores_rank_last_as_in_the_decode(dev):
+    """The rank is the decode's: NaN of either sign after everything else, the two zeros one value (tests/mis_decode_cases.py)."""
+    import mis_decode_cases as Z
+    for structure, kind in (("sparse_257", "with_nan"), ("union_40", "with_nan"), ("sparse_255", "mixed_zero_signs")):
+        c = Z.case(structure, kind)
+        got = _same(dev, c["n"], c["edge_index"], c["scores"], np.zeros(c["n"], dtype=int), 0)      # the insertion phase alone
+        assert np.array_equal(got, c["want"])                # from the empty set that is the greedy decode
+        _same(dev, c["n"], c["edge_index"], c["scores"], c["want"])
+
+
 @pytest.mark.parametrize("cap", [None, 1, 2])
 def test_union_equals_solo_calls(dev, cap):
     from difusco_amd.decode import mis_local_search_np
