@@ -21,6 +21,42 @@ def _dev(x, dtype, device):
     return x.to(device=device, dtype=dtype).contiguous()
 
 
+def _ptr(t):
+    """The address of a tensor's first element, as the library takes it."""
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _stream(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _gpu_only(who, device):
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.DifuscoHipError(f"{who} runs on the GPU only (no CPU fallback)")
+    return device
+
+
+def _workspace(size_fn, *sizes, device):
+    """The workspace of one call: (uint8 device tensor, its bytes), sized by the entry's ``_workspace_bytes``."""
+    nbytes = ctypes.c_size_t()
+    _lib.check(size_fn(*sizes, ctypes.byref(nbytes)))
+    return torch.empty(nbytes.value, dtype=torch.uint8, device=device), nbytes.value
+
+
+def _philox_table(seeds, offsets, count, noun, device):
+    """The Philox keys and first offsets of ``count`` streams (default 0; masked to 64 bits) as two int64 device tensors.  Both
+    lengths are checked before either is uploaded."""
+    mask = (1 << 64) - 1
+    table = []
+    for name, v in (("seeds", seeds), ("offsets", offsets)):
+        v = [0] * count if v is None else [int(x) & mask for x in v]
+        if len(v) != count:
+            raise ValueError(f"{name}: {len(v)} entries for {count} {noun}")
+        table.append(np.array(v, dtype=np.uint64).view(np.int64))
+    return [torch.from_numpy(t).to(device) for t in table]
+
+
 def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=False, parallel_sampling=1, *, device="cuda:0",
                 return_completed=False):
     """``adj_mat``: [parallel_sampling * E] (or [parallel_sampling, E]) heat values in the edge order of
@@ -41,21 +77,16 @@ def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=False, parallel_
     E = ei.shape[1]
     if heat.shape[1] != E:
         raise ValueError(f"adj_mat holds {heat.shape[1]} values per sample for {E} edges")
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_merge_workspace_bytes(E, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    ws, nbytes = _workspace(L.difusco_tsp_merge_workspace_bytes, E, device=device)
     row, col = ei[0].contiguous(), ei[1].contiguous()
     # one C call for all samples of the graph (the pair-key sort is shared; the per-sample loop of tsp_utils.py:100-145 runs
     # inside the library)
     tours_np = np.empty((parallel_sampling, n + 1), dtype=np.int32)
     iters = np.zeros(parallel_sampling, dtype=np.int64)
     done_np = np.zeros(parallel_sampling, dtype=np.int32)
-    _lib.check(L.difusco_tsp_merge_tours(n, E, ctypes.c_void_p(row.data_ptr()), ctypes.c_void_p(col.data_ptr()),
-                                         ctypes.c_void_p(heat.data_ptr()), ctypes.c_void_p(pts.data_ptr()), parallel_sampling,
-                                         ctypes.c_void_p(ws.data_ptr()), nbytes.value,
+    _lib.check(L.difusco_tsp_merge_tours(n, E, _ptr(row), _ptr(col), _ptr(heat), _ptr(pts), parallel_sampling, _ptr(ws), nbytes,
                                          tours_np.ctypes.data_as(ctypes.c_void_p), iters.ctypes.data_as(ctypes.c_void_p),
-                                         done_np.ctypes.data_as(ctypes.c_void_p), stream))
+                                         done_np.ctypes.data_as(ctypes.c_void_p), _stream(device)))
     tours = [t.tolist() for t in tours_np]
     done = [bool(v) for v in done_np]
     merge_iterations = float(np.mean(iters))
@@ -113,21 +144,17 @@ def merge_tours_batch(heats, points, edge_indices, sparse_graph=False, parallel_
     pts_all = torch.cat(pts).contiguous()
     if sparse_graph:
         row, col = torch.cat([e[0] for e in eis]).contiguous(), torch.cat([e[1] for e in eis]).contiguous()
-        row_p, col_p = ctypes.c_void_p(row.data_ptr()), ctypes.c_void_p(col.data_ptr())
+        row_p, col_p = _ptr(row), _ptr(col)
     else:
         row_p = col_p = None
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_merge_batch_workspace_bytes(G, graph_n.ctypes.data, graph_e.ctypes.data, graph_p.ctypes.data,
-                                                         ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_tsp_merge_batch_workspace_bytes, G, graph_n.ctypes.data, graph_e.ctypes.data,
+                            graph_p.ctypes.data, device=device)
     S = int(graph_p.sum())
     tours_np = np.empty(int(((graph_n.astype(np.int64) + 1) * graph_p).sum()), dtype=np.int32)
     iters, done_np = np.zeros(S, dtype=np.int64), np.zeros(S, dtype=np.int32)
     _lib.check(L.difusco_tsp_merge_batch(G, graph_n.ctypes.data, graph_e.ctypes.data, graph_p.ctypes.data, row_p, col_p,
-                                         ctypes.c_void_p(heat.data_ptr()), ctypes.c_void_p(pts_all.data_ptr()),
-                                         MERGE_STATE_GLOBAL if state == "global" else 0, ctypes.c_void_p(ws.data_ptr()),
-                                         nbytes.value, tours_np.ctypes.data, iters.ctypes.data, done_np.ctypes.data,
-                                         ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+                                         _ptr(heat), _ptr(pts_all), MERGE_STATE_GLOBAL if state == "global" else 0, _ptr(ws),
+                                         nbytes, tours_np.ctypes.data, iters.ctypes.data, done_np.ctypes.data, _stream(device)))
     out, t0, s0 = [], 0, 0
     for g in range(G):
         t1, s1 = t0 + par[g] * (ns[g] + 1), s0 + par[g]
@@ -160,6 +187,79 @@ def two_opt_screen_bound(max_abs_coord):
     return float(eps.value) if rc == 1 else None
 
 
+# The tour searches come in three forms.  ``_torch``: the tours [B, N + 1] of ONE instance; ``_grouped``: G instances of one
+# size, points [G, N, 2] and tours [G * P, N + 1]; ``_ragged``: lists of G instances of any sizes.  All three run one ``_ragged``
+# library entry on per-group arrays (``_per_group``, ``_RaggedBatch``) and differ in how they hand the results back (``_as_form``).
+
+
+def _grouped_arrays(points, tours):
+    """The arguments of a ``_grouped`` function as numpy arrays: (points [G, N, 2] float64, tours [G * P, N + 1], P)."""
+    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
+    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
+        raise ValueError("points must be [groups, N, 2]")
+    G, n = pts.shape[0], pts.shape[1]
+    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
+        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
+    return pts, t, t.shape[0] // G
+
+
+def _per_group(form, points, tours):
+    """The arguments of a form as (float64 point arrays, int32 tour arrays), one of each per group."""
+    if form == "torch":
+        return [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tours, dtype=np.int32)]
+    if form == "grouped":
+        pts, t, P = _grouped_arrays(points, tours)
+        return ([np.ascontiguousarray(p) for p in pts],
+                [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(pts.shape[0])])
+    return [np.ascontiguousarray(p, dtype=np.float64) for p in points], [np.ascontiguousarray(t, dtype=np.int32) for t in tours]
+
+
+def _as_form(form, tours, stats):
+    """(int64 tours per group, a dict of per-group arrays) as a form returns them: the one instance and ints; one array of all
+    tours and the arrays; as they are."""
+    if form == "torch":
+        return tours[0], {k: int(v[0]) for k, v in stats.items()}
+    if form == "grouped":
+        return np.concatenate(tours, axis=0), stats
+    return tours, stats
+
+
+class _RaggedBatch:
+    """Checked per-group point and tour arrays as every ``_ragged`` library entry takes them: the group tables on the host,
+    all points and all tours as one device tensor each.  The library refines the tours in place."""
+
+    def __init__(self, pts, trs, device):
+        self.shapes = [t.shape for t in trs]
+        self.groups = len(pts)
+        self.group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+        self.group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+        self.d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+        self.d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
+
+    @property
+    def sizes(self):
+        """The first arguments of every ``_ragged_workspace_bytes``."""
+        return self.groups, self.group_n.ctypes.data, self.group_tours.ctypes.data
+
+    @property
+    def head(self):
+        """The first arguments of every ``_ragged`` entry."""
+        return (*self.sizes, _ptr(self.d_pts), _ptr(self.d_tours))
+
+    def group_stats(self):
+        """The per-group counters of the multi-move entries, in the order of their arguments."""
+        G = self.groups
+        return {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
+                "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
+                "or_opt_moves": np.zeros(G, dtype=np.int64)}
+
+    def read_tours(self):
+        """The tours as they are on the device now: int64 numpy, one array per group."""
+        flat = self.d_tours.cpu().numpy().astype(np.int64)
+        cuts = np.cumsum([rows * width for rows, width in self.shapes])[:-1]
+        return [f.reshape(shape) for f, shape in zip(np.split(flat, cuts), self.shapes)]
+
+
 def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
     """Drop-in for ``batched_two_opt_torch`` of the reference (``difusco/utils/tsp_utils.py:12-49``): ``points``
     float64 [N,2] numpy, ``tour`` int [B, N+1] numpy (closed tours over the same points); returns
@@ -167,30 +267,24 @@ def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *,
     ``difusco_tsp_two_opt_screened``: the same tours and iterator, float64 only for the moves a float32 screen cannot rule out;
     ``stats`` (a dict) then receives ``exact_pairs``, the number of pairs that took the float64 path."""
     method = check_two_opt_method(method)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError("batched_two_opt_torch of difusco_amd runs on the GPU only (no CPU fallback)")
-    L = _lib.lib()
-    pts = _dev(np.asarray(points, dtype=np.float64), torch.float64, device)
-    tours = _dev(np.asarray(tour), torch.int32, device)
-    if tours.dim() != 2 or tours.shape[1] != pts.shape[0] + 1:
+    device = _gpu_only("batched_two_opt_torch of difusco_amd", device)
+    pts, tours = np.asarray(points, dtype=np.float64), np.asarray(tour)
+    if tours.ndim != 2 or tours.shape[1] != pts.shape[0] + 1:
         raise ValueError("tour must be [batch, N + 1] over the N points")
     n, batch = pts.shape[0], tours.shape[0]
-    nbytes = ctypes.c_size_t()
+    pts, tours = _dev(pts, torch.float64, device), _dev(tours, torch.int32, device)
+    L = _lib.lib()
     screened = method == "screened"
-    _lib.check((L.difusco_tsp_two_opt_screened_workspace_bytes if screened else L.difusco_tsp_two_opt_workspace_bytes)(
-        n, batch, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_tsp_two_opt_screened_workspace_bytes if screened else L.difusco_tsp_two_opt_workspace_bytes,
+                            n, batch, device=device)
     it, pairs = ctypes.c_int64(), ctypes.c_int64()
-    head = (n, batch, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(tours.data_ptr()), int(max_iterations),
-            ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(it))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    head = (n, batch, _ptr(pts), _ptr(tours), int(max_iterations), _ptr(ws), nbytes, ctypes.byref(it))
     if screened:
-        _lib.check(L.difusco_tsp_two_opt_screened(*head, ctypes.byref(pairs), stream))
+        _lib.check(L.difusco_tsp_two_opt_screened(*head, ctypes.byref(pairs), _stream(device)))
         if stats is not None:
             stats["exact_pairs"] = int(pairs.value)
     else:
-        _lib.check(L.difusco_tsp_two_opt(*head, stream))
+        _lib.check(L.difusco_tsp_two_opt(*head, _stream(device)))
     return tours.cpu().numpy().astype(np.int64), int(it.value)
 
 
@@ -201,34 +295,23 @@ def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0",
     Returns ``(tours int64 numpy [G * P, N + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
     ``batched_two_opt_torch`` (``difusco_tsp_two_opt_grouped_screened``)."""
     method = check_two_opt_method(method)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError("batched_two_opt_grouped runs on the GPU only (no CPU fallback)")
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
+    device = _gpu_only("batched_two_opt_grouped", device)
+    pts, t, P = _grouped_arrays(points, tours)
     G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
     pts, t = _dev(pts, torch.float64, device), _dev(t, torch.int32, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
     screened = method == "screened"
-    _lib.check((L.difusco_tsp_two_opt_grouped_screened_workspace_bytes if screened
-                else L.difusco_tsp_two_opt_grouped_workspace_bytes)(n, G, P, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_tsp_two_opt_grouped_screened_workspace_bytes if screened
+                            else L.difusco_tsp_two_opt_grouped_workspace_bytes, n, G, P, device=device)
     its = np.zeros(G, dtype=np.int64)
     pairs = ctypes.c_int64()
-    head = (n, G, P, ctypes.c_void_p(pts.data_ptr()), ctypes.c_void_p(t.data_ptr()), int(max_iterations),
-            ctypes.c_void_p(ws.data_ptr()), nbytes.value, its.ctypes.data_as(ctypes.c_void_p))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    head = (n, G, P, _ptr(pts), _ptr(t), int(max_iterations), _ptr(ws), nbytes, its.ctypes.data)
     if screened:
-        _lib.check(L.difusco_tsp_two_opt_grouped_screened(*head, ctypes.byref(pairs), stream))
+        _lib.check(L.difusco_tsp_two_opt_grouped_screened(*head, ctypes.byref(pairs), _stream(device)))
         if stats is not None:
             stats["exact_pairs"] = int(pairs.value)
     else:
-        _lib.check(L.difusco_tsp_two_opt_grouped(*head, stream))
+        _lib.check(L.difusco_tsp_two_opt_grouped(*head, _stream(device)))
     return t.cpu().numpy().astype(np.int64), its
 
 
@@ -239,11 +322,8 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     Returns ``(list of int64 numpy [P_g, n_g + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
     ``batched_two_opt_torch``; with ``method="exact"`` ``exact_pairs`` counts every pair of every sweep."""
     method = check_two_opt_method(method)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError("batched_two_opt_ragged runs on the GPU only (no CPU fallback)")
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
+    device = _gpu_only("batched_two_opt_ragged", device)
+    pts, trs = _per_group("ragged", points_list, tours_list)
     G = len(pts)
     if G < 1 or len(trs) != G:
         raise ValueError(f"{len(trs)} tour arrays for {G} instances (at least one instance)")
@@ -252,28 +332,17 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
             raise ValueError(f"points_list[{g}] must be [n, 2]")
         if t.ndim != 2 or t.shape[1] != p.shape[0] + 1 or t.shape[0] < 1:
             raise ValueError(f"tours_list[{g}] must be [P, {p.shape[0] + 1}] closed tours over the {p.shape[0]} points, P >= 1")
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
     code = TWO_OPT_METHODS.index(method)
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_two_opt_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data, code,
-                                                            ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_tsp_two_opt_ragged_workspace_bytes, *batch.sizes, code, device=device)
     its = np.zeros(G, dtype=np.int64)
     pairs = ctypes.c_int64()
-    _lib.check(L.difusco_tsp_two_opt_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
-                                            ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), code,
-                                            ctypes.c_void_p(ws.data_ptr()), nbytes.value, its.ctypes.data_as(ctypes.c_void_p),
-                                            ctypes.byref(pairs),
-                                            ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    _lib.check(L.difusco_tsp_two_opt_ragged(*batch.head, int(max_iterations), code, _ptr(ws), nbytes, its.ctypes.data,
+                                            ctypes.byref(pairs), _stream(device)))
     if stats is not None:
         stats["exact_pairs"] = int(pairs.value)
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], its
+    return batch.read_tours(), its
 
 
 LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt")
@@ -288,11 +357,9 @@ def check_local_search(local_search, two_opt_method="exact"):
 
 
 def _local_search_checked(who, pts, trs, max_iterations, max_rounds, device):
-    """The argument checks of the three local-search functions (before any library call) on float64 point arrays ``pts`` and
-    int32 tour arrays ``trs``, one per group."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError(f"{who} runs on the GPU only (no CPU fallback)")
+    """The argument checks of the local-search functions (before any library call) on float64 point arrays ``pts`` and int32
+    tour arrays ``trs``, one per group."""
+    device = _gpu_only(who, device)
     if int(max_iterations) != max_iterations or max_iterations < 0:
         raise ValueError(f"max_iterations = {max_iterations!r}: an integer >= 0")
     if int(max_rounds) != max_rounds or max_rounds < 1:
@@ -307,28 +374,22 @@ def _local_search_checked(who, pts, trs, max_iterations, max_rounds, device):
     return device
 
 
-def _local_search_run(pts, trs, max_iterations, max_rounds, device):
-    """One ``difusco_tsp_local_search_ragged`` call on checked arguments.  Returns (int64 tours per group, two_opt_iterations,
-    or_opt_iterations [G] int64, rounds [G] int32)."""
-    G = len(pts)
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+def _local_search(form, points, tours, max_iterations, device, max_rounds, stats):
+    """``batched_local_search_<form>``: the checks and one ``difusco_tsp_local_search_ragged`` call."""
+    pts, trs = _per_group(form, points, tours)
+    device = _local_search_checked(f"batched_local_search_{form}", pts, trs, max_iterations, max_rounds, device)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_local_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
-                                                                 ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    two, orr, rounds = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int32)
-    _lib.check(L.difusco_tsp_local_search_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
-                                                 ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), int(max_rounds),
-                                                 ctypes.c_void_p(ws.data_ptr()), nbytes.value, two.ctypes.data, orr.ctypes.data,
-                                                 rounds.ctypes.data,
-                                                 ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], two, orr, rounds
+    ws, nbytes = _workspace(L.difusco_tsp_local_search_ragged_workspace_bytes, *batch.sizes, device=device)
+    G = batch.groups
+    st = {"two_opt_iterations": np.zeros(G, dtype=np.int64), "or_opt_iterations": np.zeros(G, dtype=np.int64),
+          "rounds": np.zeros(G, dtype=np.int32)}
+    _lib.check(L.difusco_tsp_local_search_ragged(*batch.head, int(max_iterations), int(max_rounds), _ptr(ws), nbytes,
+                                                 *(v.ctypes.data for v in st.values()), _stream(device)))
+    out, st = _as_form(form, batch.read_tours(), st)
+    if stats is not None:
+        stats["or_opt_iterations"], stats["rounds"] = st["or_opt_iterations"], st["rounds"]
+    return out, st["two_opt_iterations"]
 
 
 def batched_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
@@ -338,12 +399,7 @@ def batched_local_search_torch(points, tour, max_iterations=1000, device="cuda:0
     Or-opt phase applies nothing or ``max_rounds`` rounds ran (``difusco_tsp_local_search_ragged``, include/difusco_hip.h; GPU
     only).  No tour ends longer than 2-opt alone leaves it.  Returns ``(tour int64 numpy [B, N+1], two_opt_iterations)``;
     ``stats`` (a dict) receives ``or_opt_iterations`` and ``rounds``."""
-    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
-    device = _local_search_checked("batched_local_search_torch", pts, trs, max_iterations, max_rounds, device)
-    out, two, orr, rounds = _local_search_run(pts, trs, max_iterations, max_rounds, device)
-    if stats is not None:
-        stats["or_opt_iterations"], stats["rounds"] = int(orr[0]), int(rounds[0])
-    return out[0], int(two[0])
+    return _local_search("torch", points, tour, max_iterations, device, max_rounds, stats)
 
 
 def batched_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
@@ -351,62 +407,36 @@ def batched_local_search_grouped(points, tours, max_iterations=1000, device="cud
     [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_local_search_torch`` call returns.
     Returns ``(tours int64 numpy [G * P, N + 1], two_opt_iterations int64 numpy [G])``; ``stats`` receives ``or_opt_iterations``
     (int64 [G]) and ``rounds`` (int32 [G])."""
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
-    G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
-    pts_l = [np.ascontiguousarray(p) for p in pts]
-    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
-    device = _local_search_checked("batched_local_search_grouped", pts_l, trs, max_iterations, max_rounds, device)
-    out, two, orr, rounds = _local_search_run(pts_l, trs, max_iterations, max_rounds, device)
-    if stats is not None:
-        stats["or_opt_iterations"], stats["rounds"] = orr, rounds
-    return np.concatenate(out, axis=0), two
+    return _local_search("grouped", points, tours, max_iterations, device, max_rounds, stats)
 
 
 def batched_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
     """``batched_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.  Returns
     ``(list of int64 numpy [P_g, n_g + 1], two_opt_iterations int64 numpy [G])``; ``stats``: as ``batched_local_search_grouped``."""
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
-    device = _local_search_checked("batched_local_search_ragged", pts, trs, max_iterations, max_rounds, device)
-    out, two, orr, rounds = _local_search_run(pts, trs, max_iterations, max_rounds, device)
-    if stats is not None:
-        stats["or_opt_iterations"], stats["rounds"] = orr, rounds
-    return out, two
+    return _local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, stats)
 
 
-def _multi_two_opt_checked(who, pts, trs, max_iterations, select_rounds, device):
-    """The argument checks of the three multi-move 2-opt functions (before any library call)."""
+def _multi_move_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device):
+    """The argument checks of the multi-move functions (before any library call)."""
     if int(select_rounds) != select_rounds or select_rounds < 1:
         raise ValueError(f"select_rounds = {select_rounds!r}: an integer >= 1")
-    return _local_search_checked(who, pts, trs, max_iterations, 1, device)
+    return _local_search_checked(who, pts, trs, max_iterations, max_rounds, device)
 
 
-def _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device):
-    """One ``difusco_tsp_multi_two_opt_ragged`` call on checked arguments.  Returns (int64 tours per group, sweeps, moves [G]
-    int64)."""
-    G = len(pts)
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+def _multi_two_opt(form, points, tours, max_iterations, device, select_rounds, stats):
+    """``batched_multi_two_opt_<form>``: the checks and one ``difusco_tsp_multi_two_opt_ragged`` call."""
+    pts, trs = _per_group(form, points, tours)
+    device = _multi_move_checked(f"batched_multi_two_opt_{form}", pts, trs, max_iterations, 1, select_rounds, device)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_multi_two_opt_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
-                                                                  ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    sweeps, moves = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
-    _lib.check(L.difusco_tsp_multi_two_opt_ragged(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()),
-                                                  ctypes.c_void_p(d_tours.data_ptr()), int(max_iterations), int(select_rounds),
-                                                  ctypes.c_void_p(ws.data_ptr()), nbytes.value, sweeps.ctypes.data, moves.ctypes.data,
-                                                  ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], sweeps, moves
+    ws, nbytes = _workspace(L.difusco_tsp_multi_two_opt_ragged_workspace_bytes, *batch.sizes, device=device)
+    st = {"sweeps": np.zeros(batch.groups, dtype=np.int64), "moves": np.zeros(batch.groups, dtype=np.int64)}
+    _lib.check(L.difusco_tsp_multi_two_opt_ragged(*batch.head, int(max_iterations), int(select_rounds), _ptr(ws), nbytes,
+                                                  st["sweeps"].ctypes.data, st["moves"].ctypes.data, _stream(device)))
+    out, st = _as_form(form, batch.read_tours(), st)
+    if stats is not None:
+        stats["moves"] = st["moves"]
+    return out, st["sweeps"]
 
 
 def batched_multi_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
@@ -415,78 +445,33 @@ def batched_multi_two_opt_torch(points, tour, max_iterations=1000, device="cuda:
     ``difusco_tsp_multi_two_opt_ragged``, include/difusco_hip.h; GPU only; not the reference's one move per sweep, so another
     2-opt optimum).  Every tour runs on its own; at most ``max_iterations`` sweeps.  Returns ``(tour int64 numpy [B, N+1],
     sweeps)``; ``stats`` (a dict) receives ``moves``, the moves applied over all tours."""
-    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
-    device = _multi_two_opt_checked("batched_multi_two_opt_torch", pts, trs, max_iterations, select_rounds, device)
-    out, sweeps, moves = _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device)
-    if stats is not None:
-        stats["moves"] = int(moves[0])
-    return out[0], int(sweeps[0])
+    return _multi_two_opt("torch", points, tour, max_iterations, device, select_rounds, stats)
 
 
 def batched_multi_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
     """``batched_multi_two_opt_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points`` float64
     [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_multi_two_opt_torch`` call returns.
     Returns ``(tours int64 numpy [G * P, N + 1], sweeps int64 numpy [G])``; ``stats`` receives ``moves`` (int64 [G])."""
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
-    G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
-    pts_l = [np.ascontiguousarray(p) for p in pts]
-    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
-    device = _multi_two_opt_checked("batched_multi_two_opt_grouped", pts_l, trs, max_iterations, select_rounds, device)
-    out, sweeps, moves = _multi_two_opt_run(pts_l, trs, max_iterations, select_rounds, device)
-    if stats is not None:
-        stats["moves"] = moves
-    return np.concatenate(out, axis=0), sweeps
+    return _multi_two_opt("grouped", points, tours, max_iterations, device, select_rounds, stats)
 
 
 def batched_multi_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, select_rounds=4, stats=None):
     """``batched_multi_two_opt_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.  Returns
     ``(list of int64 numpy [P_g, n_g + 1], sweeps int64 numpy [G])``; ``stats``: as ``batched_multi_two_opt_grouped``."""
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
-    device = _multi_two_opt_checked("batched_multi_two_opt_ragged", pts, trs, max_iterations, select_rounds, device)
-    out, sweeps, moves = _multi_two_opt_run(pts, trs, max_iterations, select_rounds, device)
-    if stats is not None:
-        stats["moves"] = moves
-    return out, sweeps
+    return _multi_two_opt("ragged", points_list, tours_list, max_iterations, device, select_rounds, stats)
 
 
-def _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device):
-    """The argument checks of the three multi-move local-search functions (before any library call)."""
-    if int(select_rounds) != select_rounds or select_rounds < 1:
-        raise ValueError(f"select_rounds = {select_rounds!r}: an integer >= 1")
-    return _local_search_checked(who, pts, trs, max_iterations, max_rounds, device)
-
-
-def _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device):
-    """One ``difusco_tsp_multi_local_search_ragged`` call on checked arguments.  Returns (int64 tours per group, the stats dict
-    of ``batched_multi_local_search_grouped``)."""
-    G = len(pts)
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+def _multi_local_search(form, points, tours, max_iterations, device, max_rounds, select_rounds):
+    """``batched_multi_local_search_<form>``: the checks and one ``difusco_tsp_multi_local_search_ragged`` call."""
+    pts, trs = _per_group(form, points, tours)
+    device = _multi_move_checked(f"batched_multi_local_search_{form}", pts, trs, max_iterations, max_rounds, select_rounds, device)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_multi_local_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
-                                                                       ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
-           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
-           "or_opt_moves": np.zeros(G, dtype=np.int64)}
-    _lib.check(L.difusco_tsp_multi_local_search_ragged(
-        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
-        int(max_iterations), int(max_rounds), int(select_rounds), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
-        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data,
-        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+    ws, nbytes = _workspace(L.difusco_tsp_multi_local_search_ragged_workspace_bytes, *batch.sizes, device=device)
+    st = batch.group_stats()
+    _lib.check(L.difusco_tsp_multi_local_search_ragged(*batch.head, int(max_iterations), int(max_rounds), int(select_rounds),
+                                                       _ptr(ws), nbytes, *(v.ctypes.data for v in st.values()), _stream(device)))
+    return _as_form(form, batch.read_tours(), st)
 
 
 def batched_multi_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4):
@@ -497,41 +482,21 @@ def batched_multi_local_search_torch(points, tour, max_iterations=1000, device="
     ``difusco_tsp_multi_local_search_ragged``, include/difusco_hip.h; GPU only).  No tour ends longer than the multi-move 2-opt
     leaves it.  Returns ``(tour int64 numpy [B, N+1], stats)``: ``stats`` holds ``two_opt_sweeps``, ``or_opt_sweeps``, ``rounds``
     (the maxima over the tours) and ``two_opt_moves``, ``or_opt_moves`` (the sums over the tours), ints."""
-    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
-    device = _multi_local_search_checked("batched_multi_local_search_torch", pts, trs, max_iterations, max_rounds, select_rounds,
-                                         device)
-    out, stats = _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device)
-    return out[0], {k: int(v[0]) for k, v in stats.items()}
+    return _multi_local_search("torch", points, tour, max_iterations, device, max_rounds, select_rounds)
 
 
 def batched_multi_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4):
     """``batched_multi_local_search_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points``
     float64 [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_multi_local_search_torch`` call
     returns.  Returns ``(tours int64 numpy [G * P, N + 1], stats)``; the entries of ``stats`` are numpy arrays [G]."""
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
-    G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
-    pts_l = [np.ascontiguousarray(p) for p in pts]
-    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
-    device = _multi_local_search_checked("batched_multi_local_search_grouped", pts_l, trs, max_iterations, max_rounds,
-                                         select_rounds, device)
-    out, stats = _multi_local_search_run(pts_l, trs, max_iterations, max_rounds, select_rounds, device)
-    return np.concatenate(out, axis=0), stats
+    return _multi_local_search("grouped", points, tours, max_iterations, device, max_rounds, select_rounds)
 
 
 def batched_multi_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
                                       select_rounds=4):
     """``batched_multi_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.
     Returns ``(list of int64 numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_multi_local_search_grouped``."""
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
-    device = _multi_local_search_checked("batched_multi_local_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds,
-                                         device)
-    return _multi_local_search_run(pts, trs, max_iterations, max_rounds, select_rounds, device)
+    return _multi_local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, select_rounds)
 
 
 TSP_KICK_SIZE, TSP_KICK_SPAN = 16, 30     # the pair of scripts/tsp_iterated_search_table.py (DESIGN 5.2g)
@@ -639,14 +604,15 @@ def _heat_graph(who, pts, trs, heat, edge_index, device):
             pad(torch.cat(hs).contiguous(), torch.float32))
 
 
-def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
-                         stats, descent="full", compact_select_max=TSP_COMPACT_SELECT_MAX, kick_bias="uniform", heat=None,
-                         edge_index=None):
-    """The checks of the three iterated-search functions (before any library call) and one
-    ``difusco_tsp_iterated_search_ragged`` call - ``descent="focused"``: one ``difusco_tsp_focused_search_ragged`` call;
-    ``kick_bias="heat"``: one ``difusco_tsp_guided_search_ragged`` call, either descent.
-    Returns (int64 tours per group, the stats dict of ``batched_multi_local_search_grouped``); ``stats`` receives the per-tour
-    arrays and ``host_syncs``."""
+def _iterated_search(form, points, tours, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds, offsets,
+                     stats, descent, compact_select_max, kick_bias, heat, edge_index):
+    """``batched_iterated_search_<form>``: the checks (before any library call) and one ``difusco_tsp_iterated_search_ragged``
+    call - ``descent="focused"``: one ``difusco_tsp_focused_search_ragged`` call; ``kick_bias="heat"``: one
+    ``difusco_tsp_guided_search_ragged`` call, either descent.  ``stats`` receives the per-tour arrays and ``host_syncs``."""
+    who = f"batched_iterated_search_{form}"
+    pts, trs = _per_group(form, points, tours)
+    if form == "torch":                             # one instance: its heat and graph are the one entry of the per-group lists
+        heat, edge_index = None if heat is None else [heat], None if edge_index is None else [edge_index]
     if int(kicks) != kicks or kicks < 0 or kicks >= 2 ** 31:
         raise ValueError(f"kicks = {kicks!r}: an integer >= 0")
     focused = check_tsp_descent(descent) == "focused"
@@ -658,62 +624,39 @@ def _iterated_search_run(who, pts, trs, max_iterations, max_rounds, select_round
     if int(compact_select_max) != compact_select_max or not 0 <= compact_select_max <= TSP_COMPACT_SELECT_MAX:
         raise ValueError(f"compact_select_max = {compact_select_max!r}: an integer in 0 .. {TSP_COMPACT_SELECT_MAX}")
     _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
-    device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
+    device = _multi_move_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
     graph = _heat_graph(who, pts, trs, heat, edge_index, device) if guided else None
     T = sum(t.shape[0] for t in trs)
-    mask = (1 << 64) - 1
-    table = []
-    for name, v in (("seeds", seeds), ("offsets", offsets)):
-        v = [0] * T if v is None else [int(x) & mask for x in v]
-        if len(v) != T:
-            raise ValueError(f"{name}: {len(v)} entries for {T} tours")
-        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
-    G = len(pts)
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    table = _philox_table(seeds, offsets, T, "tours", device)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
-    size_fn = L.difusco_tsp_focused_search_ragged_workspace_bytes if focused else L.difusco_tsp_iterated_search_ragged_workspace_bytes
     if guided:
-        _lib.check(L.difusco_tsp_guided_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data,
-                                                                      graph[0].ctypes.data, ctypes.byref(nbytes)))
+        ws, nbytes = _workspace(L.difusco_tsp_guided_search_ragged_workspace_bytes, *batch.sizes, graph[0].ctypes.data, device=device)
     else:
-        _lib.check(size_fn(G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
-           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
-           "or_opt_moves": np.zeros(G, dtype=np.int64)}
+        ws, nbytes = _workspace(L.difusco_tsp_focused_search_ragged_workspace_bytes if focused
+                                else L.difusco_tsp_iterated_search_ragged_workspace_bytes, *batch.sizes, device=device)
+    out = batch.group_stats()
     per = {"kicks_kept": np.zeros(T, dtype=np.int32), "kicks_improved": np.zeros(T, dtype=np.int32),
            "segments_swapped": np.zeros(T, dtype=np.int64), "first_length": np.zeros(T, dtype=np.float64),
            "final_length": np.zeros(T, dtype=np.float64)}
-    head = (G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
-            int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
-            ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()))
-    tail = (ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-            out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
-            out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_KICK_STATS))
-    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    head = (*batch.head, int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span, _ptr(table[0]),
+            _ptr(table[1]))
+    tail = (_ptr(ws), nbytes, *(v.ctypes.data for v in out.values()), *(per[k].ctypes.data for k in TSP_KICK_STATS))
+    if focused:
+        per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
     if guided:
         group_edges, row_ptr, col, d_heat = graph
-        if focused:
-            per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
         _lib.check(L.difusco_tsp_guided_search_ragged(
-            *head, int(compact_select_max), int(focused), group_edges.ctypes.data, ctypes.c_void_p(row_ptr.data_ptr()),
-            ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(d_heat.data_ptr()), *tail,
-            per["closing_sweeps"].ctypes.data if focused else None, stream))
+            *head, int(compact_select_max), int(focused), group_edges.ctypes.data, _ptr(row_ptr), _ptr(col), _ptr(d_heat), *tail,
+            per["closing_sweeps"].ctypes.data if focused else None, _stream(device)))
     elif focused:
-        per["closing_sweeps"] = np.zeros(T, dtype=np.int32)
         _lib.check(L.difusco_tsp_focused_search_ragged(*head, int(compact_select_max), *tail, per["closing_sweeps"].ctypes.data,
-                                                       stream))
+                                                       _stream(device)))
     else:
-        _lib.check(L.difusco_tsp_iterated_search_ragged(*head, *tail, stream))
+        _lib.check(L.difusco_tsp_iterated_search_ragged(*head, *tail, _stream(device)))
     if stats is not None:
         stats.update(per, host_syncs=int(L.difusco_tsp_search_host_syncs()))
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+    return _as_form(form, batch.read_tours(), out)
 
 
 def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
@@ -739,11 +682,8 @@ def batched_iterated_search_torch(points, tour, max_iterations=1000, device="cud
     ``edge_index=None`` -, numpy arrays or device tensors; edges not sorted by their first row are sorted (stable).  An edge
     absent from the graph counts as heat 0.  ``ValueError`` before any library call: ``"heat"`` without ``heat``, shapes that do
     not match, ``heat`` with ``"uniform"``, an unknown ``kick_bias``.  Constant heat does not reproduce ``"uniform"``."""
-    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
-    out, st = _iterated_search_run("batched_iterated_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                   kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias,
-                                   None if heat is None else [heat], None if edge_index is None else [edge_index])
-    return out[0], {k: int(v[0]) for k, v in st.items()}
+    return _iterated_search("torch", points, tour, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds,
+                            offsets, stats, descent, compact_select_max, kick_bias, heat, edge_index)
 
 
 def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
@@ -755,19 +695,8 @@ def batched_iterated_search_grouped(points, tours, max_iterations=1000, device="
     numpy [G * P, N + 1], stats)``; the entries of the returned stats are numpy arrays [G], the per-tour arrays [G * P].
     ``kick_bias="heat"``: ``heat`` and ``edge_index`` are lists with one entry per instance, as ``merge_tours_batch`` takes them
     (``heat[g]`` [P, E_g] with ``edge_index[g]`` [2, E_g]; [P, N, N] with ``edge_index=None``)."""
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
-    G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
-    pts_l = [np.ascontiguousarray(p) for p in pts]
-    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
-    out, st = _iterated_search_run("batched_iterated_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds,
-                                   device, kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias,
-                                   heat, edge_index)
-    return np.concatenate(out, axis=0), st
+    return _iterated_search("grouped", points, tours, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds,
+                            offsets, stats, descent, compact_select_max, kick_bias, heat, edge_index)
 
 
 def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
@@ -778,11 +707,8 @@ def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000,
     ``batched_multi_local_search_ragged``; ``seeds`` / ``offsets``: one per tour, group after group.  Returns ``(list of int64
     numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_iterated_search_grouped``.  ``kick_bias``, ``heat``, ``edge_index``:
     as there."""
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
-    return _iterated_search_run("batched_iterated_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device,
-                                kicks, kick_size, span, seeds, offsets, stats, descent, compact_select_max, kick_bias, heat,
-                                edge_index)
+    return _iterated_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span,
+                            seeds, offsets, stats, descent, compact_select_max, kick_bias, heat, edge_index)
 
 
 TSP_WINDOW_MIN, TSP_WINDOW_MAX, TSP_WINDOW_MAX_KICKS = 16, 1024, 1024
@@ -818,11 +744,12 @@ def check_tsp_window(local_search, window, passes=1, kicks=0, descent="full", ki
     return int(window), int(passes)
 
 
-def _window_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds, device, kicks, kick_size, span, seeds, offsets,
-                       stats, window, passes):
-    """The checks of the three windowed-search functions (before any library call) and one ``difusco_tsp_window_search_ragged``
-    call.  Returns (int64 tours per group, the stats dict of ``batched_multi_local_search_grouped``); ``stats`` receives the
-    per-tour arrays."""
+def _window_search(form, points, tours, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds, offsets,
+                   stats, window, passes):
+    """``batched_window_search_<form>``: the checks (before any library call) and one ``difusco_tsp_window_search_ragged`` call.
+    ``stats`` receives the per-tour arrays."""
+    who = f"batched_window_search_{form}"
+    pts, trs = _per_group(form, points, tours)
     if int(kicks) != kicks or not 0 <= kicks <= TSP_WINDOW_MAX_KICKS:
         raise ValueError(f"kicks = {kicks!r}: an integer in 0 .. {TSP_WINDOW_MAX_KICKS}")
     if int(window) != window or not TSP_WINDOW_MIN <= window <= TSP_WINDOW_MAX:
@@ -830,47 +757,26 @@ def _window_search_run(who, pts, trs, max_iterations, max_rounds, select_rounds,
     if int(passes) != passes or passes < 1 or passes >= 2 ** 31:
         raise ValueError(f"passes = {passes!r}: an integer >= 1")
     _, kick_size, span = check_tsp_kicks("multi2opt+oropt", 0, kick_size, span)
-    device = _multi_local_search_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
+    device = _multi_move_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device)
     for p in pts:
         if int(passes) * (-(-p.shape[0] // int(window)) + 1) * max(int(kicks), 1) >= 2 ** 32:
             raise ValueError(f"{who}: passes = {passes} with {-(-p.shape[0] // int(window)) + 1} windows and {kicks} kicks each "
                              "needs 2^32 or more Philox offsets per tour")
     T = sum(t.shape[0] for t in trs)
-    mask = (1 << 64) - 1
-    table = []
-    for name, v in (("seeds", seeds), ("offsets", offsets)):
-        v = [0] * T if v is None else [int(x) & mask for x in v]
-        if len(v) != T:
-            raise ValueError(f"{name}: {len(v)} entries for {T} tours")
-        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
-    G = len(pts)
-    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
-    group_tours = np.array([t.shape[0] for t in trs], dtype=np.int32)
+    table = _philox_table(seeds, offsets, T, "tours", device)
+    batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_tsp_window_search_ragged_workspace_bytes(G, group_n.ctypes.data, group_tours.ctypes.data, int(window),
-                                                                  ctypes.byref(nbytes)))
-    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
-    d_tours = _dev(np.concatenate([t.reshape(-1) for t in trs]), torch.int32, device)
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
-    out = {"two_opt_sweeps": np.zeros(G, dtype=np.int64), "or_opt_sweeps": np.zeros(G, dtype=np.int64),
-           "rounds": np.zeros(G, dtype=np.int32), "two_opt_moves": np.zeros(G, dtype=np.int64),
-           "or_opt_moves": np.zeros(G, dtype=np.int64)}
+    ws, nbytes = _workspace(L.difusco_tsp_window_search_ragged_workspace_bytes, *batch.sizes, int(window), device=device)
+    out = batch.group_stats()
     i32s, f64s = ("kicks_kept", "kicks_improved", "passes_kept", "windows_searched", "closing_sweeps"), ("first_length", "final_length")
     per = {k: np.zeros(T, dtype=np.int32 if k in i32s else np.float64 if k in f64s else np.int64) for k in TSP_WINDOW_STATS}
     _lib.check(L.difusco_tsp_window_search_ragged(
-        G, group_n.ctypes.data, group_tours.ctypes.data, ctypes.c_void_p(d_pts.data_ptr()), ctypes.c_void_p(d_tours.data_ptr()),
-        int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span,
-        ctypes.c_void_p(table[0].data_ptr()), ctypes.c_void_p(table[1].data_ptr()), int(window), int(passes),
-        ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-        out["two_opt_sweeps"].ctypes.data, out["or_opt_sweeps"].ctypes.data, out["rounds"].ctypes.data,
-        out["two_opt_moves"].ctypes.data, out["or_opt_moves"].ctypes.data, *(per[k].ctypes.data for k in TSP_WINDOW_STATS),
-        ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+        *batch.head, int(max_iterations), int(max_rounds), int(select_rounds), int(kicks), kick_size, span, _ptr(table[0]),
+        _ptr(table[1]), int(window), int(passes), _ptr(ws), nbytes, *(v.ctypes.data for v in out.values()),
+        *(per[k].ctypes.data for k in TSP_WINDOW_STATS), _stream(device)))
     if stats is not None:
         stats.update(per)
-    flat = d_tours.cpu().numpy().astype(np.int64)
-    cuts = np.cumsum([t.size for t in trs])[:-1]
-    return [f.reshape(t.shape) for f, t in zip(np.split(flat, cuts), trs)], out
+    return _as_form(form, batch.read_tours(), out)
 
 
 def batched_window_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
@@ -886,10 +792,8 @@ def batched_window_search_torch(points, tour, max_iterations=1000, device="cuda:
     stats)``, the stats of ``batched_multi_local_search_torch`` over the first and the closing descent; ``stats`` (a dict)
     receives the per-tour numpy arrays [B] ``first_length``, ``final_length``, ``passes_kept``, ``windows_searched``,
     ``kicks_kept``, ``kicks_improved``, ``segments_swapped``, ``window_sweeps``, ``window_moves`` and ``closing_sweeps``."""
-    pts, trs = [np.ascontiguousarray(points, dtype=np.float64)], [np.ascontiguousarray(tour, dtype=np.int32)]
-    out, st = _window_search_run("batched_window_search_torch", pts, trs, max_iterations, max_rounds, select_rounds, device, kicks,
-                                 kick_size, span, seeds, offsets, stats, window, passes)
-    return out[0], {k: int(v[0]) for k, v in st.items()}
+    return _window_search("torch", points, tour, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds,
+                          offsets, stats, window, passes)
 
 
 def batched_window_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4, kicks=0,
@@ -898,18 +802,8 @@ def batched_window_search_grouped(points, tours, max_iterations=1000, device="cu
     """``batched_window_search_torch`` of G instances at once, the arguments of ``batched_iterated_search_grouped``.  Every tour
     gets what its own call returns.  Returns ``(tours int64 numpy [G * P, N + 1], stats)``; the entries of the returned stats
     are numpy arrays [G], the per-tour arrays [G * P]."""
-    pts, t = np.asarray(points, dtype=np.float64), np.asarray(tours)
-    if pts.ndim != 3 or pts.shape[2] != 2 or pts.shape[0] < 1:
-        raise ValueError("points must be [groups, N, 2]")
-    G, n = pts.shape[0], pts.shape[1]
-    if t.ndim != 2 or t.shape[1] != n + 1 or t.shape[0] % G != 0 or t.shape[0] == 0:
-        raise ValueError("tours must be [groups * P, N + 1] closed tours over the N points of their group")
-    P = t.shape[0] // G
-    pts_l = [np.ascontiguousarray(p) for p in pts]
-    trs = [np.ascontiguousarray(t[g * P:(g + 1) * P], dtype=np.int32) for g in range(G)]
-    out, st = _window_search_run("batched_window_search_grouped", pts_l, trs, max_iterations, max_rounds, select_rounds, device,
-                                 kicks, kick_size, span, seeds, offsets, stats, window, passes)
-    return np.concatenate(out, axis=0), st
+    return _window_search("grouped", points, tours, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds,
+                          offsets, stats, window, passes)
 
 
 def batched_window_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
@@ -917,10 +811,46 @@ def batched_window_search_ragged(points_list, tours_list, max_iterations=1000, d
                                  window, passes=1):
     """``batched_window_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_iterated_search_ragged``.
     Returns ``(list of int64 numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_window_search_grouped``."""
-    pts = [np.ascontiguousarray(p, dtype=np.float64) for p in points_list]
-    trs = [np.ascontiguousarray(t, dtype=np.int32) for t in tours_list]
-    return _window_search_run("batched_window_search_ragged", pts, trs, max_iterations, max_rounds, select_rounds, device, kicks,
-                              kick_size, span, seeds, offsets, stats, window, passes)
+    return _window_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span,
+                          seeds, offsets, stats, window, passes)
+
+
+def _numel(x):
+    return x.numel() if isinstance(x, torch.Tensor) else x.size
+
+
+def _mis_graph(predictions, adj_matrix, graph, edge_index, graph_build, device):
+    """What the three MIS entries read, on the device: (float32 scores [N], the ``CsrGraph`` - built from ``edge_index`` or the
+    scipy ``adj_matrix`` unless given -, its col array)."""
+    from .graph import build_csr
+    scores = _dev(predictions, torch.float32, device).reshape(-1)
+    if graph is None:
+        if edge_index is None:
+            coo = adj_matrix.tocoo()
+            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
+        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
+                          scores.shape[0], device, method=graph_build)
+    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
+    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
+    return scores, graph, col
+
+
+def _mis_solution(solution, n):
+    """``solution`` of a search as an array or tensor of ``n`` entries: checked on the host, before any upload."""
+    solution = solution if isinstance(solution, torch.Tensor) else np.asarray(solution)
+    if _numel(solution) != n:
+        raise ValueError(f"solution holds {_numel(solution)} entries for {n} scores")
+    return solution
+
+
+def _mis_solution_on_device(solution, device):
+    """int32 [N] on the device and never the caller's tensor: the library refines in place."""
+    sol = _dev(solution, torch.int32, device).reshape(-1)
+    return sol.clone() if isinstance(solution, torch.Tensor) else sol
+
+
+def _mis_counters(stats, counters):
+    stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
 
 
 def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, device="cuda:0", graph_build="host", stats=None):
@@ -933,28 +863,15 @@ def mis_decode_np(predictions, adj_matrix=None, *, graph=None, edge_index=None, 
     float64 scores that collapse to one float32 value are a tie by id.  The adjacency must be symmetric (self loops and
     duplicate entries are allowed, a graph without any entry gives all ones).  ``stats`` (a dict) receives ``rounds``, the
     parallel rounds the decode ran.  GPU only."""
-    from .graph import build_csr
     device = torch.device(device)
     L = _lib.lib()
-    scores = _dev(predictions, torch.float32, device).reshape(-1)
+    scores, graph, col = _mis_graph(predictions, adj_matrix, graph, edge_index, graph_build, device)
     n = scores.shape[0]
-    if graph is None:
-        if edge_index is None:
-            coo = adj_matrix.tocoo()
-            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
-        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
-                          n, device, method=graph_build)
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_mis_decode_workspace_bytes(n, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_mis_decode_workspace_bytes, n, device=device)
     sol = torch.empty(n, dtype=torch.int32, device=device)
-    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
-    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
     rounds = ctypes.c_int32()
-    _lib.check(L.difusco_mis_decode(n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
-                                    ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(sol.data_ptr()),
-                                    ctypes.c_void_p(ws.data_ptr()), nbytes.value, ctypes.byref(rounds),
-                                    ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    _lib.check(L.difusco_mis_decode(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), _ptr(ws), nbytes,
+                                    ctypes.byref(rounds), _stream(device)))
     if stats is not None:
         stats["rounds"] = int(rounds.value)
     return sol.cpu().numpy().astype(int)
@@ -977,38 +894,20 @@ def mis_local_search_np(predictions, solution, adj_matrix=None, *, graph=None, e
     by the greedy insertion of the nodes that became free, in the score order of the decode, until no such swap is left or
     ``max_rounds`` rounds ran; never a smaller set, always independent and maximal.  Returns the 0/1 int numpy array; ``stats``
     (a dict) receives ``rounds``, ``swaps`` and ``inserts``.  A set that is not independent raises ``DifuscoHipError``.  GPU only."""
-    from .graph import build_csr
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError("mis_local_search_np runs on the GPU only (no CPU fallback)")
+    device = _gpu_only("mis_local_search_np", device)
     if int(max_rounds) != max_rounds or max_rounds < 0:
         raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 0")
+    n = _numel(predictions)
+    solution = _mis_solution(solution, n)
     L = _lib.lib()
-    scores = _dev(predictions, torch.float32, device).reshape(-1)
-    n = scores.shape[0]
-    sol = _dev(solution if isinstance(solution, torch.Tensor) else np.asarray(solution), torch.int32, device).reshape(-1)
-    if sol.shape[0] != n:
-        raise ValueError(f"solution holds {sol.shape[0]} entries for {n} scores")
-    if isinstance(solution, torch.Tensor):
-        sol = sol.clone()                                  # the library refines in place; the caller's tensor stays
-    if graph is None:
-        if edge_index is None:
-            coo = adj_matrix.tocoo()
-            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
-        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
-                          n, device, method=graph_build)
-    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
-    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_mis_local_search_workspace_bytes(n, int(graph.col.shape[0]), ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    scores, graph, col = _mis_graph(predictions, adj_matrix, graph, edge_index, graph_build, device)
+    sol = _mis_solution_on_device(solution, device)
+    ws, nbytes = _workspace(L.difusco_mis_local_search_workspace_bytes, n, int(graph.col.shape[0]), device=device)
     counters = (ctypes.c_int32 * 3)()
-    _lib.check(L.difusco_mis_local_search(n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()),
-                                          ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(sol.data_ptr()), int(max_rounds),
-                                          ctypes.c_void_p(ws.data_ptr()), nbytes.value, counters,
-                                          ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    _lib.check(L.difusco_mis_local_search(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), int(max_rounds), _ptr(ws),
+                                          nbytes, counters, _stream(device)))
     if stats is not None:
-        stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
+        _mis_counters(stats, counters)
     return sol.cpu().numpy().astype(int)
 
 
@@ -1037,53 +936,29 @@ def mis_iterated_search_np(predictions, solution, adj_matrix=None, *, graph=None
     ``mis_local_search_np``.  Returns the 0/1 int numpy array; ``stats`` (a dict) receives ``rounds``, ``swaps``, ``inserts``
     (all descents), ``host_syncs`` and the per-instance lists ``entered``, ``accepted``, ``size_before``, ``size_after``.
     A set that is not independent or a malformed table raises ``DifuscoHipError``.  GPU only."""
-    from .graph import build_csr
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.DifuscoHipError("mis_iterated_search_np runs on the GPU only (no CPU fallback)")
+    device = _gpu_only("mis_iterated_search_np", device)
     if int(max_rounds) != max_rounds or max_rounds < 0:
         raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 0")
     kicks, kick_size = check_mis_kicks("swap", kicks, kick_size)
-    L = _lib.lib()
-    scores = _dev(predictions, torch.float32, device).reshape(-1)
-    n = scores.shape[0]
-    sol = _dev(solution if isinstance(solution, torch.Tensor) else np.asarray(solution), torch.int32, device).reshape(-1)
-    if sol.shape[0] != n:
-        raise ValueError(f"solution holds {sol.shape[0]} entries for {n} scores")
-    if isinstance(solution, torch.Tensor):
-        sol = sol.clone()                                  # the library refines in place; the caller's tensor stays
+    n = _numel(predictions)
+    solution = _mis_solution(solution, n)
     rows = np.array([0, n], dtype=np.int64) if instance_rows is None else np.asarray(instance_rows, dtype=np.int64).reshape(-1)
     B = len(rows) - 1
     if B < 1:
         raise ValueError("instance_rows must hold n_instances + 1 >= 2 offsets")
-    mask = (1 << 64) - 1
-    table = []
-    for name, v in (("seeds", seeds), ("offsets", offsets)):
-        v = [0] * B if v is None else [int(x) & mask for x in v]
-        if len(v) != B:
-            raise ValueError(f"{name}: {len(v)} entries for {B} instances")
-        table.append(torch.from_numpy(np.array(v, dtype=np.uint64).view(np.int64)).to(device))
+    table = _philox_table(seeds, offsets, B, "instances", device)
+    L = _lib.lib()
+    scores, graph, col = _mis_graph(predictions, adj_matrix, graph, edge_index, graph_build, device)
+    sol = _mis_solution_on_device(solution, device)
     d_rows = torch.from_numpy(rows).to(device)
-    if graph is None:
-        if edge_index is None:
-            coo = adj_matrix.tocoo()
-            edge_index = np.stack([coo.row, coo.col]).astype(np.int64)
-        graph = build_csr(edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index)),
-                          n, device, method=graph_build)
-    # a graph without any entry has no col array to point at; the kernels read none (every row is empty)
-    col = graph.col if graph.col.numel() else torch.zeros(1, dtype=torch.int32, device=device)
-    nbytes = ctypes.c_size_t()
-    _lib.check(L.difusco_mis_iterated_search_workspace_bytes(n, int(graph.col.shape[0]), B, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws, nbytes = _workspace(L.difusco_mis_iterated_search_workspace_bytes, n, int(graph.col.shape[0]), B, device=device)
     counters = (ctypes.c_int32 * 3)()
     per = (ctypes.c_int32 * (4 * B))()
-    _lib.check(L.difusco_mis_iterated_search(
-        n, ctypes.c_void_p(graph.rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(scores.data_ptr()),
-        ctypes.c_void_p(sol.data_ptr()), B, ctypes.c_void_p(d_rows.data_ptr()), ctypes.c_void_p(table[0].data_ptr()),
-        ctypes.c_void_p(table[1].data_ptr()), kicks, kick_size, int(max_rounds), ctypes.c_void_p(ws.data_ptr()), nbytes.value,
-        counters, per, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    _lib.check(L.difusco_mis_iterated_search(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), B, _ptr(d_rows), _ptr(table[0]),
+                                             _ptr(table[1]), kicks, kick_size, int(max_rounds), _ptr(ws), nbytes, counters, per,
+                                             _stream(device)))
     if stats is not None:
-        stats["rounds"], stats["swaps"], stats["inserts"] = int(counters[0]), int(counters[1]), int(counters[2])
+        _mis_counters(stats, counters)
         stats["host_syncs"] = int(L.difusco_mis_search_host_syncs())
         p = np.array(per[:], dtype=np.int64).reshape(B, 4)
         for k, name in enumerate(("entered", "accepted", "size_before", "size_after")):

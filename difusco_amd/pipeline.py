@@ -16,14 +16,9 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import decode
 from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
-                     check_tsp_kicks, check_tsp_window, check_two_opt_method, batched_local_search_grouped,
-                     batched_window_search_grouped, batched_window_search_ragged, batched_window_search_torch,
-                     batched_iterated_search_grouped, batched_iterated_search_ragged, batched_iterated_search_torch,
-                     batched_local_search_ragged, batched_local_search_torch, batched_multi_local_search_grouped,
-                     batched_multi_local_search_ragged, batched_multi_local_search_torch, batched_multi_two_opt_grouped,
-                     batched_multi_two_opt_ragged, batched_multi_two_opt_torch, batched_two_opt_grouped, batched_two_opt_ragged,
-                     batched_two_opt_torch, merge_tours, merge_tours_batch)
+                     check_tsp_kicks, check_tsp_window, check_two_opt_method, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
 
@@ -85,6 +80,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
+    search = (local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -117,32 +113,9 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
                                               parallel_sampling=parallel_sampling, device=dev)
         tick("merge", t0)
         t0 = time.perf_counter()
-        if local_search == "2opt":
-            solved, ns = batched_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),   # :233-236
-                                               max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
-        elif local_search == "multi2opt":
-            solved, ns = batched_multi_two_opt_torch(np_points64, np.asarray(tours, dtype=np.int64),
-                                                     max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
-        elif local_search == "multi2opt+oropt" and window > 0:
-            solved, ls_stats = batched_window_search_torch(
-                np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
-                kick_size=kick_size, span=kick_span, seeds=[_kick_key(model.seed)] * parallel_sampling,
-                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats, window=window, passes=passes)
-            ns = ls_stats["two_opt_sweeps"]
-        elif local_search == "multi2opt+oropt" and kicks > 0:
-            solved, ls_stats = batched_iterated_search_torch(
-                np_points64, np.asarray(tours, dtype=np.int64), max_iterations=two_opt_iterations, device=dev, kicks=kicks,
-                kick_size=kick_size, span=kick_span, seeds=[_kick_key(model.seed)] * parallel_sampling,
-                offsets=_kick_offsets(r, parallel_sampling), stats=kick_stats, descent=descent,
-                **(dict(kick_bias="heat", heat=heat, edge_index=edge_index) if kick_bias == "heat" else {}))
-            ns = ls_stats["two_opt_sweeps"]
-        elif local_search == "multi2opt+oropt":
-            solved, ls_stats = batched_multi_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
-                                                                max_iterations=two_opt_iterations, device=dev)
-            ns = ls_stats["two_opt_sweeps"]
-        else:
-            solved, ns = batched_local_search_torch(np_points64, np.asarray(tours, dtype=np.int64),
-                                                    max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+        solved, ns, ls_stats = _local_search("torch", search, np_points64, np.asarray(tours, dtype=np.int64), two_opt_iterations, dev,
+                                             [_kick_key(model.seed)] * parallel_sampling, _kick_offsets(r, parallel_sampling),
+                                             heat, edge_index, kick_stats)
         tick("two_opt", t0)
         stacked.append(solved)
         merged_costs += [tour_length(np_points64, t) for t in tours]
@@ -150,21 +123,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     costs = [tour_length(np_points64, t) for t in solved]                                   # :240-246
     best = int(np.argmin(costs))
     info = {"merge_iterations": merge_iterations, "two_opt_iterations": ns, "merged_costs": merged_costs}
-    if local_search == "multi2opt":
-        info.update(two_opt_moves=ls_stats["moves"])
-    elif local_search == "multi2opt+oropt":
-        info.update(two_opt_moves=ls_stats["two_opt_moves"], or_opt_iterations=ls_stats["or_opt_sweeps"],
-                    or_opt_moves=ls_stats["or_opt_moves"], local_search_rounds=ls_stats["rounds"])
-        if window > 0:
-            info.update(_window_info(kick_stats, window, passes, 0, parallel_sampling))
-        elif kicks > 0:
-            info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"]])
-            if kick_bias == "heat":
-                info.update(local_search_kick_bias="heat")
-            if descent == "focused":
-                info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"]])
-    elif local_search != "2opt":
-        info.update(or_opt_iterations=ls_stats["or_opt_iterations"], local_search_rounds=ls_stats["rounds"])
+    info.update(_local_search_info(search, ls_stats, kick_stats, 0, parallel_sampling, 0))
     return solved[best].tolist(), costs[best], costs, info
 
 
@@ -241,11 +200,58 @@ def _kick_key(seed) -> int:
     return int(seed) & (2 ** 63 - 1)
 
 
-def _window_info(stats: dict, window: int, passes: int, first: int, P: int) -> dict:
-    """What info gains in window mode: the settings and the per-copy arrays of the copies first .. first + P - 1."""
-    cut = lambda k: [int(v) for v in stats[k][first:first + P]]
-    return dict(local_search_window=window, local_search_passes=passes, local_search_kicks_improved=cut("kicks_improved"),
-                local_search_passes_kept=cut("passes_kept"), local_search_closing_sweeps=cut("closing_sweeps"))
+def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, dev, seeds, offsets, heat, edge_index, kick_stats):
+    """The local search of one round on the merged tours, through the ``decode.batched_*`` wrapper of ``form`` ("torch",
+    "grouped" or "ragged") that ``search`` - the checked (local_search, two_opt_method, window, passes, kicks, kick_size,
+    kick_span, descent, kick_bias) - selects.  ``seeds`` / ``offsets``: the Philox key and first offset of every tour, read by
+    the kicked searches, as ``heat`` / ``edge_index`` (the round's heatmaps and their graphs) are by heat-biased kicks;
+    ``kick_stats`` receives their per-tour arrays.  Returns (tours, iterations, the search's own statistics)."""
+    local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias = search
+    run = lambda stem, **kw: getattr(decode, f"batched_{stem}_{form}")(points, tours, max_iterations=two_opt_iterations, device=dev, **kw)
+    ls_stats = {}
+    if local_search == "2opt":
+        solved, iterations = run("two_opt", method=two_opt_method)                              # pl_tsp_model.py:233-236
+    elif local_search == "multi2opt":
+        solved, iterations = run("multi_two_opt", stats=ls_stats)
+    elif local_search == "2opt+oropt":
+        solved, iterations = run("local_search", stats=ls_stats)
+    else:
+        kicked = dict(kicks=kicks, kick_size=kick_size, span=kick_span, seeds=seeds, offsets=offsets, stats=kick_stats)
+        if window > 0:
+            solved, ls_stats = run("window_search", window=window, passes=passes, **kicked)
+        elif kicks > 0:
+            solved, ls_stats = run("iterated_search", descent=descent, **kicked,
+                                   **(dict(kick_bias="heat", heat=heat, edge_index=edge_index) if kick_bias == "heat" else {}))
+        else:
+            solved, ls_stats = run("multi_local_search")
+        iterations = ls_stats["two_opt_sweeps"]
+    return solved, iterations, ls_stats
+
+
+def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: int, P: int, g: int) -> dict:
+    """What info gains from the local search of the last round: the statistics of group ``g`` of the call (``solve_tsp``: 0,
+    its scalars are ints already) and the per-copy arrays of its copies first .. first + P - 1."""
+    local_search, _, window, passes, kicks, _, _, descent, kick_bias = search
+    at = lambda k: int(np.reshape(ls_stats[k], -1)[g])
+    cut = lambda k: [int(v) for v in kick_stats[k][first:first + P]]
+    if local_search == "2opt":
+        return {}
+    if local_search == "multi2opt":
+        return dict(two_opt_moves=at("moves"))
+    if local_search == "2opt+oropt":
+        return dict(or_opt_iterations=at("or_opt_iterations"), local_search_rounds=at("rounds"))
+    info = dict(two_opt_moves=at("two_opt_moves"), or_opt_iterations=at("or_opt_sweeps"), or_opt_moves=at("or_opt_moves"),
+                local_search_rounds=at("rounds"))
+    if window > 0:
+        info.update(local_search_window=window, local_search_passes=passes, local_search_kicks_improved=cut("kicks_improved"),
+                    local_search_passes_kept=cut("passes_kept"), local_search_closing_sweeps=cut("closing_sweeps"))
+    elif kicks > 0:
+        info.update(local_search_kicks_improved=cut("kicks_improved"))
+        if kick_bias == "heat":
+            info.update(local_search_kick_bias="heat")
+        if descent == "focused":
+            info.update(local_search_closing_sweeps=cut("closing_sweeps"))
+    return info
 
 
 def _kick_stats(out: dict, call: dict, first: int, P: int):
@@ -308,10 +314,10 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
+    search = (local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
-                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, two_opt_method,
-                               merge_method, local_search, kicks, kick_size, kick_span, descent, kick_bias, window, passes)
+                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -369,32 +375,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
-            if local_search == "2opt":
-                solved, ns = batched_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
-                                                     max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
-            elif local_search == "multi2opt":
-                solved, ns = batched_multi_two_opt_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
-                                                           max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
-            elif local_search == "multi2opt+oropt" and window > 0:
-                solved, ls_stats = batched_window_search_grouped(
-                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
-                    device=dev, kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, window=window, passes=passes)
-                ns = ls_stats["two_opt_sweeps"]
-            elif local_search == "multi2opt+oropt" and kicks > 0:
-                solved, ls_stats = batched_iterated_search_grouped(
-                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations,
-                    device=dev, kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent,
-                    **(dict(kick_bias="heat", heat=heats, edge_index=eis if sparse else None) if kick_bias == "heat" else {}))
-                ns = ls_stats["two_opt_sweeps"]
-            elif local_search == "multi2opt+oropt":
-                solved, ls_stats = batched_multi_local_search_grouped(
-                    np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1), max_iterations=two_opt_iterations, device=dev)
-                ns = ls_stats["two_opt_sweeps"]
-            else:
-                solved, ns = batched_local_search_grouped(np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
-                                                          max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            solved, ns, ls_stats = _local_search("grouped", search, np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
+                                                 two_opt_iterations, dev, [k for k in keys for _ in range(P)], _kick_offsets(r, P) * G,
+                                                 heats, eis if sparse else None, kick_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g * P:(g + 1) * P])
@@ -404,21 +387,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             costs = [tour_length(np_points64[g], t) for t in sol]
             best = int(np.argmin(costs))
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]), "merged_costs": merged_costs[g]}
-            if local_search == "multi2opt":
-                info.update(two_opt_moves=int(ls_stats["moves"][g]))
-            elif local_search == "multi2opt+oropt":
-                info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
-                            or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
-                if window > 0:
-                    info.update(_window_info(kick_stats, window, passes, g * P, P))
-                elif kicks > 0:
-                    info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
-                    if kick_bias == "heat":
-                        info.update(local_search_kick_bias="heat")
-                    if descent == "focused":
-                        info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"][g * P:(g + 1) * P]])
-            elif local_search != "2opt":
-                info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+            info.update(_local_search_info(search, ls_stats, kick_stats, g * P, P, g))
             results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)
@@ -426,11 +395,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 
 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
-                    instances_per_call, step_offset, heatmaps, two_opt_method, merge_method="loop",
-                    local_search="2opt", kicks=0, kick_size=TSP_KICK_SIZE, kick_span=TSP_KICK_SPAN,
-                    descent="full", kick_bias="uniform", window=0, passes=1) -> List[tuple]:
-    """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; every argument is checked before any library call."""
-    check_local_search(local_search, two_opt_method)
+                    instances_per_call, step_offset, heatmaps, merge_method, search) -> List[tuple]:
+    """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; ``search``: its checked local-search settings, as
+    ``_local_search`` takes them.  Every argument is checked before any library call."""
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
                 for p in points]
     B = len(pts_list)
@@ -496,32 +463,9 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
                     tours.append(tg)
             tick("merge", t0)
             t0 = time.perf_counter()
-            if local_search == "2opt":
-                solved, its = batched_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
-                                                     max_iterations=two_opt_iterations, device=dev, method=two_opt_method)
-            elif local_search == "multi2opt":
-                solved, its = batched_multi_two_opt_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
-                                                           max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
-            elif local_search == "multi2opt+oropt" and window > 0:
-                solved, ls_stats = batched_window_search_ragged(
-                    np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
-                    kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, window=window, passes=passes)
-                its = ls_stats["two_opt_sweeps"]
-            elif local_search == "multi2opt+oropt" and kicks > 0:
-                solved, ls_stats = batched_iterated_search_ragged(
-                    np_points64, [np.asarray(t, dtype=np.int64) for t in tours], max_iterations=two_opt_iterations, device=dev,
-                    kicks=kicks, kick_size=kick_size, span=kick_span, seeds=[k for k in keys for _ in range(P)],
-                    offsets=_kick_offsets(r, P) * G, stats=kick_stats, descent=descent,
-                    **(dict(kick_bias="heat", heat=heats, edge_index=eis if sparse else None) if kick_bias == "heat" else {}))
-                its = ls_stats["two_opt_sweeps"]
-            elif local_search == "multi2opt+oropt":
-                solved, ls_stats = batched_multi_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
-                                                                     max_iterations=two_opt_iterations, device=dev)
-                its = ls_stats["two_opt_sweeps"]
-            else:
-                solved, its = batched_local_search_ragged(np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
-                                                          max_iterations=two_opt_iterations, device=dev, stats=ls_stats)
+            solved, its, ls_stats = _local_search("ragged", search, np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
+                                                  two_opt_iterations, dev, [k for k in keys for _ in range(P)], _kick_offsets(r, P) * G,
+                                                  heats, eis if sparse else None, kick_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g])
@@ -531,21 +475,7 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             costs = [tour_length(np_points64[g], t) for t in sol]
             best = int(np.argmin(costs))
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]), "merged_costs": merged_costs[g]}
-            if local_search == "multi2opt":
-                info.update(two_opt_moves=int(ls_stats["moves"][g]))
-            elif local_search == "multi2opt+oropt":
-                info.update(two_opt_moves=int(ls_stats["two_opt_moves"][g]), or_opt_iterations=int(ls_stats["or_opt_sweeps"][g]),
-                            or_opt_moves=int(ls_stats["or_opt_moves"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
-                if window > 0:
-                    info.update(_window_info(kick_stats, window, passes, g * P, P))
-                elif kicks > 0:
-                    info.update(local_search_kicks_improved=[int(v) for v in kick_stats["kicks_improved"][g * P:(g + 1) * P]])
-                    if kick_bias == "heat":
-                        info.update(local_search_kick_bias="heat")
-                    if descent == "focused":
-                        info.update(local_search_closing_sweeps=[int(v) for v in kick_stats["closing_sweeps"][g * P:(g + 1) * P]])
-            elif local_search != "2opt":
-                info.update(or_opt_iterations=int(ls_stats["or_opt_iterations"][g]), local_search_rounds=int(ls_stats["rounds"][g]))
+            info.update(_local_search_info(search, ls_stats, kick_stats, g * P, P, g))
             results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)
