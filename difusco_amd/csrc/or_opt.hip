@@ -191,7 +191,7 @@ __device__ __forceinline__ void apply_or_opt_move(int* __restrict__ tour, int* _
 }
 
 // One block per group: the step of its current phase.
-//   2-opt:   two_opt_apply_ragged_kernel's step - the group's minimum decides, every tour reverses its best segment; the phase
+//   2-opt:   two_opt_apply_kernel's step - the group's minimum decides, every tour reverses its best segment; the phase
 //            ends on a minimum >= -1e-6 or after max_iterations moves of this phase, and the Or-opt phase follows;
 //   Or-opt:  every tour applies its own best move if it is below the threshold; the phase ends after an iteration without a move
 //            or after max_iterations counted ones (none with max_iterations = 0).  b = its counted iterations: b = 0 or the
@@ -257,23 +257,12 @@ struct LsLayout {          // byte offsets
   int tours, nmax, nblk_max;
 };
 
-constexpr int kMaxTours = 65535;                   // a grid dimension; the limits of difusco_tsp_two_opt_ragged
-constexpr int kMaxNodes = 65535 * TI;
-
 // checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
 int local_search_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, LsLayout* L,
                         std::vector<LsTour>* tab, std::vector<LsGroup>* gtab) {
-  if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
-  if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
-  long long T = 0;
-  for (int g = 0; g < groups; ++g) {
-    if (group_n[g] < 4) return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, needs n >= 4", who, g, group_n[g]);
-    if (group_n[g] > kMaxNodes)
-      return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, at most %d nodes", who, g, group_n[g], kMaxNodes);
-    if (group_tours[g] < 1) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d tours, needs at least 1", who, g, group_tours[g]);
-    T += group_tours[g];
-    if (T > kMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kMaxTours);
-  }
+  int T = 0;
+  const int rc = check_groups(who, groups, group_n, group_tours, &T);
+  if (rc != DIFUSCO_OK) return rc;
   size_t points = 0, closed = 0, cols = 0, nblks = 0;
   L->nmax = L->nblk_max = 0;
   for (int g = 0; g < groups; ++g) {

@@ -7,16 +7,17 @@
 //   two_opt_best_kernel   every thread keeps P[j], P[j+1], d[j] of its columns in registers, a block sweeps a tile of
 //                         rows i, change = ((A_ij + A_i+1,j+1) - d_i) - d_j in float64 in the reference's operation
 //                         order, running (min, first flat index) per thread -> block -> partial[];
-//   two_opt_apply_kernel  per tour: argmin over the partials (ties: lowest flat index = first occurrence, what
-//                         torch.argmin returns on the flattened matrix); min over the batch decides (tsp_utils.py:
+//   two_opt_apply_kernel  one block per group: argmin per tour over the partials (ties: lowest flat index = first occurrence,
+//                         what torch.argmin returns on the flattened matrix); min over the group's tours decides (tsp_utils.py:
 //                         33,39: one global `min_change < -1e-6` test, every tour applies its own best move);
-//                         the segment tour[i+1 .. j] is reversed in place, the iteration counter advances.
+//                         the segment tour[i+1 .. j] is reversed in place, the group's iteration counter advances.
 // Invalid entries (j < i + 2) are zeros in the reference's matrix, so the minimum is never positive and the argmin of
 // an all-non-improving matrix is flat index 0 = a no-op reversal: the running best starts at (0.0, 0).
-// The host only polls a `done` flag every few iterations; once set, the remaining launches return immediately.
-// Three shapes of a call share the per-block code (screen_tile, screened_best_tile here; best_tile, tour_argmin, apply_move in
-// two_opt_common.h, which the local search of or_opt.hip uses as well): one
-// batch (difusco_tsp_two_opt), groups of one n (_grouped) and groups of different n (_ragged, at the end of the namespace).
+// The host only polls the count of stopped groups every few iterations; a stopped group's launches return immediately.
+// Every entry is one call of two_opt_run on groups of tours: one batch (difusco_tsp_two_opt: one group), groups of one n
+// (_grouped) and groups of different n (_ragged).  The kernels are templates over where a block finds its tour's n, array bases
+// and stop flag (UniformAddr, TableAddr); the per-block code is screen_tile, screened_best_tile here and best_tile, tour_argmin,
+// apply_move in two_opt_common.h, which the local search of or_opt.hip uses as well.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -29,138 +30,126 @@
 namespace difusco {
 namespace {
 
-struct TwoOptState {       // device-resident loop state
-  int done;
-  int pad;
-  long long iterations;
+// ---- addressing: where a block finds its tour -----------------------------------------------------------------------------------
+//
+// Groups of different n (difusco_tsp_two_opt_ragged) run the launch sequence of the equal-size entries with every kernel reading
+// its tour's n and array bases from a descriptor table instead of computing them from one n.  The table is built on the host from
+// group_n / group_tours and written to the workspace once per call.  A block reads desc[its tour], an index that is uniform over
+// the block, so the descriptor and every base derived from it stay in scalar registers and the row data of the screen still
+// arrive by scalar loads.
+// Grids: the call's maxima (nblk_max, [nchunk_max,] tours); a block beyond its own tour's nblk / nchunk returns at once.  With
+// equal sizes the grids are exactly those of the grouped entries.  A flat work list with a search over a prefix array would
+// launch no idle block, but every block would pay the search and equal sizes would no longer map to the grouped grid; an idle
+// block costs a descriptor load and an exit.
+struct RaggedTour {        // 64 bytes; offsets in elements of the array they index
+  int group, n, nblk, nchunk;
+  long long points;        // the group's first coordinate in `points` (doubles)
+  long long tours;         // the tour's first entry in `tours` (n + 1 per tour)
+  long long tp;            //                       in tp (n + 1 per tour)
+  long long cols;          //                       in dlen, q and d32 (n per tour each: one offset serves the three)
+  long long partial;       //                       in partial (nblk per tour)
+  long long bmin;          //                       in bmin (nblk * nchunk per tour)
 };
 
-// GROUPED (difusco_tsp_two_opt_grouped): tour b belongs to group b / per_group, which has points of its own
-// (points + group * 2 n) and a done flag of its own (gdone[group]); otherwise one state for the whole batch.
-template <bool GROUPED>
-__global__ void two_opt_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, int n, int batch,
-                                    double2* __restrict__ tp, double* __restrict__ dlen, const TwoOptState* st,
-                                    const int* __restrict__ gdone, int per_group) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if constexpr (GROUPED) {
-    if (gdone[b / per_group]) return;
-    points += (long long)(b / per_group) * 2 * n;
-  } else {
-    if (st->done) return;
+struct RaggedGroup {       // what the apply block and the max |coordinate| reduction of a group need
+  int first, count;        // its tours: first .. first + count - 1, all of n nodes and nblk partials,
+  int n, nblk;
+  long long points;
+  long long tours, partial;   // so tour p of the group starts at tours + p (n + 1) and partial + p nblk: no descriptor per tour
+};
+
+// Equal sizes: n and per_group travel in the kernel arguments, the bases follow from the tour's index b, and the stop flag is
+// its group's, gdone[b / per_group] - one line shared by every block of a launch.
+struct UniformAddr {
+  static constexpr bool kTable = false;
+  int n, per_group, nblk, nchunk;
+  const int* gdone;
+  __device__ __forceinline__ RaggedTour tour(int b) const {
+    const int g = b / per_group;
+    const long long row = (long long)b * n;
+    return RaggedTour{g, n, nblk, nchunk, (long long)g * 2 * n, row + b, row + b, row, (long long)b * nblk, (long long)b * nblk * nchunk};
   }
-  if (k > n) return;
-  prep_entry(points, tours + (long long)b * (n + 1), n, k, tp + (long long)b * (n + 1), dlen + (long long)b * n);
+  __device__ __forceinline__ RaggedGroup group(int g) const {
+    const long long b0 = (long long)g * per_group;
+    return RaggedGroup{g * per_group, per_group, n, nblk, (long long)g * 2 * n, b0 * (n + 1), b0 * nblk};
+  }
+  __device__ __forceinline__ bool stopped(int b) const { return gdone[b / per_group]; }
+};
+
+// Any sizes: the tables.  A group that stops also sets tdone of its tours: a block reads its tour's flag by its own index,
+// alongside the descriptor and not after it.
+struct TableAddr {
+  static constexpr bool kTable = true;
+  const RaggedTour* desc;
+  const RaggedGroup* grp;
+  int* tdone;
+  __device__ __forceinline__ RaggedTour tour(int b) const { return desc[b]; }
+  __device__ __forceinline__ RaggedGroup group(int g) const { return grp[g]; }
+  __device__ __forceinline__ bool stopped(int b) const { return tdone[b]; }
+};
+
+// ---- the exact move -------------------------------------------------------------------------------------------------------------
+
+template <class A>
+__global__ void two_opt_prep_kernel(A a, const double* __restrict__ points, const int* __restrict__ tours,
+                                    double2* __restrict__ tp, double* __restrict__ dlen) {
+  const RaggedTour d = a.tour(blockIdx.y);
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > d.n || a.stopped(blockIdx.y)) return;
+  prep_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols);
 }
 
-template <bool GROUPED>
-__global__ __launch_bounds__(256) void two_opt_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                           int n, Best* __restrict__ partial, const TwoOptState* st,
-                                                           const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.y, i0 = blockIdx.x * TI;
-  if constexpr (GROUPED) {
-    if (gdone[b / per_group]) return;
-  } else {
-    if (st->done) return;
-  }
-  const Best r = best_tile(tp + (long long)b * (n + 1), dlen + (long long)b * n, n, i0);
-  if (threadIdx.x == 0) partial[(long long)b * gridDim.x + blockIdx.x] = r;
+template <class A>
+__global__ __launch_bounds__(256) void two_opt_best_kernel(A a, const double2* __restrict__ tp, const double* __restrict__ dlen,
+                                                           Best* __restrict__ partial) {
+  const RaggedTour d = a.tour(blockIdx.y);
+  if constexpr (A::kTable)
+    if ((int)blockIdx.x >= d.nblk) return;                     // beyond the tour's own tiles
+  if (a.stopped(blockIdx.y)) return;
+  const Best r = best_tile(tp + d.tp, dlen + d.cols, d.n, blockIdx.x * TI);
+  if (threadIdx.x == 0) partial[d.partial + blockIdx.x] = r;
 }
 
-__global__ __launch_bounds__(256) void two_opt_apply_kernel(int* __restrict__ tours, int n, int batch, int nblk,
-                                                            const Best* __restrict__ partial, long long max_iterations,
-                                                            TwoOptState* st, Best* __restrict__ chosen) {
-  if (st->done) return;
-  __shared__ double gmin;
-  // per tour: argmin over its partials
-  for (int b = 0; b < batch; ++b) {
-    const Best r = tour_argmin(partial + (long long)b * nblk, nblk);
-    if (threadIdx.x == 0) chosen[b] = r;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double m = chosen[0].v;
-    for (int b = 1; b < batch; ++b) m = chosen[b].v < m ? chosen[b].v : m;
-    gmin = m;
-  }
-  __syncthreads();
-  if (!(gmin < -1e-6)) {                                  // tsp_utils.py:39,44
-    if (threadIdx.x == 0) st->done = 1;
-    return;
-  }
-  for (int b = 0; b < batch; ++b) apply_move(tours + (long long)b * (n + 1), chosen[b].idx, n);
-  if (threadIdx.x == 0) {
-    st->iterations += 1;
-    if (st->iterations >= max_iterations) st->done = 1;   // tsp_utils.py:46-47
-  }
-}
-
-// The apply step of difusco_tsp_two_opt_grouped: block g = group g, the steps of two_opt_apply_kernel over the group's own
-// tours (argmin per tour, the group's minimum decides, every tour applies its best move); a group that stops sets its flag
-// and counts itself in st->done (= number of stopped groups).
-__global__ __launch_bounds__(256) void two_opt_apply_grouped_kernel(int* __restrict__ tours, int n, int per_group, int nblk,
-                                                                    const Best* __restrict__ partial, long long max_iterations,
-                                                                    TwoOptState* st, int* __restrict__ gdone,
-                                                                    long long* __restrict__ giters, Best* __restrict__ chosen) {
+// Block g = group g: argmin per tour, the group's minimum decides, every tour applies its best move; a group that stops sets
+// its flag (table form: and those of its tours) and counts itself in *stopped.
+template <class A>
+__global__ __launch_bounds__(256) void two_opt_apply_kernel(A a, int* __restrict__ tours, const Best* __restrict__ partial,
+                                                            long long max_iterations, int* stopped, int* __restrict__ gdone,
+                                                            long long* __restrict__ giters, Best* __restrict__ chosen) {
   const int g = blockIdx.x;
   if (gdone[g]) return;
   __shared__ double gmin;
-  const int b0 = g * per_group;
-  for (int b = b0; b < b0 + per_group; ++b) {
-    const Best r = tour_argmin(partial + (long long)b * nblk, nblk);
-    if (threadIdx.x == 0) chosen[b] = r;
+  const RaggedGroup G = a.group(g);
+  auto stop = [&]() {                                          // thread 0
+    gdone[g] = 1;
+    if constexpr (A::kTable)
+      for (int b = G.first; b < G.first + G.count; ++b) a.tdone[b] = 1;
+    atomicAdd(stopped, 1);
+  };
+  for (int p = 0; p < G.count; ++p) {
+    const Best r = tour_argmin(partial + G.partial + (long long)p * G.nblk, G.nblk);
+    if (threadIdx.x == 0) chosen[G.first + p] = r;
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    double m = chosen[b0].v;
-    for (int b = b0 + 1; b < b0 + per_group; ++b) m = chosen[b].v < m ? chosen[b].v : m;
+    double m = chosen[G.first].v;
+    for (int b = G.first + 1; b < G.first + G.count; ++b) m = chosen[b].v < m ? chosen[b].v : m;
     gmin = m;
   }
   __syncthreads();
-  if (!(gmin < -1e-6)) {
-    if (threadIdx.x == 0) {
-      gdone[g] = 1;
-      atomicAdd(&st->done, 1);
-    }
+  if (!(gmin < -1e-6)) {                                       // tsp_utils.py:39,44
+    if (threadIdx.x == 0) stop();
     return;
   }
-  for (int b = b0; b < b0 + per_group; ++b) apply_move(tours + (long long)b * (n + 1), chosen[b].idx, n);
+  for (int p = 0; p < G.count; ++p) apply_move(tours + G.tours + (long long)p * (G.n + 1), chosen[G.first + p].idx, G.n);
   if (threadIdx.x == 0) {
     giters[g] += 1;
-    if (giters[g] >= max_iterations) {
-      gdone[g] = 1;
-      atomicAdd(&st->done, 1);
-    }
+    if (giters[g] >= max_iterations) stop();                   // tsp_utils.py:46-47
   }
 }
 
-// the workspace of difusco_tsp_two_opt_grouped (byte offsets): the screened entries run on the same arrays and append their own
-struct GroupedLayout {
-  size_t tp, dlen, partial, chosen, gdone, giters, st, total;
-};
-
-GroupedLayout grouped_layout(int n, int groups, int per_group) {
-  const size_t batch = (size_t)groups * per_group, nblk = (size_t)(n + TI - 1) / TI;
-  GroupedLayout L;
-  size_t off = 0;
-  L.tp = off;
-  off += up256(sizeof(double2) * batch * (n + 1));
-  L.dlen = off;
-  off += up256(sizeof(double) * batch * n);
-  L.partial = off;
-  off += up256(sizeof(Best) * batch * nblk);
-  L.chosen = off;
-  off += up256(sizeof(Best) * batch);
-  L.gdone = off;
-  off += up256(sizeof(int) * groups);
-  L.giters = off;
-  off += up256(sizeof(long long) * groups);
-  L.st = off;                            // TwoOptState: st->done = number of groups that have stopped
-  L.total = off + 256;
-  return L;
-}
-
-// ---- screened 2-opt (difusco_tsp_two_opt_screened*): the same (min, first flat index) as two_opt_best_kernel, with float64 only
-// for the pairs a float32 evaluation of the same formula cannot rule out.
+// ---- screened 2-opt (difusco_tsp_two_opt_screened*, _ragged with method 1): the same (min, first flat index) as
+// two_opt_best_kernel, with float64 only for the pairs a float32 evaluation of the same formula cannot rule out.
 //
 // One move is four launches:
 //   two_opt_prep_screen_kernel    tp / dlen as above, plus float32 copies q[k] = (P[k], P[k+1]) and d32[k] = fl32(d[k]);
@@ -175,7 +164,7 @@ GroupedLayout grouped_layout(int n, int groups, int per_group) {
 //                                 survivors are evaluated with the float64 sequence of two_opt_best_kernel and compared with
 //                                 better().  On a random tour (half of all pairs improve) and on a decoded one alike the
 //                                 survivors are the pairs within 2 eps of the minimum;
-//   two_opt_apply_grouped_kernel  unchanged.
+//   two_opt_apply_kernel          unchanged.
 // Load balance: the screen runs on a (row tile, 1024-column chunk) grid over the triangle j >= i + 2, every block 16 x 1024
 // pairs, blocks left of the triangle return at once.
 //
@@ -222,18 +211,20 @@ __device__ __forceinline__ float change32(float4 q, float d_i, float4 c, float d
 }
 
 // gmax[g] = bits of the largest |coordinate| of group g (non-negative doubles order like their bits; a NaN sorts above inf)
-__global__ void two_opt_maxabs_kernel(const double* __restrict__ points, int n2, unsigned long long* __restrict__ gmax) {
-  const int g = blockIdx.y;
+template <class A>
+__global__ void two_opt_maxabs_kernel(A a, const double* __restrict__ points, unsigned long long* __restrict__ gmax) {
+  const RaggedGroup G = a.group(blockIdx.y);
+  const double* pts = points + G.points;
   unsigned long long m = 0;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n2; k += gridDim.x * blockDim.x) {
-    const unsigned long long v = (unsigned long long)__double_as_longlong(fabs(points[(long long)g * n2 + k]));
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 2 * G.n; k += gridDim.x * blockDim.x) {
+    const unsigned long long v = (unsigned long long)__double_as_longlong(fabs(pts[k]));
     m = v > m ? v : m;
   }
   for (int off = 32; off > 0; off >>= 1) {
     const unsigned long long o = __shfl_xor(m, off);
     m = o > m ? o : m;
   }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + g, m);
+  if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + blockIdx.y, m);
 }
 
 // prep_entry plus the float32 copies of the screen (pointers at the tour's own arrays)
@@ -253,17 +244,15 @@ __device__ __forceinline__ void prep_screen_entry(const double* __restrict__ poi
   }
 }
 
-__global__ void two_opt_prep_screen_kernel(const double* __restrict__ points, const int* __restrict__ tours, int n,
+template <class A>
+__global__ void two_opt_prep_screen_kernel(A a, const double* __restrict__ points, const int* __restrict__ tours,
                                            double2* __restrict__ tp, double* __restrict__ dlen, float4* __restrict__ q,
-                                           float* __restrict__ d32, unsigned* __restrict__ tmin,
-                                           const int* __restrict__ gdone, int per_group) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (gdone[b / per_group]) return;
-  points += (long long)(b / per_group) * 2 * n;
-  if (k > n) return;
-  if (k == 0) tmin[b] = f32_key(0.0f);                         // m32 starts at the value of the no-op move
-  const long long row = (long long)b * n;
-  prep_screen_entry(points, tours + (long long)b * (n + 1), n, k, tp + (long long)b * (n + 1), dlen + row, q + row, d32 + row);
+                                           float* __restrict__ d32, unsigned* __restrict__ tmin) {
+  const RaggedTour d = a.tour(blockIdx.y);
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k > d.n || a.stopped(blockIdx.y)) return;
+  if (k == 0) tmin[blockIdx.y] = f32_key(0.0f);                // m32 starts at the value of the no-op move
+  prep_screen_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols, q + d.cols, d32 + d.cols);
 }
 
 // the columns of a chunk: thread t holds columns jbase + u * 256 + t; a column past the tour gets d_j = -inf, which makes its
@@ -323,14 +312,17 @@ __device__ __forceinline__ void screen_publish(float m, float* __restrict__ bmin
   if (key < __hip_atomic_load(tmin_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(tmin_slot, key);
 }
 
-__global__ __launch_bounds__(256) void two_opt_screen_kernel(const float4* __restrict__ q, const float* __restrict__ d32, int n,
-                                                             float* __restrict__ bmin, unsigned* __restrict__ tmin,
-                                                             const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.z, i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
-  if (jbase + SCH <= i0 + 2) return;                           // the chunk lies left of the triangle
-  if (gdone[b / per_group]) return;
-  const float m = screen_tile(q + (long long)b * n, d32 + (long long)b * n, n, i0, jbase);
-  if (threadIdx.x == 0) screen_publish(m, bmin + ((long long)b * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y, tmin + b);
+template <class A>
+__global__ __launch_bounds__(256) void two_opt_screen_kernel(A a, const float4* __restrict__ q, const float* __restrict__ d32,
+                                                             float* __restrict__ bmin, unsigned* __restrict__ tmin) {
+  const RaggedTour d = a.tour(blockIdx.z);
+  const int i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
+  if constexpr (A::kTable)
+    if ((int)blockIdx.x >= d.nblk || (int)blockIdx.y >= d.nchunk) return;   // beyond the tour's own tiles
+  if (jbase + SCH <= i0 + 2) return;                                       // the chunk lies left of the triangle
+  if (a.stopped(blockIdx.z)) return;
+  const float m = screen_tile(q + d.cols, d32 + d.cols, d.n, i0, jbase);
+  if (threadIdx.x == 0) screen_publish(m, bmin + d.bmin + (long long)blockIdx.x * d.nchunk + blockIdx.y, tmin + blockIdx.z);
 }
 
 // one block of the screened best move: rows i0 .. i0 + TI - 1 of the tour (P, D64: tp, dlen; Q, D: q, d32; n nodes, nchunk
@@ -388,335 +380,239 @@ __device__ __forceinline__ void screened_best_tile(const double2* __restrict__ P
   }
 }
 
+template <class A>
 __global__ __launch_bounds__(256) void two_opt_screened_best_kernel(
-    const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q, const float* __restrict__ d32,
-    int n, int nchunk, const float* __restrict__ bmin, const unsigned* __restrict__ tmin, const double* __restrict__ gmax,
-    Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs, const int* __restrict__ gdone, int per_group) {
-  const int b = blockIdx.y, i0 = blockIdx.x * TI, g = b / per_group;
-  if (gdone[g]) return;
-  const long long row = (long long)b * n;
-  screened_best_tile(tp + (long long)b * (n + 1), dlen + row, q + row, d32 + row, n, nchunk, i0,
-                     bmin + ((long long)b * gridDim.x + blockIdx.x) * nchunk, f32_unkey(tmin[b]), screen_eps(gmax[g]),
-                     partial + (long long)b * gridDim.x + blockIdx.x, exact_pairs);
-}
-
-struct ScreenedLayout {    // the exact entries' layout first (the exact sweep runs on the same workspace), then the screen's arrays
-  size_t q, d32, bmin, tmin, gmax, counter, total;
-};
-
-int screened_layout(int n, int groups, int per_group, ScreenedLayout* L) {
-  const size_t base = grouped_layout(n, groups, per_group).total;
-  const size_t batch = (size_t)groups * per_group, nblk = (size_t)(n + TI - 1) / TI, nchunk = (size_t)(n + SCH - 1) / SCH;
-  if (batch > 65535 || nblk > 65535 || nchunk > 65535)
-    return set_error(DIFUSCO_EINVAL, "two_opt_screened: at most 65535 tours per call and %d nodes", 65535 * TI);
-  size_t off = up256(base);
-  L->q = off;
-  off += up256(sizeof(float4) * batch * n);
-  L->d32 = off;
-  off += up256(sizeof(float) * batch * n);
-  L->bmin = off;
-  off += up256(sizeof(float) * batch * nblk * nchunk);
-  L->tmin = off;
-  off += up256(sizeof(unsigned) * batch);
-  L->gmax = off;
-  off += up256(sizeof(double) * groups);
-  L->counter = off;
-  off += 256;
-  L->total = off;
-  return DIFUSCO_OK;
-}
-
-long long evaluations(long long iterations, long long max_iterations) {   // sweeps of the exact loop that did work
-  return iterations < (max_iterations > 0 ? max_iterations : 1) ? iterations + 1 : iterations;
-}
-
-int two_opt_screened_run(int n, int groups, int per_group, const double* points, int32_t* tours, int64_t max_iterations,
-                         void* workspace, size_t workspace_bytes, int64_t* iterations_out, int64_t* exact_pairs_out,
-                         void* stream) {
-  ScreenedLayout lay;
-  const int rc = screened_layout(n, groups, per_group, &lay);
-  if (rc != DIFUSCO_OK) return rc;
-  if (workspace_bytes < lay.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_two_opt_screened: workspace %zu < %zu bytes", workspace_bytes, lay.total);
-  const int nblk = (n + TI - 1) / TI, nchunk = (n + SCH - 1) / SCH, batch = groups * per_group;
-  const GroupedLayout gl = grouped_layout(n, groups, per_group);      // the arrays of difusco_tsp_two_opt_grouped
-  char* base = (char*)workspace;
-  double2* tp = (double2*)(base + gl.tp);
-  double* dlen = (double*)(base + gl.dlen);
-  Best* partial = (Best*)(base + gl.partial);
-  Best* chosen = (Best*)(base + gl.chosen);
-  int* gdone = (int*)(base + gl.gdone);
-  long long* giters = (long long*)(base + gl.giters);
-  TwoOptState* st = (TwoOptState*)(base + gl.st);
-  float4* q = (float4*)(base + lay.q);
-  float* d32 = (float*)(base + lay.d32);
-  float* bmin = (float*)(base + lay.bmin);
-  unsigned* tmin = (unsigned*)(base + lay.tmin);
-  unsigned long long* gmax = (unsigned long long*)(base + lay.gmax);
-  unsigned long long* counter = (unsigned long long*)(base + lay.counter);
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t er = hipMemsetAsync(gdone, 0, (char*)st + sizeof(TwoOptState) - (char*)gdone, s);
-  if (er == hipSuccess) er = hipMemsetAsync(gmax, 0, lay.total - lay.gmax, s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "memset: %s", hipGetErrorString(er));
-  // M per group decides, once per call, whether the screen has a bound
-  const int mblocks = (2 * n + 255) / 256 < 64 ? (2 * n + 255) / 256 : 64;
-  hipLaunchKernelGGL(two_opt_maxabs_kernel, dim3(mblocks, groups), dim3(256), 0, s, points, 2 * n, gmax);
-  std::vector<double> maxabs(groups);
-  er = hipMemcpyAsync(maxabs.data(), gmax, sizeof(double) * groups, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt_screened max |coordinate|: %s", hipGetErrorString(er));
-  bool bounded = true;
-  for (int g = 0; g < groups; ++g) {
-    double eps = 0.0;
-    bounded = bounded && difusco_tsp_two_opt_screen_bound(maxabs[g], &eps) == 1;
-  }
-  if (!bounded) {                                              // no bound: the exact sweep, every pair in float64
-    const int rc2 = difusco_tsp_two_opt_grouped(n, groups, per_group, points, tours, max_iterations, workspace, workspace_bytes,
-                                                iterations_out, stream);
-    if (rc2 == DIFUSCO_OK && exact_pairs_out) {
-      long long sweeps = 0;
-      for (int g = 0; g < groups; ++g) sweeps += evaluations(iterations_out[g], max_iterations);
-      *exact_pairs_out = sweeps * per_group * ((long long)(n - 1) * (n - 2) / 2);
-    }
-    return rc2;
-  }
-  TwoOptState host{0, 0, 0};
-  const int poll = 8;
-  const long long loops = max_iterations > 0 ? max_iterations : 1;   // as difusco_tsp_two_opt
-  for (long long it = 0; it < loops; ++it) {
-    hipLaunchKernelGGL(two_opt_prep_screen_kernel, dim3((n + 1 + 255) / 256, batch), dim3(256), 0, s, points, tours, n, tp, dlen,
-                       q, d32, tmin, gdone, per_group);
-    hipLaunchKernelGGL(two_opt_screen_kernel, dim3(nblk, nchunk, batch), dim3(256), 0, s, q, d32, n, bmin, tmin, gdone, per_group);
-    hipLaunchKernelGGL(two_opt_screened_best_kernel, dim3(nblk, batch), dim3(256), 0, s, tp, dlen, q, d32, n, nchunk, bmin, tmin,
-                       (const double*)gmax, partial, counter, gdone, per_group);
-    hipLaunchKernelGGL(two_opt_apply_grouped_kernel, dim3(groups), dim3(256), 0, s, tours, n, per_group, nblk, partial,
-                       (long long)max_iterations, st, gdone, giters, chosen);
-    if ((it + 1) % poll == 0 || it + 1 == loops) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  unsigned long long pairs = 0;
-  er = hipMemcpyAsync(iterations_out, giters, sizeof(long long) * groups, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(&pairs, counter, sizeof(pairs), hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt_screened iterations: %s", hipGetErrorString(er));
-  if (exact_pairs_out) *exact_pairs_out = (int64_t)pairs;
-  return DIFUSCO_OK;
-}
-
-// ---- ragged 2-opt (difusco_tsp_two_opt_ragged): groups of different n in one launch sequence ---------------------------------
-//
-// The same move as the grouped entries (prep, best or screen + screened best, apply with one block per group), with every
-// kernel reading its tour's n and array bases from a descriptor table instead of computing them from one n.  The table is built
-// on the host from group_n / group_tours and written to the workspace once per call.  A block reads desc[its tour], an index that
-// is uniform over the block, so the descriptor and every base derived from it stay in scalar registers and the row data of the
-// screen still arrive by scalar loads.
-// Grids: the call's maxima (nblk_max, [nchunk_max,] tours); a block beyond its own tour's nblk / nchunk returns at once.  With
-// equal sizes the grids are exactly those of the grouped entries.  A flat work list with a search over a prefix array would
-// launch no idle block, but every block would pay the search and equal sizes would no longer map to the grouped grid; an idle
-// block costs a descriptor load and an exit.
-struct RaggedTour {        // 64 bytes; offsets in elements of the array they index
-  int group, n, nblk, nchunk;
-  long long points;        // the group's first coordinate in `points` (doubles)
-  long long tours;         // the tour's first entry in `tours` (n + 1 per tour)
-  long long tp;            //                       in tp (n + 1 per tour)
-  long long cols;          //                       in dlen, q and d32 (n per tour each: one offset serves the three)
-  long long partial;       //                       in partial (nblk per tour)
-  long long bmin;          //                       in bmin (nblk * nchunk per tour)
-};
-
-struct RaggedGroup {       // what the apply block and the max |coordinate| reduction of a group need
-  int first, count;        // its tours: desc[first .. first + count - 1], all of n nodes and nblk partials,
-  int n, nblk;
-  long long points;
-  long long tours, partial;   // so tour p of the group starts at tours + p (n + 1) and partial + p nblk: no descriptor per tour
-};
-
-__global__ void two_opt_prep_ragged_kernel(const double* __restrict__ points, const int* __restrict__ tours,
-                                           const RaggedTour* __restrict__ desc, double2* __restrict__ tp, double* __restrict__ dlen,
-                                           const int* __restrict__ tdone) {
-  const RaggedTour d = desc[blockIdx.y];
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > d.n || tdone[blockIdx.y]) return;
-  prep_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols);
-}
-
-__global__ __launch_bounds__(256) void two_opt_best_ragged_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                                  const RaggedTour* __restrict__ desc, Best* __restrict__ partial,
-                                                                  const int* __restrict__ tdone) {
-  const RaggedTour d = desc[blockIdx.y];
-  if ((int)blockIdx.x >= d.nblk || tdone[blockIdx.y]) return;
-  const Best r = best_tile(tp + d.tp, dlen + d.cols, d.n, blockIdx.x * TI);
-  if (threadIdx.x == 0) partial[d.partial + blockIdx.x] = r;
-}
-
-__global__ void two_opt_maxabs_ragged_kernel(const double* __restrict__ points, const RaggedGroup* __restrict__ grp,
-                                             unsigned long long* __restrict__ gmax) {
-  const RaggedGroup G = grp[blockIdx.y];
-  const double* pts = points + G.points;
-  unsigned long long m = 0;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < 2 * G.n; k += gridDim.x * blockDim.x) {
-    const unsigned long long v = (unsigned long long)__double_as_longlong(fabs(pts[k]));
-    m = v > m ? v : m;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    const unsigned long long o = __shfl_xor(m, off);
-    m = o > m ? o : m;
-  }
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + blockIdx.y, m);
-}
-
-__global__ void two_opt_prep_screen_ragged_kernel(const double* __restrict__ points, const int* __restrict__ tours,
-                                                  const RaggedTour* __restrict__ desc, double2* __restrict__ tp,
-                                                  double* __restrict__ dlen, float4* __restrict__ q, float* __restrict__ d32,
-                                                  unsigned* __restrict__ tmin, const int* __restrict__ tdone) {
-  const RaggedTour d = desc[blockIdx.y];
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > d.n || tdone[blockIdx.y]) return;
-  if (k == 0) tmin[blockIdx.y] = f32_key(0.0f);
-  prep_screen_entry(points + d.points, tours + d.tours, d.n, k, tp + d.tp, dlen + d.cols, q + d.cols, d32 + d.cols);
-}
-
-__global__ __launch_bounds__(256) void two_opt_screen_ragged_kernel(const float4* __restrict__ q, const float* __restrict__ d32,
-                                                                    const RaggedTour* __restrict__ desc, float* __restrict__ bmin,
-                                                                    unsigned* __restrict__ tmin, const int* __restrict__ tdone) {
-  const RaggedTour d = desc[blockIdx.z];
-  const int i0 = blockIdx.x * TI, jbase = blockIdx.y * SCH;
-  if ((int)blockIdx.x >= d.nblk || (int)blockIdx.y >= d.nchunk) return;   // beyond the tour's own tiles
-  if (jbase + SCH <= i0 + 2) return;                                       // the chunk lies left of the triangle
-  if (tdone[blockIdx.z]) return;
-  const float m = screen_tile(q + d.cols, d32 + d.cols, d.n, i0, jbase);
-  if (threadIdx.x == 0) screen_publish(m, bmin + d.bmin + (long long)blockIdx.x * d.nchunk + blockIdx.y, tmin + blockIdx.z);
-}
-
-__global__ __launch_bounds__(256) void two_opt_screened_best_ragged_kernel(
-    const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q, const float* __restrict__ d32,
-    const RaggedTour* __restrict__ desc, const float* __restrict__ bmin, const unsigned* __restrict__ tmin,
-    const double* __restrict__ gmax, Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs,
-    const int* __restrict__ tdone) {
-  const RaggedTour d = desc[blockIdx.y];
-  if ((int)blockIdx.x >= d.nblk || tdone[blockIdx.y]) return;
+    A a, const double2* __restrict__ tp, const double* __restrict__ dlen, const float4* __restrict__ q,
+    const float* __restrict__ d32, const float* __restrict__ bmin, const unsigned* __restrict__ tmin,
+    const double* __restrict__ gmax, Best* __restrict__ partial, unsigned long long* __restrict__ exact_pairs) {
+  const RaggedTour d = a.tour(blockIdx.y);
+  if constexpr (A::kTable)
+    if ((int)blockIdx.x >= d.nblk) return;                     // beyond the tour's own tiles
+  if (a.stopped(blockIdx.y)) return;
   screened_best_tile(tp + d.tp, dlen + d.cols, q + d.cols, d32 + d.cols, d.n, d.nchunk, blockIdx.x * TI,
                      bmin + d.bmin + (long long)blockIdx.x * d.nchunk, f32_unkey(tmin[blockIdx.y]), screen_eps(gmax[d.group]),
                      partial + d.partial + blockIdx.x, exact_pairs);
 }
 
-// two_opt_apply_grouped_kernel with the group's tours and their n from the tables.  A group that stops also sets tdone of its
-// tours: the other kernels read their tour's flag by the block's own index, alongside the descriptor and not after it.
-__global__ __launch_bounds__(256) void two_opt_apply_ragged_kernel(int* __restrict__ tours,
-                                                                   const RaggedGroup* __restrict__ grp,
-                                                                   const Best* __restrict__ partial, long long max_iterations,
-                                                                   TwoOptState* st, int* __restrict__ gdone,
-                                                                   int* __restrict__ tdone, long long* __restrict__ giters,
-                                                                   Best* __restrict__ chosen) {
-  const int g = blockIdx.x;
-  if (gdone[g]) return;
-  __shared__ double gmin;
-  const RaggedGroup G = grp[g];
-  auto stop = [&]() {                                          // thread 0
-    gdone[g] = 1;
-    for (int b = G.first; b < G.first + G.count; ++b) tdone[b] = 1;
-    atomicAdd(&st->done, 1);
-  };
-  for (int p = 0; p < G.count; ++p) {
-    const Best r = tour_argmin(partial + G.partial + (long long)p * G.nblk, G.nblk);
-    if (threadIdx.x == 0) chosen[G.first + p] = r;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double m = chosen[G.first].v;
-    for (int b = G.first + 1; b < G.first + G.count; ++b) m = chosen[b].v < m ? chosen[b].v : m;
-    gmin = m;
-  }
-  __syncthreads();
-  if (!(gmin < -1e-6)) {
-    if (threadIdx.x == 0) stop();
-    return;
-  }
-  for (int p = 0; p < G.count; ++p) apply_move(tours + G.tours + (long long)p * (G.n + 1), chosen[G.first + p].idx, G.n);
-  if (threadIdx.x == 0) {
-    giters[g] += 1;
-    if (giters[g] >= max_iterations) stop();
-  }
-}
+// ---- the host side: one layout, one driver --------------------------------------------------------------------------------------
 
-struct RaggedLayout {      // byte offsets; the screen's arrays (q ..) only with method 1
-  size_t desc, grp, tp, dlen, partial, chosen, gdone, tdone, giters, st, q, d32, bmin, tmin, gmax, counter, total;
-  int tours, nmax, nblk_max, nchunk_max;
+struct TwoOptCall {        // what an entry asks for; the first block is all the layout needs
+  const char* who;         // for the messages
+  bool table;              // false: `groups` groups of per_group tours of n nodes (UniformAddr); true: group_n / group_tours (TableAddr)
+  int method;              // 0 exact, 1 screened
+  int groups, n, per_group;
+  const int32_t *group_n, *group_tours;
+  const double* points;
+  int32_t* tours;
+  int64_t max_iterations;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t* iterations_out;   // host [groups]
+  int64_t* exact_pairs_out;  // host, optional
+  void* stream;
+  int n_of(int g) const { return table ? group_n[g] : n; }
+  int tours_of(int g) const { return table ? group_tours[g] : per_group; }
 };
 
-constexpr int kRaggedMaxTours = 65535;             // a grid dimension
-constexpr int kRaggedMaxNodes = 65535 * TI;
+// Byte offsets.  The exact uniform entries' arrays first, in their order, so the screened entries run the exact sweep on the same
+// workspace; desc, grp and tdone only in the table form, q .. counter only with method 1.
+struct TwoOptLayout {
+  size_t desc, grp, tp, dlen, partial, chosen, gdone, tdone, giters, stopped, q, d32, bmin, tmin, gmax, counter, total;
+  int tours, nmax, nblk_max, nchunk_max;
+  std::vector<RaggedTour> tab;     // the host tables (table form, on request)
+  std::vector<RaggedGroup> gtab;
+};
 
-// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
-int ragged_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, int method, RaggedLayout* L,
-                  std::vector<RaggedTour>* tab, std::vector<RaggedGroup>* gtab) {
-  if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
-  if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
-  if (method != 0 && method != 1) return set_error(DIFUSCO_EINVAL, "%s: method %d (0 exact, 1 screened)", who, method);
-  long long T = 0;
-  for (int g = 0; g < groups; ++g) {
-    if (group_n[g] < 4) return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, needs n >= 4", who, g, group_n[g]);
-    if (group_n[g] > kRaggedMaxNodes)
-      return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, at most %d nodes", who, g, group_n[g], kRaggedMaxNodes);
-    if (group_tours[g] < 1) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d tours, needs at least 1", who, g, group_tours[g]);
-    T += group_tours[g];
-    if (T > kRaggedMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kRaggedMaxTours);
-  }
-  if (tab) tab->clear();
-  if (gtab) gtab->clear();
-  size_t points = 0, closed = 0, cols = 0, nblks = 0, tiles = 0;
+// lays the workspace of a call out (the group arrays are checked by then); with_tables: builds the tables as well
+int two_opt_layout(const TwoOptCall& c, bool with_tables, TwoOptLayout* L) {
+  size_t points = 0, closed = 0, cols = 0, nblks = 0, tiles = 0, T = 0;
   L->nmax = L->nblk_max = L->nchunk_max = 0;
-  for (int g = 0; g < groups; ++g) {
-    const int n = group_n[g], nblk = (n + TI - 1) / TI, nchunk = (n + SCH - 1) / SCH;
+  const int kinds = c.table ? c.groups : 1;                    // uniform: one kind of group, c.groups times
+  for (int g = 0; g < kinds; ++g) {
+    const int n = c.n_of(g), nblk = (n + TI - 1) / TI, nchunk = (n + SCH - 1) / SCH;
+    const size_t count = c.table ? (size_t)c.group_tours[g] : (size_t)c.groups * c.per_group;
     L->nmax = n > L->nmax ? n : L->nmax;
     L->nblk_max = nblk > L->nblk_max ? nblk : L->nblk_max;
     L->nchunk_max = nchunk > L->nchunk_max ? nchunk : L->nchunk_max;
-    if (gtab)
-      gtab->push_back(RaggedGroup{(int)(tab ? tab->size() : 0), group_tours[g], n, nblk, (long long)points, (long long)closed,
-                                  (long long)nblks});
-    for (int p = 0; p < group_tours[g]; ++p) {
-      if (tab)
-        tab->push_back(RaggedTour{g, n, nblk, nchunk, (long long)points, (long long)closed, (long long)closed, (long long)cols,
-                                  (long long)nblks, (long long)tiles});
-      closed += (size_t)n + 1;
-      cols += (size_t)n;
-      nblks += (size_t)nblk;
-      tiles += (size_t)nblk * nchunk;
+    if (c.table && with_tables) {
+      L->gtab.push_back(RaggedGroup{(int)T, (int)count, n, nblk, (long long)points, (long long)closed, (long long)nblks});
+      for (size_t p = 0; p < count; ++p)
+        L->tab.push_back(RaggedTour{g, n, nblk, nchunk, (long long)points, (long long)(closed + p * (n + 1)),
+                                    (long long)(closed + p * (n + 1)), (long long)(cols + p * n), (long long)(nblks + p * nblk),
+                                    (long long)(tiles + p * nblk * nchunk)});
     }
+    T += count;
+    closed += count * ((size_t)n + 1);
+    cols += count * n;
+    nblks += count * nblk;
+    tiles += count * nblk * nchunk;
     points += 2 * (size_t)n;
   }
+  if (!c.table && c.method == 1 && (T > 65535 || L->nblk_max > 65535 || L->nchunk_max > 65535))
+    return set_error(DIFUSCO_EINVAL, "two_opt_screened: at most 65535 tours per call and %d nodes", 65535 * TI);
   L->tours = (int)T;
   size_t off = 0;
-  auto take = [&off](size_t bytes) {
+  auto take = [&off](bool present, size_t bytes) {
     const size_t at = off;
-    off += up256(bytes);
+    if (present) off += up256(bytes);
     return at;
   };
-  L->desc = take(sizeof(RaggedTour) * T);
-  L->grp = take(sizeof(RaggedGroup) * groups);
-  L->tp = take(sizeof(double2) * closed);
-  L->dlen = take(sizeof(double) * cols);
-  L->partial = take(sizeof(Best) * nblks);
-  L->chosen = take(sizeof(Best) * T);
-  L->gdone = take(sizeof(int) * groups);                       // gdone .. st are cleared by one memset
-  L->tdone = take(sizeof(int) * T);
-  L->giters = take(sizeof(long long) * groups);
-  L->st = take(sizeof(TwoOptState));
-  L->q = L->d32 = L->bmin = L->tmin = L->gmax = L->counter = off;
-  if (method == 1) {
-    L->q = take(sizeof(float4) * cols);
-    L->d32 = take(sizeof(float) * cols);
-    L->bmin = take(sizeof(float) * tiles);
-    L->tmin = take(sizeof(unsigned) * T);
-    L->gmax = take(sizeof(double) * groups);
-    L->counter = take(sizeof(unsigned long long));
-  }
+  L->desc = take(c.table, sizeof(RaggedTour) * T);
+  L->grp = take(c.table, sizeof(RaggedGroup) * c.groups);
+  L->tp = take(true, sizeof(double2) * closed);
+  L->dlen = take(true, sizeof(double) * cols);
+  L->partial = take(true, sizeof(Best) * nblks);
+  L->chosen = take(true, sizeof(Best) * T);
+  L->gdone = take(true, sizeof(int) * c.groups);               // gdone .. stopped are cleared by one memset
+  L->tdone = take(c.table, sizeof(int) * T);
+  L->giters = take(true, sizeof(long long) * c.groups);
+  L->stopped = take(true, sizeof(int));                        // the number of groups that have stopped
+  const bool screen = c.method == 1;
+  L->q = take(screen, sizeof(float4) * cols);
+  L->d32 = take(screen, sizeof(float) * cols);
+  L->bmin = take(screen, sizeof(float) * tiles);
+  L->tmin = take(screen, sizeof(unsigned) * T);
+  L->gmax = take(screen, sizeof(double) * c.groups);           // gmax and counter are cleared by one memset
+  L->counter = take(screen, sizeof(unsigned long long));
   L->total = off;
   return DIFUSCO_OK;
+}
+
+int two_opt_bytes(const TwoOptCall& c, size_t* bytes) {
+  TwoOptLayout lay;
+  const int rc = two_opt_layout(c, false, &lay);
+  if (rc == DIFUSCO_OK) *bytes = lay.total;
+  return rc;
+}
+
+struct TwoOptPtrs {        // (workspace, layout) as typed pointers
+  RaggedTour* desc;
+  RaggedGroup* grp;
+  double2* tp;
+  double* dlen;
+  Best *partial, *chosen;
+  int *gdone, *tdone;
+  long long* giters;
+  int* stopped;
+  float4* q;
+  float *d32, *bmin;
+  unsigned* tmin;
+  unsigned long long *gmax, *counter;
+  TwoOptPtrs(void* workspace, const TwoOptLayout& L) {
+    char* w = (char*)workspace;
+    desc = (RaggedTour*)(w + L.desc), grp = (RaggedGroup*)(w + L.grp);
+    tp = (double2*)(w + L.tp), dlen = (double*)(w + L.dlen);
+    partial = (Best*)(w + L.partial), chosen = (Best*)(w + L.chosen);
+    gdone = (int*)(w + L.gdone), tdone = (int*)(w + L.tdone);
+    giters = (long long*)(w + L.giters), stopped = (int*)(w + L.stopped);
+    q = (float4*)(w + L.q), d32 = (float*)(w + L.d32), bmin = (float*)(w + L.bmin), tmin = (unsigned*)(w + L.tmin);
+    gmax = (unsigned long long*)(w + L.gmax), counter = (unsigned long long*)(w + L.counter);
+  }
+};
+
+long long evaluations(long long iterations, long long max_iterations) {   // sweeps of the exact loop that did work
+  return iterations < (max_iterations > 0 ? max_iterations : 1) ? iterations + 1 : iterations;
+}
+
+// the max |coordinate| pass of a screened call
+template <class A>
+void launch_maxabs(const A& a, const TwoOptCall& c, const TwoOptLayout& L, const TwoOptPtrs& p, hipStream_t s) {
+  const int mblocks = (2 * L.nmax + 255) / 256 < 64 ? (2 * L.nmax + 255) / 256 : 64;
+  hipLaunchKernelGGL(two_opt_maxabs_kernel<A>, dim3(mblocks, c.groups), dim3(256), 0, s, a, c.points, p.gmax);
+}
+
+// the launches of one move: prep, best or screen + screened best, apply
+template <class A>
+void launch_move(const A& a, bool screened, const TwoOptCall& c, const TwoOptLayout& L, const TwoOptPtrs& p, hipStream_t s) {
+  const int T = L.tours;
+  const dim3 prep_grid((L.nmax + 1 + 255) / 256, T), best_grid(L.nblk_max, T);
+  if (screened) {
+    hipLaunchKernelGGL(two_opt_prep_screen_kernel<A>, prep_grid, dim3(256), 0, s, a, c.points, (const int*)c.tours, p.tp, p.dlen,
+                       p.q, p.d32, p.tmin);
+    hipLaunchKernelGGL(two_opt_screen_kernel<A>, dim3(L.nblk_max, L.nchunk_max, T), dim3(256), 0, s, a, (const float4*)p.q,
+                       (const float*)p.d32, p.bmin, p.tmin);
+    hipLaunchKernelGGL(two_opt_screened_best_kernel<A>, best_grid, dim3(256), 0, s, a, (const double2*)p.tp, (const double*)p.dlen,
+                       (const float4*)p.q, (const float*)p.d32, (const float*)p.bmin, (const unsigned*)p.tmin,
+                       (const double*)p.gmax, p.partial, p.counter);
+  } else {
+    hipLaunchKernelGGL(two_opt_prep_kernel<A>, prep_grid, dim3(256), 0, s, a, c.points, (const int*)c.tours, p.tp, p.dlen);
+    hipLaunchKernelGGL(two_opt_best_kernel<A>, best_grid, dim3(256), 0, s, a, (const double2*)p.tp, (const double*)p.dlen,
+                       p.partial);
+  }
+  hipLaunchKernelGGL(two_opt_apply_kernel<A>, dim3(c.groups), dim3(256), 0, s, a, (int*)c.tours, (const Best*)p.partial,
+                     (long long)c.max_iterations, p.stopped, p.gdone, p.giters, p.chosen);
+}
+
+// The driver of every entry (whose own argument checks have passed): layout, clearing, the tables (table form), the bound
+// decision (method 1), the moves with a host poll every 8, the read-back.
+int two_opt_run(const TwoOptCall& c) {
+  TwoOptLayout L;
+  const int rc = two_opt_layout(c, true, &L);
+  if (rc != DIFUSCO_OK) return rc;
+  if (c.workspace_bytes < L.total)
+    return set_error(DIFUSCO_EINVAL, "%s: workspace %zu < %zu bytes", c.who, c.workspace_bytes, L.total);
+  const TwoOptPtrs p(c.workspace, L);
+  const UniformAddr ua{c.n, c.per_group, L.nblk_max, L.nchunk_max, p.gdone};
+  const TableAddr ta{p.desc, p.grp, p.tdone};
+  hipStream_t s = (hipStream_t)c.stream;
+  const int groups = c.groups;
+  hipError_t er = hipSuccess;
+  if (c.table) {                                               // the tables, once per call; L holds them until the synchronisation below
+    er = hipMemcpyAsync(p.desc, L.tab.data(), sizeof(RaggedTour) * L.tours, hipMemcpyHostToDevice, s);
+    if (er == hipSuccess) er = hipMemcpyAsync(p.grp, L.gtab.data(), sizeof(RaggedGroup) * groups, hipMemcpyHostToDevice, s);
+  }
+  if (er == hipSuccess) er = hipMemsetAsync(p.gdone, 0, (char*)p.stopped + sizeof(int) - (char*)p.gdone, s);
+  bool screened = c.method == 1;
+  if (er == hipSuccess && screened) {                          // M per group decides, once per call, whether the screen has a bound
+    er = hipMemsetAsync(p.gmax, 0, L.total - L.gmax, s);
+    if (er == hipSuccess) {
+      if (c.table) launch_maxabs(ta, c, L, p, s);
+      else launch_maxabs(ua, c, L, p, s);
+    }
+    std::vector<double> maxabs(groups);
+    if (er == hipSuccess) er = hipMemcpyAsync(maxabs.data(), p.gmax, sizeof(double) * groups, hipMemcpyDeviceToHost, s);
+    if (er == hipSuccess) er = hipStreamSynchronize(s);
+    for (int g = 0; er == hipSuccess && g < groups; ++g) {
+      double eps = 0.0;
+      screened = screened && difusco_tsp_two_opt_screen_bound(maxabs[g], &eps) == 1;   // one group without a bound: exact sweep
+    }
+  } else if (er == hipSuccess && c.table) {
+    er = hipStreamSynchronize(s);
+  }
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s setup: %s", c.who, hipGetErrorString(er));
+  // the reference evaluates the moves once more after the last applied one and stops on `min_change >= -1e-6`;
+  // at most max_iterations moves are applied (tsp_utils.py:20-47)
+  const int poll = 8;
+  const long long loops = c.max_iterations > 0 ? c.max_iterations : 1;   // the reference always evaluates (and may apply) once
+  for (long long it = 0; it < loops; ++it) {
+    if (c.table) launch_move(ta, screened, c, L, p, s);
+    else launch_move(ua, screened, c, L, p, s);
+    if ((it + 1) % poll == 0 || it + 1 == loops) {
+      int stopped = 0;
+      er = hipMemcpyAsync(&stopped, p.stopped, sizeof(int), hipMemcpyDeviceToHost, s);
+      if (er == hipSuccess) er = hipStreamSynchronize(s);
+      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(er));
+      if (stopped >= groups) break;
+    }
+  }
+  unsigned long long pairs = 0;
+  er = hipMemcpyAsync(c.iterations_out, p.giters, sizeof(long long) * groups, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess && screened) er = hipMemcpyAsync(&pairs, p.counter, sizeof(pairs), hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s iterations: %s", c.who, hipGetErrorString(er));
+  if (!c.exact_pairs_out) return DIFUSCO_OK;
+  if (!screened)                                               // every pair of every sweep that did work, in float64
+    for (int g = 0; g < groups; ++g)
+      pairs += (unsigned long long)(evaluations(c.iterations_out[g], c.max_iterations) * c.tours_of(g) *
+                                    ((long long)(c.n_of(g) - 1) * (c.n_of(g) - 2) / 2));
+  *c.exact_pairs_out = (int64_t)pairs;
+  return DIFUSCO_OK;
+}
+
+TwoOptCall uniform_call(const char* who, int method, int n, int groups, int per_group) {
+  TwoOptCall c{};
+  c.who = who, c.method = method, c.n = n, c.groups = groups, c.per_group = per_group;
+  return c;
 }
 
 }  // namespace
@@ -724,13 +620,11 @@ int ragged_layout(const char* who, int groups, const int32_t* group_n, const int
 
 extern "C" {
 
+// one group of `batch` tours
 int difusco_tsp_two_opt_workspace_bytes(int n_nodes, int batch, size_t* bytes) {
   using namespace difusco;
   if (!bytes || n_nodes < 4 || batch < 1) return set_error(DIFUSCO_EINVAL, "two_opt_workspace_bytes: bad arguments");
-  const size_t nblk = (size_t)(n_nodes + TI - 1) / TI;
-  *bytes = up256(sizeof(double2) * (size_t)batch * (n_nodes + 1)) + up256(sizeof(double) * (size_t)batch * n_nodes) +
-           up256(sizeof(Best) * (size_t)batch * nblk) + up256(sizeof(Best) * (size_t)batch) + 256;
-  return DIFUSCO_OK;
+  return two_opt_bytes(uniform_call("two_opt_workspace_bytes", 0, n_nodes, 1, batch), bytes);
 }
 
 int difusco_tsp_two_opt(int n_nodes, int batch, const double* points, int32_t* tours, int64_t max_iterations,
@@ -738,55 +632,20 @@ int difusco_tsp_two_opt(int n_nodes, int batch, const double* points, int32_t* t
   using namespace difusco;
   if (n_nodes < 4 || batch < 1 || !points || !tours || !workspace || max_iterations < 0)
     return set_error(DIFUSCO_EINVAL, "tsp_two_opt: needs n_nodes >= 4, batch >= 1 and non-null device arrays");
-  size_t need = 0;
-  difusco_tsp_two_opt_workspace_bytes(n_nodes, batch, &need);
-  if (workspace_bytes < need) return set_error(DIFUSCO_EINVAL, "tsp_two_opt: workspace %zu < %zu bytes", workspace_bytes, need);
-  const int n = n_nodes, nblk = (n + TI - 1) / TI;
-  char* w = (char*)workspace;
-  double2* tp = (double2*)w;
-  w += up256(sizeof(double2) * (size_t)batch * (n + 1));
-  double* dlen = (double*)w;
-  w += up256(sizeof(double) * (size_t)batch * n);
-  Best* partial = (Best*)w;
-  w += up256(sizeof(Best) * (size_t)batch * nblk);
-  Best* chosen = (Best*)w;
-  w += up256(sizeof(Best) * (size_t)batch);
-  TwoOptState* st = (TwoOptState*)w;
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t er = hipMemsetAsync(st, 0, sizeof(TwoOptState), s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "memset: %s", hipGetErrorString(er));
-  TwoOptState host{0, 0, 0};
-  // the reference evaluates the moves once more after the last applied one and stops on `min_change >= -1e-6`;
-  // at most max_iterations moves are applied (tsp_utils.py:20-47)
-  const int poll = 8;
-  const long long loops = max_iterations > 0 ? max_iterations : 1;   // the reference always evaluates (and may apply) once
-  for (long long it = 0; it < loops; ++it) {
-    hipLaunchKernelGGL(two_opt_prep_kernel<false>, dim3((n + 1 + 255) / 256, batch), dim3(256), 0, s, points, tours, n, batch,
-                       tp, dlen, st, (const int*)nullptr, batch);
-    hipLaunchKernelGGL(two_opt_best_kernel<false>, dim3(nblk, batch), dim3(256), 0, s, tp, dlen, n, partial, st,
-                       (const int*)nullptr, batch);
-    hipLaunchKernelGGL(two_opt_apply_kernel, dim3(1), dim3(256), 0, s, tours, n, batch, nblk, partial,
-                       (long long)max_iterations, st, chosen);
-    if ((it + 1) % poll == 0 || it + 1 == loops) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
-      if (host.done) break;
-    }
-  }
-  er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
-  if (iterations_out) *iterations_out = host.iterations;
-  return DIFUSCO_OK;
+  int64_t iterations = 0;
+  TwoOptCall c = uniform_call("tsp_two_opt", 0, n_nodes, 1, batch);
+  c.points = points, c.tours = tours, c.max_iterations = max_iterations, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.iterations_out = &iterations, c.stream = stream;
+  const int rc = two_opt_run(c);
+  if (rc == DIFUSCO_OK && iterations_out) *iterations_out = iterations;
+  return rc;
 }
 
 int difusco_tsp_two_opt_grouped_workspace_bytes(int n_nodes, int groups, int per_group, size_t* bytes) {
   using namespace difusco;
   if (!bytes || n_nodes < 4 || groups < 1 || per_group < 1 || (long long)groups * per_group > (1 << 30))
     return set_error(DIFUSCO_EINVAL, "two_opt_grouped_workspace_bytes: bad arguments");
-  *bytes = grouped_layout(n_nodes, groups, per_group).total;
-  return DIFUSCO_OK;
+  return two_opt_bytes(uniform_call("two_opt_grouped_workspace_bytes", 0, n_nodes, groups, per_group), bytes);
 }
 
 int difusco_tsp_two_opt_grouped(int n_nodes, int groups, int per_group, const double* points, int32_t* tours,
@@ -797,44 +656,10 @@ int difusco_tsp_two_opt_grouped(int n_nodes, int groups, int per_group, const do
       !workspace || !iterations_out || max_iterations < 0)
     return set_error(DIFUSCO_EINVAL, "tsp_two_opt_grouped: needs n_nodes >= 4, groups, per_group >= 1, non-null device arrays "
                                      "and a host iterations_out[groups]");
-  size_t need = 0;
-  difusco_tsp_two_opt_grouped_workspace_bytes(n_nodes, groups, per_group, &need);
-  if (workspace_bytes < need)
-    return set_error(DIFUSCO_EINVAL, "tsp_two_opt_grouped: workspace %zu < %zu bytes", workspace_bytes, need);
-  const int n = n_nodes, nblk = (n + TI - 1) / TI, batch = groups * per_group;
-  const GroupedLayout gl = grouped_layout(n, groups, per_group);
-  char* w = (char*)workspace;
-  double2* tp = (double2*)(w + gl.tp);
-  double* dlen = (double*)(w + gl.dlen);
-  Best* partial = (Best*)(w + gl.partial);
-  Best* chosen = (Best*)(w + gl.chosen);
-  int* gdone = (int*)(w + gl.gdone);
-  long long* giters = (long long*)(w + gl.giters);
-  TwoOptState* st = (TwoOptState*)(w + gl.st);
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t er = hipMemsetAsync(gdone, 0, (char*)st + sizeof(TwoOptState) - (char*)gdone, s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "memset: %s", hipGetErrorString(er));
-  TwoOptState host{0, 0, 0};
-  const int poll = 8;
-  const long long loops = max_iterations > 0 ? max_iterations : 1;   // as difusco_tsp_two_opt
-  for (long long it = 0; it < loops; ++it) {
-    hipLaunchKernelGGL(two_opt_prep_kernel<true>, dim3((n + 1 + 255) / 256, batch), dim3(256), 0, s, points, tours, n, batch,
-                       tp, dlen, st, gdone, per_group);
-    hipLaunchKernelGGL(two_opt_best_kernel<true>, dim3(nblk, batch), dim3(256), 0, s, tp, dlen, n, partial, st, gdone,
-                       per_group);
-    hipLaunchKernelGGL(two_opt_apply_grouped_kernel, dim3(groups), dim3(256), 0, s, tours, n, per_group, nblk, partial,
-                       (long long)max_iterations, st, gdone, giters, chosen);
-    if ((it + 1) % poll == 0 || it + 1 == loops) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  er = hipMemcpyAsync(iterations_out, giters, sizeof(long long) * groups, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt_grouped iterations: %s", hipGetErrorString(er));
-  return DIFUSCO_OK;
+  TwoOptCall c = uniform_call("tsp_two_opt_grouped", 0, n_nodes, groups, per_group);
+  c.points = points, c.tours = tours, c.max_iterations = max_iterations, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.iterations_out = iterations_out, c.stream = stream;
+  return two_opt_run(c);
 }
 
 int difusco_tsp_two_opt_screen_bound(double max_abs_coord, double* eps) {
@@ -850,10 +675,7 @@ int difusco_tsp_two_opt_grouped_screened_workspace_bytes(int n_nodes, int groups
   using namespace difusco;
   if (!bytes || n_nodes < 4 || groups < 1 || per_group < 1 || (long long)groups * per_group > (1 << 30))
     return set_error(DIFUSCO_EINVAL, "two_opt_grouped_screened_workspace_bytes: bad arguments");
-  ScreenedLayout lay;
-  const int rc = screened_layout(n_nodes, groups, per_group, &lay);
-  if (rc == DIFUSCO_OK) *bytes = lay.total;
-  return rc;
+  return two_opt_bytes(uniform_call("two_opt_grouped_screened_workspace_bytes", 1, n_nodes, groups, per_group), bytes);
 }
 
 int difusco_tsp_two_opt_grouped_screened(int n_nodes, int groups, int per_group, const double* points, int32_t* tours,
@@ -864,17 +686,19 @@ int difusco_tsp_two_opt_grouped_screened(int n_nodes, int groups, int per_group,
       !workspace || !iterations_out || max_iterations < 0)
     return set_error(DIFUSCO_EINVAL, "tsp_two_opt_grouped_screened: needs n_nodes >= 4, groups, per_group >= 1, non-null device "
                                      "arrays and a host iterations_out[groups]");
-  return two_opt_screened_run(n_nodes, groups, per_group, points, tours, max_iterations, workspace, workspace_bytes,
-                              iterations_out, exact_pairs_out, stream);
+  TwoOptCall c = uniform_call("tsp_two_opt_screened", 1, n_nodes, groups, per_group);
+  c.points = points, c.tours = tours, c.max_iterations = max_iterations, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.iterations_out = iterations_out, c.exact_pairs_out = exact_pairs_out, c.stream = stream;
+  return two_opt_run(c);
 }
 
 int difusco_tsp_two_opt_screened_workspace_bytes(int n_nodes, int batch, size_t* bytes) {
   using namespace difusco;
   if (!bytes || n_nodes < 4 || batch < 1) return set_error(DIFUSCO_EINVAL, "two_opt_screened_workspace_bytes: bad arguments");
-  return difusco_tsp_two_opt_grouped_screened_workspace_bytes(n_nodes, 1, batch, bytes);
+  return two_opt_bytes(uniform_call("two_opt_screened_workspace_bytes", 1, n_nodes, 1, batch), bytes);
 }
 
-// one group of `batch` tours: difusco_tsp_two_opt_grouped with groups = 1 is difusco_tsp_two_opt
+// one group of `batch` tours
 int difusco_tsp_two_opt_screened(int n_nodes, int batch, const double* points, int32_t* tours, int64_t max_iterations,
                                  void* workspace, size_t workspace_bytes, int64_t* iterations_out, int64_t* exact_pairs_out,
                                  void* stream) {
@@ -882,8 +706,10 @@ int difusco_tsp_two_opt_screened(int n_nodes, int batch, const double* points, i
   if (n_nodes < 4 || batch < 1 || !points || !tours || !workspace || max_iterations < 0)
     return set_error(DIFUSCO_EINVAL, "tsp_two_opt_screened: needs n_nodes >= 4, batch >= 1 and non-null device arrays");
   int64_t iterations = 0;
-  const int rc = two_opt_screened_run(n_nodes, 1, batch, points, tours, max_iterations, workspace, workspace_bytes, &iterations,
-                                      exact_pairs_out, stream);
+  TwoOptCall c = uniform_call("tsp_two_opt_screened", 1, n_nodes, 1, batch);
+  c.points = points, c.tours = tours, c.max_iterations = max_iterations, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.iterations_out = &iterations, c.exact_pairs_out = exact_pairs_out, c.stream = stream;
+  const int rc = two_opt_run(c);
   if (rc == DIFUSCO_OK && iterations_out) *iterations_out = iterations;
   return rc;
 }
@@ -891,102 +717,34 @@ int difusco_tsp_two_opt_screened(int n_nodes, int batch, const double* points, i
 int difusco_tsp_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int method,
                                                size_t* bytes) {
   using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "two_opt_ragged_workspace_bytes: bytes is null");
-  RaggedLayout lay;
-  const int rc = ragged_layout("two_opt_ragged_workspace_bytes", groups, group_n, group_tours, method, &lay, nullptr, nullptr);
-  if (rc == DIFUSCO_OK) *bytes = lay.total;
-  return rc;
+  const char* who = "two_opt_ragged_workspace_bytes";
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "%s: bytes is null", who);
+  int T = 0;
+  const int rc = check_groups(who, groups, group_n, group_tours, &T);
+  if (rc != DIFUSCO_OK) return rc;
+  if (method != 0 && method != 1) return set_error(DIFUSCO_EINVAL, "%s: method %d (0 exact, 1 screened)", who, method);
+  TwoOptCall c{};
+  c.who = who, c.table = true, c.method = method, c.groups = groups, c.group_n = group_n, c.group_tours = group_tours;
+  return two_opt_bytes(c, bytes);
 }
 
 int difusco_tsp_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
                                int32_t* tours, int64_t max_iterations, int method, void* workspace, size_t workspace_bytes,
                                int64_t* iterations_out, int64_t* exact_pairs_out, void* stream) {
   using namespace difusco;
-  RaggedLayout lay;
-  std::vector<RaggedTour> tab;
-  std::vector<RaggedGroup> gtab;
-  const int rc = ragged_layout("tsp_two_opt_ragged", groups, group_n, group_tours, method, &lay, &tab, &gtab);
+  const char* who = "tsp_two_opt_ragged";
+  int T = 0;
+  const int rc = check_groups(who, groups, group_n, group_tours, &T);
   if (rc != DIFUSCO_OK) return rc;
+  if (method != 0 && method != 1) return set_error(DIFUSCO_EINVAL, "%s: method %d (0 exact, 1 screened)", who, method);
   if (!points || !tours || !workspace || !iterations_out || max_iterations < 0)
     return set_error(DIFUSCO_EINVAL, "tsp_two_opt_ragged: needs non-null device arrays, a host iterations_out[groups] and "
                                      "max_iterations >= 0");
-  if (workspace_bytes < lay.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_two_opt_ragged: workspace %zu < %zu bytes", workspace_bytes, lay.total);
-  char* w = (char*)workspace;
-  RaggedTour* desc = (RaggedTour*)(w + lay.desc);
-  RaggedGroup* grp = (RaggedGroup*)(w + lay.grp);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  Best* partial = (Best*)(w + lay.partial);
-  Best* chosen = (Best*)(w + lay.chosen);
-  int* gdone = (int*)(w + lay.gdone);
-  int* tdone = (int*)(w + lay.tdone);
-  long long* giters = (long long*)(w + lay.giters);
-  TwoOptState* st = (TwoOptState*)(w + lay.st);
-  float4* q = (float4*)(w + lay.q);
-  float* d32 = (float*)(w + lay.d32);
-  float* bmin = (float*)(w + lay.bmin);
-  unsigned* tmin = (unsigned*)(w + lay.tmin);
-  unsigned long long* gmax = (unsigned long long*)(w + lay.gmax);
-  unsigned long long* counter = (unsigned long long*)(w + lay.counter);
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(RaggedTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(RaggedGroup) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(gdone, 0, (char*)st + sizeof(TwoOptState) - (char*)gdone, s);
-  if (er == hipSuccess && method == 1) er = hipMemsetAsync(gmax, 0, lay.total - lay.gmax, s);
-  bool screened = method == 1;
-  if (er == hipSuccess && screened) {                          // M per group decides, once per call, whether the screen has a bound
-    const int mblocks = (2 * lay.nmax + 255) / 256 < 64 ? (2 * lay.nmax + 255) / 256 : 64;
-    hipLaunchKernelGGL(two_opt_maxabs_ragged_kernel, dim3(mblocks, groups), dim3(256), 0, s, points, grp, gmax);
-    std::vector<double> maxabs(groups);
-    er = hipMemcpyAsync(maxabs.data(), gmax, sizeof(double) * groups, hipMemcpyDeviceToHost, s);
-    if (er == hipSuccess) er = hipStreamSynchronize(s);
-    for (int g = 0; er == hipSuccess && g < groups; ++g) {
-      double eps = 0.0;
-      screened = screened && difusco_tsp_two_opt_screen_bound(maxabs[g], &eps) == 1;   // one group without a bound: exact sweep
-    }
-  } else if (er == hipSuccess) {
-    er = hipStreamSynchronize(s);
-  }
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_two_opt_ragged setup: %s", hipGetErrorString(er));
-  TwoOptState host{0, 0, 0};
-  const int poll = 8;
-  const long long loops = max_iterations > 0 ? max_iterations : 1;   // as difusco_tsp_two_opt
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
-  for (long long it = 0; it < loops; ++it) {
-    if (screened) {
-      hipLaunchKernelGGL(two_opt_prep_screen_ragged_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, q, d32, tmin,
-                         tdone);
-      hipLaunchKernelGGL(two_opt_screen_ragged_kernel, dim3(lay.nblk_max, lay.nchunk_max, T), dim3(256), 0, s, q, d32, desc, bmin,
-                         tmin, tdone);
-      hipLaunchKernelGGL(two_opt_screened_best_ragged_kernel, best_grid, dim3(256), 0, s, tp, dlen, q, d32, desc, bmin, tmin,
-                         (const double*)gmax, partial, counter, tdone);
-    } else {
-      hipLaunchKernelGGL(two_opt_prep_ragged_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, tdone);
-      hipLaunchKernelGGL(two_opt_best_ragged_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, partial, tdone);
-    }
-    hipLaunchKernelGGL(two_opt_apply_ragged_kernel, dim3(groups), dim3(256), 0, s, tours, grp, partial,
-                       (long long)max_iterations, st, gdone, tdone, giters, chosen);
-    if ((it + 1) % poll == 0 || it + 1 == loops) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "two_opt state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  unsigned long long pairs = 0;
-  er = hipMemcpyAsync(iterations_out, giters, sizeof(long long) * groups, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess && screened) er = hipMemcpyAsync(&pairs, counter, sizeof(pairs), hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_two_opt_ragged iterations: %s", hipGetErrorString(er));
-  if (!screened)                                               // every pair of every sweep that did work, in float64
-    for (int g = 0; g < groups; ++g)
-      pairs += (unsigned long long)(evaluations(iterations_out[g], max_iterations) * group_tours[g] *
-                                    ((long long)(group_n[g] - 1) * (group_n[g] - 2) / 2));
-  if (exact_pairs_out) *exact_pairs_out = (int64_t)pairs;
-  return DIFUSCO_OK;
+  TwoOptCall c{};
+  c.who = who, c.table = true, c.method = method, c.groups = groups, c.group_n = group_n, c.group_tours = group_tours;
+  c.points = points, c.tours = tours, c.max_iterations = max_iterations, c.workspace = workspace;
+  c.workspace_bytes = workspace_bytes, c.iterations_out = iterations_out, c.exact_pairs_out = exact_pairs_out, c.stream = stream;
+  return two_opt_run(c);
 }
 
 }  // extern "C"

@@ -1,10 +1,15 @@
 // What the 2-opt entries (two_opt.hip) and the local search (or_opt.hip) share: the float64 distance, the (min, first flat
-// index) reductions, the prep entry, one block of the exact 2-opt sweep and the segment reversal.  Every function is
+// index) reductions, the prep entry, one block of the exact 2-opt sweep and the segment reversal; and the check of the group
+// arrays that every _ragged tour entry starts with.  Every function is
 // per translation unit (anonymous namespace): the kernels that use them are compiled where they are launched.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
+
+#include "../../include/difusco_hip.h"
+#include "kernels.h"
 
 namespace difusco {
 namespace {
@@ -118,6 +123,26 @@ __device__ __forceinline__ void apply_move(int* __restrict__ tour, long long idx
 }
 
 size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+constexpr int kMaxTours = 65535;                   // a grid dimension
+constexpr int kMaxNodes = 65535 * TI;              // and as many row tiles
+
+// the group arrays of a _ragged entry (`who` for the message): DIFUSCO_OK and the tours of the call, or the refusal
+int check_groups(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, int* tours) {
+  if (groups < 1) return set_error(DIFUSCO_EINVAL, "%s: groups = %d, needs at least 1", who, groups);
+  if (!group_n || !group_tours) return set_error(DIFUSCO_EINVAL, "%s: group_n / group_tours is null", who);
+  long long T = 0;
+  for (int g = 0; g < groups; ++g) {
+    if (group_n[g] < 4) return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, needs n >= 4", who, g, group_n[g]);
+    if (group_n[g] > kMaxNodes)
+      return set_error(DIFUSCO_EINVAL, "%s: group %d has n = %d, at most %d nodes", who, g, group_n[g], kMaxNodes);
+    if (group_tours[g] < 1) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d tours, needs at least 1", who, g, group_tours[g]);
+    T += group_tours[g];
+    if (T > kMaxTours) return set_error(DIFUSCO_EINVAL, "%s: more than %d tours in one call", who, kMaxTours);
+  }
+  *tours = (int)T;
+  return DIFUSCO_OK;
+}
 
 }  // namespace
 }  // namespace difusco

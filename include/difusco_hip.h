@@ -542,7 +542,8 @@ int difusco_tsp_merge_batch(int graphs, const int32_t* graph_n, const int64_t* g
  * finds, per tour, the move (i,j), j >= i+2, that minimises d(t_i,t_j) + d(t_i+1,t_j+1) - d(t_i,t_i+1) - d(t_j,t_j+1)
  * (float64, the reference's operation order, first flat index on ties) and reverses tour[i+1..j]; it stops when the
  * best change over the whole batch is >= -1e-6 or after max_iterations applied moves.  *iterations_out (HOST) =
- * the reference's `iterator`.  Blocks until done. */
+ * the reference's `iterator`.  Blocks until done.  The call is one group of `batch` tours of the grouped entry below and
+ * reserves what difusco_tsp_two_opt_grouped_workspace_bytes(n_nodes, 1, batch) does. */
 int difusco_tsp_two_opt_workspace_bytes(int n_nodes, int batch, size_t* bytes);
 int difusco_tsp_two_opt(int n_nodes, int batch, const double* points, int32_t* tours, int64_t max_iterations,
                         void* workspace, size_t workspace_bytes, int64_t* iterations_out, void* stream);

@@ -1,0 +1,69 @@
+#!/usr/bin/env python
+"""Records tests/golden/two_opt_entries.json: what the six single-move 2-opt entries reserve, refuse and compute on a few tiny
+calls (the cases: tests/two_opt_entries_cases.py), as exact values, from the library that is built in the tree.
+tests/test_gpu_two_opt_entries.py compares a later library with them, so record only from a commit whose behaviour is the intended
+one, and name it:
+
+    python scripts/record_two_opt_entries.py --commit $(git rev-parse HEAD)
+
+The inputs of the runs are written into the fixture (points as integers on a 2^-16 grid: short and exact in JSON); a fixture that
+exists keeps its inputs unless ``--new_inputs`` is given.  ``--host_only`` records the sizes and refusals alone (no GPU) and keeps
+the runs of the fixture that exists."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch      # before the library: both then share one HIP runtime
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import two_opt_entries_cases as C  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--commit", required=True, help="the commit the library was built from")
+ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "two_opt_entries.json"))
+ap.add_argument("--new_inputs", action="store_true")
+ap.add_argument("--host_only", action="store_true")
+opts = ap.parse_args()
+
+
+def make_inputs():
+    rng = np.random.default_rng(20261020)
+    groups = {}
+    for n in C.SIZES:
+        groups[str(n)] = []
+        for g in range(C.GROUPS):
+            if g == 1:      # a convex polygon visited in order: no 2-opt move shortens it
+                ang = np.arange(n) * (2 * np.pi / n)
+                q = np.round((0.5 + 0.45 * np.stack([np.cos(ang), np.sin(ang)], 1)) * 65536).astype(np.int64)
+                tours = np.tile(np.concatenate([np.arange(n), [0]]), (C.PER_GROUP, 1))
+            else:
+                q = rng.choice(65536, (n, 2), replace=False)
+                q[0, 0] = 65536                                  # the largest |coordinate| is exactly 1
+                tours = np.stack([np.concatenate([[0], rng.permutation(n - 1) + 1, [0]]) for _ in range(C.PER_GROUP)])
+            groups[str(n)].append({"points_q16": q.tolist(), "tours": tours.tolist()})
+    return {"groups": groups}
+
+
+old = None
+if os.path.exists(opts.out):
+    with open(opts.out) as f:
+        old = json.load(f)
+from difusco_amd import _lib  # noqa: E402
+
+L = _lib.lib()
+doc = {"commit": opts.commit, "inputs": make_inputs() if old is None or opts.new_inputs else old["inputs"],
+       "workspace_bytes": C.workspace_sizes(L), "workspace_bytes_refusals": C.size_refusals(L), "refusals": C.refusals(L)}
+if opts.host_only:
+    doc["runs"] = old["runs"] if old else {}
+else:
+    dev = torch.device("cuda:0")
+    doc["runs"] = {C.run_name(*r): C.short_run(dev, doc["inputs"], *r) for r in C.RUNS}
+os.makedirs(os.path.dirname(opts.out), exist_ok=True)
+with open(opts.out, "w") as f:
+    f.write(json.dumps(doc, separators=(",", ":")) + "\n")
+print(f"{opts.out}: {os.path.getsize(opts.out)} bytes, {len(doc['runs'])} runs")
