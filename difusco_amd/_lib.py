@@ -165,6 +165,11 @@ def lib():
     L.difusco_mis_iterated_search.argtypes = [i32, vp, vp, f32p, vp, i32, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                               vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), vp]
     L.difusco_mis_search_host_syncs.argtypes = []
+    L.difusco_mis_resident_max_nodes.argtypes = []
+    L.difusco_mis_resident_search_workspace_bytes.argtypes = [i32, i64, i32, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_mis_resident_search.argtypes = [i32, vp, vp, f32p, vp, i32, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32),
+                                              ctypes.POINTER(ctypes.c_int32), vp]
     L.difusco_host_rowsum_f32.argtypes = [f32p, i32, ctypes.POINTER(ctypes.c_float)]
     L.difusco_mcts_heatmap_workspace_bytes.argtypes = [i32, i64, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_mcts_heatmap_prepare.argtypes = [i32, i64, vp, vp, f32p, f32p, ctypes.c_double, vp, ctypes.c_size_t,

@@ -44,6 +44,21 @@ __host__ __device__ inline unsigned mis_sort_key(unsigned bits) {
   return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
 }
 
+// What difusco_mis_iterated_search does before its first round, for the resident search (mis_resident_search.hip) to share
+// (mis_local_search.hip): the rocPRIM sort of the keys and the rank scatter, the working copy of the set, the independence check
+// and the table check, enqueued on `stream` into the first `bytes` bytes of `workspace` (the launched search's own carve, so
+// `bytes` is difusco_mis_iterated_search_workspace_bytes).  workspace == nullptr: only `bytes` is filled.  Device pointers into
+// the workspace: rank [n], sol [n] (0/1), inc [n] and per [4 * nb] (zeroed); bad / bad_table: the words the two checks set
+// (bad is set by either).
+struct MisSearchPrelude {
+  int *rank, *sol, *inc, *per, *bad, *bad_table;
+  size_t bytes;
+};
+hipError_t mis_search_prelude(void* workspace, int n, int nb, const int32_t* rowptr, const int32_t* col, const float* scores,
+                              const int32_t* solution, const int64_t* rows, hipStream_t stream, MisSearchPrelude* out);
+// difusco_mis_search_host_syncs reports `count` on this thread until the next search call
+void mis_search_set_host_syncs(int count);
+
 // the descent of difusco_tsp_multi_local_search_ragged with messages that name `who` and, optionally, the sweeps in which every
 // tour moved (HOST int64 [tours]); or_opt_multi.hip, used by the window search of tsp_window_search.hip
 int mls_descent_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);

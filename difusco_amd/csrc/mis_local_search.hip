@@ -567,6 +567,39 @@ hipError_t it_carve(void* base, int n, int nb, ItCarve* c) {
 }
 
 }  // namespace
+
+// The start of difusco_mis_iterated_search up to its first round, for mis_resident_search.hip (declared in kernels.h): the
+// same carve and the same launches, so both searches rank, copy and check alike.
+hipError_t mis_search_prelude(void* workspace, int n, int nb, const int32_t* rowptr, const int32_t* col, const float* scores,
+                              const int32_t* solution, const int64_t* rows, hipStream_t st, MisSearchPrelude* out) {
+  ItCarve w;
+  hipError_t er = it_carve(workspace, n, nb, &w);
+  if (er != hipSuccess) return er;
+  out->bytes = w.total;
+  if (!workspace) return hipSuccess;
+  // static: the asynchronous copy may read it after this function has returned.  DONE: no kernel of the launched search runs
+  static const LsCtrl h = [] {
+    LsCtrl c;
+    std::memset(&c, 0, sizeof(c));
+    c.phase = LS_DONE;
+    return c;
+  }();
+  er = ls_enqueue_begin(w.ls, n, rowptr, col, scores, solution, h, st);
+  if (er != hipSuccess) return er;
+  hipLaunchKernelGGL(mis_it_table_kernel, dim3((unsigned)(nb / 256 + 1)), dim3(256), 0, st, n, nb, rows, w.ls.ctrl);
+  hipLaunchKernelGGL(mis_it_setup_kernel, dim3((unsigned)(((n > nb ? n : nb) + 255) / 256)), dim3(256), 0, st, n, nb, rows, w.inst,
+                     w.entered_flag, w.per);
+  out->rank = w.ls.rank;
+  out->sol = w.ls.sol;
+  out->inc = w.inc;
+  out->per = w.per;
+  out->bad = &w.ls.ctrl->bad;
+  out->bad_table = &w.ls.ctrl->bad_table;
+  return hipSuccess;
+}
+
+void mis_search_set_host_syncs(int count) { g_host_syncs = count; }
+
 }  // namespace difusco
 
 extern "C" {

@@ -925,8 +925,22 @@ def check_mis_kicks(local_search, kicks, kick_size):
     return int(kicks), int(kick_size)
 
 
+MIS_SEARCH_MODES = ("launches", "resident")
+
+
+def check_mis_search_mode(local_search, mode):
+    """``local_search_mode`` of ``solve_mis`` and the runner: ``"resident"`` runs the swap search, with any ``kicks >= 0``, one GPU
+    block per instance, so it needs that search."""
+    if mode not in MIS_SEARCH_MODES:
+        raise ValueError(f"MIS local search mode {mode!r}: one of {MIS_SEARCH_MODES}")
+    if mode == "resident" and local_search != "swap":
+        raise ValueError(f"local_search_mode='resident' runs the swap search: it needs local_search='swap', not {local_search!r}")
+    return mode
+
+
 def mis_iterated_search_np(predictions, solution, adj_matrix=None, *, graph=None, edge_index=None, instance_rows=None, seeds=None,
-                           offsets=None, kicks, kick_size=4, max_rounds=1000, device="cuda:0", graph_build="host", stats=None):
+                           offsets=None, kicks, kick_size=4, max_rounds=1000, device="cuda:0", graph_build="host", stats=None,
+                           mode="launches", kicks_per_launch=0):
     """The swap search of ``mis_local_search_np`` iterated with seeded random kicks (``difusco_mis_iterated_search``,
     include/difusco_hip.h; not in the reference): after the descent, ``kicks`` times: about ``kick_size`` random nodes of every
     instance are forced in, their neighbours leave, the descent runs again and every instance keeps the result unless it is
@@ -935,11 +949,18 @@ def mis_iterated_search_np(predictions, solution, adj_matrix=None, *, graph=None
     draws at ``offsets[b] + t``); an instance gets the same answer alone or in any union.  ``kicks=0`` is
     ``mis_local_search_np``.  Returns the 0/1 int numpy array; ``stats`` (a dict) receives ``rounds``, ``swaps``, ``inserts``
     (all descents), ``host_syncs`` and the per-instance lists ``entered``, ``accepted``, ``size_before``, ``size_after``.
-    A set that is not independent or a malformed table raises ``DifuscoHipError``.  GPU only."""
+    A set that is not independent or a malformed table raises ``DifuscoHipError``.  ``mode``: ``"launches"`` (the default) runs
+    every kick as a sequence of launches over the whole call; ``"resident"`` (``difusco_mis_resident_search``) runs one GPU block
+    per instance with its state in LDS and synchronises with the host once per call: the same set, counters and ``stats`` keys
+    bit for bit, for instances of at most ``difusco_mis_resident_max_nodes()`` nodes (a larger one raises ``DifuscoHipError``);
+    ``kicks_per_launch`` bounds the kicks of one of its launches (0: the library's default).  GPU only."""
     device = _gpu_only("mis_iterated_search_np", device)
     if int(max_rounds) != max_rounds or max_rounds < 0:
         raise ValueError(f"max_rounds = {max_rounds!r}: an integer >= 0")
     kicks, kick_size = check_mis_kicks("swap", kicks, kick_size)
+    check_mis_search_mode("swap", mode)
+    if int(kicks_per_launch) != kicks_per_launch or kicks_per_launch < 0:
+        raise ValueError(f"kicks_per_launch = {kicks_per_launch!r}: an integer >= 0")
     n = _numel(predictions)
     solution = _mis_solution(solution, n)
     rows = np.array([0, n], dtype=np.int64) if instance_rows is None else np.asarray(instance_rows, dtype=np.int64).reshape(-1)
@@ -951,12 +972,18 @@ def mis_iterated_search_np(predictions, solution, adj_matrix=None, *, graph=None
     scores, graph, col = _mis_graph(predictions, adj_matrix, graph, edge_index, graph_build, device)
     sol = _mis_solution_on_device(solution, device)
     d_rows = torch.from_numpy(rows).to(device)
-    ws, nbytes = _workspace(L.difusco_mis_iterated_search_workspace_bytes, n, int(graph.col.shape[0]), B, device=device)
     counters = (ctypes.c_int32 * 3)()
     per = (ctypes.c_int32 * (4 * B))()
-    _lib.check(L.difusco_mis_iterated_search(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), B, _ptr(d_rows), _ptr(table[0]),
-                                             _ptr(table[1]), kicks, kick_size, int(max_rounds), _ptr(ws), nbytes, counters, per,
-                                             _stream(device)))
+    if mode == "resident":
+        ws, nbytes = _workspace(L.difusco_mis_resident_search_workspace_bytes, n, int(graph.col.shape[0]), B, kicks, device=device)
+        _lib.check(L.difusco_mis_resident_search(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), B, _ptr(d_rows),
+                                                 _ptr(table[0]), _ptr(table[1]), kicks, kick_size, int(max_rounds),
+                                                 int(kicks_per_launch), _ptr(ws), nbytes, counters, per, _stream(device)))
+    else:
+        ws, nbytes = _workspace(L.difusco_mis_iterated_search_workspace_bytes, n, int(graph.col.shape[0]), B, device=device)
+        _lib.check(L.difusco_mis_iterated_search(n, _ptr(graph.rowptr), _ptr(col), _ptr(scores), _ptr(sol), B, _ptr(d_rows),
+                                                 _ptr(table[0]), _ptr(table[1]), kicks, kick_size, int(max_rounds), _ptr(ws), nbytes,
+                                                 counters, per, _stream(device)))
     if stats is not None:
         _mis_counters(stats, counters)
         stats["host_syncs"] = int(L.difusco_mis_search_host_syncs())

@@ -32,7 +32,10 @@ of multi-move 2-opt and multi-move Or-opt sweeps, ``2opt_iterations`` and ``or_o
 the order of ``all_costs``, the header ``mis_local_search``; refused with ``--task tsp``), ``--mis_local_search_kicks N`` /
 ``--mis_local_search_kick_size K`` (N > 0 only with ``--mis_local_search swap``: the search iterated with N seeded kicks,
 ``decode.mis_iterated_search_np``, keyed by the instance seed; the records gain ``swap_costs``, ``kicks_entered``,
-``kicks_accepted`` and the two settings, the header the two settings), ``--tsp_local_search_kicks N`` /
+``kicks_accepted`` and the two settings, the header the two settings), ``--mis_local_search_mode {launches,resident}``
+(resident only with ``--task mis --mis_local_search swap``, any N >= 0: the search runs one GPU block per instance,
+``decode.mis_iterated_search_np(mode="resident")``; the records and the header gain ``mis_local_search_mode`` and are otherwise
+those of ``launches``), ``--tsp_local_search_kicks N`` /
 ``--tsp_local_search_kick_size K`` / ``--tsp_local_search_kick_span S`` (N > 0 only with ``--local_search multi2opt+oropt``: that
 search iterated with N seeded segment kicks, ``decode.batched_iterated_search_grouped``, every tour keyed by its instance seed;
 the records gain ``kicks_improved``, one count per copy in the order of the last round, and the three settings, the header
@@ -155,6 +158,10 @@ EXTENSION_ARGS = [
                                        help="MIS: iterate the swap search with this many seeded random kicks (needs "
                                             "--mis_local_search swap; 0: one descent)")),
     ("--mis_local_search_kick_size", dict(type=int, default=4, help="MIS: nodes forced in per kick and instance, on average")),
+    ("--mis_local_search_mode", dict(type=str, default="launches", choices=("launches", "resident"),
+                                      help="MIS: how the swap search runs: launches (a launch sequence per round and kick) or "
+                                           "resident (one GPU block per instance, one host synchronisation per call; same "
+                                           "records; needs --mis_local_search swap)")),
     ("--merge_method", dict(type=str, default="loop", choices=("loop", "batched"),
                             help="heatmap -> tour merge: loop (one library call per instance) or batched (one per chunk, same tours)")),
     ("--graph_build", dict(type=str, default="host", choices=("host", "device"),
@@ -237,6 +244,9 @@ def parse_args(argv=None):
         parser.error("--mis_local_search_kicks must be >= 0 and --mis_local_search_kick_size >= 1")
     if args.mis_local_search_kicks > 0 and args.mis_local_search != "swap":
         parser.error(f"--mis_local_search_kicks {args.mis_local_search_kicks} iterates the swap search: pass --mis_local_search swap")
+    if args.mis_local_search_mode != "launches" and (args.task != "mis" or args.mis_local_search != "swap"):
+        parser.error(f"--mis_local_search_mode {args.mis_local_search_mode} runs the MIS swap search: pass --task mis "
+                     "--mis_local_search swap")
     ignored = sorted(k for k in given if k in TRAINING_ONLY or (k == "save_numpy_heatmap" and args.task == "mis"))
     return args, ignored
 
@@ -393,7 +403,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 timings: Optional[Dict[str, float]] = None, heatmap_dir: Optional[str] = None,
                 two_opt_method: str = "exact", merge_method: str = "loop", local_search: str = "2opt",
                 mis_local_search: str = "none", mis_local_search_kicks: int = 0,
-                mis_local_search_kick_size: int = 4, tsp_local_search_kicks: int = 0,
+                mis_local_search_kick_size: int = 4, mis_local_search_mode: str = "launches", tsp_local_search_kicks: int = 0,
                 tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
                 tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
                 tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1) -> List[dict]:
@@ -448,11 +458,14 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   generators=gens, timings=timings, step_offset=0,
                                   **(dict(local_search=mis_local_search, stats=ls_stats) if swap else {}),
                                   **(dict(local_search_kicks=mis_local_search_kicks,
-                                          local_search_kick_size=mis_local_search_kick_size) if mis_local_search_kicks > 0 else {}))
+                                          local_search_kick_size=mis_local_search_kick_size) if mis_local_search_kicks > 0 else {}),
+                                  **(dict(local_search_mode="resident") if mis_local_search_mode == "resident" else {}))
             for k, i in enumerate(idx):
                 rec = mis_record(split, i, examples[i], seeds[k], res[k], ls_stats[k] if swap else None)
                 if mis_local_search_kicks > 0:
                     rec.update(mis_local_search_kicks=mis_local_search_kicks, mis_local_search_kick_size=mis_local_search_kick_size)
+                if mis_local_search_mode == "resident":
+                    rec.update(mis_local_search_mode="resident")
                 records.append(rec)
     return records
 
@@ -514,6 +527,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                local_search=args.local_search, mis_local_search=args.mis_local_search,
                                mis_local_search_kicks=args.mis_local_search_kicks,
                                mis_local_search_kick_size=args.mis_local_search_kick_size,
+                               mis_local_search_mode=args.mis_local_search_mode,
                                tsp_local_search_kicks=args.tsp_local_search_kicks,
                                tsp_local_search_kick_size=args.tsp_local_search_kick_size,
                                tsp_local_search_kick_span=args.tsp_local_search_kick_span,
@@ -561,6 +575,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             if args.mis_local_search_kicks > 0:
                 line["mis_local_search_kicks"] = args.mis_local_search_kicks
                 line["mis_local_search_kick_size"] = args.mis_local_search_kick_size
+            if args.mis_local_search_mode == "resident":
+                line["mis_local_search_mode"] = "resident"
             print(json.dumps(line), flush=True)
             lines.append(line)
             all_records += recs

@@ -130,7 +130,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, generator: Optional[torch.Generator] = None,
               timings: Optional[Dict[str, float]] = None, sequential_sampling: int = 1, *, graphed: bool = False,
               local_search: str = "none", local_search_rounds: int = 1000, stats: Optional[dict] = None,
-              local_search_kicks: int = 0, local_search_kick_size: int = 4):
+              local_search_kicks: int = 0, local_search_kick_size: int = 4, local_search_mode: str = "launches"):
     """``MISModel.test_step`` (``difusco/pl_mis_model.py:142-206``): ``sequential_sampling`` rounds of
     ``parallel_sampling`` noise samples of ONE graph through the denoising loop (disjoint union), greedy decode of every
     sample, best = largest set.  ``edge_index``: int64 [2,E] in the dataset's layout (both directions + self loops).
@@ -144,10 +144,15 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
     "swap", else ``ValueError``): the search is iterated with that many seeded kicks of about ``local_search_kick_size`` nodes
     (``decode.mis_iterated_search_np``); copy p of sequential round r is its own instance of the call, keyed by the model's
     seed at Philox offset ``2^62 + (r P + p) 2^32``.  ``stats`` then also receives ``swap_sizes`` (the sizes after
-    the first descent), ``kicks_entered`` and ``kicks_accepted``, in the order of ``sizes``.  0 is the plain swap search."""
-    from .decode import check_mis_kicks, check_mis_local_search, mis_decode_np, mis_iterated_search_np, mis_local_search_np
+    the first descent), ``kicks_entered`` and ``kicks_accepted``, in the order of ``sizes``.  0 is the plain swap search.
+    ``local_search_mode``: "launches" (default) or "resident" (only with "swap", else ``ValueError``): the search, with any
+    number of kicks >= 0, runs as ``decode.mis_iterated_search_np(mode="resident")``, one GPU block per copy, on the same
+    instance rows, seeds and offsets; results and ``stats`` are those of "launches"."""
+    from .decode import (check_mis_kicks, check_mis_local_search, check_mis_search_mode, mis_decode_np, mis_iterated_search_np,
+                         mis_local_search_np)
     check_mis_local_search(local_search)
     kicks, kick_size = check_mis_kicks(local_search, local_search_kicks, local_search_kick_size)
+    mode = check_mis_search_mode(local_search, local_search_mode)
     kick_stats = {"swap_sizes": [], "kicks_entered": [], "kicks_accepted": []}
     dev = model.device
     ei = edge_index if isinstance(edge_index, torch.Tensor) else torch.from_numpy(np.asarray(edge_index))
@@ -167,11 +172,11 @@ def solve_mis(model, n_nodes: int, edge_index, parallel_sampling: int = 1, gener
             t0 = time.perf_counter()
             decoded += sol.reshape(parallel_sampling, n_nodes).sum(axis=1).tolist()
             call = {}
-            if kicks > 0:
+            if kicks > 0 or mode == "resident":
                 P = parallel_sampling
                 sol = mis_iterated_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call,
                                              kicks=kicks, kick_size=kick_size, instance_rows=[n_nodes * p for p in range(P + 1)],
-                                             seeds=[model.seed] * P, offsets=_kick_offsets(r, P))
+                                             seeds=[model.seed] * P, offsets=_kick_offsets(r, P), mode=mode)
                 _kick_stats(kick_stats, call, 0, P)
             else:
                 sol = mis_local_search_np(scores, sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call)
@@ -486,7 +491,8 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
                     seeds: Optional[Sequence[int]] = None, generators: Optional[Sequence[torch.Generator]] = None,
                     timings: Optional[Dict[str, float]] = None, instances_per_call: Optional[int] = None,
                     step_offset: Optional[int] = None, *, local_search: str = "none", local_search_rounds: int = 1000,
-                    stats: Optional[list] = None, local_search_kicks: int = 0, local_search_kick_size: int = 4) -> List[tuple]:
+                    stats: Optional[list] = None, local_search_kicks: int = 0, local_search_kick_size: int = 4,
+                    local_search_mode: str = "launches") -> List[tuple]:
     """``solve_mis`` of B graphs: ``instances`` = [(n_nodes, edge_index), ...].  Returns the list of what ``solve_mis`` returns
     for every graph (run with ``seed = seeds[b]``, ``generator = generators[b]``).  Up to ``instances_per_call`` graphs share
     one sampling loop over their union (``MISModel.sample_batch``) and one greedy decode of the union (``mis_decode_np``: the
@@ -498,11 +504,13 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
     ``local_search_kicks``, ``local_search_kick_size``: as ``solve_mis``; every one of the P copies of an instance is its own
     row of the call's instance table, keyed by the instance's sampling seed (``seeds[b]`` as ``sample_batch`` resolves it) at
     offset ``2^62 + (r P + p) 2^32``, so the records do not depend on the chunking; the per-instance dicts then also hold
-    ``swap_sizes``, ``kicks_entered`` and ``kicks_accepted``."""
-    from .decode import check_mis_kicks, check_mis_local_search, mis_decode_np, mis_iterated_search_np, mis_local_search_np
+    ``swap_sizes``, ``kicks_entered`` and ``kicks_accepted``.  ``local_search_mode``: as ``solve_mis``."""
+    from .decode import (check_mis_kicks, check_mis_local_search, check_mis_search_mode, mis_decode_np, mis_iterated_search_np,
+                         mis_local_search_np)
     from .graph import build_csr
     check_mis_local_search(local_search)
     kicks, kick_size = check_mis_kicks(local_search, local_search_kicks, local_search_kick_size)
+    mode = check_mis_search_mode(local_search, local_search_mode)
     instances = list(instances)
     B = len(instances)
     if B < 1:
@@ -542,11 +550,11 @@ def solve_mis_batch(model, instances, parallel_sampling: int = 1, sequential_sam
                 for g, n in enumerate(ns):
                     decoded[g] += sol[off[g]:off[g + 1]].reshape(P, n).sum(axis=1).tolist()
                 call = {}
-                if kicks > 0:
+                if kicks > 0 or mode == "resident":
                     sol = mis_iterated_search_np(
                         torch.cat(scores), sol, graph=graph, device=dev, max_rounds=local_search_rounds, stats=call, kicks=kicks,
                         kick_size=kick_size, instance_rows=[int(off[g]) + n * p for g, n in enumerate(ns) for p in range(P)] + [int(off[-1])],
-                        seeds=[k for k in keys for _ in range(P)], offsets=_kick_offsets(r, P) * len(ns))
+                        seeds=[k for k in keys for _ in range(P)], offsets=_kick_offsets(r, P) * len(ns), mode=mode)
                     for g in range(len(ns)):
                         _kick_stats(kick_stats[g], call, g * P, P)
                 else:

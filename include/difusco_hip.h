@@ -493,6 +493,30 @@ int difusco_mis_iterated_search(int n_nodes, const int32_t* rowptr, const int32_
                                 int32_t counters[3] /* host */, int32_t* per_instance /* host, optional */, void* stream);
 int difusco_mis_search_host_syncs(void);
 
+/* ---- the iterated search above with one resident GPU block per instance (additive to ABI 13).  The arguments of
+ * difusco_mis_iterated_search up to max_rounds, and THE SAME RULE: for every input that entry accepts and whose instances all
+ * have at most difusco_mis_resident_max_nodes() nodes (a constant of the build, >= 2048), solution, counters and per_instance
+ * come back exactly as that entry returns them; kicks = 0 is difusco_mis_local_search.  What differs is the execution: after
+ * the launched search's own start (sort, ranks, working copy, the independence and table checks) one block per table row runs
+ * its instance from the first descent to the last keep with the per-node state in LDS, and the host enqueues
+ * ceil(kicks / kicks_per_launch) launches (at least one) back to back without reading anything in between; the incumbent and
+ * the counters stay in the workspace between launches.  kicks_per_launch bounds the run time of one launch; 0 = the library's
+ * default (256).  One copy-out and ONE host synchronisation per call, whatever kicks is: difusco_mis_search_host_syncs reports
+ * this entry too.  counters[0], the rounds of the call, is the sum over the kicks + 1 descents of the rounds of the instance
+ * that descended longest, which is what a union's descent counts; that array is why _workspace_bytes takes kicks.  The
+ * workspace is never smaller than difusco_mis_iterated_search_workspace_bytes for the same call.
+ * DIFUSCO_EINVAL as difusco_mis_iterated_search and on kicks_per_launch < 0; DIFUSCO_EUNSUPPORTED when an instance has more
+ * nodes than the limit (checked on the device before anything is written; the message names the instance and the limit).
+ * solution is left unchanged by every refusal.  Blocks. */
+int difusco_mis_resident_max_nodes(void);
+int difusco_mis_resident_search_workspace_bytes(int n_nodes, int64_t n_edges, int n_instances, int32_t kicks, size_t* bytes);
+int difusco_mis_resident_search(int n_nodes, const int32_t* rowptr, const int32_t* col, const float* scores,
+                                int32_t* solution /* in/out, device */, int n_instances, const int64_t* instance_rows,
+                                const uint64_t* instance_seeds, const uint64_t* instance_offsets, int32_t kicks,
+                                int32_t kick_size, int32_t max_rounds, int32_t kicks_per_launch /* 0 = default */,
+                                void* workspace, size_t workspace_bytes, int32_t counters[3] /* host */,
+                                int32_t* per_instance /* host, optional */, void* stream);
+
 /* ---- heatmap -> tour: the greedy edge insertion the reference runs on the host right after the
  * sampling loop, difusco/utils/tsp_utils.py:89-145 (merge_tours) + utils/cython_merge/cython_merge.pyx:19-104
  * (merge_cython), restricted to the E entries of the sparse heatmap instead of the N x N densification.
