@@ -22,6 +22,20 @@
 // order (a stable sort's order, as the CPU oracle does) and then the negative-score candidates, and reports
 // completed = 0 so that callers (and tests) know the tour is outside the regime pinned to the reference.  In that
 // regime merge_iterations counts the entries this implementation looked at, not the reference's.
+//
+// Non-finite scores rank as a stable ascending sort of -(A + A^T) / dist ranks them (numpy puts NaN last):
+//   1. scores > 0 by decreasing score, +inf first (positive heat at distance 0, +inf heat);
+//   2. the zero block: S == +-0 and every pair that is no edge, in flat-index order;
+//   3. scores < 0 by decreasing score;
+//   4. score -inf (negative heat at distance 0, -inf heat);
+//   5. NaN of either sign (0/0, NaN heat, inf + -inf);
+// equal scores, and the NaNs among themselves, in flat-index order.  pair_score_at states this once for every entry:
+// it rewrites a candidate's NaN score to ONE sign-bit NaN pattern and marks the list positions that hold no candidate
+// (non-heads of a run, self loops) with a second sign-bit NaN pattern and a `pair` value that is no pair.  Under
+// rocPRIM's descending float order (sign-bit patterns are compared bit-inverted: -inf, then the sign-bit NaNs by
+// increasing mantissa) the sorted list is blocks 1, 2 (its listed part), 3, 4, 5 and then, strictly after every
+// candidate, the positions that are none.  completed = 1 exactly when all N-1 insertions came from block 1, and an
+// entry of block 5 is never counted before a terminating entry of block 1.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,11 +63,36 @@ __global__ void pair_key_kernel(const int* __restrict__ row, const int* __restri
   val[e] = (unsigned)e;
 }
 
+// How scores rank (header comment), stated once for the device kernels and the host walks.  A candidate's NaN score is
+// stored as kScoreNaN; a list position that holds no candidate as kScoreNoPair with pair = kNoPair.  Both are sign-bit NaNs:
+// radix_sort_pairs_desc puts them after -inf, and kScoreNaN (the smaller mantissa) strictly before kScoreNoPair.
+constexpr unsigned long long kScoreNaN = 0xfff8000000000000ULL;
+constexpr unsigned long long kScoreNoPair = 0xffffffffffffffffULL;
+constexpr unsigned long long kNoPair = 0xffffffffffffffffULL;      // decodes to ids >= any n: refused by pair_nodes
+
+__host__ __device__ __forceinline__ double score_from_bits(unsigned long long bits) {
+  double v;
+  memcpy(&v, &bits, sizeof(v));
+  return v;
+}
+// block 1: the only entries the pinned walk (host loop and wave) inserts; false for NaN
+__host__ __device__ __forceinline__ bool score_in_pinned_regime(double score) { return score > 0.0; }
+// blocks 3-5: visited after the zero block, in list order (a listed entry of block 2 is found by the zero-block scan)
+__host__ __device__ __forceinline__ bool score_after_zero_block(double score) { return score < 0.0 || score != score; }
+// the node ids of a sorted-list entry; false for anything that is not a candidate pair of an n-node graph
+__host__ __device__ __forceinline__ bool pair_nodes(unsigned long long pair, int n, int* i, int* j) {
+  const unsigned long long a = pair >> 32, b = pair & 0xffffffffULL;
+  *i = (int)a;
+  *j = (int)b;
+  return a < b && b < (unsigned long long)n;
+}
+
 // The score of position p of a pair-sorted edge list (one graph's, `n_edges` long).  The first position of a run of equal
 // keys owns the pair: it sums the run's heat in float32 (a_ij first when both directions exist, like A + A^T evaluated at
 // (i,j), i < j; float addition commutes, so (j,i) gets the same value) and emits score + packed (i,j).
-// Everything else (non-heads, self loops) gets score = -inf and sorts to the end.  `key_mask` strips the graph index that the
-// batched entry keeps above lo * n + hi (all ones for the single-graph entries).  Shared by pair_score_kernel and
+// Everything else (non-heads, self loops) is no candidate: kScoreNoPair / kNoPair, strictly after every candidate in the
+// sorted list, so that the first counters[0] sorted entries are exactly the candidates.  `key_mask` strips the graph index
+// that the batched entry keeps above lo * n + hi (all ones for the single-graph entries).  Shared by pair_score_kernel and
 // pair_score_batch_kernel: one statement of the arithmetic.
 __device__ __forceinline__ void pair_score_at(const unsigned long long* __restrict__ key, const unsigned* __restrict__ val,
                                               const float* __restrict__ heat, const float* __restrict__ points, long long p,
@@ -62,9 +101,8 @@ __device__ __forceinline__ void pair_score_at(const unsigned long long* __restri
                                               unsigned* __restrict__ counters) {   // [0] pairs, [1] self loops with S > 0
   const unsigned long long raw = key[p];
   const unsigned long long k = raw & key_mask;
-  const double ninf = -std::numeric_limits<double>::infinity();
-  score[p] = ninf;
-  pair[p] = k;
+  score[p] = score_from_bits(kScoreNoPair);
+  pair[p] = kNoPair;
   if (p > 0 && key[p - 1] == raw) return;
   float s = heat[val[p]];
   long long q = p + 1;
@@ -82,7 +120,8 @@ __device__ __forceinline__ void pair_score_at(const unsigned long long* __restri
   const double dx = (double)points[2 * lo] - (double)points[2 * hi];
   const double dy = (double)points[2 * lo + 1] - (double)points[2 * hi + 1];
   const double dist = sqrt(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));   // np.linalg.norm: no fused multiply-add
-  score[p] = (double)s / dist;
+  const double sc = (double)s / dist;
+  score[p] = sc != sc ? score_from_bits(kScoreNaN) : sc;
   pair[p] = ((unsigned long long)lo << 32) | (unsigned long long)hi;
   atomicAdd(&counters[0], 1u);
 }
@@ -238,23 +277,33 @@ struct HostPaths {
 // accident of numpy's unstable argsort; here it is flat-index order (what a stable sort gives, and what
 // oracle/tsp_decode_oracle.py does): pairs (a, b), a < b, lexicographic.  Only path end points can be joined, so
 // the scan walks end points instead of all N^2 / 2 pairs.  Called by the per-sample host walk and by the batched entry.
-void finish_outside_regime(HostPaths& s, int n_nodes, const unsigned long long* pairs, const double* scores, size_t count) {
+// After the zero block come the listed entries that score_after_zero_block names, in list order: negative scores by
+// decreasing score, -inf, NaN last.  Every entry is a candidate pair by construction (the callers pass at most the
+// counters[0] candidates, which sort before every other position); one that does not decode to two nodes of the graph
+// is refused, never used as an index.
+int finish_outside_regime(HostPaths& s, int n_nodes, const unsigned long long* pairs, const double* scores, size_t count) {
   const long long N = n_nodes;
-  std::unordered_set<unsigned long long> negative;
-  for (size_t q = 0; q < count; ++q)
-    if (scores[q] < 0.0) negative.insert(pairs[q]);
+  int i, j;
+  std::unordered_set<unsigned long long> later;
+  for (size_t q = 0; q < count; ++q) {
+    if (!pair_nodes(pairs[q], n_nodes, &i, &j))
+      return set_error(DIFUSCO_EINVAL, "tsp_merge_tour: sorted entry %zu of the tail is no pair of a %d-node graph", q, n_nodes);
+    if (score_after_zero_block(scores[q])) later.insert(pairs[q]);
+  }
   for (int a = 0; a < n_nodes && s.merge_count < N - 1; ++a) {
     if (s.nb1[a] >= 0) continue;
     for (int b = a + 1; b < n_nodes && s.merge_count < N - 1; ++b) {
       if (s.nb1[b] >= 0) continue;
-      if (!negative.empty() && negative.count(((unsigned long long)a << 32) | (unsigned long long)b)) continue;
+      if (!later.empty() && later.count(((unsigned long long)a << 32) | (unsigned long long)b)) continue;
       if (s.try_insert(a, b) && s.nb1[a] >= 0) break;
     }
   }
   for (size_t q = 0; q < count && s.merge_count < N - 1; ++q) {
-    if (!(scores[q] < 0.0)) continue;
-    s.try_insert((int)(pairs[q] >> 32), (int)(pairs[q] & 0xffffffffULL));
+    if (!score_after_zero_block(scores[q])) continue;
+    pair_nodes(pairs[q], n_nodes, &i, &j);
+    s.try_insert(i, j);
   }
+  return DIFUSCO_OK;
 }
 
 // The closing edge of the Hamiltonian path and the walk from node 0 (tsp_utils.py:134-141).
@@ -313,8 +362,10 @@ int merge_one_sample(const Carve& c, int n_nodes, long long E, const float* heat
   int within = 0;
   size_t k = 0;
   for (; k < n_pairs && paths.merge_count < N - 1; ++k) {
-    if (!(scores[k] > 0.0)) break;                       // the pinned regime ends with the positive scores
-    const int i = (int)(pairs[k] >> 32), j = (int)(pairs[k] & 0xffffffffULL);
+    if (!score_in_pinned_regime(scores[k])) break;       // the pinned regime ends with the positive scores
+    int i, j;
+    if (!pair_nodes(pairs[k], n_nodes, &i, &j))
+      return set_error(DIFUSCO_EINVAL, "tsp_merge_tour: sorted entry %zu is no pair of a %d-node graph", k, n_nodes);
     // dense order: (i,j) and (j,i) are adjacent with equal scores; the first one met does the insertion
     iterations += 1;
     paths.try_insert(i, j);
@@ -322,8 +373,9 @@ int merge_one_sample(const Carve& c, int n_nodes, long long E, const float* heat
     iterations += 1;
   }
   if (paths.merge_count == N - 1) within = 1;
-  if (paths.merge_count < N - 1) finish_outside_regime(paths, n_nodes, pairs.data() + k, scores.data() + k, n_pairs - k);
-  const int rc = close_and_walk(paths, n_nodes, tour_out);
+  int rc = DIFUSCO_OK;
+  if (paths.merge_count < N - 1) rc = finish_outside_regime(paths, n_nodes, pairs.data() + k, scores.data() + k, n_pairs - k);
+  if (rc == DIFUSCO_OK) rc = close_and_walk(paths, n_nodes, tour_out);
   if (rc != DIFUSCO_OK) return rc;
   if (merge_iterations) *merge_iterations = iterations;
   if (completed) *completed = within;
@@ -462,12 +514,15 @@ __device__ __forceinline__ void merge_insert_wave(const MergeSample& d, const do
     const long long q = base + lane;
     const double sc = q < E ? score[q] : 0.0;
     const unsigned long long pr = q < E ? pair[q] : 0ULL;
-    // the walk ends at the first score that is not > 0 (NaN included); lanes [0, n_pos) hold candidate pairs
-    const unsigned long long not_pos = __ballot(!(q < E && sc > 0.0));
+    // the walk ends at the first score outside block 1 (NaN sorts last: it never cuts the positive scores short); lanes
+    // [0, n_pos) hold candidate pairs - by construction, and a lane whose entry does not decode to two nodes of the graph
+    // reads no state
+    const unsigned long long not_pos = __ballot(!(q < E && score_in_pinned_regime(sc)));
     const int n_pos = not_pos ? __ffsll((unsigned long long)not_pos) - 1 : kMergeWave;
-    const int i = (int)(pr >> 32), j = (int)(pr & 0xffffffffULL);
+    int i, j;
+    const bool is_pair = pair_nodes(pr, n, &i, &j);
     // degrees only grow: a pair with a full endpoint can never be accepted later
-    unsigned long long alive = __ballot(lane < n_pos && nb1[i] < 0 && nb1[j] < 0);
+    unsigned long long alive = __ballot(lane < n_pos && is_pair && nb1[i] < 0 && nb1[j] < 0);
     while (alive) {
       const int l = __ffsll(alive) - 1;
       alive &= alive - 1;
@@ -797,8 +852,8 @@ int difusco_tsp_merge_batch(int graphs, const int32_t* graph_n, const int64_t* g
       paths.degree[v] = (paths.nb0[v] >= 0) + (paths.nb1[v] >= 0);
     }
     paths.merge_count = r.merge_count;
-    finish_outside_regime(paths, d.n, pairs.data(), scores.data(), tail);
-    rc = close_and_walk(paths, d.n, tour_out);
+    rc = finish_outside_regime(paths, d.n, pairs.data(), scores.data(), tail);
+    if (rc == DIFUSCO_OK) rc = close_and_walk(paths, d.n, tour_out);
     if (rc != DIFUSCO_OK) return rc;
   }
   return DIFUSCO_OK;

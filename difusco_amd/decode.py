@@ -60,7 +60,14 @@ def _philox_table(seeds, offsets, count, noun, device):
 def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=False, parallel_sampling=1, *, device="cuda:0",
                 return_completed=False):
     """``adj_mat``: [parallel_sampling * E] (or [parallel_sampling, E]) heat values in the edge order of
-    ``edge_index_np`` ([2, E], the ONE graph's edges); ``np_points`` [N, 2].  numpy arrays or torch tensors."""
+    ``edge_index_np`` ([2, E], the ONE graph's edges); ``np_points`` [N, 2].  numpy arrays or torch tensors.
+
+    Candidate pairs are visited as a stable ascending sort of ``-(A + A^T) / dist`` visits them: scores ``> 0`` by decreasing
+    score (``+inf`` first: positive heat between coincident cities, ``+inf`` heat); then the zero block (``S == +-0`` and
+    every pair that is no edge) in flat-index order; then negative scores by decreasing score; then ``-inf`` (negative heat
+    between coincident cities, ``-inf`` heat); NaN of either sign (``0/0``, NaN heat, ``inf + -inf``) last.  Equal scores,
+    and the NaNs among themselves, by flat index.  ``completed`` is True exactly when all N - 1 insertions came from the
+    scores ``> 0``; a NaN is never counted by ``merge_iterations`` before such a terminating entry."""
     device = torch.device(device)
     L = _lib.lib()
     pts = _dev(np_points, torch.float32, device)

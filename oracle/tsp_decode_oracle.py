@@ -23,16 +23,21 @@ def _find(link, i):
     return r
 
 
-def merge_dense(points, adj_mat):
+def merge_dense(points, adj_mat, key_map=None):
     """cython_merge.pyx:19-104 on a dense symmetric matrix.  Returns (A_tour [N,N] 0/1, merge_iterations,
     completed) where completed says that the N-1 insertions happened on entries with a negative sort key
-    (positive heat / distance), i.e. before the zero block."""
+    (positive heat / distance), i.e. before the zero block.  Non-finite keys rank as the stable ascending sort ranks
+    them: -inf first, then negative, +-0 (equal), positive, +inf, NaN of either sign last, equal keys (and the NaNs)
+    by flat index.  ``key_map`` (tests only) rewrites the flat key array before the sort, to state a WRONG rule that a
+    test must tell from this one."""
     pts = np.asarray(points, dtype=np.float64)
     adj = np.asarray(adj_mat, dtype=np.float64)
     n = pts.shape[0]
     dist = np.linalg.norm(pts[:, None] - pts, axis=-1)
     with np.errstate(divide="ignore", invalid="ignore"):
         key = (-adj / dist).flatten()
+    if key_map is not None:
+        key = np.asarray(key_map(key), dtype=np.float64)
     order = np.argsort(key, kind="stable")
     begin, end = np.arange(n), np.arange(n)
     A = np.zeros((n, n))
@@ -73,9 +78,9 @@ def merge_dense(points, adj_mat):
     return A, it, completed
 
 
-def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=True, parallel_sampling=1):
+def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=True, parallel_sampling=1, key_map=None):
     """tsp_utils.py:89-145 (dense branch :105-108, sparse branch :109-116, tour walk :131-141).  Returns (tours, mean merge_iterations,
-    completed flags)."""
+    completed flags).  ``key_map``: see merge_dense."""
     n = np_points.shape[0]
     if sparse_graph:
         parts = np.split(np.asarray(adj_mat, dtype=np.float32).reshape(-1), parallel_sampling, axis=0)
@@ -83,13 +88,14 @@ def merge_tours(adj_mat, np_points, edge_index_np, sparse_graph=True, parallel_s
         parts = [p[0] for p in np.split(np.asarray(adj_mat, dtype=np.float32).reshape(-1, n, n), parallel_sampling, axis=0)]
     tours, iters, done = [], [], []
     for part in parts:
-        if sparse_graph:
-            a = np.zeros((n, n), dtype=np.float32)
-            np.add.at(a, (edge_index_np[0], edge_index_np[1]), part)
-        else:
-            a = part
-        dense = a + a.T                                  # float32 add, as scipy's toarray() + toarray()
-        real, it, ok = merge_dense(np_points, dense)
+        with np.errstate(invalid="ignore", over="ignore"):   # NaN / infinite heat, float32 sums that overflow: part of the rule
+            if sparse_graph:
+                a = np.zeros((n, n), dtype=np.float32)
+                np.add.at(a, (edge_index_np[0], edge_index_np[1]), part)
+            else:
+                a = part
+            dense = a + a.T                              # float32 add, as scipy's toarray() + toarray()
+        real, it, ok = merge_dense(np_points, dense, key_map)
         tour = [0]
         while len(tour) < n + 1:
             nb = np.nonzero(real[tour[-1]])[0]
