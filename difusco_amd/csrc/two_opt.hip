@@ -189,26 +189,9 @@ __global__ __launch_bounds__(256) void two_opt_apply_kernel(A a, int* __restrict
 //  difusco_tsp_two_opt_screen_bound says so and the call runs the exact sweep.
 //  Nothing above depends on n: the bound is per pair, from M alone, so in a ragged call (difusco_tsp_two_opt_ragged) it holds
 //  for every tour with the M of its own group, whatever the sizes of the other groups.
-constexpr double kScreenEpsPerM = 0x1.8p-18;       // 96 * 2^-24
-constexpr double kScreenMinM = 0x1p-32, kScreenMaxM = 0x1p60;
+//  kScreenEpsPerM, kScreenMinM / kScreenMaxM, screen_eps, f32_key and change32 are in two_opt_common.h: the resident 2-opt
+//  (two_opt_resident.hip) screens with them as well.
 constexpr int SCH = 256 * JPT;                     // columns per chunk of the screen
-
-__host__ __device__ inline double screen_eps(double m) { return m * kScreenEpsPerM; }
-
-// order-preserving key of a float32 (no NaN): a < b  <=>  key(a) < key(b)
-__device__ __forceinline__ unsigned f32_key(float v) {
-  const unsigned bits = __float_as_uint(v);
-  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
-__device__ __forceinline__ float f32_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__device__ __forceinline__ float dist32(float dx, float dy) { return __builtin_amdgcn_sqrtf(__builtin_fmaf(dx, dx, dy * dy)); }
-
-// q = (P_i, P_i+1), c = (P_j, P_j+1)
-__device__ __forceinline__ float change32(float4 q, float d_i, float4 c, float d_j) {
-  const float d0 = dist32(q.x - c.x, q.y - c.y), d1 = dist32(q.z - c.z, q.w - c.w);
-  return ((d0 + d1) - d_i) - d_j;
-}
 
 // gmax[g] = bits of the largest |coordinate| of group g (non-negative doubles order like their bits; a NaN sorts above inf)
 template <class A>

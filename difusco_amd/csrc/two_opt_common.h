@@ -1,4 +1,5 @@
-// What the 2-opt entries (two_opt.hip) and the local search (or_opt.hip) share: the float64 distance, the (min, first flat
+// What the 2-opt entries (two_opt.hip), the resident 2-opt (two_opt_resident.hip) and the local search (or_opt.hip) share: the
+// float64 distance and pair change, the float32 pair change of the screen and its bound, the (min, first flat
 // index) reductions, the prep entry, one block of the exact 2-opt sweep and the segment reversal; and the check of the group
 // arrays that every _ragged tour entry starts with.  Every function is
 // per translation unit (anonymous namespace): the kernels that use them are compiled where they are launched.
@@ -35,6 +36,36 @@ __device__ __forceinline__ void prep_entry(const double* __restrict__ points, co
     const double dx = p.x - points[2 * c1], dy = p.y - points[2 * c1 + 1];
     dlen[k] = dist2d(dx, dy);                                   // A_i,i+1 (tsp_utils.py:28)
   }
+}
+
+// one pair's change A_ij + A_i+1,j+1 - A_i,i+1 - A_j,j+1, evaluated left to right (tsp_utils.py:31) as best_tile evaluates it:
+// a = P_i, a1 = P_i+1, pj = P_j, pj1 = P_j+1, d_i and d_j their dlen
+__device__ __forceinline__ double change64(double2 a, double2 a1, double2 pj, double2 pj1, double d_i, double d_j) {
+  const double x0 = a.x - pj.x, y0 = a.y - pj.y;
+  const double x1 = a1.x - pj1.x, y1 = a1.y - pj1.y;
+  return __dsub_rn(__dsub_rn(__dadd_rn(dist2d(x0, y0), dist2d(x1, y1)), d_i), d_j);
+}
+
+// ---- the float32 screen of a pair (the bound is derived in two_opt.hip): |c32 - c64| <= eps(M) = 96 * 2^-24 * M for
+// 2^-32 <= M <= 2^60, M = the largest |coordinate| of the instance; outside that range, or with a non-finite M, no bound.
+constexpr double kScreenEpsPerM = 0x1.8p-18;       // 96 * 2^-24
+constexpr double kScreenMinM = 0x1p-32, kScreenMaxM = 0x1p60;
+
+__host__ __device__ inline double screen_eps(double m) { return m * kScreenEpsPerM; }
+
+// order-preserving key of a float32 (no NaN): a < b  <=>  key(a) < key(b)
+__device__ __forceinline__ unsigned f32_key(float v) {
+  const unsigned bits = __float_as_uint(v);
+  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
+}
+__device__ __forceinline__ float f32_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ float dist32(float dx, float dy) { return __builtin_amdgcn_sqrtf(__builtin_fmaf(dx, dx, dy * dy)); }
+
+// q = (P_i, P_i+1), c = (P_j, P_j+1)
+__device__ __forceinline__ float change32(float4 q, float d_i, float4 c, float d_j) {
+  const float d0 = dist32(q.x - c.x, q.y - c.y), d1 = dist32(q.z - c.z, q.w - c.w);
+  return ((d0 + d1) - d_i) - d_j;
 }
 
 constexpr int TI = 16;     // rows per block

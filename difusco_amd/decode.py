@@ -194,6 +194,24 @@ def two_opt_screen_bound(max_abs_coord):
     return float(eps.value) if rc == 1 else None
 
 
+TWO_OPT_MODES = ("launches", "resident")
+
+
+def check_two_opt_mode(local_search, mode):
+    """``two_opt_mode`` of ``solve_tsp``, ``solve_tsp_batch`` and the runner: ``"resident"`` runs the single-move 2-opt with one
+    GPU block per instance, so it needs ``local_search="2opt"``; the 2-opt phases of the other searches have no resident form."""
+    if mode not in TWO_OPT_MODES:
+        raise ValueError(f"two-opt mode {mode!r}: one of {TWO_OPT_MODES}")
+    if mode == "resident" and local_search != "2opt":
+        raise ValueError(f"two_opt_mode='resident' runs the single-move 2-opt: it needs local_search='2opt', not {local_search!r}")
+    return mode
+
+
+def two_opt_resident_max_cells():
+    """The largest group ``mode="resident"`` takes: ``P * (n + 1)`` entries of closed tours (a constant of the build, >= 2048)."""
+    return int(_lib.lib().difusco_tsp_two_opt_resident_max_cells())
+
+
 # The tour searches come in three forms.  ``_torch``: the tours [B, N + 1] of ONE instance; ``_grouped``: G instances of one
 # size, points [G, N, 2] and tours [G * P, N + 1]; ``_ragged``: lists of G instances of any sizes.  All three run one ``_ragged``
 # library entry on per-group arrays (``_per_group``, ``_RaggedBatch``) and differ in how they hand the results back (``_as_form``).
@@ -267,14 +285,45 @@ class _RaggedBatch:
         return [f.reshape(shape) for f, shape in zip(np.split(flat, cuts), self.shapes)]
 
 
-def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
+def _two_opt_resident(form, points, tours, max_iterations, device, method, stats, moves_per_launch):
+    """``batched_two_opt_<form>`` with ``mode="resident"``: one ``difusco_tsp_two_opt_resident`` call on the per-group arrays."""
+    pts, trs = _per_group(form, points, tours)
+    if len(pts) < 1 or len(trs) != len(pts):
+        raise ValueError(f"{len(trs)} tour arrays for {len(pts)} instances (at least one instance)")
+    for g, (p, t) in enumerate(zip(pts, trs)):
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"points of instance {g} must be [n, 2]")
+        if t.ndim != 2 or t.shape[1] != p.shape[0] + 1 or t.shape[0] < 1:
+            raise ValueError(f"tours of instance {g} must be [P, {p.shape[0] + 1}] closed tours over the {p.shape[0]} points, P >= 1")
+    batch = _RaggedBatch(pts, trs, device)
+    L = _lib.lib()
+    code = TWO_OPT_METHODS.index(method)
+    ws, nbytes = _workspace(L.difusco_tsp_two_opt_resident_workspace_bytes, *batch.sizes, code, device=device)
+    its = np.zeros(batch.groups, dtype=np.int64)
+    pairs, syncs = ctypes.c_int64(), ctypes.c_int32()
+    _lib.check(L.difusco_tsp_two_opt_resident(*batch.head, int(max_iterations), code, int(moves_per_launch), _ptr(ws), nbytes,
+                                              its.ctypes.data, ctypes.byref(pairs), ctypes.byref(syncs), _stream(device)))
+    if stats is not None:
+        stats["exact_pairs"], stats["host_syncs"] = int(pairs.value), int(syncs.value)
+    out, st = _as_form(form, batch.read_tours(), {"iterations": its})
+    return out, st["iterations"]
+
+
+def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, method="exact", stats=None, mode="launches",
+                          moves_per_launch=0):
     """Drop-in for ``batched_two_opt_torch`` of the reference (``difusco/utils/tsp_utils.py:12-49``): ``points``
     float64 [N,2] numpy, ``tour`` int [B, N+1] numpy (closed tours over the same points); returns
     ``(tour int64 numpy [B, N+1], iterator)``.  Runs ``difusco_tsp_two_opt``; GPU only.  ``method="screened"`` runs
     ``difusco_tsp_two_opt_screened``: the same tours and iterator, float64 only for the moves a float32 screen cannot rule out;
-    ``stats`` (a dict) then receives ``exact_pairs``, the number of pairs that took the float64 path."""
+    ``stats`` (a dict) then receives ``exact_pairs``, the number of pairs that took the float64 path.  ``mode="resident"`` runs
+    ``difusco_tsp_two_opt_resident`` instead: one GPU block keeps the tours in LDS and applies move after move without a launch
+    or a host read per move (at most ``moves_per_launch`` per launch, 0 = the library's default); the same tours and iterator
+    with either ``method``, for at most ``two_opt_resident_max_cells()`` tour entries (``B * (N + 1)``; more raises
+    ``DifuscoHipError``, there is no fallback); ``stats`` receives ``exact_pairs`` and ``host_syncs``."""
     method = check_two_opt_method(method)
     device = _gpu_only("batched_two_opt_torch of difusco_amd", device)
+    if check_two_opt_mode("2opt", mode) == "resident":
+        return _two_opt_resident("torch", points, tour, max_iterations, device, method, stats, moves_per_launch)
     pts, tours = np.asarray(points, dtype=np.float64), np.asarray(tour)
     if tours.ndim != 2 or tours.shape[1] != pts.shape[0] + 1:
         raise ValueError("tour must be [batch, N + 1] over the N points")
@@ -295,14 +344,18 @@ def batched_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *,
     return tours.cpu().numpy().astype(np.int64), int(it.value)
 
 
-def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
+def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, method="exact", stats=None, mode="launches",
+                            moves_per_launch=0):
     """``batched_two_opt_torch`` of G instances at once: ``points`` float64 [G, N, 2], ``tours`` int [G * P, N + 1] with the P
     tours of instance g at rows g P .. g P + P - 1.  Every instance gets exactly what ``batched_two_opt_torch(points[g],
     tours[g P:(g+1) P])`` returns (its own stop test and iteration count); runs ``difusco_tsp_two_opt_grouped``, GPU only.
     Returns ``(tours int64 numpy [G * P, N + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
-    ``batched_two_opt_torch`` (``difusco_tsp_two_opt_grouped_screened``)."""
+    ``batched_two_opt_torch`` (``difusco_tsp_two_opt_grouped_screened``).  ``mode`` / ``moves_per_launch``: as
+    ``batched_two_opt_torch``, one block per instance; the limit holds for every instance (``P * (N + 1)`` entries)."""
     method = check_two_opt_method(method)
     device = _gpu_only("batched_two_opt_grouped", device)
+    if check_two_opt_mode("2opt", mode) == "resident":
+        return _two_opt_resident("grouped", points, tours, max_iterations, device, method, stats, moves_per_launch)
     pts, t, P = _grouped_arrays(points, tours)
     G, n = pts.shape[0], pts.shape[1]
     pts, t = _dev(pts, torch.float64, device), _dev(t, torch.int32, device)
@@ -322,14 +375,19 @@ def batched_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0",
     return t.cpu().numpy().astype(np.int64), its
 
 
-def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, method="exact", stats=None):
+def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, method="exact", stats=None,
+                           mode="launches", moves_per_launch=0):
     """``batched_two_opt_torch`` of G instances of ANY sizes at once: ``points_list[g]`` float64 [n_g, 2], ``tours_list[g]`` int
     [P_g, n_g + 1] closed tours over them.  Every instance gets exactly what ``batched_two_opt_torch(points_list[g],
     tours_list[g])`` returns (its own stop test, iteration count and tie rule); runs ``difusco_tsp_two_opt_ragged``, GPU only.
     Returns ``(list of int64 numpy [P_g, n_g + 1], iterations int64 numpy [G])``.  ``method`` / ``stats``: as
-    ``batched_two_opt_torch``; with ``method="exact"`` ``exact_pairs`` counts every pair of every sweep."""
+    ``batched_two_opt_torch``; with ``method="exact"`` ``exact_pairs`` counts every pair of every sweep.  ``mode`` /
+    ``moves_per_launch``: as ``batched_two_opt_torch``, one block per instance (``P_g * (n_g + 1)`` entries each); an instance
+    without a screen bound then takes the exact sweep for itself only."""
     method = check_two_opt_method(method)
     device = _gpu_only("batched_two_opt_ragged", device)
+    if check_two_opt_mode("2opt", mode) == "resident":
+        return _two_opt_resident("ragged", points_list, tours_list, max_iterations, device, method, stats, moves_per_launch)
     pts, trs = _per_group("ragged", points_list, tours_list)
     G = len(pts)
     if G < 1 or len(trs) != G:

@@ -21,7 +21,10 @@ every chunk starts its steps at offset 0, and the chunks (``plan_chunks``) are c
 depend on the world size, the rank an instance lands on, or what the model ran before.
 
 Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``default_instances_per_call``),
-``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--local_search
+``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--two_opt_mode
+{launches,resident}`` (TSP with ``--local_search 2opt``: ``resident`` runs that 2-opt with one GPU block per instance,
+``mode="resident"`` of ``decode.batched_two_opt_grouped``; the records and the header gain ``two_opt_mode`` and are otherwise
+the same), ``--local_search
 {2opt,2opt+oropt,multi2opt,multi2opt+oropt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
 ``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``; ``multi2opt``,
 ``decode.batched_multi_two_opt_grouped``: every sweep applies all disjoint improving 2-opt moves it selects, ``2opt_iterations``
@@ -124,6 +127,10 @@ EXTENSION_ARGS = [
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
     ("--two_opt_method", dict(type=str, default="exact", choices=("exact", "screened"),
                               help="2-opt sweep: exact (float64 for every pair) or screened (float32 screen, same moves)")),
+    ("--two_opt_mode", dict(type=str, default="launches", choices=("launches", "resident"),
+                            help="TSP: how the single-move 2-opt runs: launches (a launch sequence per move) or resident (one "
+                                 "GPU block per instance keeps the tours in LDS, no launch or host read per move; same "
+                                 "records; needs --local_search 2opt and P * (N + 1) within the library's limit)")),
     ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt"),
                              help="tour refinement: 2opt (the reference's), 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
                                   "records gain or_opt_iterations and local_search_rounds) or multi2opt (every sweep applies all "
@@ -206,6 +213,9 @@ def parse_args(argv=None):
         parser.error("--ckpt_path is required (the weights to evaluate)")
     if args.local_search != "2opt" and args.two_opt_method != "exact":
         parser.error(f"--local_search {args.local_search} runs the exact 2-opt sweep: --two_opt_method {args.two_opt_method} is not built")
+    if args.two_opt_mode != "launches" and (args.task != "tsp" or args.local_search != "2opt"):
+        parser.error(f"--two_opt_mode {args.two_opt_mode} runs the single-move 2-opt of TSP tours: pass --task tsp "
+                     "--local_search 2opt")
     if args.tsp_local_search_kicks < 0 or not 1 <= args.tsp_local_search_kick_size <= 64 or args.tsp_local_search_kick_span < 1:
         parser.error("--tsp_local_search_kicks must be >= 0, --tsp_local_search_kick_size in 1 .. 64 and "
                      "--tsp_local_search_kick_span >= 1")
@@ -406,7 +416,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 mis_local_search_kick_size: int = 4, mis_local_search_mode: str = "launches", tsp_local_search_kicks: int = 0,
                 tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
                 tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
-                tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1) -> List[dict]:
+                tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1,
+                two_opt_mode: str = "launches") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -434,9 +445,12 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   **(dict(local_search_window=tsp_local_search_window, local_search_passes=tsp_local_search_passes)
                                      if tsp_local_search_window > 0 else {}),
                                   **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
-                                  **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}))
+                                  **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}),
+                                  **(dict(two_opt_mode="resident") if two_opt_mode == "resident" else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
+                if two_opt_mode == "resident":
+                    records[-1].update(two_opt_mode="resident")
                 if tsp_local_search_window > 0:
                     records[-1].update(tsp_local_search_window=tsp_local_search_window,
                                        tsp_local_search_passes=tsp_local_search_passes)
@@ -534,7 +548,7 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_descent=args.tsp_local_search_descent,
                                tsp_local_search_kick_bias=args.tsp_local_search_kick_bias,
                                tsp_local_search_window=args.tsp_local_search_window,
-                               tsp_local_search_passes=args.tsp_local_search_passes)
+                               tsp_local_search_passes=args.tsp_local_search_passes, two_opt_mode=args.two_opt_mode)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -557,6 +571,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                     "two_opt_method": args.two_opt_method, "graph_build": model.graph_build, "ignored_args": ignored}
             if mixed:
                 line["mixed_size_chunks"] = True
+            if args.two_opt_mode == "resident":
+                line["two_opt_mode"] = "resident"
             if args.local_search != "2opt":
                 line["local_search"] = args.local_search
             if args.mis_local_search != "none":

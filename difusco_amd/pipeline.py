@@ -18,7 +18,7 @@ import torch
 
 from . import decode
 from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
-                     check_tsp_kicks, check_tsp_window, check_two_opt_method, merge_tours, merge_tours_batch)
+                     check_tsp_kicks, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
 
@@ -41,7 +41,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               sequential_sampling: int = 1, *, graphed: bool = False, two_opt_method: str = "exact",
               local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
               local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
-              local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1):
+              local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1,
+              two_opt_mode: str = "launches"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -73,14 +74,18 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     ``local_search_passes`` passes over windows of W positions and ``local_search_kicks`` kicks (>= 0) per window and pass, of
     ``local_search_kick_size`` and ``local_search_kick_span``; the copies are keyed as above; info gains
     ``local_search_window``, ``local_search_passes`` and, of the last round, one per copy, ``local_search_kicks_improved``,
-    ``local_search_passes_kept`` and ``local_search_closing_sweeps``."""
+    ``local_search_passes_kept`` and ``local_search_closing_sweeps``.  ``two_opt_mode``: "launches" (default) or "resident"
+    (only with ``local_search="2opt"``, else ``ValueError``): the 2-opt runs with one GPU block for the instance
+    (``mode="resident"`` of ``decode.batched_two_opt_torch``), same results with either ``two_opt_method``; the
+    ``parallel_sampling`` tours must fit its limit, there is no fallback."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
+    two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
-    search = (local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias)
+    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -207,15 +212,16 @@ def _kick_key(seed) -> int:
 
 def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, dev, seeds, offsets, heat, edge_index, kick_stats):
     """The local search of one round on the merged tours, through the ``decode.batched_*`` wrapper of ``form`` ("torch",
-    "grouped" or "ragged") that ``search`` - the checked (local_search, two_opt_method, window, passes, kicks, kick_size,
+    "grouped" or "ragged") that ``search`` - the checked (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size,
     kick_span, descent, kick_bias) - selects.  ``seeds`` / ``offsets``: the Philox key and first offset of every tour, read by
     the kicked searches, as ``heat`` / ``edge_index`` (the round's heatmaps and their graphs) are by heat-biased kicks;
     ``kick_stats`` receives their per-tour arrays.  Returns (tours, iterations, the search's own statistics)."""
-    local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias = search
+    local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias = search
     run = lambda stem, **kw: getattr(decode, f"batched_{stem}_{form}")(points, tours, max_iterations=two_opt_iterations, device=dev, **kw)
     ls_stats = {}
     if local_search == "2opt":
-        solved, iterations = run("two_opt", method=two_opt_method)                              # pl_tsp_model.py:233-236
+        solved, iterations = run("two_opt", method=two_opt_method,                              # pl_tsp_model.py:233-236
+                                 **(dict(mode="resident") if two_opt_mode == "resident" else {}))
     elif local_search == "multi2opt":
         solved, iterations = run("multi_two_opt", stats=ls_stats)
     elif local_search == "2opt+oropt":
@@ -293,7 +299,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     merge_method: str = "loop", local_search: str = "2opt", local_search_kicks: int = 0,
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
                     local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
-                    local_search_passes: int = 1) -> List[tuple]:
+                    local_search_passes: int = 1, two_opt_mode: str = "launches") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -311,15 +317,17 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     an instance is its own tour, keyed by the instance's seed, so an instance gets what its solo call gets.
     ``local_search_descent``, ``local_search_kick_bias``: as ``solve_tsp``; "heat" passes every instance's own heatmaps of the
     round (the tensors the merge received, on the device) and its own graph.  ``local_search_window``,
-    ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets."""
+    ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets.  ``two_opt_mode``: as ``solve_tsp``,
+    one GPU block per instance, for arrays and sequences of instances alike."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
+    two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
-    search = (local_search, two_opt_method, window, passes, kicks, kick_size, kick_span, descent, kick_bias)
+    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search)

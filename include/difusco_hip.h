@@ -617,6 +617,37 @@ int difusco_tsp_two_opt_ragged(int groups, const int32_t* group_n, const int32_t
                                int32_t* tours, int64_t max_iterations, int method, void* workspace, size_t workspace_bytes,
                                int64_t* iterations_out, int64_t* exact_pairs_out, void* stream);
 
+/* Resident 2-opt (additive to ABI 13): difusco_tsp_two_opt_ragged with one resident GPU block per group.  The arrays and
+ * conventions of that entry, and THE SAME RULE: group g ends with exactly the tours and iterations_out[g] that
+ * difusco_tsp_two_opt_ragged gives it, with either method.  What differs is the execution: a block keeps the tours of its group,
+ * their points in tour order, the edge lengths and (method 1) the float32 copies in LDS and runs move after move - sweep,
+ * argmin per tour, group minimum, stop test, reversals - between block barriers, without a launch or a host read per move.
+ * A group fits if group_tours[g] * (group_n[g] + 1) <= difusco_tsp_two_opt_resident_max_cells(), a constant of the build for
+ * both methods, >= 2048 (TSP-500 with 4 tours: 2004 cells).  The sizes are host arrays, so a group above the limit is refused
+ * on the host before any GPU work: DIFUSCO_EUNSUPPORTED, the message names the group, its cells and the limit, `tours` is
+ * untouched; there is no fallback to the launched entry.
+ * method: 0 the exact sweep, 1 the screened one under the bound of difusco_tsp_two_opt_screen_bound with the group's own largest
+ * |coordinate|, reduced inside its block.  A group without a bound takes the exact sweep FOR ITSELF ONLY; in
+ * difusco_tsp_two_opt_ragged one such group sends the whole call to the exact sweep.  The tours and iteration counts are the same
+ * either way; only exact_pairs_out can tell the difference.
+ * moves_per_launch: a launch applies at most that many moves per group; 0 = the library's default (1024).  The tours, the counts
+ * and the stop flags stay in global memory between launches, a stopped group's block returns at once.  The host enqueues
+ * ceil(max(max_iterations, 1) / moves_per_launch) launches at most and reads the state once after each: that read tells whether
+ * another launch is needed and, after the last one, is the result.  Hence one host synchronisation per launch that ran, none
+ * inside a launch; host_syncs_out (HOST, optional) reports the number.
+ * exact_pairs_out (HOST, optional): the pairs of the call evaluated in float64, counted by the kernel - with method 0, and for a
+ * group without a bound, every pair of every sweep; with method 1 never more than that.
+ * workspace: _workspace_bytes, a few bytes per group.  DIFUSCO_EINVAL before any GPU work on everything
+ * difusco_tsp_two_opt_ragged refuses and on moves_per_launch < 0.  Blocks until every group is done. */
+int difusco_tsp_two_opt_resident_max_cells(void);
+int difusco_tsp_two_opt_resident_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int method,
+                                                 size_t* bytes);
+int difusco_tsp_two_opt_resident(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                 int32_t* tours, int64_t max_iterations, int method, int32_t moves_per_launch /* 0 = default */,
+                                 void* workspace, size_t workspace_bytes, int64_t* iterations_out /* host */,
+                                 int64_t* exact_pairs_out /* host, optional */, int32_t* host_syncs_out /* host, optional */,
+                                 void* stream);
+
 /* Local search, 2-opt + Or-opt (additive to ABI 13): the arrays, conventions and limits of difusco_tsp_two_opt_ragged.  Every
  * group runs rounds of two phases on its own tours, independent of the other groups:
  *   2-opt phase   exactly difusco_tsp_two_opt(n_g, group_tours[g], ...) with max_iterations (the exact sweep) -> a moves;
