@@ -526,6 +526,137 @@ def batched_multi_two_opt_ragged(points_list, tours_list, max_iterations=1000, d
     return _multi_two_opt("ragged", points_list, tours_list, max_iterations, device, select_rounds, stats)
 
 
+TSP_CLOSINGS = ("full", "none")           # --tsp_local_search_closing of the runner: closing=True / False
+
+
+def check_tsp_candidates(local_search, candidates, kicks=0, window=0, two_opt_mode="launches"):
+    """``local_search_candidates`` of ``solve_tsp``, ``solve_tsp_batch`` and the runner (0: off): the neighbour-list sweeps are
+    a mode of the multi-move 2-opt alone; the kicked, windowed and resident searches have no neighbour-list form."""
+    if int(candidates) != candidates or candidates < 0:
+        raise ValueError(f"local_search_candidates = {candidates!r}: an integer >= 0")
+    if candidates > 0:
+        if local_search != "multi2opt":
+            raise ValueError(f"local_search_candidates = {candidates} runs the neighbour-list multi-move 2-opt: it needs "
+                             f"local_search='multi2opt', not {local_search!r}")
+        if kicks > 0 or window > 0:
+            raise ValueError(f"local_search_candidates = {candidates} combines with neither kicks nor windows")
+        if two_opt_mode == "resident":
+            raise ValueError(f"local_search_candidates = {candidates} does not combine with two_opt_mode='resident'")
+    return int(candidates)
+
+
+def tsp_candidate_lists(edge_index, sizes, candidates):
+    """The candidate lists of ``batched_nbr_two_opt_*`` from a k-NN ``edge_index`` ([2, sum n_g k], the layout of
+    ``knn_edge_index_gpu``: the k neighbours of a node in a row, nearest first, node ids offset by the sizes before; or a list of
+    one [2, n_g k] per graph with local node ids): per node
+    its first ``candidates`` neighbours that are not the node itself, order kept, local to the graph.  Needs ``candidates <=
+    k - 1``.  Returns one int32 device tensor [n_g, candidates] per graph."""
+    sizes = [int(n) for n in sizes]
+    total = sum(sizes)
+    local = isinstance(edge_index, (list, tuple))
+    cols = torch.cat([e[1] for e in edge_index]) if local else edge_index[1]
+    if cols.ndim != 1 or cols.shape[0] % total != 0:
+        raise ValueError(f"edge_index must be [2, {total} k]")
+    k = cols.shape[0] // total
+    if not 1 <= candidates <= k - 1:
+        raise ValueError(f"candidates = {candidates}: 1 .. {k - 1} of a graph with k = {k}")
+    nb = cols.reshape(total, k)
+    first = torch.repeat_interleave(torch.tensor(np.cumsum([0] + sizes[:-1]), device=nb.device),
+                                    torch.tensor(sizes, device=nb.device)).reshape(total, 1)
+    if not local:
+        nb = nb - first
+    me = torch.arange(total, device=nb.device).reshape(total, 1) - first
+    order = torch.argsort((nb == me).to(torch.int8), dim=1, stable=True)                 # the node itself last, the rest as they were
+    lists = torch.gather(nb, 1, order)[:, :candidates].to(torch.int32)
+    return list(torch.split(lists, sizes))
+
+
+def _nbr_lists(form, pts, neighbors, candidates, device):
+    """The checked lists of ``batched_nbr_two_opt_<form>`` as one flat int32 device tensor and their K."""
+    sizes = [p.shape[0] for p in pts]
+    if neighbors is None:
+        if int(candidates) != candidates or candidates < 1:
+            raise ValueError(f"candidates = {candidates!r}: an integer >= 1")
+        for g, n in enumerate(sizes):
+            if candidates > n - 1:
+                raise ValueError(f"candidates = {candidates}: instance {g} has {n} points, at most {n - 1} other cities")
+        from .graph import knn_edge_index_gpu
+        ei = knn_edge_index_gpu(np.concatenate(pts), int(candidates) + 1, device=device, sizes=sizes)
+        per = tsp_candidate_lists(ei, sizes, int(candidates))
+    else:
+        if form == "torch":
+            per = [neighbors]
+        elif form == "grouped":
+            if len(neighbors) != len(pts):
+                raise ValueError(f"neighbors holds {len(neighbors)} instances for {len(pts)}")
+            per = list(neighbors)
+        else:
+            per = list(neighbors)
+            if len(per) != len(pts):
+                raise ValueError(f"{len(per)} neighbour arrays for {len(pts)} instances")
+        per = [nb if isinstance(nb, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(nb)) for nb in per]
+        K = per[0].shape[1] if per[0].ndim == 2 else 0
+        for g, (nb, n) in enumerate(zip(per, sizes)):
+            if nb.ndim != 2 or nb.shape[0] != n or nb.shape[1] != K or K < 1:
+                raise ValueError(f"neighbors of instance {g} must be [{n}, K] with one K >= 1 for the call")
+            if nb.dtype.is_floating_point or nb.dtype.is_complex or nb.dtype == torch.bool:
+                raise ValueError(f"neighbors of instance {g} must be integers, not {nb.dtype}")
+    K = int(per[0].shape[1])
+    flat = torch.cat([nb.to(device=device, dtype=torch.int32).reshape(-1) for nb in per]).contiguous()
+    return flat, K
+
+
+def _nbr_two_opt(form, points, tours, max_iterations, device, candidates, neighbors, closing, select_rounds, stats):
+    """``batched_nbr_two_opt_<form>``: the checks and one ``difusco_tsp_nbr_two_opt_ragged`` call."""
+    pts, trs = _per_group(form, points, tours)
+    device = _multi_move_checked(f"batched_nbr_two_opt_{form}", pts, trs, max_iterations, 1, select_rounds, device)
+    lists, K = _nbr_lists(form, pts, neighbors, candidates, device)
+    closing = int(bool(closing))
+    batch = _RaggedBatch(pts, trs, device)
+    L = _lib.lib()
+    ws, nbytes = _workspace(L.difusco_tsp_nbr_two_opt_ragged_workspace_bytes, *batch.sizes, K, closing, device=device)
+    G = batch.groups
+    st = {"sweeps": np.zeros(G, dtype=np.int64), "full_sweeps": np.zeros(G, dtype=np.int64), "moves": np.zeros(G, dtype=np.int64)}
+    _lib.check(L.difusco_tsp_nbr_two_opt_ragged(*batch.head, _ptr(lists), K, closing, int(max_iterations), int(select_rounds),
+                                                _ptr(ws), nbytes, *(v.ctypes.data for v in st.values()), _stream(device)))
+    out, st = _as_form(form, batch.read_tours(), st)
+    if stats is not None:
+        stats.update(st)
+    return out, st["sweeps"]
+
+
+def batched_nbr_two_opt_torch(points, tour, max_iterations=1000, device="cuda:0", *, candidates=8, neighbors=None, closing=True,
+                              select_rounds=4, stats=None):
+    """Neighbour-list multi-move 2-opt of the tours of ONE instance, the arguments of ``batched_multi_two_opt_torch``: a sweep
+    evaluates only the pairs whose new head or tail edge joins a city to one of its listed neighbours, O(N K) instead of all
+    pairs, and applies the disjoint improving moves it selects; a tour whose neighbour sweep finds nothing stops
+    (``closing=False``) or goes on with the full sweeps of ``batched_multi_two_opt_torch`` until one finds nothing
+    (``closing=True``: the end tour is a full 2-opt optimum).  The rule: ``difusco_tsp_nbr_two_opt_ragged``,
+    include/difusco_hip.h; GPU only.  ``neighbors``: int [N, K], row a the listed cities of a (an entry outside 0 .. N-1 or
+    equal to a is a pad), numpy or a tensor; None builds the ``candidates`` nearest other cities of every city with
+    ``knn_edge_index_gpu`` (``candidates <= N - 1``).  At most ``max_iterations`` sweeps over both phases.  Returns ``(tour
+    int64 numpy [B, N+1], sweeps)``; ``stats`` (a dict) receives ``sweeps``, ``full_sweeps`` (those counted in the closing
+    phase) and ``moves``."""
+    return _nbr_two_opt("torch", points, tour, max_iterations, device, candidates, neighbors, closing, select_rounds, stats)
+
+
+def batched_nbr_two_opt_grouped(points, tours, max_iterations=1000, device="cuda:0", *, candidates=8, neighbors=None, closing=True,
+                                select_rounds=4, stats=None):
+    """``batched_nbr_two_opt_torch`` of G instances at once, the arguments of ``batched_multi_two_opt_grouped``; ``neighbors``:
+    int [G, N, K] or None.  Every instance gets what its own ``batched_nbr_two_opt_torch`` call returns.  Returns ``(tours int64
+    numpy [G * P, N + 1], sweeps int64 numpy [G])``; ``stats`` receives ``sweeps``, ``full_sweeps`` and ``moves`` (int64 [G])."""
+    return _nbr_two_opt("grouped", points, tours, max_iterations, device, candidates, neighbors, closing, select_rounds, stats)
+
+
+def batched_nbr_two_opt_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, candidates=8, neighbors=None,
+                               closing=True, select_rounds=4, stats=None):
+    """``batched_nbr_two_opt_torch`` of G instances of ANY sizes at once, the arguments of ``batched_multi_two_opt_ragged``;
+    ``neighbors``: a list of int [n_g, K] with one K, or None.  Returns ``(list of int64 numpy [P_g, n_g + 1], sweeps int64
+    numpy [G])``; ``stats``: as ``batched_nbr_two_opt_grouped``."""
+    return _nbr_two_opt("ragged", points_list, tours_list, max_iterations, device, candidates, neighbors, closing, select_rounds,
+                        stats)
+
+
 def _multi_local_search(form, points, tours, max_iterations, device, max_rounds, select_rounds):
     """``batched_multi_local_search_<form>``: the checks and one ``difusco_tsp_multi_local_search_ragged`` call."""
     pts, trs = _per_group(form, points, tours)

@@ -53,7 +53,10 @@ records and the header gain the setting), ``--tsp_local_search_window W`` / ``--
 ``--local_search multi2opt+oropt``, a full descent and uniform kicks: the windowed iterated search,
 ``decode.batched_window_search_grouped``, R passes over windows of W positions with ``--tsp_local_search_kicks`` kicks (>= 0) per
 window and pass, keyed as the kicks are; the records gain ``kicks_improved``, ``passes_kept`` and ``closing_sweeps``, one count per
-copy, and with the header the two settings and the three kick settings), ``--merge_method {loop,batched}``
+copy, and with the header the two settings and the three kick settings), ``--tsp_local_search_candidates K`` /
+``--tsp_local_search_closing {full,none}`` (K > 0 only with ``--local_search multi2opt``: the multi-move 2-opt on neighbour
+lists of K cities, ``decode.batched_nbr_two_opt_grouped``, closed by full sweeps unless ``none``; the records gain
+``two_opt_full_sweeps`` and with the header the two settings; without K every record is what it was), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -158,6 +161,13 @@ EXTENSION_ARGS = [
     ("--tsp_local_search_passes", dict(type=int, default=1,
                                         help="TSP: passes of the windowed search, odd ones shifted by half a window (needs "
                                              "--tsp_local_search_window W > 0)")),
+    ("--tsp_local_search_candidates", dict(type=int, default=0,
+                                            help="TSP: K > 0 runs the multi-move 2-opt on neighbour lists of K cities, then closes "
+                                                 "as --tsp_local_search_closing says (needs --local_search multi2opt, no kicks, no "
+                                                 "window; 0: off; records gain two_opt_full_sweeps)")),
+    ("--tsp_local_search_closing", dict(type=str, default="full", choices=("full", "none"),
+                                         help="TSP: what follows the neighbour-list sweeps: full (full sweeps until one finds "
+                                              "nothing: a 2-opt optimum) or none (needs --tsp_local_search_candidates K > 0)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -248,6 +258,16 @@ def parse_args(argv=None):
                      "--tsp_local_search_kick_bias heat")
     if args.tsp_local_search_window > 0 and args.task != "tsp":
         parser.error(f"--tsp_local_search_window {args.tsp_local_search_window} refines TSP tours: not with --task {args.task}")
+    K = args.tsp_local_search_candidates
+    if K < 0:
+        parser.error("--tsp_local_search_candidates must be >= 0")
+    if K > 0 and args.task != "tsp":
+        parser.error(f"--tsp_local_search_candidates {K} refines TSP tours: not with --task {args.task}")
+    if K > 0 and args.local_search != "multi2opt":
+        parser.error(f"--tsp_local_search_candidates {K} runs the neighbour-list multi-move 2-opt: pass --local_search multi2opt")
+    if K == 0 and args.tsp_local_search_closing != "full":
+        parser.error(f"--tsp_local_search_closing {args.tsp_local_search_closing} closes the neighbour-list sweeps: pass "
+                     "--tsp_local_search_candidates K > 0")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -366,7 +386,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
            "gt_cost": tsp_gt_cost(ex.points, ex.tour), "solved_cost": float(cost), "all_costs": [float(c) for c in costs],
            "merged_costs": [float(c) for c in info["merged_costs"]], "2opt_iterations": int(info["two_opt_iterations"]),
            "merge_iterations": float(info["merge_iterations"]), "seed": int(seed), "tour": [int(v) for v in tour]}
-    for k in ("or_opt_iterations", "local_search_rounds", "two_opt_moves", "or_opt_moves"):      # --local_search other than 2opt
+    for k in ("or_opt_iterations", "local_search_rounds", "two_opt_moves", "or_opt_moves",      # --local_search other than 2opt
+              "two_opt_full_sweeps"):                                                            # --tsp_local_search_candidates K > 0
         if k in info:
             rec[k] = int(info[k])
     if "local_search_kicks_improved" in info:      # --tsp_local_search_kicks N > 0
@@ -417,7 +438,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 tsp_local_search_kick_size: int = TSP_KICK_SIZE, tsp_local_search_kick_span: int = TSP_KICK_SPAN,
                 tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
                 tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1,
-                two_opt_mode: str = "launches") -> List[dict]:
+                two_opt_mode: str = "launches", tsp_local_search_candidates: int = 0,
+                tsp_local_search_closing: str = "full") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -446,9 +468,15 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                      if tsp_local_search_window > 0 else {}),
                                   **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
                                   **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}),
-                                  **(dict(two_opt_mode="resident") if two_opt_mode == "resident" else {}))
+                                  **(dict(two_opt_mode="resident") if two_opt_mode == "resident" else {}),
+                                  **(dict(local_search_candidates=tsp_local_search_candidates,
+                                          local_search_closing=tsp_local_search_closing == "full")
+                                     if tsp_local_search_candidates > 0 else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
+                if tsp_local_search_candidates > 0:
+                    records[-1].update(tsp_local_search_candidates=tsp_local_search_candidates,
+                                       tsp_local_search_closing=tsp_local_search_closing)
                 if two_opt_mode == "resident":
                     records[-1].update(two_opt_mode="resident")
                 if tsp_local_search_window > 0:
@@ -548,7 +576,9 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_descent=args.tsp_local_search_descent,
                                tsp_local_search_kick_bias=args.tsp_local_search_kick_bias,
                                tsp_local_search_window=args.tsp_local_search_window,
-                               tsp_local_search_passes=args.tsp_local_search_passes, two_opt_mode=args.two_opt_mode)
+                               tsp_local_search_passes=args.tsp_local_search_passes, two_opt_mode=args.two_opt_mode,
+                               tsp_local_search_candidates=args.tsp_local_search_candidates,
+                               tsp_local_search_closing=args.tsp_local_search_closing)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -584,6 +614,9 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["tsp_local_search_kicks"] = args.tsp_local_search_kicks
                 line["tsp_local_search_kick_size"] = args.tsp_local_search_kick_size
                 line["tsp_local_search_kick_span"] = args.tsp_local_search_kick_span
+            if args.tsp_local_search_candidates > 0:
+                line["tsp_local_search_candidates"] = args.tsp_local_search_candidates
+                line["tsp_local_search_closing"] = args.tsp_local_search_closing
             if args.tsp_local_search_descent == "focused":
                 line["tsp_local_search_descent"] = "focused"
             if args.tsp_local_search_kick_bias == "heat":

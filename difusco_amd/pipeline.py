@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import decode
-from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
+from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_tsp_candidates, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
                      check_tsp_kicks, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours, merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
@@ -42,7 +42,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
               local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
               local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1,
-              two_opt_mode: str = "launches"):
+              two_opt_mode: str = "launches", local_search_candidates: int = 0, local_search_closing: bool = True):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -77,7 +77,13 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     ``local_search_passes_kept`` and ``local_search_closing_sweeps``.  ``two_opt_mode``: "launches" (default) or "resident"
     (only with ``local_search="2opt"``, else ``ValueError``): the 2-opt runs with one GPU block for the instance
     (``mode="resident"`` of ``decode.batched_two_opt_torch``), same results with either ``two_opt_method``; the
-    ``parallel_sampling`` tours must fit its limit, there is no fallback."""
+    ``parallel_sampling`` tours must fit its limit, there is no fallback.  ``local_search_candidates`` = K > 0 (only with
+    "multi2opt", no kicks, no window, not "resident", else ``ValueError``; 0, the default, changes nothing): the neighbour-list
+    multi-move 2-opt (``decode.batched_nbr_two_opt_torch``): sweeps over the K listed neighbours of every city, then, with
+    ``local_search_closing`` (default), full sweeps until one finds nothing.  With ``sparse_factor`` > 0 and K <=
+    ``sparse_factor`` - 1 the lists are the first K non-self neighbours of the instance's own ``edge_index``, else the K nearest
+    cities of a k-NN call of their own.  info gains ``local_search_candidates``, ``local_search_closing`` and
+    ``two_opt_full_sweeps`` (of the last round)."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
@@ -85,7 +91,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
-    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias)
+    nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
+    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -216,12 +223,15 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
     kick_span, descent, kick_bias) - selects.  ``seeds`` / ``offsets``: the Philox key and first offset of every tour, read by
     the kicked searches, as ``heat`` / ``edge_index`` (the round's heatmaps and their graphs) are by heat-biased kicks;
     ``kick_stats`` receives their per-tour arrays.  Returns (tours, iterations, the search's own statistics)."""
-    local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias = search
+    local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr = search
     run = lambda stem, **kw: getattr(decode, f"batched_{stem}_{form}")(points, tours, max_iterations=two_opt_iterations, device=dev, **kw)
     ls_stats = {}
     if local_search == "2opt":
         solved, iterations = run("two_opt", method=two_opt_method,                              # pl_tsp_model.py:233-236
                                  **(dict(mode="resident") if two_opt_mode == "resident" else {}))
+    elif local_search == "multi2opt" and nbr[0] > 0:
+        solved, iterations = run("nbr_two_opt", candidates=nbr[0], closing=nbr[1], stats=ls_stats,
+                                 neighbors=_candidate_lists(form, points, edge_index, nbr[0]))
     elif local_search == "multi2opt":
         solved, iterations = run("multi_two_opt", stats=ls_stats)
     elif local_search == "2opt+oropt":
@@ -239,14 +249,31 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
     return solved, iterations, ls_stats
 
 
+def _candidate_lists(form: str, points, edge_index, K: int):
+    """The neighbour lists of the K-candidate 2-opt from the instances' own k-NN graphs (``edge_index`` of the form: one
+    [2, n k] tensor, or one per instance with local node ids) where they hold K other cities per node; else None, and the
+    search builds the lists with a k-NN call of its own."""
+    if edge_index is None:
+        return None
+    eis = [edge_index] if form == "torch" else list(edge_index)
+    sizes = [len(points)] if form == "torch" else [len(p) for p in points]
+    if any(e.shape[1] // n - 1 < K for e, n in zip(eis, sizes)):
+        return None
+    lists = decode.tsp_candidate_lists(eis, sizes, K)
+    return lists[0] if form == "torch" else lists
+
+
 def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: int, P: int, g: int) -> dict:
     """What info gains from the local search of the last round: the statistics of group ``g`` of the call (``solve_tsp``: 0,
     its scalars are ints already) and the per-copy arrays of its copies first .. first + P - 1."""
-    local_search, _, window, passes, kicks, _, _, descent, kick_bias = search
+    local_search, _, window, passes, kicks, _, _, descent, kick_bias, nbr = search
     at = lambda k: int(np.reshape(ls_stats[k], -1)[g])
     cut = lambda k: [int(v) for v in kick_stats[k][first:first + P]]
     if local_search == "2opt":
         return {}
+    if local_search == "multi2opt" and nbr[0] > 0:
+        return dict(two_opt_moves=at("moves"), local_search_candidates=nbr[0], local_search_closing=nbr[1],
+                    two_opt_full_sweeps=at("full_sweeps"))
     if local_search == "multi2opt":
         return dict(two_opt_moves=at("moves"))
     if local_search == "2opt+oropt":
@@ -299,7 +326,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     merge_method: str = "loop", local_search: str = "2opt", local_search_kicks: int = 0,
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
                     local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
-                    local_search_passes: int = 1, two_opt_mode: str = "launches") -> List[tuple]:
+                    local_search_passes: int = 1, two_opt_mode: str = "launches", local_search_candidates: int = 0,
+                    local_search_closing: bool = True) -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -318,7 +346,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     ``local_search_descent``, ``local_search_kick_bias``: as ``solve_tsp``; "heat" passes every instance's own heatmaps of the
     round (the tensors the merge received, on the device) and its own graph.  ``local_search_window``,
     ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets.  ``two_opt_mode``: as ``solve_tsp``,
-    one GPU block per instance, for arrays and sequences of instances alike."""
+    one GPU block per instance, for arrays and sequences of instances alike.  ``local_search_candidates``,
+    ``local_search_closing``: as ``solve_tsp``, per instance, for arrays and sequences alike."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
@@ -327,7 +356,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
-    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias)
+    nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
+    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search)

@@ -699,6 +699,44 @@ int difusco_tsp_multi_two_opt_ragged(int groups, const int32_t* group_n, const i
                                      int32_t* tours, int64_t max_iterations, int select_rounds, void* workspace,
                                      size_t workspace_bytes, int64_t* sweeps_out, int64_t* moves_out, void* stream);
 
+/* Neighbour-list multi-move 2-opt with a closing full descent (additive to ABI 13; not in the reference): the arrays,
+ * conventions and limits of difusco_tsp_multi_two_opt_ragged, and its notation.  New inputs:
+ *   neighbors  DEVICE int32: for every group g [group_n[g], K] entries, the groups concatenated.  An entry of city a is a city
+ *              index local to the group.  An entry outside 0 .. n-1, or equal to a, is a pad and is skipped; no kernel indexes
+ *              memory with it.  Duplicate entries are allowed.  N(a) = the non-pad entries of city a.
+ *   K >= 1, closing in {0, 1}.
+ * Every TOUR runs on its own and keeps its own phase.  A tour starts in the neighbour phase.  One NEIGHBOUR SWEEP of a tour of n
+ * nodes (tour[k] = the city at position k, tour[n] = tour[0]):
+ *   1. Candidates.  For i+2 <= j <= n-1, column j is a candidate of row i (0 .. n-3) iff tour[j] in N(tour[i]) or tour[i] in
+ *      N(tour[j]) or tour[j+1] in N(tour[i+1]) or tour[i+1] in N(tour[j+1]): the pairs whose new head edge (tour[i], tour[j]) or
+ *      new tail edge (tour[i+1], tour[j+1]) joins a city to one of its listed neighbours, in either direction.  Position n is
+ *      position 0: the pair (i, n-1) has the tail edge (tour[i+1], tour[0]).
+ *   2. Row proposals.  Row i evaluates change(i, j) of difusco_tsp_multi_two_opt_ragged, bit for bit, for its candidate columns
+ *      only, keeps the lowest change, ties to the lowest j, and proposes (i, j_i) iff that change is < -1e-6.  Key (change, i),
+ *      range [i, j_i + 1), as there.
+ *   3. Selection and apply: steps 2 and 3 of difusco_tsp_multi_two_opt_ragged, unchanged.
+ *   4. Closing.  A tour whose neighbour sweep has no proposal is done if closing = 0.  With closing = 1 it moves to the full
+ *      phase: from its next sweep on its sweeps are those of difusco_tsp_multi_two_opt_ragged (every column is a candidate),
+ *      until one of them has no proposal; then the tour is done.  The switch is made per tour on the device.
+ *   5. Stop test.  A sweep counts for a group if one of its tours moved, and counts as a full sweep as well if one of the tours
+ *      that moved was in the full phase.  A group stops when all its tours are done or after max_iterations counted sweeps, over
+ *      both phases; with max_iterations = 0 no sweep counts and nothing is applied.
+ * So: with lists that name every other city every column is a candidate, and tours, sweeps and moves equal
+ * difusco_tsp_multi_two_opt_ragged bit for bit; a tour is never longer than its start, every move shortens it by more than 1e-6;
+ * with closing = 1 a tour that stops before the cap has no improving 2-opt move left; a tour's result does not depend on which
+ * other tours or groups share the call, nor on how the threads are scheduled (a row's lowest (change, j) is combined with
+ * atomic minima, whose result does not depend on their order).
+ * sweeps_out, full_sweeps_out, moves_out: HOST int64 [groups]: the counted sweeps, the part of them counted as full sweeps, and
+ * the moves applied over all tours of the group.  DIFUSCO_EINVAL before any GPU work on the conditions of
+ * difusco_tsp_multi_two_opt_ragged, null neighbors, K < 1, closing outside {0, 1} and a short workspace.  Blocks until every
+ * group is done. */
+int difusco_tsp_nbr_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int K, int closing,
+                                                   size_t* bytes);
+int difusco_tsp_nbr_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                   int32_t* tours, const int32_t* neighbors, int K, int closing, int64_t max_iterations,
+                                   int select_rounds, void* workspace, size_t workspace_bytes, int64_t* sweeps_out,
+                                   int64_t* full_sweeps_out, int64_t* moves_out, void* stream);
+
 /* Multi-move local search, 2-opt + Or-opt (additive to ABI 13; not in the reference): the arrays, conventions and limits of
  * difusco_tsp_two_opt_ragged, the notation of the two comments above: the tour is closed (tour[n] == tour[0]), P_k is the point at
  * position k, d_k = |P_k P_k+1|, everything is float64 with every operation rounded on its own, a distance is two products, one
