@@ -145,6 +145,9 @@ def lib():
     L.difusco_tsp_nbr_two_opt_ragged.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
     L.difusco_tsp_multi_local_search_ragged_workspace_bytes.argtypes = [i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_multi_local_search_ragged.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp, vp, vp]
+    L.difusco_tsp_nbr_local_search_ragged_workspace_bytes.argtypes = [i32, vp, vp, i32, i32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_nbr_local_search_ragged.argtypes = [i32, vp, vp, vp, vp, vp, i32, i32, i64, i32, i32, vp, ctypes.c_size_t, vp, vp, vp, vp,
+                                                      vp, vp, vp, vp]
     L.difusco_tsp_iterated_search_ragged_workspace_bytes.argtypes = [i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_iterated_search_ragged.argtypes = [i32, vp, vp, vp, vp, i64, i32, i32, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, vp, vp, vp, ctypes.c_size_t] + [vp] * 11

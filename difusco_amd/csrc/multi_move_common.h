@@ -1,4 +1,5 @@
-// What the multi-move searches share (two_opt_multi.hip, or_opt_multi.hip): the row-best loop of the 2-opt and the selection of
+// What the multi-move searches share (two_opt_multi.hip, two_opt_nbr.hip, or_opt_multi.hip, or_opt_nbr.hip,
+// tsp_window_search.hip; the Or-opt row loop is in or_opt_rows.h): the row-best loop of the 2-opt and the selection of
 // a set of proposals with pairwise disjoint position ranges.  Every function is per translation unit (anonymous namespace), as
 // in two_opt_common.h.
 //
@@ -316,6 +317,22 @@ __device__ __forceinline__ void reverse_winners(int* __restrict__ tour, const in
       tour[x] = tour[y];
       tour[y] = tmp;
     }
+  }
+}
+
+// ---- what the neighbour-list searches share (two_opt_nbr.hip, or_opt_nbr.hip): the 2-opt pairs of a listed pair of cities.
+// The up to two pairs of (position p, listed city c at position q) and their changes.  f(i, j, change) is called for every
+// valid pair: 0 <= i, i + 2 <= j <= n - 1 (hence i <= n - 3).
+template <class F>
+__device__ __forceinline__ void nbr_pairs(const double2* __restrict__ P, const double* __restrict__ D, int n, int p, int q, F f) {
+  {                                                              // head: tour[i] and tour[j] are the two cities
+    const int i = p < q ? p : q, j = p < q ? q : p;
+    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
+  }
+  {                                                              // tail: tour[i+1] and tour[j+1]; position 0 is also position n
+    const int pp = p == 0 ? n : p, qq = q == 0 ? n : q;
+    const int i = (pp < qq ? pp : qq) - 1, j = (pp < qq ? qq : pp) - 1;      // 0 <= i, j <= n - 1
+    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
   }
 }
 

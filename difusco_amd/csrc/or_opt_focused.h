@@ -41,12 +41,12 @@ __device__ __forceinline__ void or_pair_best(double2 q1, double2 q2, double2 q3,
   const double e1 = dist2d(pj.x - q1.x, pj.y - q1.y), e2 = dist2d(pj.x - q2.x, pj.y - q2.y), e3 = dist2d(pj.x - q3.x, pj.y - q3.y);
   const double f1 = dist2d(pj1.x - q1.x, pj1.y - q1.y), f2 = dist2d(pj1.x - q2.x, pj1.y - q2.y),
                f3 = dist2d(pj1.x - q3.x, pj1.y - q3.y);
-  const double rem1 = __dadd_rn(r1, dj), rem2 = __dadd_rn(r2, dj), rem3 = __dadd_rn(r3, dj);
-  const double d0 = __dsub_rn(__dadd_rn(__dadd_rn(c1, e1), f1), rem1);
-  const double d1 = __dsub_rn(__dadd_rn(__dadd_rn(c2, e1), f2), rem2);
-  const double d2 = __dsub_rn(__dadd_rn(__dadd_rn(c2, e2), f1), rem2);
-  const double d3 = __dsub_rn(__dadd_rn(__dadd_rn(c3, e1), f3), rem3);
-  const double d4 = __dsub_rn(__dadd_rn(__dadd_rn(c3, e3), f1), rem3);
+  const double rem1 = or_removed(r1, dj), rem2 = or_removed(r2, dj), rem3 = or_removed(r3, dj);
+  const double d0 = or_delta(c1, e1, f1, rem1);
+  const double d1 = or_delta(c2, e1, f2, rem2);
+  const double d2 = or_delta(c2, e2, f1, rem2);
+  const double d3 = or_delta(c3, e1, f3, rem3);
+  const double d4 = or_delta(c3, e3, f1, rem3);
   const bool left = j < i;
   const bool ok1 = i <= n - 2 && (left || j > i + 1), ok2 = i <= n - 3 && (left || j > i + 2), ok3 = i <= n - 4 && (left || j > i + 3);
   double m = ok1 ? d0 : INFINITY;

@@ -76,22 +76,7 @@ __global__ void nbr_prep_kernel(const double* __restrict__ points, const int* __
   }
 }
 
-// The up to two pairs of (position p, listed city c at position q) and their changes.  f(i, j, change) is called for every
-// valid pair: 0 <= i, i + 2 <= j <= n - 1 (hence i <= n - 3).
-template <class F>
-__device__ __forceinline__ void nbr_pairs(const double2* __restrict__ P, const double* __restrict__ D, int n, int p, int q, F f) {
-  {                                                              // head: tour[i] and tour[j] are the two cities
-    const int i = p < q ? p : q, j = p < q ? q : p;
-    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
-  }
-  {                                                              // tail: tour[i+1] and tour[j+1]; position 0 is also position n
-    const int pp = p == 0 ? n : p, qq = q == 0 ? n : q;
-    const int i = (pp < qq ? pp : qq) - 1, j = (pp < qq ? qq : pp) - 1;      // 0 <= i, j <= n - 1
-    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
-  }
-}
-
-// the walk both row kernels share: thread (p, s) of tour blockIdx.y
+// the walk both row kernels share (nbr_pairs: multi_move_common.h): thread (p, s) of tour blockIdx.y
 template <class F>
 __device__ __forceinline__ void nbr_walk(const int* __restrict__ tours, const int* __restrict__ neighbors,
                                          const NbTour* __restrict__ desc, const double2* __restrict__ tp,

@@ -410,7 +410,7 @@ def batched_two_opt_ragged(points_list, tours_list, max_iterations=1000, device=
     return batch.read_tours(), its
 
 
-LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt")
+LOCAL_SEARCHES = ("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt", "nbr2opt+oropt")
 
 
 def check_local_search(local_search, two_opt_method="exact"):
@@ -531,9 +531,22 @@ TSP_CLOSINGS = ("full", "none")           # --tsp_local_search_closing of the ru
 
 def check_tsp_candidates(local_search, candidates, kicks=0, window=0, two_opt_mode="launches"):
     """``local_search_candidates`` of ``solve_tsp``, ``solve_tsp_batch`` and the runner (0: off): the neighbour-list sweeps are
-    a mode of the multi-move 2-opt alone; the kicked, windowed and resident searches have no neighbour-list form."""
+    a mode of the multi-move 2-opt (``local_search="multi2opt"`` with K > 0) and the search ``local_search="nbr2opt+oropt"``,
+    which needs K >= 1; the kicked, windowed and resident searches have no neighbour-list form.  The neighbour-list 2-opt +
+    Or-opt search has a NAME OF ITS OWN instead of being ``"multi2opt+oropt"`` with K > 0, because that combination is refused,
+    and the host tests of the neighbour-list 2-opt (``check_tsp_candidates``, the runner's parser) pin the refusal."""
     if int(candidates) != candidates or candidates < 0:
         raise ValueError(f"local_search_candidates = {candidates!r}: an integer >= 0")
+    if local_search == "nbr2opt+oropt":
+        # a name of its own: "multi2opt+oropt" with candidates stays refused below, as the host tests of the neighbour-list 2-opt pin
+        if candidates < 1:
+            raise ValueError("local_search='nbr2opt+oropt' runs the neighbour-list 2-opt + Or-opt search: it needs "
+                             "local_search_candidates = K >= 1, not 0")
+        if kicks > 0 or window > 0:
+            raise ValueError(f"local_search='nbr2opt+oropt' combines with neither kicks nor windows")
+        if two_opt_mode == "resident":
+            raise ValueError("local_search='nbr2opt+oropt' does not combine with two_opt_mode='resident'")
+        return int(candidates)
     if candidates > 0:
         if local_search != "multi2opt":
             raise ValueError(f"local_search_candidates = {candidates} runs the neighbour-list multi-move 2-opt: it needs "
@@ -693,6 +706,57 @@ def batched_multi_local_search_ragged(points_list, tours_list, max_iterations=10
     """``batched_multi_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.
     Returns ``(list of int64 numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_multi_local_search_grouped``."""
     return _multi_local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, select_rounds)
+
+
+def _nbr_local_search(form, points, tours, max_iterations, device, max_rounds, select_rounds, candidates, neighbors, closing):
+    """``batched_nbr_local_search_<form>``: the checks and one ``difusco_tsp_nbr_local_search_ragged`` call."""
+    pts, trs = _per_group(form, points, tours)
+    device = _multi_move_checked(f"batched_nbr_local_search_{form}", pts, trs, max_iterations, max_rounds, select_rounds, device)
+    lists, K = _nbr_lists(form, pts, neighbors, candidates, device)
+    closing = int(bool(closing))
+    batch = _RaggedBatch(pts, trs, device)
+    L = _lib.lib()
+    ws, nbytes = _workspace(L.difusco_tsp_nbr_local_search_ragged_workspace_bytes, *batch.sizes, K, closing, device=device)
+    st = batch.group_stats()
+    st["full_sweeps"] = np.zeros(batch.groups, dtype=np.int64)
+    st["full_rounds"] = np.zeros(batch.groups, dtype=np.int32)
+    _lib.check(L.difusco_tsp_nbr_local_search_ragged(*batch.head, _ptr(lists), K, closing, int(max_iterations), int(max_rounds),
+                                                     int(select_rounds), _ptr(ws), nbytes, *(v.ctypes.data for v in st.values()),
+                                                     _stream(device)))
+    return _as_form(form, batch.read_tours(), st)
+
+
+def batched_nbr_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
+                                   candidates=8, neighbors=None, closing=True):
+    """Neighbour-list multi-move 2-opt + Or-opt local search of the tours of ONE instance, the arguments of
+    ``batched_multi_local_search_torch`` plus the lists of ``batched_nbr_two_opt_torch`` (``candidates`` / ``neighbors``): the
+    rounds of ``batched_multi_local_search_torch``, but a sweep of either phase evaluates only the moves one of whose new edges -
+    the head or tail edge of a 2-opt move, one of the two insertion edges of an Or-opt move - joins a city to one of its listed
+    neighbours, O(N K) instead of all pairs.  A tour whose round applied no Or-opt move stops (``closing=False``) or goes on
+    with the full rounds of ``batched_multi_local_search_torch`` until one applies no Or-opt move (``closing=True``: a tour
+    that stops below the caps has no improving 2-opt or Or-opt move left).  The rule: ``difusco_tsp_nbr_local_search_ragged``,
+    include/difusco_hip.h; GPU only.  The caps count over both stages.  Returns ``(tour int64 numpy [B, N+1], stats)``: the
+    five counters of ``batched_multi_local_search_torch`` and ``full_sweeps``, ``full_rounds`` (the maxima over the tours of the
+    sweeps in which a tour moved in, and the rounds it ran in, the full stage), ints."""
+    return _nbr_local_search("torch", points, tour, max_iterations, device, max_rounds, select_rounds, candidates, neighbors, closing)
+
+
+def batched_nbr_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, select_rounds=4,
+                                     candidates=8, neighbors=None, closing=True):
+    """``batched_nbr_local_search_torch`` of G instances at once, the arguments of ``batched_multi_local_search_grouped``;
+    ``neighbors``: int [G, N, K] or None.  Every instance gets what its own ``batched_nbr_local_search_torch`` call returns.
+    Returns ``(tours int64 numpy [G * P, N + 1], stats)``; the entries of ``stats`` are numpy arrays [G]."""
+    return _nbr_local_search("grouped", points, tours, max_iterations, device, max_rounds, select_rounds, candidates, neighbors,
+                             closing)
+
+
+def batched_nbr_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16,
+                                    select_rounds=4, candidates=8, neighbors=None, closing=True):
+    """``batched_nbr_local_search_torch`` of G instances of ANY sizes at once, the arguments of
+    ``batched_multi_local_search_ragged``; ``neighbors``: a list of int [n_g, K] with one K, or None.  Returns ``(list of int64
+    numpy [P_g, n_g + 1], stats)``; ``stats``: as ``batched_nbr_local_search_grouped``."""
+    return _nbr_local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, select_rounds, candidates,
+                             neighbors, closing)
 
 
 TSP_KICK_SIZE, TSP_KICK_SPAN = 16, 30     # the pair of scripts/tsp_iterated_search_table.py (DESIGN 5.2g)

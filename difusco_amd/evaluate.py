@@ -25,7 +25,7 @@ Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``defaul
 {launches,resident}`` (TSP with ``--local_search 2opt``: ``resident`` runs that 2-opt with one GPU block per instance,
 ``mode="resident"`` of ``decode.batched_two_opt_grouped``; the records and the header gain ``two_opt_mode`` and are otherwise
 the same), ``--local_search
-{2opt,2opt+oropt,multi2opt,multi2opt+oropt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
+{2opt,2opt+oropt,multi2opt,multi2opt+oropt,nbr2opt+oropt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
 ``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``; ``multi2opt``,
 ``decode.batched_multi_two_opt_grouped``: every sweep applies all disjoint improving 2-opt moves it selects, ``2opt_iterations``
 counts sweeps and the records gain ``two_opt_moves``; ``multi2opt+oropt``, ``decode.batched_multi_local_search_grouped``: rounds
@@ -56,7 +56,10 @@ window and pass, keyed as the kicks are; the records gain ``kicks_improved``, ``
 copy, and with the header the two settings and the three kick settings), ``--tsp_local_search_candidates K`` /
 ``--tsp_local_search_closing {full,none}`` (K > 0 only with ``--local_search multi2opt``: the multi-move 2-opt on neighbour
 lists of K cities, ``decode.batched_nbr_two_opt_grouped``, closed by full sweeps unless ``none``; the records gain
-``two_opt_full_sweeps`` and with the header the two settings; without K every record is what it was), ``--merge_method {loop,batched}``
+``two_opt_full_sweeps`` and with the header the two settings; without K every record is what it was; ``--local_search
+nbr2opt+oropt`` needs K >= 1: the 2-opt + Or-opt search on these lists, ``decode.batched_nbr_local_search_grouped`` - a name of its
+own because ``multi2opt+oropt`` with K > 0 stays refused -, the records of ``multi2opt+oropt`` plus, after every other field,
+``local_search_full_sweeps`` and ``local_search_full_rounds``), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -134,13 +137,15 @@ EXTENSION_ARGS = [
                             help="TSP: how the single-move 2-opt runs: launches (a launch sequence per move) or resident (one "
                                  "GPU block per instance keeps the tours in LDS, no launch or host read per move; same "
                                  "records; needs --local_search 2opt and P * (N + 1) within the library's limit)")),
-    ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt"),
+    ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt", "nbr2opt+oropt"),
                              help="tour refinement: 2opt (the reference's), 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
                                   "records gain or_opt_iterations and local_search_rounds) or multi2opt (every sweep applies all "
                                   "disjoint improving 2-opt moves it selects; 2opt_iterations counts sweeps, records gain "
                                   "two_opt_moves) or multi2opt+oropt (rounds of multi-move 2-opt and multi-move Or-opt "
                                   "sweeps; 2opt_iterations and or_opt_iterations count sweeps, records gain two_opt_moves, "
-                                  "or_opt_moves and local_search_rounds)")),
+                                  "or_opt_moves and local_search_rounds) or nbr2opt+oropt (multi2opt+oropt on neighbour lists, "
+                                  "needs --tsp_local_search_candidates K >= 1; records gain local_search_full_sweeps and "
+                                  "local_search_full_rounds as well)")),
     ("--tsp_local_search_kicks", dict(type=int, default=0,
                                        help="TSP: iterate the multi-move local search with this many seeded segment kicks "
                                             "(needs --local_search multi2opt+oropt; 0: one descent)")),
@@ -263,8 +268,13 @@ def parse_args(argv=None):
         parser.error("--tsp_local_search_candidates must be >= 0")
     if K > 0 and args.task != "tsp":
         parser.error(f"--tsp_local_search_candidates {K} refines TSP tours: not with --task {args.task}")
-    if K > 0 and args.local_search != "multi2opt":
-        parser.error(f"--tsp_local_search_candidates {K} runs the neighbour-list multi-move 2-opt: pass --local_search multi2opt")
+    if K > 0 and args.local_search not in ("multi2opt", "nbr2opt+oropt"):
+        parser.error(f"--tsp_local_search_candidates {K} runs the neighbour-list multi-move 2-opt: pass --local_search multi2opt "
+                     "(or nbr2opt+oropt, the neighbour-list 2-opt + Or-opt search)")
+    if args.local_search == "nbr2opt+oropt" and args.task != "tsp":
+        parser.error(f"--local_search nbr2opt+oropt refines TSP tours: not with --task {args.task}")
+    if args.local_search == "nbr2opt+oropt" and K == 0:
+        parser.error("--local_search nbr2opt+oropt runs on neighbour lists: pass --tsp_local_search_candidates K >= 1")
     if K == 0 and args.tsp_local_search_closing != "full":
         parser.error(f"--tsp_local_search_closing {args.tsp_local_search_closing} closes the neighbour-list sweeps: pass "
                      "--tsp_local_search_candidates K > 0")
@@ -396,6 +406,9 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
         rec["closing_sweeps"] = [int(v) for v in info["local_search_closing_sweeps"]]
     if "local_search_passes_kept" in info:         # --tsp_local_search_window W > 0
         rec["passes_kept"] = [int(v) for v in info["local_search_passes_kept"]]
+    for k in ("local_search_full_sweeps", "local_search_full_rounds"):      # --local_search nbr2opt+oropt
+        if k in info:
+            rec[k] = int(info[k])
     return rec
 
 

@@ -83,7 +83,12 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     ``local_search_closing`` (default), full sweeps until one finds nothing.  With ``sparse_factor`` > 0 and K <=
     ``sparse_factor`` - 1 the lists are the first K non-self neighbours of the instance's own ``edge_index``, else the K nearest
     cities of a k-NN call of their own.  info gains ``local_search_candidates``, ``local_search_closing`` and
-    ``two_opt_full_sweeps`` (of the last round)."""
+    ``two_opt_full_sweeps`` (of the last round).  ``local_search="nbr2opt+oropt"`` (needs ``local_search_candidates`` = K >= 1,
+    K = 0 is a ``ValueError``; accepts ``local_search_closing``; no kicks, no window, not "resident"): the 2-opt + Or-opt search
+    of "multi2opt+oropt" on the same lists (``decode.batched_nbr_local_search_torch``), closed by full rounds with
+    ``local_search_closing``.  It is a name of its own, not "multi2opt+oropt" with K > 0: that combination stays refused, as the
+    host tests of the neighbour-list 2-opt pin.  info holds what "multi2opt+oropt" gives, ``local_search_candidates``,
+    ``local_search_closing``, ``local_search_full_sweeps`` and ``local_search_full_rounds``."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
@@ -236,6 +241,10 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
         solved, iterations = run("multi_two_opt", stats=ls_stats)
     elif local_search == "2opt+oropt":
         solved, iterations = run("local_search", stats=ls_stats)
+    elif local_search == "nbr2opt+oropt":
+        solved, ls_stats = run("nbr_local_search", candidates=nbr[0], closing=nbr[1],
+                               neighbors=_candidate_lists(form, points, edge_index, nbr[0]))
+        iterations = ls_stats["two_opt_sweeps"]
     else:
         kicked = dict(kicks=kicks, kick_size=kick_size, span=kick_span, seeds=seeds, offsets=offsets, stats=kick_stats)
         if window > 0:
@@ -280,7 +289,10 @@ def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: i
         return dict(or_opt_iterations=at("or_opt_iterations"), local_search_rounds=at("rounds"))
     info = dict(two_opt_moves=at("two_opt_moves"), or_opt_iterations=at("or_opt_sweeps"), or_opt_moves=at("or_opt_moves"),
                 local_search_rounds=at("rounds"))
-    if window > 0:
+    if local_search == "nbr2opt+oropt":
+        info.update(local_search_candidates=nbr[0], local_search_closing=nbr[1], local_search_full_sweeps=at("full_sweeps"),
+                    local_search_full_rounds=at("full_rounds"))
+    elif window > 0:
         info.update(local_search_window=window, local_search_passes=passes, local_search_kicks_improved=cut("kicks_improved"),
                     local_search_passes_kept=cut("passes_kept"), local_search_closing_sweeps=cut("closing_sweeps"))
     elif kicks > 0:

@@ -774,6 +774,53 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
                                           size_t workspace_bytes, int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out,
                                           int32_t* rounds_out, int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, void* stream);
 
+/* Neighbour-list multi-move local search, 2-opt + Or-opt, with a closing full descent (additive to ABI 13; not in the
+ * reference): the arrays, conventions, limits and notation of difusco_tsp_multi_local_search_ragged, plus neighbors (DEVICE int32,
+ * [group_n[g], K] per group, the groups concatenated), K >= 1 and closing in {0, 1} with exactly the conventions of
+ * difusco_tsp_nbr_two_opt_ragged: city ids local to the group; an entry outside 0 .. n-1, or equal to its city, is a pad, is
+ * skipped and never indexes memory; duplicates are allowed; N(a) = the non-pad entries of city a.
+ * Every TOUR runs on its own and keeps its own stage (neighbour or full), phase, round and counters on the device.
+ * NEIGHBOUR STAGE (every tour starts in it): the rounds of difusco_tsp_multi_local_search_ragged with candidate sweeps:
+ *   2-opt phase   the neighbour sweep of difusco_tsp_nbr_two_opt_ragged, its steps 1-3 unchanged, until a sweep has no proposal;
+ *   Or-opt phase  sweeps of three steps, until a sweep has no proposal:
+ *     1. Candidates.  For the candidate (v, i, j) of difusco_tsp_local_search_ragged, (L, reversed) = variant v, let a and b be the
+ *        cities at positions i+1 and i+L, swapped when reversed: the move creates the insertion edges (tour[j], a) and
+ *        (b, tour[j+1]); position n is position 0.  Column j is a candidate of (v, i) iff tour[j] in N(a) or a in N(tour[j]) or
+ *        tour[j+1] in N(b) or b in N(tour[j+1]): one of the two insertion edges joins a city to one of its listed neighbours, in
+ *        either direction.  The gap edge (P_i, P_i+L+1) does not depend on j and defines no candidates.
+ *     2. Row proposals.  Row i = 0 .. n-2 keeps the lowest delta over its candidates only - the delta of
+ *        difusco_tsp_local_search_ragged, bit for bit -, ties to the lowest v and then the lowest j, and proposes iff that delta is
+ *        < -1e-6.  Key (delta, i) and range as in difusco_tsp_multi_local_search_ragged.
+ *     3. Selection and apply: steps 2 and 3 of difusco_tsp_multi_local_search_ragged's Or-opt phase, verbatim.
+ * CLOSING.  A neighbour-stage round whose Or-opt phase applied nothing ends the neighbour stage.  With closing = 0 the tour is
+ * done.  With closing = 1 the tour moves to the FULL STAGE: it goes on with the two phases of
+ * difusco_tsp_multi_local_search_ragged (every column is a candidate), and rounds of these, until the Or-opt phase of one of
+ * them applies nothing.  The switch is made per tour on the device.  The first pair of full phases takes the place of the stop
+ * of the round that ended the neighbour stage and runs under that round's number; every later full round starts a new round.
+ * CAPS.  max_iterations and max_rounds are per tour and count over both stages together: max_iterations the sweeps in which the
+ * tour moved (with 0 nothing is applied), max_rounds the rounds started.  A tour that hits a cap is done in whatever stage it is
+ * in; it does not enter the full stage because of a cap: a tour whose max_rounds-th round applied an Or-opt move is done.
+ * So: with lists that name every other city every column is a candidate, and the tours and the five counters shared with
+ * difusco_tsp_multi_local_search_ragged equal that entry's bit for bit, with either closing - the full phases then find
+ * nothing, full_sweeps is 0 and, for a tour that stops below both caps, full_rounds is 1 -; every move shortens its tour by more than 1e-6; with closing = 1 a tour
+ * that stops below both caps has no improving 2-opt move and no improving Or-opt move left; a tour's result depends neither on
+ * what shares the call nor on how the threads are scheduled (a row's lowest (delta, v, j) is combined with atomic minima, whose
+ * result does not depend on their order).
+ * Outputs, HOST arrays [groups]: the five of difusco_tsp_multi_local_search_ragged with its max / sum conventions, over both
+ * stages; full_sweeps_out (int64): the maximum over the group's tours of the sweeps in which the tour moved while in the full
+ * stage; full_rounds_out (int32): the maximum over the tours of the rounds run in the full stage (0: no tour reached it).
+ * DIFUSCO_EINVAL before any GPU work on the conditions of difusco_tsp_multi_local_search_ragged and of
+ * difusco_tsp_nbr_two_opt_ragged: null neighbors, K < 1, closing outside {0, 1}, max_rounds < 1, select_rounds < 1, a null
+ * output array, a short workspace.  Blocks until every group is done. */
+int difusco_tsp_nbr_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int K,
+                                                        int closing, size_t* bytes);
+int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                        int32_t* tours, const int32_t* neighbors, int K, int closing, int64_t max_iterations,
+                                        int max_rounds, int select_rounds, void* workspace, size_t workspace_bytes,
+                                        int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out,
+                                        int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int64_t* full_sweeps_out,
+                                        int32_t* full_rounds_out, void* stream);
+
 /* Iterated multi-move local search: seeded segment kicks between descents (additive to ABI 13; not in the reference): the
  * arrays, conventions and limits of difusco_tsp_multi_local_search_ragged, plus kicks >= 0, kick_size in 1 .. 64, span >= 1 and
  * tour_seeds / tour_offsets: DEVICE uint64 [T], T = the tours of the call in tour order (group after group): the Philox key and
