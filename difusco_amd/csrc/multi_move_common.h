@@ -1,7 +1,8 @@
-// What the multi-move searches share (two_opt_multi.hip, two_opt_nbr.hip, or_opt_multi.hip, or_opt_nbr.hip,
-// tsp_window_search.hip; the Or-opt row loop is in or_opt_rows.h): the row-best loop of the 2-opt and the selection of
-// a set of proposals with pairwise disjoint position ranges.  Every function is per translation unit (anonymous namespace), as
-// in two_opt_common.h.
+// What the multi-move searches share (two_opt_multi.hip, or_opt_multi.hip, or_opt_nbr.hip, tsp_window_search.hip; the Or-opt row
+// loop is in or_opt_rows.h, the neighbour stage in nbr_rows.h): the row-best loop of the 2-opt, the selection of a set of
+// proposals with pairwise disjoint position ranges and, at the end, the host side the group-wise entries share - the tour
+// descriptor, the walk over the groups that fills it and the launch loop with its poll.  Every function is per translation unit
+// (anonymous namespace), as in two_opt_common.h.
 //
 // Selection never does work proportional to the lengths of the ranges.  A proposal is a row i with a key (ordered bits of its
 // value rowv[i], i) and a half-open position range [a, b), 0 <= a < b <= n.  Per round:
@@ -22,6 +23,8 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstdint>
+#include <vector>
 
 #include "two_opt_common.h"
 
@@ -320,22 +323,6 @@ __device__ __forceinline__ void reverse_winners(int* __restrict__ tour, const in
   }
 }
 
-// ---- what the neighbour-list searches share (two_opt_nbr.hip, or_opt_nbr.hip): the 2-opt pairs of a listed pair of cities.
-// The up to two pairs of (position p, listed city c at position q) and their changes.  f(i, j, change) is called for every
-// valid pair: 0 <= i, i + 2 <= j <= n - 1 (hence i <= n - 3).
-template <class F>
-__device__ __forceinline__ void nbr_pairs(const double2* __restrict__ P, const double* __restrict__ D, int n, int p, int q, F f) {
-  {                                                              // head: tour[i] and tour[j] are the two cities
-    const int i = p < q ? p : q, j = p < q ? q : p;
-    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
-  }
-  {                                                              // tail: tour[i+1] and tour[j+1]; position 0 is also position n
-    const int pp = p == 0 ? n : p, qq = q == 0 ? n : q;
-    const int i = (pp < qq ? pp : qq) - 1, j = (pp < qq ? qq : pp) - 1;      // 0 <= i, j <= n - 1
-    if (j >= i + 2) f(i, j, change64(P[i], P[i + 1], P[j], P[j + 1], D[i], D[j]));
-  }
-}
-
 // ---- what the searches of or_opt_multi.hip and tsp_window_search.hip share beyond the selection: the Or-opt variants, the range
 // of a proposal of either phase, the Or-opt apply, the fixed-association tour length and the segment swaps of a kick
 
@@ -421,10 +408,88 @@ __device__ __forceinline__ void kick_swaps(int* __restrict__ tour, const int* __
   }
 }
 
+// ---- the host side the group-wise entries share (two_opt_multi.hip, or_opt_multi.hip, or_opt_nbr.hip)
+
 int table_levels(int n) {                          // floor(log2(n + 1)) + 1
   int l = 0;
   while ((2LL << l) <= (long long)n + 1) ++l;
   return l + 1;
+}
+
+struct TourDesc {          // a tour of a call; offsets in elements of the array they index
+  int n, nblk_two, nblk_or, group;   // row tiles of a full 2-opt sweep (rows 0 .. n - 3) and of a full Or-opt sweep (0 .. n - 2)
+  long long points;        // the group's first coordinate in `points` (doubles)
+  long long nbr;           // the group's first entry in `neighbors` (n K per group; 0 without lists)
+  long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
+  long long cols;          //                       in dlen, rowv, rowj, live, winners, pos and rowkey (n per tour)
+  long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
+};
+
+struct GroupTotals {       // of a call: the tours, the largest group and its row tiles, the elements the sections hold
+  int tours, nmax, nblk_two, nblk_or;
+  size_t closed, cols, cells, points, nbr;
+};
+
+// Checks the group arrays of a _ragged entry and, with `lists`, K, closing and the launch limit of the n K list entries of a
+// group; then walks the groups: `tot` receives the totals, `tab` (optional) the descriptor of every tour.
+int walk_groups(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, bool lists, int K, int closing,
+                GroupTotals* tot, std::vector<TourDesc>* tab) {
+  *tot = GroupTotals{};
+  const int rc = check_groups(who, groups, group_n, group_tours, &tot->tours);
+  if (rc != DIFUSCO_OK) return rc;
+  if (lists && K < 1) return set_error(DIFUSCO_EINVAL, "%s: K = %d, needs at least 1", who, K);
+  if (lists && closing != 0 && closing != 1) return set_error(DIFUSCO_EINVAL, "%s: closing = %d, needs 0 or 1", who, closing);
+  for (int g = 0; g < groups; ++g) {
+    const int n = group_n[g];
+    const int nblk_two = (n - 2 + TI - 1) / TI, nblk_or = (n - 1 + TI - 1) / TI;
+    if (lists && (long long)n * K > (long long)INT32_MAX * 256)
+      return set_error(DIFUSCO_EINVAL, "%s: group %d has n K = %lld list entries, too many for one launch", who, g, (long long)n * K);
+    if (n > tot->nmax) tot->nmax = n, tot->nblk_two = nblk_two, tot->nblk_or = nblk_or;
+    for (int p = 0; p < group_tours[g]; ++p) {
+      if (tab)
+        tab->push_back(TourDesc{n, nblk_two, nblk_or, g, (long long)tot->points, (long long)tot->nbr, (long long)tot->closed,
+                                (long long)tot->cols, (long long)tot->cells});
+      tot->closed += (size_t)n + 1;
+      tot->cols += (size_t)n;
+      tot->cells += (size_t)table_levels(n) * ((size_t)n + 1);
+    }
+    tot->points += 2 * (size_t)n;
+    if (lists) tot->nbr += (size_t)n * (size_t)K;
+  }
+  return DIFUSCO_OK;
+}
+
+struct Sections {          // hands out the sections of a workspace, each rounded up to 256 bytes; an absent one is empty
+  size_t off = 0;
+  size_t take(size_t bytes, bool present = true) {
+    const size_t at = off;
+    if (present) off += up256(bytes);
+    return at;
+  }
+};
+
+struct Polled {            // of poll_launches: the HIP status, the host synchronisations
+  hipError_t status;
+  int syncs;
+};
+
+// The launch loop of a search whose device state counts its stopped groups in the int at `stopped`: calls enqueue() - one launch
+// sequence - up to `limit` times; every `poll`-th time, and at the last, copies the word back, synchronises and ends if every
+// group has stopped.
+template <class Enqueue>
+Polled poll_launches(long long limit, int poll, int groups, const int* stopped, hipStream_t s, Enqueue enqueue) {
+  Polled r{hipSuccess, 0};
+  int done = 0;
+  for (long long it = 0; it < limit; ++it) {
+    enqueue();
+    if ((it + 1) % poll == 0 || it + 1 == limit) {
+      r.status = hipMemcpyAsync(&done, stopped, sizeof(int), hipMemcpyDeviceToHost, s);
+      if (r.status == hipSuccess) r.status = hipStreamSynchronize(s);
+      r.syncs += 1;
+      if (r.status != hipSuccess || done >= groups) break;
+    }
+  }
+  return r;
 }
 
 }  // namespace

@@ -30,7 +30,9 @@
 // tsp_window_search.hip shares with this file: PhaseRange, or_opt_winners, tour_length).
 //
 // The host side of all four entries is at the end of this file, once: mls_layout describes the workspace - the sections of the
-// descent and, as the entry needs them, the iterated state, the focus state and the heat tables - and builds the host tables,
+// descent and, as the entry needs them, the iterated state, the focus state and the heat tables - and builds the host tables
+// (the walk over the groups and the launch loop with its poll are multi_move_common.h's, shared with two_opt_multi.hip and
+// or_opt_nbr.hip),
 // MlPtrs holds the sections as typed pointers, and mls_run(MlCall) checks the arguments, sets the state up, enqueues launch
 // sequences under their bound, polls, reads the state back and reduces it to the outputs.  The entries fill an MlCall: its mode
 // (one descent, iterated, iterated with focused descents), whether the kicks are drawn by heat, the arguments and the outputs.
@@ -51,12 +53,9 @@ namespace {
 
 enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2, kKeep = 3 };   // kKeep: the iterated search only
 
-struct MlTour {            // offsets in elements of the array they index
+struct MlTour {            // TourDesc (multi_move_common.h) without the lists: the kernels here keep the record they were built on
   int n, nblk_two, nblk_or, group;
-  long long points;        // the group's first coordinate in `points` (doubles)
-  long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
-  long long cols;          //                       in dlen, rowv, rowj, live and winners (n per tour)
-  long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
+  long long points, closed, cols, table;
 };
 
 struct MlTourState {       // device-resident loop state of a tour, zero at the start of a call
@@ -315,7 +314,8 @@ struct MlLayout {          // byte offsets; the optional parts follow the descen
   size_t smark, tmark, arows, acols, foc, full;  // kFocusPart
   size_t W, q, htab, hgrp, bad;                  // kHeatPart
   size_t total;
-  int tours, nmax, nblk_max, emax;               // emax: the most edges of a group
+  GroupTotals tot;
+  int emax;                                      // the most edges of a group
 };
 
 struct MlTables {          // the host tables of a call
@@ -329,72 +329,60 @@ struct MlTables {          // the host tables of a call
 // (optional) receives the tables
 int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts,
                const int32_t* group_edges, MlLayout* L, MlTables* tabs) {
-  int T = 0;
-  const int rc = check_groups(who, groups, group_n, group_tours, &T);
+  *L = MlLayout{};
+  std::vector<TourDesc> tab;
+  const int rc = walk_groups(who, groups, group_n, group_tours, false, 0, 0, &L->tot, tabs ? &tab : nullptr);
   if (rc != DIFUSCO_OK) return rc;
+  for (const TourDesc& d : tab) tabs->tours.push_back(MlTour{d.n, d.nblk_two, d.nblk_or, d.group, d.points, d.closed, d.cols, d.table});
   const bool heat = parts & kHeatPart;
   if (heat && !group_edges) return set_error(DIFUSCO_EINVAL, "%s: group_edges is null", who);
   for (int g = 0; heat && g < groups; ++g)
     if (group_edges[g] < 0) return set_error(DIFUSCO_EINVAL, "%s: group %d has %d edges", who, g, (int)group_edges[g]);
-  size_t points = 0, closed = 0, cols = 0, cells = 0, rows = 0, edges = 0, heats = 0;
-  *L = MlLayout{};
+  size_t rows = 0, edges = 0, heats = 0;         // the group table and the heat bookkeeping: a walk of its own
   for (int g = 0; g < groups; ++g) {
     const int n = group_n[g], E = heat ? group_edges[g] : 0;
-    const int nblk_two = (n - 2 + TI - 1) / TI, nblk_or = (n - 1 + TI - 1) / TI;   // rows 0 .. n - 3 and 0 .. n - 2
-    L->nmax = n > L->nmax ? n : L->nmax;
-    L->nblk_max = nblk_or > L->nblk_max ? nblk_or : L->nblk_max;
     L->emax = E > L->emax ? E : L->emax;
     if (tabs) tabs->groups.push_back(MlGroup{group_tours[g], 0});
     if (tabs && heat) tabs->heat_groups.push_back(MlHeatGroup{n, E, (long long)rows, (long long)edges});
     for (int p = 0; p < group_tours[g]; ++p) {
-      if (tabs)
-        tabs->tours.push_back(MlTour{n, nblk_two, nblk_or, g, (long long)points, (long long)closed, (long long)cols, (long long)cells});
       if (tabs && heat) tabs->heat_tours.push_back(MlHeatTour{(long long)rows, (long long)edges, (long long)heats, n, E});
-      closed += (size_t)n + 1;
-      cols += (size_t)n;
-      cells += (size_t)table_levels(n) * ((size_t)n + 1);
       heats += (size_t)E;
     }
-    points += 2 * (size_t)n;
     rows += (size_t)n + 1;
     edges += (size_t)E;
   }
-  L->tours = (int)T;
-  size_t off = 0;
-  auto take = [&off](bool present, size_t bytes) {
-    const size_t at = off;
-    if (present) off += up256(bytes);
-    return at;
-  };
-  L->desc = take(true, sizeof(MlTour) * T);
-  L->tp = take(true, sizeof(double2) * closed);
-  L->dlen = take(true, sizeof(double) * cols);
-  L->rowv = take(true, sizeof(double) * cols);
-  L->rowj = take(true, sizeof(int) * cols);
-  L->live = take(true, sizeof(int) * cols);
-  L->winners = take(true, sizeof(int) * cols);
-  L->tabv = take(true, sizeof(unsigned long long) * cells);
-  L->tabi = take(true, sizeof(int) * cells);
-  L->marks = take(true, sizeof(int2) * closed);
-  L->cum = take(true, sizeof(int2) * closed);
-  L->grp = take(true, sizeof(MlGroup) * groups);
-  L->ts = take(true, sizeof(MlTourState) * T);
-  L->st = take(true, sizeof(MlState));
+  const GroupTotals& t = L->tot;
+  const size_t T = t.tours;
+  Sections s;
+  L->desc = s.take(sizeof(MlTour) * T);
+  L->tp = s.take(sizeof(double2) * t.closed);
+  L->dlen = s.take(sizeof(double) * t.cols);
+  L->rowv = s.take(sizeof(double) * t.cols);
+  L->rowj = s.take(sizeof(int) * t.cols);
+  L->live = s.take(sizeof(int) * t.cols);
+  L->winners = s.take(sizeof(int) * t.cols);
+  L->tabv = s.take(sizeof(unsigned long long) * t.cells);
+  L->tabi = s.take(sizeof(int) * t.cells);
+  L->marks = s.take(sizeof(int2) * t.closed);
+  L->cum = s.take(sizeof(int2) * t.closed);
+  L->grp = s.take(sizeof(MlGroup) * groups);
+  L->ts = s.take(sizeof(MlTourState) * T);
+  L->st = s.take(sizeof(MlState));
   const bool iter = parts & kIterPart, focus = parts & kFocusPart;
-  L->inc = take(iter, sizeof(int) * closed);
-  L->iters = take(iter, sizeof(MlIter) * T);
-  L->smark = take(focus, sizeof(int) * cols);
-  L->tmark = take(focus, sizeof(int) * cols);
-  L->arows = take(focus, sizeof(int) * cols);
-  L->acols = take(focus, sizeof(int) * cols);
-  L->foc = take(focus, sizeof(MlFocus) * T);
-  L->full = take(focus, sizeof(MlTourState) * T);
-  L->W = take(heat, sizeof(unsigned long long) * closed);
-  L->q = take(heat, sizeof(unsigned short) * heats);
-  L->htab = take(heat, sizeof(MlHeatTour) * T);
-  L->hgrp = take(heat, sizeof(MlHeatGroup) * groups);
-  L->bad = take(heat, sizeof(int));
-  L->total = off;
+  L->inc = s.take(sizeof(int) * t.closed, iter);
+  L->iters = s.take(sizeof(MlIter) * T, iter);
+  L->smark = s.take(sizeof(int) * t.cols, focus);
+  L->tmark = s.take(sizeof(int) * t.cols, focus);
+  L->arows = s.take(sizeof(int) * t.cols, focus);
+  L->acols = s.take(sizeof(int) * t.cols, focus);
+  L->foc = s.take(sizeof(MlFocus) * T, focus);
+  L->full = s.take(sizeof(MlTourState) * T, focus);
+  L->W = s.take(sizeof(unsigned long long) * t.closed, heat);
+  L->q = s.take(sizeof(unsigned short) * heats, heat);
+  L->htab = s.take(sizeof(MlHeatTour) * T, heat);
+  L->hgrp = s.take(sizeof(MlHeatGroup) * groups, heat);
+  L->bad = s.take(sizeof(int), heat);
+  L->total = s.off;
   return DIFUSCO_OK;
 }
 
@@ -532,7 +520,7 @@ int mls_run(const MlCall& c) {
   const MlPtrs p(c.workspace, lay);
   const HeatArgs<true> hx{c.row_ptr, c.col, p.q, p.htab, p.W};
   hipStream_t s = (hipStream_t)c.stream;
-  const int T = lay.tours;
+  const int T = lay.tot.tours;
   std::vector<MlTourState> states(T);                            // zero; with no descent every tour starts at its keep step
   for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
   int bad = 0;
@@ -556,7 +544,7 @@ int mls_run(const MlCall& c) {
       er = hipMemcpyAsync(p.hgrp, tabs.heat_groups.data(), sizeof(MlHeatGroup) * groups, hipMemcpyHostToDevice, s);
     if (er == hipSuccess) er = hipMemsetAsync(p.bad, 0, sizeof(int), s);
     if (er == hipSuccess) {
-      const long long longest = (long long)lay.nmax + 1 > lay.emax ? (long long)lay.nmax + 1 : lay.emax;
+      const long long longest = (long long)lay.tot.nmax + 1 > lay.emax ? (long long)lay.tot.nmax + 1 : lay.emax;
       hipLaunchKernelGGL(heat_graph_check_kernel, dim3((unsigned)((longest + 255) / 256), groups), dim3(256), 0, s, c.row_ptr, c.col,
                          p.hgrp, p.bad);
       er = hipMemcpyAsync(&bad, p.bad, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -578,13 +566,11 @@ int mls_run(const MlCall& c) {
   const long long per = no_descent ? 1 : (c.max_iterations > INT64_MAX - ends ? INT64_MAX : c.max_iterations + ends);
   const long long descents = plain ? 1 : (long long)c.kicks + (focused ? 2 : 1);
   const long long limit = per > INT64_MAX / descents ? INT64_MAX : per * descents;
-  MlState host{0, 0};
-  const int poll = plain ? 4 : 8;
-  const int split = lay.nmax;                                    // blocks of the row part: the list holds at most n - 1 rows
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T), focus_grid(split + lay.nblk_max, T);
+  const int split = lay.tot.nmax;                                // blocks of the row part: the list holds at most n - 1 rows
+  const dim3 prep_grid((lay.tot.nmax + 1 + 255) / 256, T), best_grid(lay.tot.nblk_or, T), focus_grid(split + lay.tot.nblk_or, T);
   const long long cap = (long long)c.max_iterations;
   const auto select_kernel = plain ? mls_select_kernel : mls_select_iterated_kernel;
-  for (long long it = 0; it < limit; ++it) {
+  const Polled polled = poll_launches(limit, plain ? 4 : 8, groups, &p.st->done, s, [&] {
     if (!no_descent) {
       hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, c.points, c.tours, p.desc, p.tp, p.dlen, p.ts);
       // a focused tour reads kDone in `full`: the full sweep skips it, the focused one takes it
@@ -603,14 +589,9 @@ int mls_run(const MlCall& c) {
     }
     if (!plain && c.heat) mls_launch_keep_kick<true>(c, p, T, no_descent, hx);
     if (!plain && !c.heat) mls_launch_keep_kick<false>(c, p, T, no_descent, HeatArgs<false>{});
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, p.st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (!plain) ++g_host_syncs;
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
+  });
+  if (!plain) g_host_syncs += polled.syncs;
+  if (polled.status != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(polled.status));
   std::vector<MlIter> its(plain ? 0 : T);
   std::vector<MlFocus> focs(focused ? T : 0);
   er = hipMemcpyAsync(states.data(), p.ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);

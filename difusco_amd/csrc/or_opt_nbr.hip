@@ -1,24 +1,17 @@
 // Neighbour-list multi-move 2-opt + Or-opt search with a closing full descent (difusco_tsp_nbr_local_search_ragged): the rounds
 // of or_opt_multi.hip, but in the NEIGHBOUR STAGE a row of either phase evaluates only its candidate columns - the 2-opt pairs of
-// two_opt_nbr.hip, and the Or-opt candidates (v, i, j) one of whose two insertion edges (tour[j], a), (b, tour[j+1]) joins a city
-// to one of its listed neighbours, in either direction.  A tour whose neighbour-stage round applied no Or-opt move either stops
+// two_opt_multi.hip's neighbour sweeps, and the Or-opt candidates (v, i, j) one of whose two insertion edges (tour[j], a),
+// (b, tour[j+1]) joins a city to one of its listed neighbours, in either direction.  A tour whose neighbour-stage round applied no Or-opt move either stops
 // (closing = 0) or goes on in the FULL STAGE (closing = 1) with the rounds of or_opt_multi.hip until one of them applies no
 // Or-opt move.  The rule is stated in include/difusco_hip.h and restated in numpy in tests/nbr_local_search_emulation.py; a 2-opt
 // change is change64's (two_opt_common.h) and an Or-opt delta is or_delta's (or_opt_rows.h), bit for bit.
 //
 // One sweep is four launches without closing and six with it; every tour carries a stage word and a phase word that are written
 // by the selection kernel only, so within a sweep every kernel reads the same stage and phase:
-//   nls_prep_kernel         tp / dlen of every running tour; in the neighbour stage also pos[city] = its position, and the rows
-//                           are reset: rowkey = no key, rowj = -1;
-//   nls_row_value_kernel    neighbour stage only.  One thread per (position p, list slot s) of a tour: x = tour[p], y = its s-th
-//                           listed city, q = pos[y].  2-opt phase: nbr_pairs (multi_move_common.h), the walk of two_opt_nbr.hip.
-//                           Or-opt phase: or_nbr_candidates - each of the two cities takes the role of a segment end while the
-//                           other is the anchor, up to 20 candidates per thread, the bounds tested before any point is read.  A
-//                           value below the threshold does a 64-bit atomic min of its ordered bits on rowkey[i]; the others are
-//                           dropped at once;
-//   nls_row_col_kernel      the same walk again: a candidate whose value equals rowkey[i] writes rowv[i] (every such thread writes
-//                           the same bits) and does a 32-bit unsigned atomic min of its code - j, Or-opt: v n + j - on rowj[i].
-//                           The row ends with its lowest (value, code) whatever the order of the threads;
+//   nls_prep_kernel         tp / dlen of every running tour; in the neighbour stage also the reset of the rows (nbr_reset_row);
+//   nls_row_value_kernel    neighbour stage only: nbr_row_value (nbr_rows.h, shared with two_opt_multi.hip) - the walk of the
+//                           lists with the 2-opt pairs or, in the Or-opt phase, the Or-opt candidates: the lowest value of a row;
+//   nls_row_col_kernel      neighbour stage only: nbr_row_col, the lowest code - j, Or-opt: v n + j - of that value;
 //   nls_full_two_kernel     full stage, 2-opt phase only: row_best_tile (multi_move_common.h);
 //   nls_full_or_kernel      full stage, Or-opt phase only: or_row_best_tile (or_opt_rows.h).  A kernel of its own, so that its
 //                           register demand is not the 2-opt loop's;
@@ -34,6 +27,7 @@
 #include "../../include/difusco_hip.h"
 #include "kernels.h"
 #include "multi_move_common.h"
+#include "nbr_rows.h"
 #include "or_opt_rows.h"
 #include "two_opt_common.h"
 
@@ -42,15 +36,6 @@ namespace {
 
 enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2 };
 enum Stage : int { kNbr = 0, kFullStage = 1 };
-
-struct NlTour {            // offsets in elements of the array they index
-  int n, nblk_two, nblk_or, group;
-  long long points;        // the group's first coordinate in `points` (doubles)
-  long long nbr;           // the group's first entry in `neighbors` (n K per group)
-  long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
-  long long cols;          //                       in dlen, pos, rowkey, rowv, rowj, live and winners (n per tour)
-  long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
-};
 
 struct NlTourState {       // device-resident loop state of a tour, zero at the start of a call
   int stage, phase;
@@ -69,111 +54,53 @@ struct NlState {
   int pad;
 };
 
-__global__ void nls_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const NlTour* __restrict__ desc,
+__global__ void nls_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const TourDesc* __restrict__ desc,
                                 double2* __restrict__ tp, double* __restrict__ dlen, int* __restrict__ pos,
                                 unsigned long long* __restrict__ rowkey, int* __restrict__ rowj, const NlTourState* __restrict__ ts) {
-  const NlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   const NlTourState s = ts[blockIdx.y];
   if (k > d.n || s.phase == kDone) return;
   prep_entry(points + d.points, tours + d.closed, d.n, k, tp + d.closed, dlen + d.cols);
-  if (k < d.n && s.stage == kNbr) {
-    pos[d.cols + tours[d.closed + k]] = k;                      // a tour is a permutation of 0 .. n-1 (the entry's convention)
-    rowkey[d.cols + k] = kNoKey;
-    rowj[d.cols + k] = -1;
-  }
-}
-
-// The Or-opt candidates of (position p, listed city at position q): each of the two cities is the segment end, at position e, and
-// the other the anchor.  As `a` (the end joined to tour[j]) the end gives j = the anchor's position; as `b` (the end joined to
-// tour[j+1]) it gives j = the anchor's position minus 1, position 0 read as n.  The end is the segment's first city (i = e - 1)
-// or its last (i = e - L), by variant and orientation.  f(i, v n + j, delta) is called for every valid candidate: 0 <= i <=
-// n - 1 - L (hence 1 <= e <= n - 1: position 0 never moves), j outside [i, i + L]; 0 <= j <= n - 1 holds by construction.  The
-// bounds are tested before or_candidate_delta reads a point.
-template <class F>
-__device__ __forceinline__ void or_nbr_candidates(const double2* __restrict__ P, const double* __restrict__ D, int n, int p, int q,
-                                                  F f) {
-#pragma unroll
-  for (int role = 0; role < 2; ++role) {
-    const int e = role ? q : p, anchor = role ? p : q;
-    const int ja = anchor, jb = (anchor == 0 ? n : anchor) - 1;
-#pragma unroll
-    for (int v = 0; v < 5; ++v) {
-      const int L = variant_len(v);
-      const bool rev = variant_rev(v);
-      const int ia = rev ? e - L : e - 1, ib = rev ? e - 1 : e - L;   // the end as a, as b
-      if (ia >= 0 && ia <= n - 1 - L && (ja < ia || ja > ia + L)) f(ia, v * n + ja, or_candidate_delta(P, D, v, ia, ja));
-      if (ib >= 0 && ib <= n - 1 - L && (jb < ib || jb > ib + L)) f(ib, v * n + jb, or_candidate_delta(P, D, v, ib, jb));
-    }
-  }
-}
-
-// the walk both row kernels share: thread (p, s) of tour blockIdx.y; f(row, code, value)
-template <class F>
-__device__ __forceinline__ void nls_walk(const int* __restrict__ tours, const int* __restrict__ neighbors,
-                                         const NlTour* __restrict__ desc, const double2* __restrict__ tp,
-                                         const double* __restrict__ dlen, const int* __restrict__ pos, int K,
-                                         const NlTourState* __restrict__ ts, F f) {
-  const NlTourState s = ts[blockIdx.y];
-  if (s.stage != kNbr || s.phase == kDone) return;
-  const NlTour d = desc[blockIdx.y];
-  const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= (long long)d.n * K) return;
-  const int p = (int)(e / K), slot = (int)(e % K);
-  const int x = tours[d.closed + p];
-  const int y = neighbors[d.nbr + (long long)x * K + slot];
-  if (y < 0 || y >= d.n || y == x) return;                       // a pad: nothing is indexed with it
-  const int q = pos[d.cols + y];
-  if (s.phase == kTwoOpt)
-    nbr_pairs(tp + d.closed, dlen + d.cols, d.n, p, q, f);
-  else
-    or_nbr_candidates(tp + d.closed, dlen + d.cols, d.n, p, q, f);
+  if (k < d.n && s.stage == kNbr) nbr_reset_row(d, tours, k, pos, rowkey, rowj);
 }
 
 __global__ __launch_bounds__(256) void nls_row_value_kernel(const int* __restrict__ tours, const int* __restrict__ neighbors,
-                                                            const NlTour* __restrict__ desc, const double2* __restrict__ tp,
+                                                            const TourDesc* __restrict__ desc, const double2* __restrict__ tp,
                                                             const double* __restrict__ dlen, const int* __restrict__ pos, int K,
                                                             unsigned long long* __restrict__ rowkey,
                                                             const NlTourState* __restrict__ ts) {
-  unsigned long long* keys = rowkey + desc[blockIdx.y].cols;
-  nls_walk(tours, neighbors, desc, tp, dlen, pos, K, ts, [keys](int i, int, double value) {
-    if (value < kThreshold) atomicMin(&keys[i], ordered_bits(value));
-  });
+  const NlTourState s = ts[blockIdx.y];
+  if (s.stage != kNbr || s.phase == kDone) return;
+  nbr_row_value(desc[blockIdx.y], s.phase == kOrOpt, tours, neighbors, tp, dlen, pos, K, rowkey);
 }
 
 __global__ __launch_bounds__(256) void nls_row_col_kernel(const int* __restrict__ tours, const int* __restrict__ neighbors,
-                                                          const NlTour* __restrict__ desc, const double2* __restrict__ tp,
+                                                          const TourDesc* __restrict__ desc, const double2* __restrict__ tp,
                                                           const double* __restrict__ dlen, const int* __restrict__ pos, int K,
                                                           const unsigned long long* __restrict__ rowkey, double* __restrict__ rowv,
                                                           int* __restrict__ rowj, const NlTourState* __restrict__ ts) {
-  const long long cols = desc[blockIdx.y].cols;
-  const unsigned long long* keys = rowkey + cols;
-  double* vals = rowv + cols;
-  unsigned* codes = (unsigned*)(rowj + cols);                    // -1 is the highest unsigned: no column yet; 5 n fits 32 bits
-  nls_walk(tours, neighbors, desc, tp, dlen, pos, K, ts, [keys, vals, codes](int i, int code, double value) {
-    if (value < kThreshold && ordered_bits(value) == keys[i]) {
-      vals[i] = value;
-      atomicMin(&codes[i], (unsigned)code);
-    }
-  });
+  const NlTourState s = ts[blockIdx.y];
+  if (s.stage != kNbr || s.phase == kDone) return;
+  nbr_row_col(desc[blockIdx.y], s.phase == kOrOpt, tours, neighbors, tp, dlen, pos, K, rowkey, rowv, rowj);
 }
 
 __global__ __launch_bounds__(256) void nls_full_two_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                           const NlTour* __restrict__ desc, double* __restrict__ rowv,
+                                                           const TourDesc* __restrict__ desc, double* __restrict__ rowv,
                                                            int* __restrict__ rowj, const NlTourState* __restrict__ ts) {
   const NlTourState s = ts[blockIdx.y];
   if (s.stage != kFullStage || s.phase != kTwoOpt) return;
-  const NlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   if ((int)blockIdx.x >= d.nblk_two) return;
   row_best_tile(tp + d.closed, dlen + d.cols, d.n, blockIdx.x * TI, rowv + d.cols, rowj + d.cols);
 }
 
 __global__ __launch_bounds__(256) void nls_full_or_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                          const NlTour* __restrict__ desc, double* __restrict__ rowv,
+                                                          const TourDesc* __restrict__ desc, double* __restrict__ rowv,
                                                           int* __restrict__ rowj, const NlTourState* __restrict__ ts) {
   const NlTourState s = ts[blockIdx.y];
   if (s.stage != kFullStage || s.phase != kOrOpt) return;
-  const NlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   if ((int)blockIdx.x >= d.nblk_or) return;
   or_row_best_tile(tp + d.closed, dlen + d.cols, d.n, blockIdx.x * TI, rowv + d.cols, rowj + d.cols);
 }
@@ -186,14 +113,14 @@ __device__ __forceinline__ void report_done(NlGroup* g, NlState* st) {
 // the select step of one tour (the block): the selection and the moves of mls_select_kernel, and the tour's stage, phase, round
 // and counters
 __global__ __launch_bounds__(kSelectThreads) void nls_select_kernel(
-    int* __restrict__ tours, const NlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
     int closing, NlState* st, NlGroup* grp, NlTourState* ts) {
   const int t = blockIdx.x;
   const int phase = ts[t].phase;                                 // written by thread 0 of this block at its end only
   if (phase == kDone) return;
-  const NlTour d = desc[t];
+  const TourDesc d = desc[t];
   const int n = d.n;
   const int* rowj = rowj_all + d.cols;
   int* winners = winners_all + d.cols;
@@ -246,62 +173,33 @@ __global__ __launch_bounds__(kSelectThreads) void nls_select_kernel(
 
 struct NlLayout {          // byte offsets
   size_t desc, tp, dlen, pos, rowkey, rowv, rowj, live, winners, tabv, tabi, marks, cum, grp, ts, st, total;
-  int tours, nmax, nblk_max;
+  GroupTotals tot;
 };
 
-// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
+// checks the host arrays and lays the workspace out; `tab` (optional) receives the descriptors
 int nls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, int K, int closing, NlLayout* L,
-               std::vector<NlTour>* tab, std::vector<NlGroup>* gtab) {
-  int T = 0;
-  const int rc = check_groups(who, groups, group_n, group_tours, &T);
+               std::vector<TourDesc>* tab) {
+  const int rc = walk_groups(who, groups, group_n, group_tours, true, K, closing, &L->tot, tab);
   if (rc != DIFUSCO_OK) return rc;
-  if (K < 1) return set_error(DIFUSCO_EINVAL, "%s: K = %d, needs at least 1", who, K);
-  if (closing != 0 && closing != 1) return set_error(DIFUSCO_EINVAL, "%s: closing = %d, needs 0 or 1", who, closing);
-  size_t points = 0, nbr = 0, closed = 0, cols = 0, cells = 0;
-  L->nmax = L->nblk_max = 0;
-  for (int g = 0; g < groups; ++g) {
-    const int n = group_n[g];
-    const int nblk_two = (n - 2 + TI - 1) / TI, nblk_or = (n - 1 + TI - 1) / TI;   // rows 0 .. n - 3 and 0 .. n - 2
-    if ((long long)n * K > (long long)INT32_MAX * 256)
-      return set_error(DIFUSCO_EINVAL, "%s: group %d has n K = %lld list entries, too many for one launch", who, g, (long long)n * K);
-    L->nmax = n > L->nmax ? n : L->nmax;
-    L->nblk_max = nblk_or > L->nblk_max ? nblk_or : L->nblk_max;
-    if (gtab) gtab->push_back(NlGroup{group_tours[g], 0});
-    for (int p = 0; p < group_tours[g]; ++p) {
-      if (tab)
-        tab->push_back(NlTour{n, nblk_two, nblk_or, g, (long long)points, (long long)nbr, (long long)closed, (long long)cols,
-                              (long long)cells});
-      closed += (size_t)n + 1;
-      cols += (size_t)n;
-      cells += (size_t)table_levels(n) * ((size_t)n + 1);
-    }
-    points += 2 * (size_t)n;
-    nbr += (size_t)n * (size_t)K;
-  }
-  L->tours = (int)T;
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += up256(bytes);
-    return at;
-  };
-  L->desc = take(sizeof(NlTour) * T);
-  L->tp = take(sizeof(double2) * closed);
-  L->dlen = take(sizeof(double) * cols);
-  L->pos = take(sizeof(int) * cols);
-  L->rowkey = take(sizeof(unsigned long long) * cols);
-  L->rowv = take(sizeof(double) * cols);
-  L->rowj = take(sizeof(int) * cols);
-  L->live = take(sizeof(int) * cols);
-  L->winners = take(sizeof(int) * cols);
-  L->tabv = take(sizeof(unsigned long long) * cells);
-  L->tabi = take(sizeof(int) * cells);
-  L->marks = take(sizeof(int2) * closed);
-  L->cum = take(sizeof(int2) * closed);
-  L->grp = take(sizeof(NlGroup) * groups);
-  L->ts = take(sizeof(NlTourState) * T);                         // ts .. st are cleared by one memset
-  L->st = take(sizeof(NlState));
-  L->total = off;
+  const GroupTotals& t = L->tot;
+  Sections s;
+  L->desc = s.take(sizeof(TourDesc) * t.tours);
+  L->tp = s.take(sizeof(double2) * t.closed);
+  L->dlen = s.take(sizeof(double) * t.cols);
+  L->pos = s.take(sizeof(int) * t.cols);
+  L->rowkey = s.take(sizeof(unsigned long long) * t.cols);
+  L->rowv = s.take(sizeof(double) * t.cols);
+  L->rowj = s.take(sizeof(int) * t.cols);
+  L->live = s.take(sizeof(int) * t.cols);
+  L->winners = s.take(sizeof(int) * t.cols);
+  L->tabv = s.take(sizeof(unsigned long long) * t.cells);
+  L->tabi = s.take(sizeof(int) * t.cells);
+  L->marks = s.take(sizeof(int2) * t.closed);
+  L->cum = s.take(sizeof(int2) * t.closed);
+  L->grp = s.take(sizeof(NlGroup) * groups);
+  L->ts = s.take(sizeof(NlTourState) * t.tours);                 // ts .. st are cleared by one memset
+  L->st = s.take(sizeof(NlState));
+  L->total = s.off;
   return DIFUSCO_OK;
 }
 
@@ -315,7 +213,7 @@ int difusco_tsp_nbr_local_search_ragged_workspace_bytes(int groups, const int32_
   using namespace difusco;
   if (!bytes) return set_error(DIFUSCO_EINVAL, "nbr_local_search_ragged_workspace_bytes: bytes is null");
   NlLayout lay;
-  const int rc = nls_layout("nbr_local_search_ragged_workspace_bytes", groups, group_n, group_tours, K, closing, &lay, nullptr, nullptr);
+  const int rc = nls_layout("nbr_local_search_ragged_workspace_bytes", groups, group_n, group_tours, K, closing, &lay, nullptr);
   if (rc == DIFUSCO_OK) *bytes = lay.total;
   return rc;
 }
@@ -329,9 +227,8 @@ int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, cons
   using namespace difusco;
   const char* who = "tsp_nbr_local_search_ragged";
   NlLayout lay;
-  std::vector<NlTour> tab;
-  std::vector<NlGroup> gtab;
-  const int rc = nls_layout(who, groups, group_n, group_tours, K, closing, &lay, &tab, &gtab);
+  std::vector<TourDesc> tab;
+  const int rc = nls_layout(who, groups, group_n, group_tours, K, closing, &lay, &tab);
   if (rc != DIFUSCO_OK) return rc;
   if (!neighbors) return set_error(DIFUSCO_EINVAL, "%s: neighbors is null", who);
   if (!points || !tours || !workspace || !two_opt_sweeps_out || !or_opt_sweeps_out || !rounds_out || !two_opt_moves_out ||
@@ -349,7 +246,7 @@ int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, cons
   }
   if (max_iterations == 0) return DIFUSCO_OK;                    // no sweep may move a tour: nothing is applied
   char* w = (char*)workspace;
-  NlTour* desc = (NlTour*)(w + lay.desc);
+  TourDesc* desc = (TourDesc*)(w + lay.desc);
   double2* tp = (double2*)(w + lay.tp);
   double* dlen = (double*)(w + lay.dlen);
   int* pos = (int*)(w + lay.pos);
@@ -366,9 +263,11 @@ int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, cons
   NlTourState* ts = (NlTourState*)(w + lay.ts);
   NlState* st = (NlState*)(w + lay.st);
   hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
+  const int T = lay.tot.tours;
+  std::vector<NlGroup> gtab(groups);
+  for (int g = 0; g < groups; ++g) gtab[g] = NlGroup{group_tours[g], 0};
   // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(NlTour) * T, hipMemcpyHostToDevice, s);
+  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(TourDesc) * T, hipMemcpyHostToDevice, s);
   if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(NlGroup) * groups, hipMemcpyHostToDevice, s);
   if (er == hipSuccess) er = hipMemsetAsync(ts, 0, lay.total - lay.ts, s);       // ts .. st, the end of the workspace
   if (er == hipSuccess) er = hipStreamSynchronize(s);
@@ -377,11 +276,9 @@ int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, cons
   // the round in which the tour goes on to the full stage.
   const long long ends = 2LL * max_rounds + 2;
   const long long limit = max_iterations > INT64_MAX - ends ? INT64_MAX : max_iterations + ends;
-  NlState host{0, 0};
-  const int poll = 4;
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
-  const dim3 walk_grid((unsigned)(((long long)lay.nmax * K + 255) / 256), T);
-  for (long long it = 0; it < limit; ++it) {
+  const dim3 prep_grid((lay.tot.nmax + 1 + 255) / 256, T), best_grid(lay.tot.nblk_or, T);
+  const dim3 walk_grid((unsigned)(((long long)lay.tot.nmax * K + 255) / 256), T);
+  const Polled polled = poll_launches(limit, 4, groups, &st->done, s, [&] {
     hipLaunchKernelGGL(nls_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, pos, rowkey, rowj, ts);
     hipLaunchKernelGGL(nls_row_value_kernel, walk_grid, dim3(256), 0, s, tours, neighbors, desc, tp, dlen, pos, K, rowkey, ts);
     hipLaunchKernelGGL(nls_row_col_kernel, walk_grid, dim3(256), 0, s, tours, neighbors, desc, tp, dlen, pos, K, rowkey, rowv, rowj,
@@ -392,13 +289,8 @@ int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, cons
     }
     hipLaunchKernelGGL(nls_select_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, rowv, rowj, live, winners, tabv, tabi,
                        marks, cum, (long long)max_iterations, max_rounds, select_rounds, closing, st, grp, ts);
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", who, hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
+  });
+  if (polled.status != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", who, hipGetErrorString(polled.status));
   std::vector<NlTourState> states(T);
   er = hipMemcpyAsync(states.data(), ts, sizeof(NlTourState) * T, hipMemcpyDeviceToHost, s);
   if (er == hipSuccess) er = hipStreamSynchronize(s);

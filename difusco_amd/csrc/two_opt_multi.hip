@@ -1,18 +1,36 @@
-// Multi-move 2-opt (difusco_tsp_multi_two_opt_ragged): every sweep applies a set of improving 2-opt moves whose position ranges
-// are pairwise disjoint, not the one best move.  The rule is stated in include/difusco_hip.h and restated in numpy in
-// tests/multi_two_opt_emulation.py; the arithmetic of a change is best_tile's (two_opt_common.h), bit for bit.
+// The group-synchronised multi-move 2-opt, both entries.  Every sweep applies a set of improving 2-opt moves whose position
+// ranges are pairwise disjoint, not the one best move; the tours of a group count their sweeps together and stop together.
+//   difusco_tsp_multi_two_opt_ragged   every row of a sweep evaluates all its columns (FULL sweeps).  The rule is stated in
+//                                      include/difusco_hip.h and restated in numpy in tests/multi_two_opt_emulation.py;
+//   difusco_tsp_nbr_two_opt_ragged     a row evaluates only its CANDIDATE columns - the pairs (i, j) whose new head edge
+//                                      (tour[i], tour[j]) or new tail edge (tour[i+1], tour[j+1]) joins a city to one of its
+//                                      listed neighbours, in either direction (NEIGHBOUR sweeps, nbr_rows.h).  A tour whose
+//                                      neighbour sweep has no proposal either stops (closing = 0) or goes on with full sweeps
+//                                      (closing = 1) until one of them has no proposal.  tests/nbr_two_opt_emulation.py.
+// The arithmetic of a change is best_tile's / change64's (two_opt_common.h), bit for bit.
 //
-// One sweep is three launches:
-//   multi_prep_kernel       tp / dlen of every tour that is still running (prep_entry);
-//   multi_row_best_kernel   one block per (row tile of 16, tour), the loop of best_tile: a thread keeps 4 columns of every
-//                           1024-column chunk in registers and 16 running bests (change, j), one per row of the tile, across all
-//                           chunks; one block reduction per row ends the tile.  A tile's block walks all its column chunks, so a
-//                           row's best is complete when the block writes it and nothing is combined between blocks;
-//   multi_select_kernel     one block of 1024 threads per tour: the selection rounds, the reversals, the stop test and the
-//                           counters, all on the device.  The host enqueues sweeps and polls a counter of stopped groups.
+// Every tour carries ONE state word - full sweeps (0), neighbour sweeps, stopped - that the selection kernel alone writes, so
+// within a sweep every kernel reads the same state.  The plain entry starts every tour in full sweeps, which is the memset that
+// clears the loop state; the neighbour entry sets the words to neighbour sweeps behind it.  One kernel set:
+//   mt_prep_kernel        tp / dlen of every tour that is still running (prep_entry); in neighbour sweeps also the reset of the
+//                         rows (nbr_reset_row);
+//   mt_row_value_kernel   neighbour sweeps only: nbr_row_value, the lowest change of every row;
+//   mt_row_col_kernel     neighbour sweeps only: nbr_row_col, the lowest column of that change;
+//   mt_row_full_kernel    full sweeps only.  One block per (row tile of 16, tour), row_best_tile (multi_move_common.h): a thread
+//                         keeps 4 columns of every 1024-column chunk in registers and 16 running bests (change, j), one per row of
+//                         the tile, across all chunks; one block reduction per row ends the tile.  A tile's block walks all its
+//                         column chunks, so a row's best is complete when the block writes it;
+//   mt_select_kernel      one block of 1024 threads per tour: the selection rounds (select_disjoint), the reversals, the switch
+//                         from neighbour to full sweeps, the group's stop test and the counters, all on the device.
+// The kernels of the sweeps a tour is not in return on their first branch.  The plain entry launches prep, full rows and select;
+// the neighbour entry launches all five (the full rows with closing only).  The host enqueues sweeps and polls a counter of
+// stopped groups (poll_launches).
 //
 // The selection (multi_move_common.h, shared with or_opt_multi.hip) never does work proportional to the lengths of the ranges:
 // it is O(n log n) per round.  The winners of all rounds are disjoint; a wave reverses one winner's stretch at a time.
+//
+// Workspace: mt_layout.  The plain entry's holds no pos / rowkey sections.  The neighbour entry's is up256(4 tours) bytes smaller
+// than it was while a tour had a done word and a phase word: that is the one section the merged state word removes.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -21,22 +39,21 @@
 #include "../../include/difusco_hip.h"
 #include "kernels.h"
 #include "multi_move_common.h"
+#include "nbr_rows.h"
 #include "two_opt_common.h"
 
 namespace difusco {
 namespace {
 
-struct MtTour {            // offsets in elements of the array they index
-  int n, nblk, group, pad;
-  long long points;        // the group's first coordinate in `points` (doubles)
-  long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
-  long long cols;          //                       in dlen, rowv, rowj, live and winners (n per tour)
-  long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
-};
+enum : int { kFullSweeps = 0, kNbrSweeps = 1, kStopped = 2 };   // a tour's state word
 
 struct MtGroupState {      // device-resident loop state of a group, zero at the start of a call
-  int stopped, arrived, moved, pad;
-  long long sweeps;
+  int arrived, flags;      // flags: what the tours have reported of this sweep; kGroupStopped stays
+  long long sweeps, full_sweeps;
+};
+
+struct MtGroup {           // the tours of a group: desc[first .. first + count - 1]
+  int first, count;
 };
 
 struct MtState {
@@ -44,56 +61,77 @@ struct MtState {
   int pad;
 };
 
-__global__ void multi_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours,
-                                  const MtTour* __restrict__ desc, double2* __restrict__ tp, double* __restrict__ dlen,
-                                  const int* __restrict__ tdone) {
-  const MtTour d = desc[blockIdx.y];
+constexpr int kMoved = 1, kMovedFull = 2, kRunning = 4;      // what a tour reports of a sweep
+constexpr int kGroupStopped = 8;                             // set by the group's stop test, read by later launches only
+
+__global__ void mt_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const TourDesc* __restrict__ desc,
+                               double2* __restrict__ tp, double* __restrict__ dlen, int* __restrict__ pos,
+                               unsigned long long* __restrict__ rowkey, int* __restrict__ rowj, const int* __restrict__ tstate) {
+  const TourDesc d = desc[blockIdx.y];
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > d.n || tdone[blockIdx.y]) return;
+  const int state = tstate[blockIdx.y];
+  if (k > d.n || state == kStopped) return;
   prep_entry(points + d.points, tours + d.closed, d.n, k, tp + d.closed, dlen + d.cols);
+  if (k < d.n && state == kNbrSweeps) nbr_reset_row(d, tours, k, pos, rowkey, rowj);
 }
 
-__global__ __launch_bounds__(256) void multi_row_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                             const MtTour* __restrict__ desc, double* __restrict__ rowv,
-                                                             int* __restrict__ rowj, const int* __restrict__ tdone) {
-  const MtTour d = desc[blockIdx.y];
-  if ((int)blockIdx.x >= d.nblk || tdone[blockIdx.y]) return;
+__global__ __launch_bounds__(256) void mt_row_value_kernel(const int* __restrict__ tours, const int* __restrict__ neighbors,
+                                                           const TourDesc* __restrict__ desc, const double2* __restrict__ tp,
+                                                           const double* __restrict__ dlen, const int* __restrict__ pos, int K,
+                                                           unsigned long long* __restrict__ rowkey,
+                                                           const int* __restrict__ tstate) {
+  if (tstate[blockIdx.y] != kNbrSweeps) return;
+  nbr_row_value(desc[blockIdx.y], false, tours, neighbors, tp, dlen, pos, K, rowkey);
+}
+
+__global__ __launch_bounds__(256) void mt_row_col_kernel(const int* __restrict__ tours, const int* __restrict__ neighbors,
+                                                         const TourDesc* __restrict__ desc, const double2* __restrict__ tp,
+                                                         const double* __restrict__ dlen, const int* __restrict__ pos, int K,
+                                                         const unsigned long long* __restrict__ rowkey, double* __restrict__ rowv,
+                                                         int* __restrict__ rowj, const int* __restrict__ tstate) {
+  if (tstate[blockIdx.y] != kNbrSweeps) return;
+  nbr_row_col(desc[blockIdx.y], false, tours, neighbors, tp, dlen, pos, K, rowkey, rowv, rowj);
+}
+
+__global__ __launch_bounds__(256) void mt_row_full_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
+                                                          const TourDesc* __restrict__ desc, double* __restrict__ rowv,
+                                                          int* __restrict__ rowj, const int* __restrict__ tstate) {
+  const TourDesc d = desc[blockIdx.y];
+  if ((int)blockIdx.x >= d.nblk_two || tstate[blockIdx.y] != kFullSweeps) return;
   row_best_tile(tp + d.closed, dlen + d.cols, d.n, blockIdx.x * TI, rowv + d.cols, rowj + d.cols);
 }
 
-struct GroupRef {          // the tours of a group: desc[first .. first + count - 1]
-  int first, count;
-};
-
 // thread 0 of a tour's block reports to its group; the last tour of the group to report does the group's stop test
-__device__ __forceinline__ void report_to_group(MtGroupState* gs, GroupRef g, bool moved, long long max_iterations,
-                                                int* tdone, MtState* st) {
-  if (moved) atomicOr(&gs->moved, 1);
+__device__ __forceinline__ void report_to_group(MtGroupState* gs, MtGroup g, int flags, long long max_iterations, int* tstate,
+                                                MtState* st) {
+  if (flags) atomicOr(&gs->flags, flags);
   __threadfence();
   if (atomicAdd(&gs->arrived, 1) != g.count - 1) return;
   __threadfence();
-  const int any = atomicExch(&gs->moved, 0);
+  const int any = atomicExch(&gs->flags, 0);
   gs->arrived = 0;
-  if (any) gs->sweeps += 1;                                      // a sweep counts if one of the group's tours moved
-  if (!any || gs->sweeps >= max_iterations) {
-    gs->stopped = 1;
-    for (int b = g.first; b < g.first + g.count; ++b) tdone[b] = 1;
+  if (any & kMoved) gs->sweeps += 1;                             // a sweep counts if one of the group's tours moved,
+  if (any & kMovedFull) gs->full_sweeps += 1;                    // and as a full sweep if one that moved was in full sweeps
+  if (!(any & kRunning) || gs->sweeps >= max_iterations) {
+    gs->flags = kGroupStopped;
+    for (int b = g.first; b < g.first + g.count; ++b) tstate[b] = kStopped;
     atomicAdd(&st->done, 1);
   }
 }
 
-__global__ __launch_bounds__(kSelectThreads) void multi_select_kernel(
-    int* __restrict__ tours, const MtTour* __restrict__ desc, const GroupRef* __restrict__ grp, const double* __restrict__ rowv_all,
+__global__ __launch_bounds__(kSelectThreads) void mt_select_kernel(
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const MtGroup* __restrict__ grp, const double* __restrict__ rowv_all,
     int* __restrict__ rowj_all, int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all,
     int* __restrict__ tabi_all, int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int select_rounds,
-    MtState* st, MtGroupState* gstate, int* tdone, long long* __restrict__ tmoves) {
+    int closing, MtState* st, MtGroupState* gstate, int* tstate, long long* __restrict__ tmoves) {
   const int t = blockIdx.x;
-  const MtTour d = desc[t];
+  const TourDesc d = desc[t];
   MtGroupState* gs = gstate + d.group;
-  if (gs->stopped) return;                                       // written by an earlier launch only
-  const GroupRef G = grp[d.group];
-  if (tdone[t]) {
-    if (threadIdx.x == 0) report_to_group(gs, G, false, max_iterations, tdone, st);
+  if (gs->flags & kGroupStopped) return;                         // written by an earlier launch only
+  const MtGroup G = grp[d.group];
+  const int state = tstate[t];                                   // every thread reads it before thread 0 may write it below:
+  if (state == kStopped) {                                       // select_disjoint has barriers
+    if (threadIdx.x == 0) report_to_group(gs, G, 0, max_iterations, tstate, st);
     return;
   }
   const int n = d.n;
@@ -101,10 +139,11 @@ __global__ __launch_bounds__(kSelectThreads) void multi_select_kernel(
   const int total = select_disjoint(TwoOptRange{rowj_all + d.cols}, n - 2, n, rowv_all + d.cols, live_all + d.cols,
                                     winners_all + d.cols, tabv_all + d.table, tabi_all + d.table, marks_all + d.closed,
                                     cum_all + d.closed, select_rounds, &nwin);
-  if (total == 0) {                                              // no proposal: the tour is done
+  if (total == 0) {                                              // no proposal: on to the full sweeps, or done
     if (threadIdx.x == 0) {
-      tdone[t] = 1;
-      report_to_group(gs, G, false, max_iterations, tdone, st);
+      const bool go_on = state == kNbrSweeps && closing;
+      tstate[t] = go_on ? kFullSweeps : kStopped;
+      report_to_group(gs, G, go_on ? kRunning : 0, max_iterations, tstate, st);
     }
     return;
   }
@@ -112,62 +151,162 @@ __global__ __launch_bounds__(kSelectThreads) void multi_select_kernel(
   reverse_winners(tours + d.closed, winners_all + d.cols, rowj_all + d.cols, total);
   if (threadIdx.x == 0) {
     tmoves[t] += total;
-    report_to_group(gs, G, true, max_iterations, tdone, st);
+    report_to_group(gs, G, kRunning | kMoved | (state == kFullSweeps ? kMovedFull : 0), max_iterations, tstate, st);
   }
 }
 
-struct MtLayout {          // byte offsets
-  size_t desc, grp, tp, dlen, rowv, rowj, live, winners, tabv, tabi, marks, cum, gstate, tdone, tmoves, st, total;
-  int tours, nmax, nblk_max;
+// ---- the host side: one workspace description (mt_layout, MtPtrs) and one driver (mt_run) behind the two entries
+
+struct MtLayout {          // byte offsets; pos and rowkey are empty without lists
+  size_t desc, grp, tp, dlen, pos, rowkey, rowv, rowj, live, winners, tabv, tabi, marks, cum, gstate, tstate, tmoves, st, total;
+  GroupTotals tot;
 };
 
-// checks the host arrays and lays the workspace out; `tab` / `gtab` (optional) receive the tables
-int multi_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, MtLayout* L,
-                 std::vector<MtTour>* tab, std::vector<GroupRef>* gtab) {
-  int T = 0;
-  const int rc = check_groups(who, groups, group_n, group_tours, &T);
+// checks the host arrays and lays the workspace out; `tab` (optional) receives the descriptors
+int mt_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, bool lists, int K, int closing,
+              MtLayout* L, std::vector<TourDesc>* tab) {
+  const int rc = walk_groups(who, groups, group_n, group_tours, lists, K, closing, &L->tot, tab);
   if (rc != DIFUSCO_OK) return rc;
-  size_t points = 0, closed = 0, cols = 0, cells = 0;
-  int first = 0;
-  L->nmax = L->nblk_max = 0;
-  for (int g = 0; g < groups; ++g) {
-    const int n = group_n[g], nblk = (n - 2 + TI - 1) / TI;       // rows 0 .. n - 3
-    L->nmax = n > L->nmax ? n : L->nmax;
-    L->nblk_max = nblk > L->nblk_max ? nblk : L->nblk_max;
-    if (gtab) gtab->push_back(GroupRef{first, group_tours[g]});
-    first += group_tours[g];
-    for (int p = 0; p < group_tours[g]; ++p) {
-      if (tab) tab->push_back(MtTour{n, nblk, g, 0, (long long)points, (long long)closed, (long long)cols, (long long)cells});
-      closed += (size_t)n + 1;
-      cols += (size_t)n;
-      cells += (size_t)table_levels(n) * ((size_t)n + 1);
-    }
-    points += 2 * (size_t)n;
+  const GroupTotals& t = L->tot;
+  Sections s;
+  L->desc = s.take(sizeof(TourDesc) * t.tours);
+  L->grp = s.take(sizeof(MtGroup) * groups);
+  L->tp = s.take(sizeof(double2) * t.closed);
+  L->dlen = s.take(sizeof(double) * t.cols);
+  L->pos = s.take(sizeof(int) * t.cols, lists);
+  L->rowkey = s.take(sizeof(unsigned long long) * t.cols, lists);
+  L->rowv = s.take(sizeof(double) * t.cols);
+  L->rowj = s.take(sizeof(int) * t.cols);
+  L->live = s.take(sizeof(int) * t.cols);
+  L->winners = s.take(sizeof(int) * t.cols);
+  L->tabv = s.take(sizeof(unsigned long long) * t.cells);
+  L->tabi = s.take(sizeof(int) * t.cells);
+  L->marks = s.take(sizeof(int2) * t.closed);
+  L->cum = s.take(sizeof(int2) * t.closed);
+  // gstate .. st are cleared by one memset.  The neighbour entry reserves the 32 bytes per group that its group record took
+  // before the state words were merged, so that its size differs from the earlier one by the merged word alone.
+  L->gstate = s.take((lists ? 32 : sizeof(MtGroupState)) * groups);
+  L->tstate = s.take(sizeof(int) * t.tours);
+  L->tmoves = s.take(sizeof(long long) * t.tours);
+  L->st = s.take(sizeof(MtState));
+  L->total = s.off;
+  return DIFUSCO_OK;
+}
+
+int mt_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, bool lists, int K,
+                       int closing, size_t* bytes) {
+  if (!bytes) return set_error(DIFUSCO_EINVAL, "%s: bytes is null", who);
+  MtLayout lay;
+  const int rc = mt_layout(who, groups, group_n, group_tours, lists, K, closing, &lay, nullptr);
+  if (rc == DIFUSCO_OK) *bytes = lay.total;
+  return rc;
+}
+
+struct MtPtrs {            // the sections of a workspace; pos and rowkey are never read without lists
+  TourDesc* desc;
+  MtGroup* grp;
+  double2* tp;
+  double *dlen, *rowv;
+  int *pos, *rowj, *live, *winners, *tabi, *tstate;
+  unsigned long long *rowkey, *tabv;
+  int2 *marks, *cum;
+  MtGroupState* gstate;
+  long long* tmoves;
+  MtState* st;
+  MtPtrs(void* workspace, const MtLayout& L) {
+    char* w = (char*)workspace;
+    desc = (TourDesc*)(w + L.desc), grp = (MtGroup*)(w + L.grp), tp = (double2*)(w + L.tp), dlen = (double*)(w + L.dlen);
+    pos = (int*)(w + L.pos), rowkey = (unsigned long long*)(w + L.rowkey), rowv = (double*)(w + L.rowv), rowj = (int*)(w + L.rowj);
+    live = (int*)(w + L.live), winners = (int*)(w + L.winners), tabv = (unsigned long long*)(w + L.tabv), tabi = (int*)(w + L.tabi);
+    marks = (int2*)(w + L.marks), cum = (int2*)(w + L.cum), gstate = (MtGroupState*)(w + L.gstate), tstate = (int*)(w + L.tstate);
+    tmoves = (long long*)(w + L.tmoves), st = (MtState*)(w + L.st);
   }
-  L->tours = (int)T;
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += up256(bytes);
-    return at;
-  };
-  L->desc = take(sizeof(MtTour) * T);
-  L->grp = take(sizeof(GroupRef) * groups);
-  L->tp = take(sizeof(double2) * closed);
-  L->dlen = take(sizeof(double) * cols);
-  L->rowv = take(sizeof(double) * cols);
-  L->rowj = take(sizeof(int) * cols);
-  L->live = take(sizeof(int) * cols);
-  L->winners = take(sizeof(int) * cols);
-  L->tabv = take(sizeof(unsigned long long) * cells);
-  L->tabi = take(sizeof(int) * cells);
-  L->marks = take(sizeof(int2) * closed);
-  L->cum = take(sizeof(int2) * closed);
-  L->gstate = take(sizeof(MtGroupState) * groups);               // gstate .. st are cleared by one memset
-  L->tdone = take(sizeof(int) * T);
-  L->tmoves = take(sizeof(long long) * T);
-  L->st = take(sizeof(MtState));
-  L->total = off;
+};
+
+struct MtCall {            // a call of one of the two entries
+  const char* who;         // the entry, in front of every message
+  const char* outputs;     // how the entry's refusal names its host output arrays
+  bool lists;              // the neighbour entry
+  int groups;
+  const int32_t *group_n, *group_tours;
+  const double* points;
+  int32_t* tours;
+  const int32_t* neighbors;
+  int K, closing;
+  int64_t max_iterations;
+  int select_rounds;
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t *sweeps_out, *full_sweeps_out, *moves_out;             // full_sweeps_out: the neighbour entry
+  void* stream;
+};
+
+// The two entries.  Checks the arguments, sets the device state up, enqueues sweeps until every group has stopped, and reads the
+// counters back.
+int mt_run(const MtCall& c) {
+  const int groups = c.groups;
+  MtLayout lay;
+  std::vector<TourDesc> tab;
+  const int rc = mt_layout(c.who, groups, c.group_n, c.group_tours, c.lists, c.K, c.closing, &lay, &tab);
+  if (rc != DIFUSCO_OK) return rc;
+  if (c.lists && !c.neighbors) return set_error(DIFUSCO_EINVAL, "%s: neighbors is null", c.who);
+  if (!c.points || !c.tours || !c.workspace || !c.sweeps_out || (c.lists && !c.full_sweeps_out) || !c.moves_out || c.max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "%s: needs non-null device arrays, host %s [groups] and max_iterations >= 0", c.who, c.outputs);
+  if (c.select_rounds < 1) return set_error(DIFUSCO_EINVAL, "%s: select_rounds = %d, needs at least 1", c.who, c.select_rounds);
+  if (c.workspace_bytes < lay.total)
+    return set_error(DIFUSCO_EINVAL, "%s: workspace %zu < %zu bytes", c.who, c.workspace_bytes, lay.total);
+  for (int g = 0; g < groups; ++g) {
+    c.sweeps_out[g] = c.moves_out[g] = 0;
+    if (c.lists) c.full_sweeps_out[g] = 0;
+  }
+  if (c.max_iterations == 0) return DIFUSCO_OK;                  // no sweep counts: nothing is applied
+  const MtPtrs p(c.workspace, lay);
+  hipStream_t s = (hipStream_t)c.stream;
+  const int T = lay.tot.tours, K = c.K, closing = c.lists ? c.closing : 0;
+  std::vector<MtGroup> gtab(groups);
+  for (int g = 0, first = 0; g < groups; first += c.group_tours[g++]) gtab[g] = MtGroup{first, c.group_tours[g]};
+  // the tables, once per call; the host vectors live until the synchronisation below
+  hipError_t er = hipMemcpyAsync(p.desc, tab.data(), sizeof(TourDesc) * T, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(p.grp, gtab.data(), sizeof(MtGroup) * groups, hipMemcpyHostToDevice, s);
+  if (er == hipSuccess) er = hipMemsetAsync(p.gstate, 0, lay.total - lay.gstate, s);   // every tour in full sweeps
+  if (er == hipSuccess && c.lists) er = hipMemsetD32Async((hipDeviceptr_t)p.tstate, kNbrSweeps, T, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s setup: %s", c.who, hipGetErrorString(er));
+  // A launch sequence is a counted sweep of a group or one in which none of its tours moved.  Full sweeps: the first of the
+  // latter stops the group - at most max_iterations + 1 sequences.  With lists, in the first of the latter every running tour of
+  // the group is without a proposal: it stops or moves to full sweeps, so from then on every running tour is in full sweeps, and
+  // the second stops them all - at most max_iterations + 2.
+  const int64_t ends = c.lists ? 2 : 1;
+  const long long limit = c.max_iterations > INT64_MAX - ends ? INT64_MAX : c.max_iterations + ends;
+  const dim3 prep_grid((lay.tot.nmax + 1 + 255) / 256, T), best_grid(lay.tot.nblk_two, T);
+  const dim3 walk_grid((unsigned)(((long long)lay.tot.nmax * K + 255) / 256), T);
+  const Polled polled = poll_launches(limit, 4, groups, &p.st->done, s, [&] {
+    hipLaunchKernelGGL(mt_prep_kernel, prep_grid, dim3(256), 0, s, c.points, c.tours, p.desc, p.tp, p.dlen, p.pos, p.rowkey, p.rowj,
+                       p.tstate);
+    if (c.lists) {
+      hipLaunchKernelGGL(mt_row_value_kernel, walk_grid, dim3(256), 0, s, c.tours, c.neighbors, p.desc, p.tp, p.dlen, p.pos, K,
+                         p.rowkey, p.tstate);
+      hipLaunchKernelGGL(mt_row_col_kernel, walk_grid, dim3(256), 0, s, c.tours, c.neighbors, p.desc, p.tp, p.dlen, p.pos, K,
+                         p.rowkey, p.rowv, p.rowj, p.tstate);
+    }
+    if (!c.lists || closing)
+      hipLaunchKernelGGL(mt_row_full_kernel, best_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, p.tstate);
+    hipLaunchKernelGGL(mt_select_kernel, dim3(T), dim3(kSelectThreads), 0, s, c.tours, p.desc, p.grp, p.rowv, p.rowj, p.live,
+                       p.winners, p.tabv, p.tabi, p.marks, p.cum, (long long)c.max_iterations, c.select_rounds, closing, p.st,
+                       p.gstate, p.tstate, p.tmoves);
+  });
+  if (polled.status != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(polled.status));
+  std::vector<MtGroupState> states(groups);
+  std::vector<long long> moves(T);
+  er = hipMemcpyAsync(states.data(), p.gstate, sizeof(MtGroupState) * groups, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipMemcpyAsync(moves.data(), p.tmoves, sizeof(long long) * T, hipMemcpyDeviceToHost, s);
+  if (er == hipSuccess) er = hipStreamSynchronize(s);
+  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "%s counters: %s", c.who, hipGetErrorString(er));
+  for (int g = 0; g < groups; ++g) {
+    c.sweeps_out[g] = states[g].sweeps;
+    if (c.lists) c.full_sweeps_out[g] = states[g].full_sweeps;
+    for (int b = gtab[g].first; b < gtab[g].first + gtab[g].count; ++b) c.moves_out[g] += moves[b];
+  }
   return DIFUSCO_OK;
 }
 
@@ -177,85 +316,29 @@ int multi_layout(const char* who, int groups, const int32_t* group_n, const int3
 extern "C" {
 
 int difusco_tsp_multi_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes) {
-  using namespace difusco;
-  if (!bytes) return set_error(DIFUSCO_EINVAL, "multi_two_opt_ragged_workspace_bytes: bytes is null");
-  MtLayout lay;
-  const int rc = multi_layout("multi_two_opt_ragged_workspace_bytes", groups, group_n, group_tours, &lay, nullptr, nullptr);
-  if (rc == DIFUSCO_OK) *bytes = lay.total;
-  return rc;
+  return difusco::mt_workspace_bytes("multi_two_opt_ragged_workspace_bytes", groups, group_n, group_tours, false, 0, 0, bytes);
 }
 
 int difusco_tsp_multi_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
                                      int32_t* tours, int64_t max_iterations, int select_rounds, void* workspace,
                                      size_t workspace_bytes, int64_t* sweeps_out, int64_t* moves_out, void* stream) {
-  using namespace difusco;
-  MtLayout lay;
-  std::vector<MtTour> tab;
-  std::vector<GroupRef> gtab;
-  const int rc = multi_layout("tsp_multi_two_opt_ragged", groups, group_n, group_tours, &lay, &tab, &gtab);
-  if (rc != DIFUSCO_OK) return rc;
-  if (!points || !tours || !workspace || !sweeps_out || !moves_out || max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_two_opt_ragged: needs non-null device arrays, host sweeps_out and moves_out "
-                                     "[groups] and max_iterations >= 0");
-  if (select_rounds < 1)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_two_opt_ragged: select_rounds = %d, needs at least 1", select_rounds);
-  if (workspace_bytes < lay.total)
-    return set_error(DIFUSCO_EINVAL, "tsp_multi_two_opt_ragged: workspace %zu < %zu bytes", workspace_bytes, lay.total);
-  for (int g = 0; g < groups; ++g) sweeps_out[g] = moves_out[g] = 0;
-  if (max_iterations == 0) return DIFUSCO_OK;                    // no sweep counts: nothing is applied
-  char* w = (char*)workspace;
-  MtTour* desc = (MtTour*)(w + lay.desc);
-  GroupRef* grp = (GroupRef*)(w + lay.grp);
-  double2* tp = (double2*)(w + lay.tp);
-  double* dlen = (double*)(w + lay.dlen);
-  double* rowv = (double*)(w + lay.rowv);
-  int* rowj = (int*)(w + lay.rowj);
-  int* live = (int*)(w + lay.live);
-  int* winners = (int*)(w + lay.winners);
-  unsigned long long* tabv = (unsigned long long*)(w + lay.tabv);
-  int* tabi = (int*)(w + lay.tabi);
-  int2* marks = (int2*)(w + lay.marks);
-  int2* cum = (int2*)(w + lay.cum);
-  MtGroupState* gstate = (MtGroupState*)(w + lay.gstate);
-  int* tdone = (int*)(w + lay.tdone);
-  long long* tmoves = (long long*)(w + lay.tmoves);
-  MtState* st = (MtState*)(w + lay.st);
-  hipStream_t s = (hipStream_t)stream;
-  const int T = lay.tours;
-  // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(desc, tab.data(), sizeof(MtTour) * T, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(grp, gtab.data(), sizeof(GroupRef) * groups, hipMemcpyHostToDevice, s);
-  if (er == hipSuccess) er = hipMemsetAsync(gstate, 0, lay.total - lay.gstate, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_two_opt_ragged setup: %s", hipGetErrorString(er));
-  // a launch sequence is a counted sweep of a group or the one that finds it without a proposal: at most max_iterations + 1
-  const long long limit = max_iterations < INT64_MAX ? max_iterations + 1 : INT64_MAX;
-  MtState host{0, 0};
-  const int poll = 4;
-  const dim3 prep_grid((lay.nmax + 1 + 255) / 256, T), best_grid(lay.nblk_max, T);
-  for (long long it = 0; it < limit; ++it) {
-    hipLaunchKernelGGL(multi_prep_kernel, prep_grid, dim3(256), 0, s, points, tours, desc, tp, dlen, tdone);
-    hipLaunchKernelGGL(multi_row_best_kernel, best_grid, dim3(256), 0, s, tp, dlen, desc, rowv, rowj, tdone);
-    hipLaunchKernelGGL(multi_select_kernel, dim3(T), dim3(kSelectThreads), 0, s, tours, desc, grp, rowv, rowj, live, winners, tabv,
-                       tabi, marks, cum, (long long)max_iterations, select_rounds, st, gstate, tdone, tmoves);
-    if ((it + 1) % poll == 0 || it + 1 == limit) {
-      er = hipMemcpyAsync(&host, st, sizeof(host), hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-      if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "multi_two_opt state: %s", hipGetErrorString(er));
-      if (host.done >= groups) break;
-    }
-  }
-  std::vector<MtGroupState> states(groups);
-  std::vector<long long> moves(T);
-  er = hipMemcpyAsync(states.data(), gstate, sizeof(MtGroupState) * groups, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipMemcpyAsync(moves.data(), tmoves, sizeof(long long) * T, hipMemcpyDeviceToHost, s);
-  if (er == hipSuccess) er = hipStreamSynchronize(s);
-  if (er != hipSuccess) return set_error(DIFUSCO_EHIP, "tsp_multi_two_opt_ragged counters: %s", hipGetErrorString(er));
-  for (int g = 0; g < groups; ++g) {
-    sweeps_out[g] = states[g].sweeps;
-    for (int b = gtab[g].first; b < gtab[g].first + gtab[g].count; ++b) moves_out[g] += moves[b];
-  }
-  return DIFUSCO_OK;
+  return difusco::mt_run({"tsp_multi_two_opt_ragged", "sweeps_out and moves_out", false, groups, group_n, group_tours, points, tours,
+                          nullptr, 0, 0, max_iterations, select_rounds, workspace, workspace_bytes, sweeps_out, nullptr, moves_out,
+                          stream});
+}
+
+int difusco_tsp_nbr_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int K, int closing,
+                                                   size_t* bytes) {
+  return difusco::mt_workspace_bytes("nbr_two_opt_ragged_workspace_bytes", groups, group_n, group_tours, true, K, closing, bytes);
+}
+
+int difusco_tsp_nbr_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                   int32_t* tours, const int32_t* neighbors, int K, int closing, int64_t max_iterations,
+                                   int select_rounds, void* workspace, size_t workspace_bytes, int64_t* sweeps_out,
+                                   int64_t* full_sweeps_out, int64_t* moves_out, void* stream) {
+  return difusco::mt_run({"tsp_nbr_two_opt_ragged", "sweeps_out, full_sweeps_out and moves_out", true, groups, group_n, group_tours,
+                          points, tours, neighbors, K, closing, max_iterations, select_rounds, workspace, workspace_bytes, sweeps_out,
+                          full_sweeps_out, moves_out, stream});
 }
 
 }  // extern "C"

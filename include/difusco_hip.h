@@ -729,7 +729,9 @@ int difusco_tsp_multi_two_opt_ragged(int groups, const int32_t* group_n, const i
  * sweeps_out, full_sweeps_out, moves_out: HOST int64 [groups]: the counted sweeps, the part of them counted as full sweeps, and
  * the moves applied over all tours of the group.  DIFUSCO_EINVAL before any GPU work on the conditions of
  * difusco_tsp_multi_two_opt_ragged, null neighbors, K < 1, closing outside {0, 1} and a short workspace.  Blocks until every
- * group is done. */
+ * group is done.  The workspace holds what difusco_tsp_multi_two_opt_ragged's holds plus a position and a key per city and tour;
+ * a tour's done and phase words are one state word, so _workspace_bytes returns 256 * ceil(4 tours / 256) bytes less than it did
+ * while they were two (callers size the workspace by the function, so nothing else moves). */
 int difusco_tsp_nbr_two_opt_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int K, int closing,
                                                    size_t* bytes);
 int difusco_tsp_nbr_two_opt_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,

@@ -56,7 +56,7 @@ if opts.kernel_stats:
     rows = {}
     with open(opts.kernel_stats) as f:
         for r in csv.DictReader(f):
-            for name in ("multi_prep_kernel", "multi_row_best_kernel", "multi_select_kernel"):
+            for name in ("mt_prep_kernel", "mt_row_full_kernel", "mt_select_kernel"):
                 if name in r["Name"]:
                     rows[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6,
                                   "avg_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3,

@@ -1,4 +1,4 @@
-"""CPU restatement of the neighbour-list multi-move 2-opt (difusco_amd/csrc/two_opt_nbr.hip, ``difusco_tsp_nbr_two_opt_ragged``)
+"""CPU restatement of the neighbour-list multi-move 2-opt (difusco_amd/csrc/two_opt_multi.hip, ``difusco_tsp_nbr_two_opt_ragged``)
 in numpy float64.  TEST INFRASTRUCTURE ONLY.  Changes, selection and apply are those of ``multi_two_opt_emulation``; this file
 adds the candidate mask of a neighbour sweep, the per-tour phase and the counters.
 
