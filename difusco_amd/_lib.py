@@ -139,6 +139,10 @@ def lib():
                                                ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32), vp]
     L.difusco_tsp_local_search_ragged_workspace_bytes.argtypes = [i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_local_search_ragged.argtypes = [i32, vp, vp, vp, vp, i64, i32, vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.difusco_tsp_local_search_resident_max_cells.argtypes = []
+    L.difusco_tsp_local_search_resident_workspace_bytes.argtypes = [i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_local_search_resident.argtypes = [i32, vp, vp, vp, vp, i64, i32, ctypes.c_int32, vp, ctypes.c_size_t, vp, vp, vp,
+                                                    ctypes.POINTER(ctypes.c_int32), vp]
     L.difusco_tsp_multi_two_opt_ragged_workspace_bytes.argtypes = [i32, vp, vp, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_multi_two_opt_ragged.argtypes = [i32, vp, vp, vp, vp, i64, i32, vp, ctypes.c_size_t, vp, vp, vp]
     L.difusco_tsp_nbr_two_opt_ragged_workspace_bytes.argtypes = [i32, vp, vp, i32, i32, ctypes.POINTER(ctypes.c_size_t)]

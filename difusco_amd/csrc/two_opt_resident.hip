@@ -40,6 +40,7 @@
 
 #include "../../include/difusco_hip.h"
 #include "kernels.h"
+#include "resident_team.h"
 #include "two_opt_common.h"
 
 namespace difusco {
@@ -52,7 +53,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kDefaultMovesPerLaunch = 1024;
 constexpr int kStaticLds = 16 * kWaves + 16;
 
-constexpr int up4(int x) { return (x + 3) & ~3; }
 constexpr size_t lds_bytes(bool screen, int S, int T) { return screen ? 48 * (size_t)S + 20 * (size_t)T : 28 * (size_t)S + 16 * (size_t)T; }
 static_assert(lds_bytes(true, kMaxCells, up4(kMaxCells / 5)) + kStaticLds <= 163840, "a group of kMaxCells cells must fit the LDS of a CU");
 static_assert(kMaxCells >= 2048 && kMaxCells % 4 == 0, "TSP-500 with 4 samples is 2004 cells");
@@ -92,15 +92,6 @@ __device__ __forceinline__ Lds carve(unsigned char* base, int S, int T) {
   return L;
 }
 
-__device__ __forceinline__ Best wave_best(Best b) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const Best o{__shfl_xor(b.v, off, 64), __shfl_xor(b.idx, off, 64)};
-    if (better(o.v, o.idx, b)) b = o;
-  }
-  return b;
-}
-
 // dlen / q / d32 of cell c from tp: the arithmetic of prep_entry and prep_screen_entry on the same operands
 template <bool kScreen>
 __device__ __forceinline__ void edge_entry(const Lds& L, int c) {
@@ -121,30 +112,6 @@ __device__ __forceinline__ void rebuild(const Lds& L, int cells, int stride, int
   if (kScreen)
     for (int p = threadIdx.x; p < P; p += blockDim.x) L.tkey[p] = f32_key(0.0f);
   __syncthreads();
-}
-
-// The split of a tour's pairs over a team: the pairs (i, j), j >= i + 2, in row-major order (row i holds the n - 2 - i pairs
-// (i, i + 2 + q)); a thread takes the pairs first, first + step, ... of that order, step = the team size.  Consecutive threads
-// then read consecutive columns and, mostly, one row.  work is false for a thread of a team without a tour.
-struct Split {
-  int first, step;
-  bool work;
-};
-
-// f(i, j) for every pair of the thread: <= pairs / team size + 1 calls; the row search runs <= n turns over the whole sweep
-template <class F>
-__device__ __forceinline__ void for_pairs(int n, const Split& s, F f) {
-  int i = 0, q = s.first, len = n - 2;
-  for (;;) {
-    while (len > 0 && q >= len) {
-      q -= len;
-      ++i;
-      --len;
-    }
-    if (len <= 0) break;
-    f(i, i + 2 + q);
-    q += s.step;
-  }
 }
 
 // the exact sweep of one tour (its arrays at `base`): the thread's best move; counts its pairs

@@ -439,46 +439,87 @@ def _local_search_checked(who, pts, trs, max_iterations, max_rounds, device):
     return device
 
 
-def _local_search(form, points, tours, max_iterations, device, max_rounds, stats):
-    """``batched_local_search_<form>``: the checks and one ``difusco_tsp_local_search_ragged`` call."""
+TSP_LOCAL_SEARCH_MODES = ("launches", "resident")
+
+
+def check_tsp_local_search_mode(local_search, mode):
+    """``local_search_mode`` of ``solve_tsp``, ``solve_tsp_batch`` and the runner: ``"resident"`` runs the 2-opt + Or-opt search
+    with one GPU block per instance, so it needs ``local_search="2opt+oropt"``; the other searches have no such form (the
+    single-move 2-opt has its own, ``two_opt_mode``)."""
+    if mode not in TSP_LOCAL_SEARCH_MODES:
+        raise ValueError(f"local search mode {mode!r}: one of {TSP_LOCAL_SEARCH_MODES}")
+    if mode == "resident" and local_search != "2opt+oropt":
+        raise ValueError(f"local_search_mode={mode!r} runs the 2-opt + Or-opt search: it needs local_search='2opt+oropt', "
+                         f"not {local_search!r}")
+    return mode
+
+
+def local_search_resident_max_cells():
+    """The largest group ``batched_local_search_*(mode="resident")`` takes: ``P * (n + 1)`` entries of closed tours (a constant
+    of the build, >= 2048)."""
+    return int(_lib.lib().difusco_tsp_local_search_resident_max_cells())
+
+
+def _local_search(form, points, tours, max_iterations, device, max_rounds, stats, mode="launches", steps_per_launch=0):
+    """``batched_local_search_<form>``: the checks and one ``difusco_tsp_local_search_ragged`` call, or with ``mode="resident"``
+    one ``difusco_tsp_local_search_resident`` call, on the per-group arrays."""
+    resident = check_tsp_local_search_mode("2opt+oropt", mode) == "resident"
     pts, trs = _per_group(form, points, tours)
     device = _local_search_checked(f"batched_local_search_{form}", pts, trs, max_iterations, max_rounds, device)
     batch = _RaggedBatch(pts, trs, device)
     L = _lib.lib()
-    ws, nbytes = _workspace(L.difusco_tsp_local_search_ragged_workspace_bytes, *batch.sizes, device=device)
     G = batch.groups
     st = {"two_opt_iterations": np.zeros(G, dtype=np.int64), "or_opt_iterations": np.zeros(G, dtype=np.int64),
           "rounds": np.zeros(G, dtype=np.int32)}
-    _lib.check(L.difusco_tsp_local_search_ragged(*batch.head, int(max_iterations), int(max_rounds), _ptr(ws), nbytes,
-                                                 *(v.ctypes.data for v in st.values()), _stream(device)))
+    if resident:
+        ws, nbytes = _workspace(L.difusco_tsp_local_search_resident_workspace_bytes, *batch.sizes, device=device)
+        syncs = ctypes.c_int32()
+        _lib.check(L.difusco_tsp_local_search_resident(*batch.head, int(max_iterations), int(max_rounds), int(steps_per_launch),
+                                                       _ptr(ws), nbytes, *(v.ctypes.data for v in st.values()), ctypes.byref(syncs),
+                                                       _stream(device)))
+    else:
+        ws, nbytes = _workspace(L.difusco_tsp_local_search_ragged_workspace_bytes, *batch.sizes, device=device)
+        _lib.check(L.difusco_tsp_local_search_ragged(*batch.head, int(max_iterations), int(max_rounds), _ptr(ws), nbytes,
+                                                     *(v.ctypes.data for v in st.values()), _stream(device)))
     out, st = _as_form(form, batch.read_tours(), st)
     if stats is not None:
         stats["or_opt_iterations"], stats["rounds"] = st["or_opt_iterations"], st["rounds"]
+        if resident:
+            stats["host_syncs"] = int(syncs.value)
     return out, st["two_opt_iterations"]
 
 
-def batched_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+def batched_local_search_torch(points, tour, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None, mode="launches",
+                               steps_per_launch=0):
     """2-opt + Or-opt local search of the tours of ONE instance, the arguments of ``batched_two_opt_torch``: rounds of a 2-opt
     phase (exactly ``batched_two_opt_torch`` with ``max_iterations``) and an Or-opt phase (every tour moves its best segment of
     1-3 cities, forwards or reversed, while that shortens it by more than 1e-6; at most ``max_iterations`` iterations) until an
     Or-opt phase applies nothing or ``max_rounds`` rounds ran (``difusco_tsp_local_search_ragged``, include/difusco_hip.h; GPU
     only).  No tour ends longer than 2-opt alone leaves it.  Returns ``(tour int64 numpy [B, N+1], two_opt_iterations)``;
-    ``stats`` (a dict) receives ``or_opt_iterations`` and ``rounds``."""
-    return _local_search("torch", points, tour, max_iterations, device, max_rounds, stats)
+    ``stats`` (a dict) receives ``or_opt_iterations`` and ``rounds``.  ``mode="resident"`` runs
+    ``difusco_tsp_local_search_resident`` instead: one GPU block keeps the tours in LDS through both phases and all rounds,
+    without a launch or a host read per step (at most ``steps_per_launch`` 2-opt moves and Or-opt iterations per launch, 0 =
+    the library's default); the same tours and counters, for at most ``local_search_resident_max_cells()`` tour entries
+    (``B * (N + 1)``; more raises ``DifuscoHipError``, there is no fallback); ``stats`` also receives ``host_syncs``."""
+    return _local_search("torch", points, tour, max_iterations, device, max_rounds, stats, mode, steps_per_launch)
 
 
-def batched_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+def batched_local_search_grouped(points, tours, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None, mode="launches",
+                                 steps_per_launch=0):
     """``batched_local_search_torch`` of G instances at once, the arguments of ``batched_two_opt_grouped``: ``points`` float64
     [G, N, 2], ``tours`` int [G * P, N + 1].  Every instance gets what its own ``batched_local_search_torch`` call returns.
     Returns ``(tours int64 numpy [G * P, N + 1], two_opt_iterations int64 numpy [G])``; ``stats`` receives ``or_opt_iterations``
-    (int64 [G]) and ``rounds`` (int32 [G])."""
-    return _local_search("grouped", points, tours, max_iterations, device, max_rounds, stats)
+    (int64 [G]) and ``rounds`` (int32 [G]).  ``mode`` / ``steps_per_launch``: as ``batched_local_search_torch``, one block per
+    instance; the limit holds for every instance (``P * (N + 1)`` entries)."""
+    return _local_search("grouped", points, tours, max_iterations, device, max_rounds, stats, mode, steps_per_launch)
 
 
-def batched_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None):
+def batched_local_search_ragged(points_list, tours_list, max_iterations=1000, device="cuda:0", *, max_rounds=16, stats=None,
+                                mode="launches", steps_per_launch=0):
     """``batched_local_search_torch`` of G instances of ANY sizes at once, the arguments of ``batched_two_opt_ragged``.  Returns
-    ``(list of int64 numpy [P_g, n_g + 1], two_opt_iterations int64 numpy [G])``; ``stats``: as ``batched_local_search_grouped``."""
-    return _local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, stats)
+    ``(list of int64 numpy [P_g, n_g + 1], two_opt_iterations int64 numpy [G])``; ``stats``: as ``batched_local_search_grouped``.
+    ``mode`` / ``steps_per_launch``: as ``batched_local_search_torch`` (``P_g * (n_g + 1)`` entries per instance)."""
+    return _local_search("ragged", points_list, tours_list, max_iterations, device, max_rounds, stats, mode, steps_per_launch)
 
 
 def _multi_move_checked(who, pts, trs, max_iterations, max_rounds, select_rounds, device):

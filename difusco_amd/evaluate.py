@@ -24,7 +24,9 @@ Extensions: ``--seed``, ``--instances_per_call`` (chunk length; default ``defaul
 ``--two_opt_method {exact,screened}`` (``decode.batched_two_opt_grouped``: same records either way), ``--two_opt_mode
 {launches,resident}`` (TSP with ``--local_search 2opt``: ``resident`` runs that 2-opt with one GPU block per instance,
 ``mode="resident"`` of ``decode.batched_two_opt_grouped``; the records and the header gain ``two_opt_mode`` and are otherwise
-the same), ``--local_search
+the same), ``--tsp_local_search_mode {launches,resident}`` (TSP with ``--local_search 2opt+oropt``: ``resident`` runs that
+search with one GPU block per instance, ``mode="resident"`` of ``decode.batched_local_search_grouped``; the records and the header
+gain ``tsp_local_search_mode`` and are otherwise the same), ``--local_search
 {2opt,2opt+oropt,multi2opt,multi2opt+oropt,nbr2opt+oropt}`` (``2opt+oropt``, ``decode.batched_local_search_grouped``: Or-opt moves after 2-opt, never a longer tour; the records gain
 ``or_opt_iterations`` and ``local_search_rounds``, the header ``local_search``; ``multi2opt``,
 ``decode.batched_multi_two_opt_grouped``: every sweep applies all disjoint improving 2-opt moves it selects, ``2opt_iterations``
@@ -137,6 +139,11 @@ EXTENSION_ARGS = [
                             help="TSP: how the single-move 2-opt runs: launches (a launch sequence per move) or resident (one "
                                  "GPU block per instance keeps the tours in LDS, no launch or host read per move; same "
                                  "records; needs --local_search 2opt and P * (N + 1) within the library's limit)")),
+    ("--tsp_local_search_mode", dict(type=str, default="launches", choices=("launches", "resident"),
+                                     help="TSP: how the 2-opt + Or-opt search runs: launches (a launch sequence per iteration) or "
+                                          "resident (one GPU block per instance keeps the tours in LDS through both phases and all "
+                                          "rounds; same records; needs --local_search 2opt+oropt and P * (N + 1) within the "
+                                          "library's limit)")),
     ("--local_search", dict(type=str, default="2opt", choices=("2opt", "2opt+oropt", "multi2opt", "multi2opt+oropt", "nbr2opt+oropt"),
                              help="tour refinement: 2opt (the reference's), 2opt+oropt (rounds of 2-opt and Or-opt segment moves; "
                                   "records gain or_opt_iterations and local_search_rounds) or multi2opt (every sweep applies all "
@@ -231,6 +238,9 @@ def parse_args(argv=None):
     if args.two_opt_mode != "launches" and (args.task != "tsp" or args.local_search != "2opt"):
         parser.error(f"--two_opt_mode {args.two_opt_mode} runs the single-move 2-opt of TSP tours: pass --task tsp "
                      "--local_search 2opt")
+    if args.tsp_local_search_mode != "launches" and (args.task != "tsp" or args.local_search != "2opt+oropt"):
+        parser.error(f"--tsp_local_search_mode {args.tsp_local_search_mode} runs the 2-opt + Or-opt search of TSP tours: pass "
+                     "--task tsp --local_search 2opt+oropt")
     if args.tsp_local_search_kicks < 0 or not 1 <= args.tsp_local_search_kick_size <= 64 or args.tsp_local_search_kick_span < 1:
         parser.error("--tsp_local_search_kicks must be >= 0, --tsp_local_search_kick_size in 1 .. 64 and "
                      "--tsp_local_search_kick_span >= 1")
@@ -452,7 +462,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
                 tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1,
                 two_opt_mode: str = "launches", tsp_local_search_candidates: int = 0,
-                tsp_local_search_closing: str = "full") -> List[dict]:
+                tsp_local_search_closing: str = "full", tsp_local_search_mode: str = "launches") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -482,6 +492,7 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
                                   **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}),
                                   **(dict(two_opt_mode="resident") if two_opt_mode == "resident" else {}),
+                                  **(dict(local_search_mode="resident") if tsp_local_search_mode == "resident" else {}),
                                   **(dict(local_search_candidates=tsp_local_search_candidates,
                                           local_search_closing=tsp_local_search_closing == "full")
                                      if tsp_local_search_candidates > 0 else {}))
@@ -492,6 +503,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                        tsp_local_search_closing=tsp_local_search_closing)
                 if two_opt_mode == "resident":
                     records[-1].update(two_opt_mode="resident")
+                if tsp_local_search_mode == "resident":
+                    records[-1].update(tsp_local_search_mode="resident")
                 if tsp_local_search_window > 0:
                     records[-1].update(tsp_local_search_window=tsp_local_search_window,
                                        tsp_local_search_passes=tsp_local_search_passes)
@@ -591,7 +604,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_window=args.tsp_local_search_window,
                                tsp_local_search_passes=args.tsp_local_search_passes, two_opt_mode=args.two_opt_mode,
                                tsp_local_search_candidates=args.tsp_local_search_candidates,
-                               tsp_local_search_closing=args.tsp_local_search_closing)
+                               tsp_local_search_closing=args.tsp_local_search_closing,
+                               tsp_local_search_mode=args.tsp_local_search_mode)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -616,6 +630,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["mixed_size_chunks"] = True
             if args.two_opt_mode == "resident":
                 line["two_opt_mode"] = "resident"
+            if args.tsp_local_search_mode == "resident":
+                line["tsp_local_search_mode"] = "resident"
             if args.local_search != "2opt":
                 line["local_search"] = args.local_search
             if args.mis_local_search != "none":

@@ -18,7 +18,8 @@ import torch
 
 from . import decode
 from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_tsp_candidates, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
-                     check_tsp_kicks, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours, merge_tours_batch)
+                     check_tsp_kicks, check_tsp_local_search_mode, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours,
+                     merge_tours_batch)
 from .graph import knn_edge_index_gpu
 
 
@@ -42,7 +43,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               local_search: str = "2opt", local_search_kicks: int = 0, local_search_kick_size: int = TSP_KICK_SIZE,
               local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
               local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1,
-              two_opt_mode: str = "launches", local_search_candidates: int = 0, local_search_closing: bool = True):
+              two_opt_mode: str = "launches", local_search_candidates: int = 0, local_search_closing: bool = True,
+              local_search_mode: str = "launches"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -88,16 +90,20 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     of "multi2opt+oropt" on the same lists (``decode.batched_nbr_local_search_torch``), closed by full rounds with
     ``local_search_closing``.  It is a name of its own, not "multi2opt+oropt" with K > 0: that combination stays refused, as the
     host tests of the neighbour-list 2-opt pin.  info holds what "multi2opt+oropt" gives, ``local_search_candidates``,
-    ``local_search_closing``, ``local_search_full_sweeps`` and ``local_search_full_rounds``."""
+    ``local_search_closing``, ``local_search_full_sweeps`` and ``local_search_full_rounds``.  ``local_search_mode``: "launches"
+    (default) or "resident" (only with ``local_search="2opt+oropt"``, else ``ValueError``): that search runs with one GPU block
+    for the instance (``mode="resident"`` of ``decode.batched_local_search_torch``), same tours and info; the
+    ``parallel_sampling`` tours must fit its limit, there is no fallback."""
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
+    ls_mode = check_tsp_local_search_mode(local_search, local_search_mode)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
-    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
+    search = (local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
     n = pts64.shape[0]
@@ -224,11 +230,11 @@ def _kick_key(seed) -> int:
 
 def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, dev, seeds, offsets, heat, edge_index, kick_stats):
     """The local search of one round on the merged tours, through the ``decode.batched_*`` wrapper of ``form`` ("torch",
-    "grouped" or "ragged") that ``search`` - the checked (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size,
+    "grouped" or "ragged") that ``search`` - the checked (local_search, (two_opt_method, two_opt_mode, local_search_mode), window, passes, kicks, kick_size,
     kick_span, descent, kick_bias) - selects.  ``seeds`` / ``offsets``: the Philox key and first offset of every tour, read by
     the kicked searches, as ``heat`` / ``edge_index`` (the round's heatmaps and their graphs) are by heat-biased kicks;
     ``kick_stats`` receives their per-tour arrays.  Returns (tours, iterations, the search's own statistics)."""
-    local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr = search
+    local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr = search
     run = lambda stem, **kw: getattr(decode, f"batched_{stem}_{form}")(points, tours, max_iterations=two_opt_iterations, device=dev, **kw)
     ls_stats = {}
     if local_search == "2opt":
@@ -240,7 +246,7 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
     elif local_search == "multi2opt":
         solved, iterations = run("multi_two_opt", stats=ls_stats)
     elif local_search == "2opt+oropt":
-        solved, iterations = run("local_search", stats=ls_stats)
+        solved, iterations = run("local_search", stats=ls_stats, **(dict(mode="resident") if ls_mode == "resident" else {}))
     elif local_search == "nbr2opt+oropt":
         solved, ls_stats = run("nbr_local_search", candidates=nbr[0], closing=nbr[1],
                                neighbors=_candidate_lists(form, points, edge_index, nbr[0]))
@@ -339,7 +345,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
                     local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
                     local_search_passes: int = 1, two_opt_mode: str = "launches", local_search_candidates: int = 0,
-                    local_search_closing: bool = True) -> List[tuple]:
+                    local_search_closing: bool = True, local_search_mode: str = "launches") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -359,17 +365,19 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     round (the tensors the merge received, on the device) and its own graph.  ``local_search_window``,
     ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets.  ``two_opt_mode``: as ``solve_tsp``,
     one GPU block per instance, for arrays and sequences of instances alike.  ``local_search_candidates``,
-    ``local_search_closing``: as ``solve_tsp``, per instance, for arrays and sequences alike."""
+    ``local_search_closing``: as ``solve_tsp``, per instance, for arrays and sequences alike.  ``local_search_mode``: as
+    ``solve_tsp``, one GPU block per instance, for arrays and sequences of instances alike."""
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
     two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
+    ls_mode = check_tsp_local_search_mode(local_search, local_search_mode)
     kicks, kick_size, kick_span = check_tsp_kicks(local_search, local_search_kicks, local_search_kick_size, local_search_kick_span)
     descent = check_tsp_descent(local_search_descent, kicks)
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
-    search = (local_search, (two_opt_method, two_opt_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
+    search = (local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
                                seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search)

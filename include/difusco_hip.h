@@ -671,6 +671,37 @@ int difusco_tsp_local_search_ragged(int groups, const int32_t* group_n, const in
                                     int32_t* tours, int64_t max_iterations, int max_rounds, void* workspace, size_t workspace_bytes,
                                     int64_t* two_opt_iterations_out, int64_t* or_opt_iterations_out, int32_t* rounds_out, void* stream);
 
+/* Resident local search (additive to ABI 13): difusco_tsp_local_search_ragged with one resident GPU block per group.  The arrays
+ * and conventions of that entry, and THE SAME RULE: group g ends with exactly the tours, two_opt_iterations_out[g],
+ * or_opt_iterations_out[g] and rounds_out[g] that difusco_tsp_local_search_ragged gives it - the rounds of (exact 2-opt phase,
+ * Or-opt phase), max_iterations per phase, the threshold -1e-6, the flat-index ties, the one evaluated 2-opt move at
+ * max_iterations = 0, the stop after a round with b = 0 or after max_rounds rounds.  What differs is the execution: a block keeps
+ * the tours of its group, their points in tour order, the group's points, the edge lengths, the best move of every tour and the
+ * stretch an Or-opt move shifts in LDS and runs step after step - sweep, argmin per tour, group minimum, stop test, moves, switch
+ * of phase and round - between block barriers, without a launch or a host read per step.  A STEP is one 2-opt move of the group
+ * or one counted Or-opt iteration.
+ * A group fits if group_tours[g] * (group_n[g] + 1) <= difusco_tsp_local_search_resident_max_cells(), a constant of the build,
+ * >= 2048 (TSP-500 with 4 tours: 2004 cells).  The sizes are host arrays, so a group above the limit is refused on the host
+ * before any GPU work: DIFUSCO_EUNSUPPORTED, the message names the group, its cells and the limit, `tours` is untouched; there
+ * is no fallback to the launched entry.
+ * steps_per_launch: a launch applies at most that many steps per group; 0 = the library's default (1024).  The tours and the
+ * state of every group (phase, round, iterations of the phase, the counters) stay in global memory between launches, a stopped
+ * group's block returns at once.  A launch ends for a group when the group stops or when a sweep finds a move after
+ * steps_per_launch steps; the next launch repeats that sweep.  The host reads the state once after each launch and enqueues
+ * another one only if a group still runs: one host synchronisation per launch that ran, none inside a launch, and
+ * max(1, ceil(steps of the slowest group / steps_per_launch)) launches per call; host_syncs_out (HOST, optional) reports the
+ * number.
+ * workspace: _workspace_bytes, a few bytes per group.  DIFUSCO_EINVAL before any GPU work on everything
+ * difusco_tsp_local_search_ragged refuses, on steps_per_launch < 0 and on a workspace below _workspace_bytes.  Blocks until every
+ * group is done. */
+int difusco_tsp_local_search_resident_max_cells(void);
+int difusco_tsp_local_search_resident_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes);
+int difusco_tsp_local_search_resident(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                      int32_t* tours, int64_t max_iterations, int max_rounds, int32_t steps_per_launch /* 0 = default */,
+                                      void* workspace, size_t workspace_bytes, int64_t* two_opt_iterations_out /* host */,
+                                      int64_t* or_opt_iterations_out /* host */, int32_t* rounds_out /* host */,
+                                      int32_t* host_syncs_out /* host, optional */, void* stream);
+
 /* Multi-move 2-opt (additive to ABI 13; not in the reference, which applies one move per sweep): the arrays, conventions and
  * limits of difusco_tsp_two_opt_ragged.  Every TOUR runs on its own.  With P_k the point at position k of the closed tour
  * (P_n = P_0) and d_k = |P_k P_k+1|, one SWEEP of a tour of n nodes is:
