@@ -18,10 +18,10 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip.so")
 PROF_LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip_prof.so")
-SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "two_opt_resident.hip", "or_opt.hip", "local_search_resident.hip", "two_opt_multi.hip", "or_opt_multi.hip", "or_opt_nbr.hip", "tsp_window_search.hip", "knn.hip", "mis_decode.hip", "mis_local_search.hip", "mis_resident_search.hip", "formats.hip", "graph_build.hip", "api.hip"]
+SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "or_opt.hip", "tsp_resident.hip", "two_opt_multi.hip", "or_opt_multi.hip", "or_opt_nbr.hip", "tsp_window_search.hip", "knn.hip", "mis_decode.hip", "mis_local_search.hip", "mis_resident_search.hip", "formats.hip", "graph_build.hip", "api.hip"]
 PROF_SOURCES = SOURCES + ["edge_layer_abl.hip", "stage_lab.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "edge_layer_common.h"), os.path.join(CSRC, "edge_layer_kernel.h"),
-           os.path.join(CSRC, "two_opt_common.h"), os.path.join(CSRC, "resident_team.h"), os.path.join(CSRC, "or_opt_move.h"), os.path.join(CSRC, "multi_move_common.h"), os.path.join(CSRC, "or_opt_rows.h"), os.path.join(CSRC, "nbr_rows.h"), os.path.join(CSRC, "or_opt_focused.h"),
+           os.path.join(CSRC, "two_opt_common.h"), os.path.join(CSRC, "or_opt_move.h"), os.path.join(CSRC, "multi_move_common.h"), os.path.join(CSRC, "or_opt_rows.h"), os.path.join(CSRC, "nbr_rows.h"), os.path.join(CSRC, "or_opt_focused.h"),
            os.path.join(CSRC, "or_opt_heat.h"),
            os.path.join(os.path.dirname(PKG), "include", "difusco_hip.h")]
 
@@ -50,11 +50,9 @@ EXTRA_FLAGS["formats.hip"] = ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-
 EXTRA_FLAGS["graph_build.hip"] = ["-ffp-contract=off"]
 # or_opt.hip reproduces a numpy float64 program bit for bit (its arithmetic is written with the rounding intrinsics as well)
 EXTRA_FLAGS["or_opt.hip"] = ["-ffp-contract=off"]
-# two_opt_resident.hip equals two_opt.hip bit for bit: the shared arithmetic is written with the rounding intrinsics, and nothing
-# else in the file may contract either
-EXTRA_FLAGS["two_opt_resident.hip"] = ["-ffp-contract=off"]
-# local_search_resident.hip equals or_opt.hip (and tests/or_opt_emulation.py) bit for bit, likewise
-EXTRA_FLAGS["local_search_resident.hip"] = ["-ffp-contract=off"]
+# tsp_resident.hip: its 2-opt entry equals two_opt.hip bit for bit and its local search or_opt.hip (and tests/or_opt_emulation.py):
+# the shared arithmetic is written with the rounding intrinsics, and nothing else in the file may contract either
+EXTRA_FLAGS["tsp_resident.hip"] = ["-ffp-contract=off"]
 # two_opt_multi.hip likewise: its tours equal tests/multi_two_opt_emulation.py and tests/nbr_two_opt_emulation.py bit for bit
 EXTRA_FLAGS["two_opt_multi.hip"] = ["-ffp-contract=off"]
 # or_opt_multi.hip likewise: tests/multi_local_search_emulation.py

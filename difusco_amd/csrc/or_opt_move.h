@@ -1,4 +1,4 @@
-// What the launched local search (or_opt.hip) and the resident one (local_search_resident.hip) share beside two_opt_common.h: the
+// What the launched local search (or_opt.hip) and the resident one (tsp_resident.hip) share beside two_opt_common.h: the
 // Or-opt variants, the threshold, the phases of a group and the Or-opt move on one tour.  Per translation unit (anonymous
 // namespace), like two_opt_common.h.
 #pragma once

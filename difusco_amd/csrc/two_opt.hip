@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void two_opt_apply_kernel(A a, int* __restrict
 //  Nothing above depends on n: the bound is per pair, from M alone, so in a ragged call (difusco_tsp_two_opt_ragged) it holds
 //  for every tour with the M of its own group, whatever the sizes of the other groups.
 //  kScreenEpsPerM, kScreenMinM / kScreenMaxM, screen_eps, f32_key and change32 are in two_opt_common.h: the resident 2-opt
-//  (two_opt_resident.hip) screens with them as well.
+//  (tsp_resident.hip) screens with them as well.
 constexpr int SCH = 256 * JPT;                     // columns per chunk of the screen
 
 // gmax[g] = bits of the largest |coordinate| of group g (non-negative doubles order like their bits; a NaN sorts above inf)

@@ -1,4 +1,4 @@
-// What the 2-opt entries (two_opt.hip), the resident 2-opt (two_opt_resident.hip) and the local search (or_opt.hip) share: the
+// What the 2-opt entries (two_opt.hip), the resident searches (tsp_resident.hip) and the local search (or_opt.hip) share: the
 // float64 distance and pair change, the float32 pair change of the screen and its bound, the (min, first flat
 // index) reductions, the prep entry, one block of the exact 2-opt sweep and the segment reversal; and the check of the group
 // arrays that every _ragged tour entry starts with.  Every function is
