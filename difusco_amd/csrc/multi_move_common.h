@@ -1,4 +1,4 @@
-// What the multi-move searches share (two_opt_multi.hip, or_opt_multi.hip, or_opt_nbr.hip, tsp_window_search.hip; the Or-opt row
+// What the multi-move searches share (two_opt_multi.hip, or_opt_multi.hip with its headers, tsp_window_search.hip; the Or-opt row
 // loop is in or_opt_rows.h, the neighbour stage in nbr_rows.h): the row-best loop of the 2-opt, the selection of a set of
 // proposals with pairwise disjoint position ranges and, at the end, the host side the group-wise entries share - the tour
 // descriptor, the walk over the groups that fills it and the launch loop with its poll.  Every function is per translation unit
@@ -408,7 +408,7 @@ __device__ __forceinline__ void kick_swaps(int* __restrict__ tour, const int* __
   }
 }
 
-// ---- the host side the group-wise entries share (two_opt_multi.hip, or_opt_multi.hip, or_opt_nbr.hip)
+// ---- the host side the group-wise entries share (two_opt_multi.hip, or_opt_multi.hip)
 
 int table_levels(int n) {                          // floor(log2(n + 1)) + 1
   int l = 0;
@@ -418,8 +418,8 @@ int table_levels(int n) {                          // floor(log2(n + 1)) + 1
 
 struct TourDesc {          // a tour of a call; offsets in elements of the array they index
   int n, nblk_two, nblk_or, group;   // row tiles of a full 2-opt sweep (rows 0 .. n - 3) and of a full Or-opt sweep (0 .. n - 2)
-  long long points;        // the group's first coordinate in `points` (doubles)
-  long long nbr;           // the group's first entry in `neighbors` (n K per group; 0 without lists)
+  long long points;        // the group's first coordinate in `points` (doubles, 2 n per group); a group's first entry in
+                           // `neighbors` (n K per group) follows from it: (points >> 1) K, see nbr_walk (nbr_rows.h)
   long long closed;        // the tour's first entry in tours, tp, marks and cum (n + 1 per tour)
   long long cols;          //                       in dlen, rowv, rowj, live, winners, pos and rowkey (n per tour)
   long long table;         //                       in tabv and tabi (levels (n + 1) per tour)
@@ -427,7 +427,7 @@ struct TourDesc {          // a tour of a call; offsets in elements of the array
 
 struct GroupTotals {       // of a call: the tours, the largest group and its row tiles, the elements the sections hold
   int tours, nmax, nblk_two, nblk_or;
-  size_t closed, cols, cells, points, nbr;
+  size_t closed, cols, cells, points;
 };
 
 // Checks the group arrays of a _ragged entry and, with `lists`, K, closing and the launch limit of the n K list entries of a
@@ -447,14 +447,13 @@ int walk_groups(const char* who, int groups, const int32_t* group_n, const int32
     if (n > tot->nmax) tot->nmax = n, tot->nblk_two = nblk_two, tot->nblk_or = nblk_or;
     for (int p = 0; p < group_tours[g]; ++p) {
       if (tab)
-        tab->push_back(TourDesc{n, nblk_two, nblk_or, g, (long long)tot->points, (long long)tot->nbr, (long long)tot->closed,
-                                (long long)tot->cols, (long long)tot->cells});
+        tab->push_back(TourDesc{n, nblk_two, nblk_or, g, (long long)tot->points, (long long)tot->closed, (long long)tot->cols,
+                                (long long)tot->cells});
       tot->closed += (size_t)n + 1;
       tot->cols += (size_t)n;
       tot->cells += (size_t)table_levels(n) * ((size_t)n + 1);
     }
     tot->points += 2 * (size_t)n;
-    if (lists) tot->nbr += (size_t)n * (size_t)K;
   }
   return DIFUSCO_OK;
 }

@@ -1,4 +1,4 @@
-// The neighbour stage of the neighbour-list searches (two_opt_multi.hip, or_opt_nbr.hip), once: a row of a sweep evaluates only
+// The neighbour stage of the neighbour-list searches (two_opt_multi.hip, or_opt_nbr.h), once: a row of a sweep evaluates only
 // its CANDIDATE columns - the moves one of whose new edges joins a city to one of its listed neighbours, in either direction.
 //   nbr_reset_row   entry k of a tour in front of a sweep: pos[city] = its position, rowkey = no key, rowj = -1;
 //   nbr_walk        thread (position p, list slot s) of a tour: x = tour[p], y = its s-th listed city, q = pos[y]; the 2-opt pairs
@@ -77,7 +77,7 @@ __device__ __forceinline__ void nbr_walk(const TourDesc& d, bool or_opt, const i
   if (e >= (long long)d.n * K) return;
   const int p = (int)(e / K), slot = (int)(e % K);
   const int x = tours[d.closed + p];
-  const int y = neighbors[d.nbr + (long long)x * K + slot];
+  const int y = neighbors[(d.points >> 1) * K + (long long)x * K + slot];   // the group's lists start at (cities before it) K
   if (y < 0 || y >= d.n || y == x) return;                       // a pad: nothing is indexed with it
   const int q = pos[d.cols + y];
   if (or_opt)

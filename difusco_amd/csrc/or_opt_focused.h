@@ -169,13 +169,13 @@ __device__ __forceinline__ void focused_cols(const double2* __restrict__ P, cons
 // blocks 0 .. split - 1 of a tour are its row part (one list entry each), the blocks behind them its column part (a tile each);
 // the host fixes both counts from the largest n of the call, the list lengths live in `foc`, surplus blocks return at once
 __global__ __launch_bounds__(256) void mls_focused_row_best_kernel(
-    const double2* __restrict__ tp, const double* __restrict__ dlen, const MlTour* __restrict__ desc, double* __restrict__ rowv,
+    const double2* __restrict__ tp, const double* __restrict__ dlen, const TourDesc* __restrict__ desc, double* __restrict__ rowv,
     int* __restrict__ rowj, const MlTourState* __restrict__ ts, const MlFocus* __restrict__ foc, const int* __restrict__ arows,
     const int* __restrict__ acols, const int2* __restrict__ marks, int split) {
   const MlFocus f = foc[blockIdx.y];
   const int phase = ts[blockIdx.y].phase;                        // uniform over the block
   if (f.mode != kFocused || (phase != kTwoOpt && phase != kOrOpt)) return;
-  const MlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   const double2* P = tp + d.closed;
   const double* D = dlen + d.cols;
   if ((int)blockIdx.x < split) {
@@ -279,15 +279,15 @@ __device__ __forceinline__ void focus_rebuild(const int* __restrict__ tour, cons
 
 // `full`: the phase words mls_row_best_kernel reads - a tour's own while it is in a full descent, kDone while it is focused
 __global__ __launch_bounds__(kSelectThreads) void mls_select_focused_kernel(
-    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
     int compact_select_max, MlState* st, MlGroup* grp, MlTourState* ts, MlTourState* full, MlFocus* foc, int* __restrict__ smark_all,
     int* __restrict__ tmark_all, int* __restrict__ arows_all, int* __restrict__ acols_all) {
   const int t = blockIdx.x;
   if (foc[t].mode != kFocused) {                                 // written by thread 0 of the keep / kick step only
-    mls_select_tour<true>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
-                          max_iterations, max_rounds, select_rounds, st, grp, ts);
+    mls_select_tour<kSelectIterated>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                                     max_iterations, max_rounds, select_rounds, st, grp, ts);
     if (threadIdx.x == 0) full[t].phase = ts[t].phase;
     return;
   }
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_focused_kernel(
   const int phase = s->phase, round = s->round, or_moved = s->or_moved;
   const long long sweeps = s->sweeps;
   if (phase != kTwoOpt && phase != kOrOpt) return;
-  const MlTour d = desc[t];
+  const TourDesc d = desc[t];
   const int n = d.n, rows = phase == kTwoOpt ? n - 2 : n - 1;
   const bool or_opt = phase == kOrOpt;
   int* tour = tours + d.closed;
@@ -372,14 +372,14 @@ __global__ __launch_bounds__(kSelectThreads) void mls_select_focused_kernel(
 // kick (kicks > 0): the closing full descent of the incumbent starts; at its keep the tour is done.  kHeat: as there.
 template <bool kHeat>
 __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_focused_kernel(
-    const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const MlTour* __restrict__ desc,
+    const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const TourDesc* __restrict__ desc,
     const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets, int kicks, int kick_size,
     int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters, MlTourState* full, MlFocus* foc,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, int* __restrict__ smark_all, int* __restrict__ tmark_all,
     int* __restrict__ arows_all, int* __restrict__ acols_all, HeatArgs<kHeat> hx) {
   const int t = blockIdx.x;
   if (ts[t].phase != kKeep) return;                              // written by thread 0 of this block at its end only
-  const MlTour d = desc[t];
+  const TourDesc d = desc[t];
   const int n = d.n;
   int* tour = tours + d.closed;
   int* inc = inc_all + d.closed;

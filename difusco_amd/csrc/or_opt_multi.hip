@@ -6,8 +6,8 @@
 // One sweep is three launches, whatever the phases of the tours:
 //   mls_prep_kernel       tp / dlen of every tour that is still running (prep_entry);
 //   mls_row_best_kernel   one block per (row tile of 16, tour), the loop of the tour's phase.  2-opt: row_best_tile
-//                         (multi_move_common.h), the loop of two_opt_multi.hip.  Or-opt: or_row_best_tile (or_opt_rows.h, shared
-//                         with or_opt_nbr.hip), the loop of or_opt_tile -
+//                         (multi_move_common.h), the loop of two_opt_multi.hip.  Or-opt: or_row_best_tile (or_opt_rows.h), the
+//                         loop of or_opt_tile -
 //                         a thread keeps 4 columns of every 1024-column chunk in registers, walks the rows of the tile upwards and
 //                         carries |P_j P_i+2|, |P_j P_i+3| (and the two from P_j+1) to the next row, two square roots per (i, j)
 //                         for all five variants; the row-only terms are computed once per tile in LDS - with 16 running bests
@@ -28,14 +28,18 @@
 // the first cut of a draw is drawn by the heat of the incumbent's edges (or_opt_heat.h).  Both keep / kick kernels draw a kick
 // with kick_draws here and apply it with kick_swaps (multi_move_common.h, which also holds what the window search of
 // tsp_window_search.hip shares with this file: PhaseRange, or_opt_winners, tour_length).
+// The listed search (difusco_tsp_nbr_local_search_ragged) is one descent whose rounds start in a neighbour stage: its row kernels
+// (or_opt_nbr.h, included behind the select kernels here) replace the first two, and the select step is the one here with the
+// switch of stage (mls_select_tour<kSelectListed>).
 //
-// The host side of all four entries is at the end of this file, once: mls_layout describes the workspace - the sections of the
-// descent and, as the entry needs them, the iterated state, the focus state and the heat tables - and builds the host tables
-// (the walk over the groups and the launch loop with its poll are multi_move_common.h's, shared with two_opt_multi.hip and
-// or_opt_nbr.hip),
+// The host side of all five entries is at the end of this file, once: mls_layout describes the workspace - the sections of the
+// descent and, as the entry needs them, the list sections, the iterated state, the focus state and the heat tables - and builds
+// the host tables (the walk over the groups and the launch loop with its poll are multi_move_common.h's, shared with
+// two_opt_multi.hip),
 // MlPtrs holds the sections as typed pointers, and mls_run(MlCall) checks the arguments, sets the state up, enqueues launch
 // sequences under their bound, polls, reads the state back and reduces it to the outputs.  The entries fill an MlCall: its mode
-// (one descent, iterated, iterated with focused descents), whether the kicks are drawn by heat, the arguments and the outputs.
+// (one descent, one descent on neighbour lists, iterated, iterated with focused descents), whether the kicks are drawn by heat,
+// the arguments and the outputs.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -45,23 +49,25 @@
 #include "common.h"
 #include "kernels.h"
 #include "multi_move_common.h"
-#include "or_opt_rows.h"      // LMAX, or_delta, or_row_best_tile: shared with or_opt_nbr.hip
+#include "or_opt_rows.h"      // LMAX, or_delta, or_row_best_tile
 #include "two_opt_common.h"
 
 namespace difusco {
 namespace {
 
-enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2, kKeep = 3 };   // kKeep: the iterated search only
-
-struct MlTour {            // TourDesc (multi_move_common.h) without the lists: the kernels here keep the record they were built on
-  int n, nblk_two, nblk_or, group;
-  long long points, closed, cols, table;
-};
+// kKeep: the iterated search only.  kFullTwoOpt, kFullOrOpt: the listed search only - its tours start in the neighbour stage,
+// where kTwoOpt and kOrOpt are the phases on neighbour rows, and go on in the full stage with these two
+enum Phase : int { kTwoOpt = 0, kOrOpt = 1, kDone = 2, kKeep = 3, kFullTwoOpt = 4, kFullOrOpt = 5 };
 
 struct MlTourState {       // device-resident loop state of a tour, zero at the start of a call
   int phase, round;        // round: zero-based
   int or_moved, pad;       // the Or-opt phase of this round has applied a move
   long long sweeps, two_opt_sweeps, or_opt_sweeps, two_opt_moves, or_opt_moves;   // sweeps: in which the tour moved
+};
+
+struct MlStage {           // what the listed search counts of a tour's full stage, behind the MlTourState records; zero at the start
+  long long full_sweeps;   // sweeps in which the tour moved in the full stage
+  int full_rounds, pad;    // rounds run in the full stage
 };
 
 struct MlGroup {           // tours of the group, and how many of them are done (zero at the start of a call)
@@ -73,18 +79,18 @@ struct MlState {
   int pad;
 };
 
-__global__ void mls_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const MlTour* __restrict__ desc,
+__global__ void mls_prep_kernel(const double* __restrict__ points, const int* __restrict__ tours, const TourDesc* __restrict__ desc,
                                 double2* __restrict__ tp, double* __restrict__ dlen, const MlTourState* __restrict__ ts) {
-  const MlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k > d.n || ts[blockIdx.y].phase == kDone) return;
   prep_entry(points + d.points, tours + d.closed, d.n, k, tp + d.closed, dlen + d.cols);
 }
 
 __global__ __launch_bounds__(256) void mls_row_best_kernel(const double2* __restrict__ tp, const double* __restrict__ dlen,
-                                                           const MlTour* __restrict__ desc, double* __restrict__ rowv,
+                                                           const TourDesc* __restrict__ desc, double* __restrict__ rowv,
                                                            int* __restrict__ rowj, const MlTourState* __restrict__ ts) {
-  const MlTour d = desc[blockIdx.y];
+  const TourDesc d = desc[blockIdx.y];
   const int phase = ts[blockIdx.y].phase;                        // uniform over the block
   if (phase == kDone || (int)blockIdx.x >= (phase == kTwoOpt ? d.nblk_two : d.nblk_or)) return;
   const int i0 = blockIdx.x * TI;
@@ -99,18 +105,25 @@ __device__ __forceinline__ void report_done(MlGroup* g, MlState* st) {
   if (atomicAdd(&g->done, 1) == g->count - 1) atomicAdd(&st->done, 1);
 }
 
-// the select step of one tour (the block).  kIterated: where the descent ends, the tour goes to the keep / kick step of the
-// iterated search (mls_keep_kick_kernel) instead of being done.
-template <bool kIterated>
+enum SelectMode : int { kSelectPlain = 0, kSelectIterated = 1, kSelectListed = 2 };
+
+// the select step of one tour (the block).  kSelectIterated: where the descent ends, the tour goes to the keep / kick step of the
+// iterated search (mls_keep_kick_kernel) instead of being done.  kSelectListed: the tour starts in the neighbour stage; an Or-opt
+// phase without a move there ends the stage, and with `closing` the round goes on with full phases, counted in stages[t].
+// The other two modes read neither `closing` nor `stages`.
+template <SelectMode kMode>
 __device__ __forceinline__ void mls_select_tour(
-    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
-    MlState* st, MlGroup* grp, MlTourState* ts) {
+    MlState* st, MlGroup* grp, MlTourState* ts, int closing = 0, MlStage* stages = nullptr) {
+  constexpr bool kListed = kMode == kSelectListed;
   const int t = blockIdx.x;
-  const int phase = ts[t].phase;                                 // written by thread 0 of this block at its end only
-  if (phase == kDone) return;
-  const MlTour d = desc[t];
+  const int word = ts[t].phase;                                  // written by thread 0 of this block at its end only
+  if (word == kDone) return;
+  const bool full = kListed && word >= kFullTwoOpt;              // the tour is in the full stage of the listed search
+  const int phase = full ? word - kFullTwoOpt : word;            // kTwoOpt or kOrOpt, in either stage
+  const TourDesc d = desc[t];
   const int n = d.n;
   const int* rowj = rowj_all + d.cols;
   int* winners = winners_all + d.cols;
@@ -122,18 +135,23 @@ __device__ __forceinline__ void mls_select_tour(
   if (total == 0) {                                              // no proposal: the phase ends
     if (threadIdx.x == 0) {
       if (phase == kTwoOpt) {
-        s->phase = kOrOpt;
+        s->phase = full ? kFullOrOpt : kOrOpt;
         s->or_moved = 0;
+      } else if (kListed && !full && !s->or_moved && closing) {  // the neighbour stage ends: the round goes on with full phases
+        s->phase = kFullTwoOpt;
+        stages[t].full_rounds = 1;
       } else if (!s->or_moved || s->round + 1 >= max_rounds) {
-        if constexpr (kIterated) {
+        if constexpr (kMode == kSelectIterated) {
           s->phase = kKeep;
         } else {
           s->phase = kDone;
           report_done(grp + d.group, st);
         }
       } else {
-        s->phase = kTwoOpt;
+        s->phase = full ? kFullTwoOpt : kTwoOpt;
         s->round += 1;
+        if constexpr (kListed)
+          if (full) stages[t].full_rounds += 1;
       }
     }
     return;
@@ -144,6 +162,8 @@ __device__ __forceinline__ void mls_select_tour(
     or_opt_winners(tours + d.closed, (int*)(cum_all + d.closed), winners, rowj, n, total);   // cum is free after the selection
   if (threadIdx.x == 0) {
     s->sweeps += 1;
+    if constexpr (kListed)
+      if (full) stages[t].full_sweeps += 1;
     if (phase == kTwoOpt) {
       s->two_opt_sweeps += 1;
       s->two_opt_moves += total;
@@ -153,7 +173,7 @@ __device__ __forceinline__ void mls_select_tour(
       s->or_moved = 1;
     }
     if (s->sweeps >= max_iterations) {
-      if constexpr (kIterated) {
+      if constexpr (kMode == kSelectIterated) {
         s->phase = kKeep;
       } else {
         s->phase = kDone;
@@ -164,29 +184,40 @@ __device__ __forceinline__ void mls_select_tour(
 }
 
 __global__ __launch_bounds__(kSelectThreads) void mls_select_kernel(
-    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
     MlState* st, MlGroup* grp, MlTourState* ts) {
-  mls_select_tour<false>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
-                         max_iterations, max_rounds, select_rounds, st, grp, ts);
+  mls_select_tour<kSelectPlain>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                                max_iterations, max_rounds, select_rounds, st, grp, ts);
+}
+
+// the listed search (difusco_tsp_nbr_local_search_ragged): its row kernels are in or_opt_nbr.h
+__global__ __launch_bounds__(kSelectThreads) void mls_select_listed_kernel(
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
+    int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
+    int closing, MlState* st, MlGroup* grp, MlTourState* ts, MlStage* stages) {
+  mls_select_tour<kSelectListed>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                                 max_iterations, max_rounds, select_rounds, st, grp, ts, closing, stages);
 }
 
 // ---- the iterated search (difusco_tsp_iterated_search_ragged): descents of the search above with seeded segment kicks between
 // them.  The rule is stated in include/difusco_hip.h and restated in numpy in tests/tsp_iterated_search_emulation.py.
 
 __global__ __launch_bounds__(kSelectThreads) void mls_select_iterated_kernel(
-    int* __restrict__ tours, const MlTour* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
+    int* __restrict__ tours, const TourDesc* __restrict__ desc, const double* __restrict__ rowv_all, const int* __restrict__ rowj_all,
     int* __restrict__ live_all, int* __restrict__ winners_all, unsigned long long* __restrict__ tabv_all, int* __restrict__ tabi_all,
     int2* __restrict__ marks_all, int2* __restrict__ cum_all, long long max_iterations, int max_rounds, int select_rounds,
     MlState* st, MlGroup* grp, MlTourState* ts) {
-  mls_select_tour<true>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
-                        max_iterations, max_rounds, select_rounds, st, grp, ts);
+  mls_select_tour<kSelectIterated>(tours, desc, rowv_all, rowj_all, live_all, winners_all, tabv_all, tabi_all, marks_all, cum_all,
+                                   max_iterations, max_rounds, select_rounds, st, grp, ts);
 }
 
 }  // namespace
 }  // namespace difusco
 
+#include "or_opt_nbr.h"       // the row kernels of the listed search
 #include "or_opt_heat.h"      // the heat-biased draws of the guided search: its kernels stand here, between the select and the
                               // keep / kick kernels
 
@@ -237,12 +268,12 @@ __device__ __forceinline__ void kick_draws(const unsigned long long* __restrict_
 // kHeat: `a` of a draw comes from the running weights of I (heat_prefix, heat_pick), computed behind the keep copy.
 template <bool kHeat>
 __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
-    const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const MlTour* __restrict__ desc,
+    const double* __restrict__ points, int* __restrict__ tours, int* __restrict__ inc_all, const TourDesc* __restrict__ desc,
     const unsigned long long* __restrict__ seeds, const unsigned long long* __restrict__ offsets, int kicks, int kick_size,
     int span, int no_descent, MlState* st, MlGroup* grp, MlTourState* ts, MlIter* iters, HeatArgs<kHeat> hx) {
   const int t = blockIdx.x;
   if (ts[t].phase != kKeep) return;                              // written by thread 0 of this block at its end only
-  const MlTour d = desc[t];
+  const TourDesc d = desc[t];
   const int n = d.n;
   int* tour = tours + d.closed;
   int* inc = inc_all + d.closed;
@@ -301,15 +332,16 @@ __global__ __launch_bounds__(kSelectThreads) void mls_keep_kick_kernel(
 
 #include "or_opt_focused.h"   // the focused search: its kernels, which use the types and device functions above
 
-// ---- the host side: one workspace description (mls_layout, MlPtrs) and one driver (mls_run) behind the four entries
+// ---- the host side: one workspace description (mls_layout, MlPtrs) and one driver (mls_run) behind the five entries
 
 namespace difusco {
 namespace {
 
-enum MlPart : unsigned { kIterPart = 1, kFocusPart = 2, kHeatPart = 4 };   // the optional parts of a workspace
+enum MlPart : unsigned { kIterPart = 1, kFocusPart = 2, kHeatPart = 4, kListPart = 8 };   // the optional parts of a workspace
 
 struct MlLayout {          // byte offsets; the optional parts follow the descent's in this order, an absent one is empty
   size_t desc, tp, dlen, rowv, rowj, live, winners, tabv, tabi, marks, cum, grp, ts, st;
+  size_t pos, rowkey;                            // kListPart: the sections of nbr_rows.h, in front of grp; and MlStage, in `ts`
   size_t inc, iters;                             // kIterPart: the incumbents and MlIter
   size_t smark, tmark, arows, acols, foc, full;  // kFocusPart
   size_t W, q, htab, hgrp, bad;                  // kHeatPart
@@ -319,21 +351,20 @@ struct MlLayout {          // byte offsets; the optional parts follow the descen
 };
 
 struct MlTables {          // the host tables of a call
-  std::vector<MlTour> tours;
+  std::vector<TourDesc> tours;
   std::vector<MlGroup> groups;
   std::vector<MlHeatTour> heat_tours;            // kHeatPart: a group's first row_ptr / col entry, a tour's first heat entry
   std::vector<MlHeatGroup> heat_groups;
 };
 
-// checks the group arrays (group_edges with kHeatPart) and lays out the workspace of a call that needs `parts`; `tabs`
-// (optional) receives the tables
-int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts,
+// checks the group arrays (K and closing with kListPart, group_edges with kHeatPart) and lays out the workspace of a call that
+// needs `parts`; `tabs` (optional) receives the tables
+int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts, int K, int closing,
                const int32_t* group_edges, MlLayout* L, MlTables* tabs) {
   *L = MlLayout{};
-  std::vector<TourDesc> tab;
-  const int rc = walk_groups(who, groups, group_n, group_tours, false, 0, 0, &L->tot, tabs ? &tab : nullptr);
+  const bool lists = parts & kListPart;
+  const int rc = walk_groups(who, groups, group_n, group_tours, lists, K, closing, &L->tot, tabs ? &tabs->tours : nullptr);
   if (rc != DIFUSCO_OK) return rc;
-  for (const TourDesc& d : tab) tabs->tours.push_back(MlTour{d.n, d.nblk_two, d.nblk_or, d.group, d.points, d.closed, d.cols, d.table});
   const bool heat = parts & kHeatPart;
   if (heat && !group_edges) return set_error(DIFUSCO_EINVAL, "%s: group_edges is null", who);
   for (int g = 0; heat && g < groups; ++g)
@@ -354,7 +385,7 @@ int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_
   const GroupTotals& t = L->tot;
   const size_t T = t.tours;
   Sections s;
-  L->desc = s.take(sizeof(MlTour) * T);
+  L->desc = s.take(sizeof(TourDesc) * T);
   L->tp = s.take(sizeof(double2) * t.closed);
   L->dlen = s.take(sizeof(double) * t.cols);
   L->rowv = s.take(sizeof(double) * t.cols);
@@ -365,8 +396,10 @@ int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_
   L->tabi = s.take(sizeof(int) * t.cells);
   L->marks = s.take(sizeof(int2) * t.closed);
   L->cum = s.take(sizeof(int2) * t.closed);
+  L->pos = s.take(sizeof(int) * t.cols, lists);
+  L->rowkey = s.take(sizeof(unsigned long long) * t.cols, lists);
   L->grp = s.take(sizeof(MlGroup) * groups);
-  L->ts = s.take(sizeof(MlTourState) * T);
+  L->ts = s.take((sizeof(MlTourState) + (lists ? sizeof(MlStage) : 0)) * T);     // with lists T MlStage behind T MlTourState
   L->st = s.take(sizeof(MlState));
   const bool iter = parts & kIterPart, focus = parts & kFocusPart;
   L->inc = s.take(sizeof(int) * t.closed, iter);
@@ -386,18 +419,18 @@ int mls_layout(const char* who, int groups, const int32_t* group_n, const int32_
   return DIFUSCO_OK;
 }
 
-// the four `_workspace_bytes` entries
-int mls_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts,
-                        const int32_t* group_edges, size_t* bytes) {
+// the five `_workspace_bytes` entries
+int mls_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, unsigned parts, int K,
+                        int closing, const int32_t* group_edges, size_t* bytes) {
   if (!bytes) return set_error(DIFUSCO_EINVAL, "%s: bytes is null", who);
   MlLayout lay;
-  const int rc = mls_layout(who, groups, group_n, group_tours, parts, group_edges, &lay, nullptr);
+  const int rc = mls_layout(who, groups, group_n, group_tours, parts, K, closing, group_edges, &lay, nullptr);
   if (rc == DIFUSCO_OK) *bytes = lay.total;
   return rc;
 }
 
 struct MlPtrs {            // the sections of a workspace; those of a part the layout does not hold are never read
-  MlTour* desc;
+  TourDesc* desc;
   double2* tp;
   double *dlen, *rowv;
   int *rowj, *live, *winners;
@@ -407,6 +440,9 @@ struct MlPtrs {            // the sections of a workspace; those of a part the l
   MlGroup* grp;
   MlTourState* ts;
   MlState* st;
+  MlStage* stages;
+  int* pos;
+  unsigned long long* rowkey;
   int* inc;
   MlIter* iters;
   int *smark, *tmark, *arows, *acols;
@@ -419,10 +455,11 @@ struct MlPtrs {            // the sections of a workspace; those of a part the l
   int* bad;
   MlPtrs(void* workspace, const MlLayout& L) {
     char* w = (char*)workspace;
-    desc = (MlTour*)(w + L.desc), tp = (double2*)(w + L.tp), dlen = (double*)(w + L.dlen), rowv = (double*)(w + L.rowv);
+    desc = (TourDesc*)(w + L.desc), tp = (double2*)(w + L.tp), dlen = (double*)(w + L.dlen), rowv = (double*)(w + L.rowv);
     rowj = (int*)(w + L.rowj), live = (int*)(w + L.live), winners = (int*)(w + L.winners);
     tabv = (unsigned long long*)(w + L.tabv), tabi = (int*)(w + L.tabi), marks = (int2*)(w + L.marks), cum = (int2*)(w + L.cum);
     grp = (MlGroup*)(w + L.grp), ts = (MlTourState*)(w + L.ts), st = (MlState*)(w + L.st);
+    stages = (MlStage*)(ts + L.tot.tours), pos = (int*)(w + L.pos), rowkey = (unsigned long long*)(w + L.rowkey);
     inc = (int*)(w + L.inc), iters = (MlIter*)(w + L.iters);
     smark = (int*)(w + L.smark), tmark = (int*)(w + L.tmark), arows = (int*)(w + L.arows), acols = (int*)(w + L.acols);
     foc = (MlFocus*)(w + L.foc), full = (MlTourState*)(w + L.full);
@@ -433,9 +470,10 @@ struct MlPtrs {            // the sections of a workspace; those of a part the l
 
 thread_local int g_host_syncs = 0;   // host synchronisations of this thread's last iterated call (difusco_tsp_search_host_syncs)
 
-enum MlMode : int { kPlain = 0, kIterFull = 1, kIterFocused = 2 };   // one descent; descents and kicks; focused descents after kicks
+// one descent; descents and kicks; focused descents after kicks; one descent that starts on neighbour lists
+enum MlMode : int { kPlain = 0, kIterFull = 1, kIterFocused = 2, kListed = 3 };
 
-struct MlCall {            // a call of one of the four entries
+struct MlCall {            // a call of one of the five entries
   const char* who;         // the entry, in front of every message
   MlMode mode;
   bool heat;               // the kicks are drawn by heat (the guided entry)
@@ -445,6 +483,8 @@ struct MlCall {            // a call of one of the four entries
   const int32_t *group_n, *group_tours;
   const double* points;
   int32_t* tours;
+  const int32_t* neighbors;                      // kListed, with K and closing
+  int K, closing;
   int64_t max_iterations;
   int max_rounds, select_rounds;
   int32_t kicks, kick_size, span;                // from here to `heat_values`: the iterated modes
@@ -457,6 +497,8 @@ struct MlCall {            // a call of one of the four entries
   int64_t *two_opt_sweeps_out, *or_opt_sweeps_out;
   int32_t* rounds_out;
   int64_t *two_opt_moves_out, *or_opt_moves_out;
+  int64_t* full_sweeps_out;                      // kListed: the two counters of the full stage, [groups]
+  int32_t* full_rounds_out;
   int32_t *kicks_kept_out, *kicks_improved_out;  // the per-tour outputs: the iterated modes
   int64_t* segments_swapped_out;
   double *first_length_out, *final_length_out;
@@ -480,21 +522,23 @@ void mls_launch_keep_kick(const MlCall& c, const MlPtrs& p, int T, int no_descen
                        offsets, (int)c.kicks, (int)c.kick_size, (int)c.span, no_descent, p.st, p.grp, p.ts, p.iters, hx);
 }
 
-// The four entries.  Checks the arguments, sets the device state up, enqueues launch sequences - a sweep of every tour that is
+// The five entries.  Checks the arguments, sets the device state up, enqueues launch sequences - a sweep of every tour that is
 // still descending and, in the iterated modes, the keep / kick step - until every group has stopped, and reduces the tours'
 // counters to the outputs.
 int mls_run(const MlCall& c) {
-  const bool plain = c.mode == kPlain, focused = c.mode == kIterFocused;
+  // plain: one descent, no keep / kick step - on full rows, or (listed) with a neighbour stage in front of them
+  const bool listed = c.mode == kListed, plain = listed || c.mode == kPlain, focused = c.mode == kIterFocused;
   const int groups = c.groups;
   if (!plain) g_host_syncs = 0;
   MlLayout lay;
   MlTables tabs;
-  const int rc = mls_layout(c.who, groups, c.group_n, c.group_tours, c.parts, c.group_edges, &lay, &tabs);
+  const int rc = mls_layout(c.who, groups, c.group_n, c.group_tours, c.parts, c.K, c.closing, c.group_edges, &lay, &tabs);
   if (rc != DIFUSCO_OK) return rc;
+  if (listed && !c.neighbors) return set_error(DIFUSCO_EINVAL, "%s: neighbors is null", c.who);
   if (!c.points || !c.tours || !c.workspace || !c.two_opt_sweeps_out || !c.or_opt_sweeps_out || !c.rounds_out ||
-      !c.two_opt_moves_out || !c.or_opt_moves_out || c.max_iterations < 0)
-    return set_error(DIFUSCO_EINVAL, "%s: needs non-null device arrays, the five host output arrays [groups] and "
-                                     "max_iterations >= 0", c.who);
+      !c.two_opt_moves_out || !c.or_opt_moves_out || (listed && (!c.full_sweeps_out || !c.full_rounds_out)) || c.max_iterations < 0)
+    return set_error(DIFUSCO_EINVAL, "%s: needs non-null device arrays, the %s host output arrays [groups] and "
+                                     "max_iterations >= 0", c.who, listed ? "seven" : "five");
   if (!plain && (!c.tour_seeds || !c.tour_offsets || !c.kicks_kept_out || !c.kicks_improved_out || !c.segments_swapped_out ||
                  !c.first_length_out || !c.final_length_out || (focused && !c.closing_sweeps_out)))
     return set_error(DIFUSCO_EINVAL, "%s: needs the device arrays tour_seeds / tour_offsets and %s", c.who, c.tour_outputs);
@@ -513,6 +557,7 @@ int mls_run(const MlCall& c) {
   for (int g = 0; g < groups; ++g) {
     c.two_opt_sweeps_out[g] = c.or_opt_sweeps_out[g] = c.two_opt_moves_out[g] = c.or_opt_moves_out[g] = 0;
     c.rounds_out[g] = 1;                                         // every descent starts round 1
+    if (listed) c.full_sweeps_out[g] = 0, c.full_rounds_out[g] = 0;
   }
   // no sweep may move a tour.  One descent: nothing is applied; the iterated modes: a call of keeps and kicks only
   const int no_descent = c.max_iterations == 0;
@@ -525,7 +570,7 @@ int mls_run(const MlCall& c) {
   for (int b = 0; b < T; ++b) states[b].phase = no_descent ? kKeep : kTwoOpt;
   int bad = 0;
   // the tables, once per call; the host vectors live until the synchronisation below
-  hipError_t er = hipMemcpyAsync(p.desc, tabs.tours.data(), sizeof(MlTour) * T, hipMemcpyHostToDevice, s);
+  hipError_t er = hipMemcpyAsync(p.desc, tabs.tours.data(), sizeof(TourDesc) * T, hipMemcpyHostToDevice, s);
   if (er == hipSuccess) er = hipMemcpyAsync(p.grp, tabs.groups.data(), sizeof(MlGroup) * groups, hipMemcpyHostToDevice, s);
   if (plain) {
     if (er == hipSuccess) er = hipMemsetAsync(p.ts, 0, lay.total - lay.ts, s);   // ts .. st, the end of this workspace
@@ -561,17 +606,33 @@ int mls_run(const MlCall& c) {
                        c.heat_values, p.htab, p.q);
   // A launch sequence either moves a tour (at most max_iterations per descent), ends one of its phases (two per round) - in the
   // iterated modes the last of them runs the keep / kick step -, or, with no descent, is one keep / kick step: the bound per
-  // descent.  A tour runs its first descent, one per kick and, focused, the closing one.
-  const long long ends = 2LL * c.max_rounds;
+  // descent.  Listed, two more end phases: those of the round in which the tour goes on to the full stage.  A tour runs its first
+  // descent, one per kick and, focused, the closing one.
+  const long long ends = 2LL * c.max_rounds + (listed ? 2 : 0);
   const long long per = no_descent ? 1 : (c.max_iterations > INT64_MAX - ends ? INT64_MAX : c.max_iterations + ends);
   const long long descents = plain ? 1 : (long long)c.kicks + (focused ? 2 : 1);
   const long long limit = per > INT64_MAX / descents ? INT64_MAX : per * descents;
   const int split = lay.tot.nmax;                                // blocks of the row part: the list holds at most n - 1 rows
   const dim3 prep_grid((lay.tot.nmax + 1 + 255) / 256, T), best_grid(lay.tot.nblk_or, T), focus_grid(split + lay.tot.nblk_or, T);
+  const dim3 walk_grid((unsigned)(((long long)lay.tot.nmax * c.K + 255) / 256), T);   // listed: a thread per (position, list slot)
   const long long cap = (long long)c.max_iterations;
   const auto select_kernel = plain ? mls_select_kernel : mls_select_iterated_kernel;
   const Polled polled = poll_launches(limit, plain ? 4 : 8, groups, &p.st->done, s, [&] {
-    if (!no_descent) {
+    if (listed) {            // the rows of the neighbour stage, with closing also those of the full stage, and the select step
+      hipLaunchKernelGGL(nls_prep_kernel, prep_grid, dim3(256), 0, s, c.points, c.tours, p.desc, p.tp, p.dlen, p.pos, p.rowkey, p.rowj,
+                         p.ts);
+      hipLaunchKernelGGL(nls_row_value_kernel, walk_grid, dim3(256), 0, s, c.tours, c.neighbors, p.desc, p.tp, p.dlen, p.pos, c.K,
+                         p.rowkey, p.ts);
+      hipLaunchKernelGGL(nls_row_col_kernel, walk_grid, dim3(256), 0, s, c.tours, c.neighbors, p.desc, p.tp, p.dlen, p.pos, c.K,
+                         p.rowkey, p.rowv, p.rowj, p.ts);
+      if (c.closing) {
+        hipLaunchKernelGGL(nls_full_two_kernel, best_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, p.ts);
+        hipLaunchKernelGGL(nls_full_or_kernel, best_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, p.ts);
+      }
+      hipLaunchKernelGGL(mls_select_listed_kernel, dim3(T), dim3(kSelectThreads), 0, s, c.tours, p.desc, p.rowv, p.rowj, p.live,
+                         p.winners, p.tabv, p.tabi, p.marks, p.cum, cap, c.max_rounds, c.select_rounds, c.closing, p.st, p.grp, p.ts,
+                         p.stages);
+    } else if (!no_descent) {
       hipLaunchKernelGGL(mls_prep_kernel, prep_grid, dim3(256), 0, s, c.points, c.tours, p.desc, p.tp, p.dlen, p.ts);
       // a focused tour reads kDone in `full`: the full sweep skips it, the focused one takes it
       hipLaunchKernelGGL(mls_row_best_kernel, best_grid, dim3(256), 0, s, p.tp, p.dlen, p.desc, p.rowv, p.rowj, focused ? p.full : p.ts);
@@ -594,7 +655,9 @@ int mls_run(const MlCall& c) {
   if (polled.status != hipSuccess) return set_error(DIFUSCO_EHIP, "%s state: %s", c.who, hipGetErrorString(polled.status));
   std::vector<MlIter> its(plain ? 0 : T);
   std::vector<MlFocus> focs(focused ? T : 0);
+  std::vector<MlStage> stages(listed ? T : 0);
   er = hipMemcpyAsync(states.data(), p.ts, sizeof(MlTourState) * T, hipMemcpyDeviceToHost, s);
+  if (listed && er == hipSuccess) er = hipMemcpyAsync(stages.data(), p.stages, sizeof(MlStage) * T, hipMemcpyDeviceToHost, s);
   if (!plain && er == hipSuccess) er = hipMemcpyAsync(its.data(), p.iters, sizeof(MlIter) * T, hipMemcpyDeviceToHost, s);
   if (focused && er == hipSuccess) er = hipMemcpyAsync(focs.data(), p.foc, sizeof(MlFocus) * T, hipMemcpyDeviceToHost, s);
   if (er == hipSuccess) er = hipStreamSynchronize(s);
@@ -610,6 +673,8 @@ int mls_run(const MlCall& c) {
     c.two_opt_moves_out[g] += x.two_opt_moves;
     c.or_opt_moves_out[g] += x.or_opt_moves;
     if (c.tour_sweeps_out) c.tour_sweeps_out[b] = x.sweeps;
+    if (listed && stages[b].full_sweeps > c.full_sweeps_out[g]) c.full_sweeps_out[g] = stages[b].full_sweeps;
+    if (listed && stages[b].full_rounds > c.full_rounds_out[g]) c.full_rounds_out[g] = stages[b].full_rounds;
     if (plain) continue;
     c.kicks_kept_out[b] = its[b].kept;
     c.kicks_improved_out[b] = its[b].improved;
@@ -651,7 +716,7 @@ int mls_iterated_entry(const char* who, MlMode mode, bool heat, unsigned parts, 
 // the descent of difusco_tsp_multi_local_search_ragged for the window search (tsp_window_search.hip, declared in kernels.h): the
 // messages name `who`, and tour_sweeps_out (HOST [tours], optional) receives the sweeps in which every tour moved
 int mls_descent_workspace_bytes(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, size_t* bytes) {
-  return mls_workspace_bytes(who, groups, group_n, group_tours, 0, nullptr, bytes);
+  return mls_workspace_bytes(who, groups, group_n, group_tours, 0, 0, 0, nullptr, bytes);
 }
 
 int mls_descent(const char* who, int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
@@ -674,7 +739,7 @@ extern "C" {
 
 int difusco_tsp_multi_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
                                                           size_t* bytes) {
-  return difusco::mls_workspace_bytes("multi_local_search_ragged_workspace_bytes", groups, group_n, group_tours, 0, nullptr, bytes);
+  return difusco::mls_workspace_bytes("multi_local_search_ragged_workspace_bytes", groups, group_n, group_tours, 0, 0, 0, nullptr, bytes);
 }
 
 int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
@@ -686,10 +751,36 @@ int difusco_tsp_multi_local_search_ragged(int groups, const int32_t* group_n, co
                               two_opt_moves_out, or_opt_moves_out, nullptr, stream);
 }
 
+int difusco_tsp_nbr_local_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours, int K,
+                                                        int closing, size_t* bytes) {
+  using namespace difusco;
+  return mls_workspace_bytes("nbr_local_search_ragged_workspace_bytes", groups, group_n, group_tours, kListPart, K, closing, nullptr,
+                             bytes);
+}
+
+int difusco_tsp_nbr_local_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                        int32_t* tours, const int32_t* neighbors, int K, int closing, int64_t max_iterations,
+                                        int max_rounds, int select_rounds, void* workspace, size_t workspace_bytes,
+                                        int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out,
+                                        int64_t* two_opt_moves_out, int64_t* or_opt_moves_out, int64_t* full_sweeps_out,
+                                        int32_t* full_rounds_out, void* stream) {
+  using namespace difusco;
+  MlCall c{};
+  c.who = "tsp_nbr_local_search_ragged", c.mode = kListed, c.parts = kListPart;
+  c.groups = groups, c.group_n = group_n, c.group_tours = group_tours, c.points = points, c.tours = tours;
+  c.neighbors = neighbors, c.K = K, c.closing = closing;
+  c.max_iterations = max_iterations, c.max_rounds = max_rounds, c.select_rounds = select_rounds;
+  c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+  c.two_opt_sweeps_out = two_opt_sweeps_out, c.or_opt_sweeps_out = or_opt_sweeps_out, c.rounds_out = rounds_out;
+  c.two_opt_moves_out = two_opt_moves_out, c.or_opt_moves_out = or_opt_moves_out;
+  c.full_sweeps_out = full_sweeps_out, c.full_rounds_out = full_rounds_out;
+  return mls_run(c);
+}
+
 int difusco_tsp_iterated_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
                                                        size_t* bytes) {
   using namespace difusco;
-  return mls_workspace_bytes("tsp_iterated_search_ragged_workspace_bytes", groups, group_n, group_tours, kIterPart, nullptr, bytes);
+  return mls_workspace_bytes("tsp_iterated_search_ragged_workspace_bytes", groups, group_n, group_tours, kIterPart, 0, 0, nullptr, bytes);
 }
 
 int difusco_tsp_search_host_syncs(void) { return difusco::g_host_syncs; }
@@ -698,14 +789,14 @@ int difusco_tsp_focused_search_ragged_workspace_bytes(int groups, const int32_t*
                                                       size_t* bytes) {
   using namespace difusco;
   return mls_workspace_bytes("tsp_focused_search_ragged_workspace_bytes", groups, group_n, group_tours, kIterPart | kFocusPart,
-                             nullptr, bytes);
+                             0, 0, nullptr, bytes);
 }
 
 int difusco_tsp_guided_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
                                                      const int32_t* group_edges, size_t* bytes) {
   using namespace difusco;
   return mls_workspace_bytes("tsp_guided_search_ragged_workspace_bytes", groups, group_n, group_tours,
-                             kIterPart | kFocusPart | kHeatPart, group_edges, bytes);   // one size for both descents
+                             kIterPart | kFocusPart | kHeatPart, 0, 0, group_edges, bytes);   // one size for both descents
 }
 
 int difusco_tsp_iterated_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,

@@ -1,4 +1,4 @@
-// What the Or-opt sweeps of the multi-move searches share (or_opt_multi.hip with or_opt_focused.h, or_opt_nbr.hip): the delta of a
+// What the Or-opt sweeps of the multi-move searches share (or_opt_multi.hip with or_opt_focused.h and or_opt_nbr.h): the delta of a
 // candidate, in one place, the full row-best loop and the delta of a single candidate (v, i, j).  Every function is per translation
 // unit (anonymous namespace), as in multi_move_common.h.
 #pragma once

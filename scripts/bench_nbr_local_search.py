@@ -75,7 +75,7 @@ if opts.kernel_stats:
     with open(opts.kernel_stats) as f:
         for r in csv.DictReader(f):
             for name in ("nls_prep_kernel", "nls_row_value_kernel", "nls_row_col_kernel", "nls_full_two_kernel", "nls_full_or_kernel",
-                         "nls_select_kernel"):
+                         "mls_select_listed_kernel"):
                 if name in r["Name"]:
                     rows[name] = {"calls": int(r["Calls"]), "total_ms": float(r["TotalDurationNs"]) / 1e6,
                                   "avg_us": float(r["AverageNs"]) / 1e3, "min_us": float(r["MinNs"]) / 1e3,

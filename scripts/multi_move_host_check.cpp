@@ -1,16 +1,17 @@
-// The host side of the group-wise multi-move entries (two_opt_multi.hip, or_opt_nbr.hip, or_opt_multi.hip) as a stand-alone
+// The host side of the group-wise multi-move entries (two_opt_multi.hip, or_opt_multi.hip) as a stand-alone
 // program for a sanitizer run without a GPU: the layout, size and refusal paths over the sizes and refusals of
 // tests/multi_move_entries_cases.py.  No call here reaches a HIP call - a refused call returns in front of the first one.
 // Build the host side with the sanitizers and run it (gfx950 cross-compiles; the device code is not executed):
 //
 //   cd difusco_amd/csrc && hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//       two_opt_multi.hip or_opt_nbr.hip or_opt_multi.hip ../../scripts/multi_move_host_check.cpp -fsanitize=address,undefined \
+//       two_opt_multi.hip or_opt_multi.hip ../../scripts/multi_move_host_check.cpp -fsanitize=address,undefined \
 //       -o /tmp/multi_move_host_check && /tmp/multi_move_host_check
 //
 // It prints one line per call: the return code and the bytes or the message.  The lines of a correct library are those of
-// tests/golden/multi_move_entries.json (the neighbour 2-opt sizes less the merged state word); the exit status is 1 if a call
-// that must be refused is not, or the other way round.
+// tests/golden/multi_move_entries.json (the sizes with the closed forms of tests/multi_move_entries_cases.py applied) and, for the
+// entries of or_opt_multi.hip, of tests/golden/tsp_search_entries.json; the exit status is 1 if a call that must be refused is not,
+// or the other way round.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -55,6 +56,8 @@ int main() {
     report(what, difusco_tsp_multi_two_opt_ragged_workspace_bytes(G, s.n.data(), s.tours.data(), &bytes), true, bytes);
     snprintf(what, sizeof(what), "size multi_local_search shape%zu", k);
     report(what, difusco_tsp_multi_local_search_ragged_workspace_bytes(G, s.n.data(), s.tours.data(), &bytes), true, bytes);
+    snprintf(what, sizeof(what), "size iterated_search shape%zu", k);
+    report(what, difusco_tsp_iterated_search_ragged_workspace_bytes(G, s.n.data(), s.tours.data(), &bytes), true, bytes);
     snprintf(what, sizeof(what), "size focused_search shape%zu", k);
     report(what, difusco_tsp_focused_search_ragged_workspace_bytes(G, s.n.data(), s.tours.data(), &bytes), true, bytes);
     std::vector<int32_t> edges;
@@ -71,7 +74,8 @@ int main() {
   }
   // the refusals: every call departs from the valid one in the named arguments
   const int32_t n_ok[2] = {5, 9}, t_ok[2] = {2, 1}, n_bad[2] = {5, 3}, t_bad[2] = {0, 1}, n_big[2] = {5, 1 << 19};
-  size_t bytes = 0, need_mt = 0, need_nb = 0, need_nl = 0;
+  size_t bytes = 0, need_mt = 0, need_nb = 0, need_nl = 0, need_ml = 0;
+  report("valid multi_local_search size", difusco_tsp_multi_local_search_ragged_workspace_bytes(2, n_ok, t_ok, &need_ml), true, need_ml);
   report("valid multi_two_opt size", difusco_tsp_multi_two_opt_ragged_workspace_bytes(2, n_ok, t_ok, &need_mt), true, need_mt);
   report("valid nbr_two_opt size", difusco_tsp_nbr_two_opt_ragged_workspace_bytes(2, n_ok, t_ok, 2, 1, &need_nb), true, need_nb);
   report("valid nbr_local_search size", difusco_tsp_nbr_local_search_ragged_workspace_bytes(2, n_ok, t_ok, 2, 1, &need_nl), true, need_nl);
@@ -87,7 +91,7 @@ int main() {
 
   std::vector<double> points(64);
   std::vector<int32_t> tours(64), nbr(64), r32(4), f32(4);
-  std::vector<char> ws(need_nb > need_nl ? need_nb : need_nl);
+  std::vector<char> ws(need_nb > need_nl ? need_nb : need_nl);            // the plain entries need less
   std::vector<int64_t> a(4), b(4), c(4), d(4), e(4);
   double* P = points.data();
   int32_t *T = tours.data(), *N = nbr.data();
@@ -123,6 +127,12 @@ int main() {
   report("nbr_local_search select_rounds_0", difusco_tsp_nbr_local_search_ragged(2, n_ok, t_ok, P, T, N, 2, 1, 10, 2, 0, W, need_nl - 1, a.data(), b.data(), r32.data(), c.data(), d.data(), e.data(), f32.data(), nullptr), false, 0);
   report("nbr_local_search workspace_short", difusco_tsp_nbr_local_search_ragged(2, n_ok, t_ok, P, T, N, 2, 1, 10, 2, 4, W, need_nl - 1, a.data(), b.data(), r32.data(), c.data(), d.data(), e.data(), f32.data(), nullptr), false, 0);
   report("nbr_local_search max_iterations_0", difusco_tsp_nbr_local_search_ragged(2, n_ok, t_ok, P, T, N, 2, 1, 0, 2, 4, W, need_nl, a.data(), b.data(), r32.data(), c.data(), d.data(), e.data(), f32.data(), nullptr), true, 0);
+  // difusco_tsp_multi_local_search_ragged: the driver it shares with the listed entry
+  report("multi_local_search n_3", difusco_tsp_multi_local_search_ragged(2, n_bad, t_ok, P, T, 10, 2, 4, W, need_ml, a.data(), b.data(), r32.data(), c.data(), d.data(), nullptr), false, 0);
+  report("multi_local_search null_or_opt_moves_out", difusco_tsp_multi_local_search_ragged(2, n_ok, t_ok, P, T, 10, 2, 4, W, need_ml, a.data(), b.data(), r32.data(), c.data(), nullptr, nullptr), false, 0);
+  report("multi_local_search max_rounds_0", difusco_tsp_multi_local_search_ragged(2, n_ok, t_ok, P, T, 10, 0, 0, W, need_ml, a.data(), b.data(), r32.data(), c.data(), d.data(), nullptr), false, 0);
+  report("multi_local_search workspace_short", difusco_tsp_multi_local_search_ragged(2, n_ok, t_ok, P, T, 10, 2, 4, W, need_ml - 1, a.data(), b.data(), r32.data(), c.data(), d.data(), nullptr), false, 0);
+  report("multi_local_search max_iterations_0", difusco_tsp_multi_local_search_ragged(2, n_ok, t_ok, P, T, 0, 2, 4, W, need_ml, a.data(), b.data(), r32.data(), c.data(), d.data(), nullptr), true, 0);
   printf("%d unexpected return codes\n", failures);
   return failures ? 1 : 0;
 }

@@ -1,4 +1,4 @@
-"""CPU restatement of the neighbour-list multi-move 2-opt + Or-opt search (difusco_amd/csrc/or_opt_nbr.hip,
+"""CPU restatement of the neighbour-list multi-move 2-opt + Or-opt search (difusco_amd/csrc/or_opt_multi.hip with or_opt_nbr.h,
 ``difusco_tsp_nbr_local_search_ragged``) in numpy float64.  TEST INFRASTRUCTURE ONLY.  Deltas, ranges, selection and apply are
 those of ``multi_local_search_emulation``, the 2-opt neighbour sweep is ``nbr_two_opt_emulation.sweep``; this file adds the
 candidate mask of an Or-opt neighbour sweep, the per-tour stage and the counters.

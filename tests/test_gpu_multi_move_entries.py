@@ -2,8 +2,9 @@
 ``difusco_tsp_nbr_local_search_ragged`` against recorded behaviour (tests/golden/multi_move_entries.json,
 scripts/record_multi_move_entries.py): the bytes each ``_workspace_bytes`` reserves, the return code and message of every refusal,
 and on short runs the tours and every counter array, all as exact values.  The emulation suites pin the rules; this pins what
-they leave open - the sizes Python allocates by, the messages, the order of the checks - for changes to the host side.  The one
-figure that is not the recorded one is written once, in ``multi_move_entries_cases.merged_state_word_bytes``."""
+they leave open - the sizes Python allocates by, the messages, the order of the checks - for changes to the host side.  The
+figures that are not the recorded ones are written once each, in ``multi_move_entries_cases.merged_state_word_bytes`` and
+``tour_descriptor_bytes``."""
 import json
 import os
 
