@@ -66,6 +66,9 @@ int mls_descent(const char* who, int groups, const int32_t* group_n, const int32
                 int32_t* tours, int64_t max_iterations, int max_rounds, int select_rounds, void* workspace, size_t workspace_bytes,
                 int64_t* two_opt_sweeps_out, int64_t* or_opt_sweeps_out, int32_t* rounds_out, int64_t* two_opt_moves_out,
                 int64_t* or_opt_moves_out, int64_t* tour_sweeps_out, void* stream);
+// difusco_tsp_search_host_syncs reports `count` on this thread until the next search call (or_opt_multi.hip; for the k-opt search
+// of tsp_kopt_search.hip)
+void tsp_search_set_host_syncs(int count);
 
 hipError_t linear_rows(const float* x, const float* w, const float* bias, const float* residual, float* y,
                        long long m, int k, int n_out, long long ldy, hipStream_t stream);

@@ -733,6 +733,8 @@ int mls_descent(const char* who, int groups, const int32_t* group_n, const int32
   return mls_run(c);
 }
 
+void tsp_search_set_host_syncs(int count) { g_host_syncs = count; }
+
 }  // namespace difusco
 
 extern "C" {

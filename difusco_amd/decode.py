@@ -1012,6 +1012,103 @@ def batched_iterated_search_ragged(points_list, tours_list, max_iterations=1000,
                             seeds, offsets, stats, descent, compact_select_max, kick_bias, heat, edge_index)
 
 
+TSP_KOPT_MAX_SAMPLES, TSP_KOPT_MAX_DEPTH = 4096, 10       # difusco_tsp_kopt_search_ragged
+TSP_KOPT_SAMPLES, TSP_KOPT_DEPTH, TSP_KOPT_ROUNDS, TSP_KOPT_PATIENCE, TSP_KOPT_ALPHA, TSP_KOPT_BETA = 1024, 10, 64, 10, 1.0, 10.0
+TSP_KOPT_STATS = ("rounds", "actions", "depth_sum", "reverted", "first_length", "final_length")
+
+
+def check_tsp_kopt(rounds, samples=TSP_KOPT_SAMPLES, depth=TSP_KOPT_DEPTH):
+    """``rounds`` / ``samples`` / ``depth`` of the sampled k-opt search (``rounds = 0``: the stage is off)."""
+    if int(rounds) != rounds or not 0 <= rounds < 2 ** 31:
+        raise ValueError(f"kopt rounds = {rounds!r}: an integer >= 0")
+    if int(samples) != samples or not 1 <= samples <= TSP_KOPT_MAX_SAMPLES:
+        raise ValueError(f"kopt samples = {samples!r}: an integer in 1 .. {TSP_KOPT_MAX_SAMPLES}")
+    if int(depth) != depth or not 1 <= depth <= TSP_KOPT_MAX_DEPTH:
+        raise ValueError(f"kopt depth = {depth!r}: an integer in 1 .. {TSP_KOPT_MAX_DEPTH}")
+    return int(rounds), int(samples), int(depth)
+
+
+def kopt_explore(alpha, samples, rounds):
+    """The ``explore`` table of ``difusco_tsp_kopt_search_ragged``: ``alpha * sqrt(log1p(r * samples))``, float64 [rounds]."""
+    return alpha * np.sqrt(np.log1p(np.arange(rounds, dtype=np.float64) * float(samples)))
+
+
+def _kopt_search(form, points, tours, heat, edge_index, samples, depth, rounds, patience, alpha, beta, seeds, offsets, stats, device):
+    """``batched_kopt_search_<form>``: the checks (before any library call) and one ``difusco_tsp_kopt_search_ragged`` call."""
+    who = f"batched_kopt_search_{form}"
+    pts, trs = _per_group(form, points, tours)
+    if form == "torch":
+        heat, edge_index = None if heat is None else [heat], None if edge_index is None else [edge_index]
+    if heat is None:
+        raise ValueError(f"{who}: needs heat= (and edge_index= unless the heat is dense)")
+    rounds, samples, depth = check_tsp_kopt(rounds, samples, depth)
+    if int(patience) != patience or not 1 <= patience < 2 ** 31:
+        raise ValueError(f"patience = {patience!r}: an integer >= 1")
+    if not (np.isfinite(alpha) and alpha >= 0) or not (np.isfinite(beta) and beta >= 0):
+        raise ValueError(f"alpha = {alpha!r}, beta = {beta!r}: finite values >= 0")
+    device = _local_search_checked(who, pts, trs, 0, 1, device)
+    ex = np.ascontiguousarray(kopt_explore(alpha, samples, rounds), dtype=np.float64)
+    graph = _heat_graph(who, pts, trs, heat, edge_index, device)
+    T = sum(t.shape[0] for t in trs)
+    table = _philox_table(seeds, offsets, T, "tours", device)
+    batch = _RaggedBatch(pts, trs, device)
+    L = _lib.lib()
+    group_edges, row_ptr, col, d_heat = graph
+    ws, nbytes = _workspace(L.difusco_tsp_kopt_search_ragged_workspace_bytes, *batch.sizes, group_edges.ctypes.data, samples, depth,
+                            device=device)
+    per = {"rounds": np.zeros(T, dtype=np.int32), "actions": np.zeros(T, dtype=np.int32), "depth_sum": np.zeros(T, dtype=np.int64),
+           "reverted": np.zeros(T, dtype=np.int32), "first_length": np.zeros(T, dtype=np.float64),
+           "final_length": np.zeros(T, dtype=np.float64)}
+    _lib.check(L.difusco_tsp_kopt_search_ragged(
+        *batch.head, group_edges.ctypes.data, _ptr(row_ptr), _ptr(col), _ptr(d_heat), _ptr(table[0]), _ptr(table[1]), samples, depth,
+        rounds, int(patience), float(beta), ex.ctypes.data if rounds else None, _ptr(ws), nbytes,
+        *(per[k].ctypes.data for k in TSP_KOPT_STATS), _stream(device)))
+    if stats is not None:
+        stats.update(per, host_syncs=int(L.difusco_tsp_search_host_syncs()))
+    out = batch.read_tours()
+    return out[0] if form == "torch" else np.concatenate(out, axis=0) if form == "grouped" else out
+
+
+def batched_kopt_search_torch(points, tours, *, heat, edge_index=None, samples=TSP_KOPT_SAMPLES, depth=TSP_KOPT_DEPTH,
+                              rounds=TSP_KOPT_ROUNDS, patience=TSP_KOPT_PATIENCE, alpha=TSP_KOPT_ALPHA, beta=TSP_KOPT_BETA,
+                              seeds=None, offsets=None, stats=None, device="cuda:0"):
+    """Heatmap-guided sampled k-opt search of B tours of one instance (the rule: ``difusco_tsp_kopt_search_ragged``,
+    include/difusco_hip.h; GPU only; a parallel restatement of the reference's heatmap + MCTS stage, not a port).  Per round
+    every tour runs ``samples`` simulations: each opens the tour at a drawn position and, up to ``depth`` times, draws a new edge
+    among the candidate entries of the open end whose learned weight (100 x heat at first) plus an exploration term
+    (``alpha * sqrt(log1p(r * samples))`` over the entry's use count) stands out of its row, and closes it with a prefix
+    reversal - a sequential k-opt move, k up to ``depth + 1``.  The best closing gain of the round is applied when it is above
+    1e-6 and raises the weights of its new edges by ``beta * (x + x^2 / 2)``, x the relative gain.  A tour stops after ``rounds``
+    rounds or ``patience * N`` simulations in a row without an applied action.  Run the local search first: the search has no
+    2-opt stage of its own.  ``heat`` / ``edge_index``: as ``batched_iterated_search_torch`` with ``kick_bias="heat"`` takes
+    them; ``seeds`` / ``offsets`` [B]: the Philox key and first offset of every tour (round r draws at ``offsets[b] + r``); a
+    tour gets the same answer alone or in any call.  Returns the tours, int64 numpy [B, N + 1], none longer than its input;
+    ``stats`` (a dict) receives the per-tour numpy arrays [B] ``rounds``, ``actions``, ``depth_sum``, ``reverted``,
+    ``first_length``, ``final_length`` and ``host_syncs``.  ``rounds=0`` returns the input."""
+    return _kopt_search("torch", points, tours, heat, edge_index, samples, depth, rounds, patience, alpha, beta, seeds, offsets, stats,
+                        device)
+
+
+def batched_kopt_search_grouped(points, tours, *, heat, edge_index=None, samples=TSP_KOPT_SAMPLES, depth=TSP_KOPT_DEPTH,
+                                rounds=TSP_KOPT_ROUNDS, patience=TSP_KOPT_PATIENCE, alpha=TSP_KOPT_ALPHA, beta=TSP_KOPT_BETA,
+                                seeds=None, offsets=None, stats=None, device="cuda:0"):
+    """``batched_kopt_search_torch`` of G instances at once: ``points`` [G, N, 2], ``tours`` [G * P, N + 1]; ``heat`` and
+    ``edge_index`` are lists with one entry per instance (``heat[g]`` [P, E_g] with ``edge_index[g]`` [2, E_g]; [P, N, N] with
+    ``edge_index=None``); ``seeds`` / ``offsets`` [G * P].  Every tour gets what its own call returns."""
+    return _kopt_search("grouped", points, tours, heat, edge_index, samples, depth, rounds, patience, alpha, beta, seeds, offsets,
+                        stats, device)
+
+
+def batched_kopt_search_ragged(points_list, tours_list, *, heat, edge_index=None, samples=TSP_KOPT_SAMPLES, depth=TSP_KOPT_DEPTH,
+                               rounds=TSP_KOPT_ROUNDS, patience=TSP_KOPT_PATIENCE, alpha=TSP_KOPT_ALPHA, beta=TSP_KOPT_BETA,
+                               seeds=None, offsets=None, stats=None, device="cuda:0"):
+    """``batched_kopt_search_torch`` of G instances of ANY sizes at once: one point array [n_g, 2] and one tour array
+    [P_g, n_g + 1] per instance, ``heat`` / ``edge_index`` as ``batched_kopt_search_grouped``; ``seeds`` / ``offsets``: one per
+    tour, group after group.  Returns a list of int64 numpy [P_g, n_g + 1]."""
+    return _kopt_search("ragged", points_list, tours_list, heat, edge_index, samples, depth, rounds, patience, alpha, beta, seeds,
+                        offsets, stats, device)
+
+
 TSP_WINDOW_MIN, TSP_WINDOW_MAX, TSP_WINDOW_MAX_KICKS = 16, 1024, 1024
 # the recommended window mode: the lowest row of scripts/tsp_window_search_table.py (DESIGN 5.2k)
 TSP_WINDOW, TSP_WINDOW_KICK_SIZE, TSP_WINDOW_KICK_SPAN = 128, 8, 30

@@ -61,7 +61,11 @@ lists of K cities, ``decode.batched_nbr_two_opt_grouped``, closed by full sweeps
 ``two_opt_full_sweeps`` and with the header the two settings; without K every record is what it was; ``--local_search
 nbr2opt+oropt`` needs K >= 1: the 2-opt + Or-opt search on these lists, ``decode.batched_nbr_local_search_grouped`` - a name of its
 own because ``multi2opt+oropt`` with K > 0 stays refused -, the records of ``multi2opt+oropt`` plus, after every other field,
-``local_search_full_sweeps`` and ``local_search_full_rounds``), ``--merge_method {loop,batched}``
+``local_search_full_sweeps`` and ``local_search_full_rounds``), ``--tsp_kopt_rounds R`` / ``--tsp_kopt_samples S`` /
+``--tsp_kopt_depth D`` (R > 0 only with ``--task tsp``: up to R rounds of the heatmap-guided sampled k-opt search,
+``decode.batched_kopt_search_grouped``, on every tour after the local search and on each sample's own heatmap, keyed by its
+instance seed; the records gain ``kopt_actions``, one count per copy, and with the header the three settings; with R = 0 every
+record is what it was), ``--merge_method {loop,batched}``
 (``decode.merge_tours_batch``: one merge call per chunk, same records either way), ``--graph_build {host,device}``
 (``graph.build_csr``: where ``edge_index`` becomes the CSR, same records either way), ``--mixed_size_chunks``
 (TSP: chunks are runs of consecutive instances of any N, ``mixed_size_chunks``; off: runs of equal N), ``--device``,
@@ -130,6 +134,7 @@ TRAINING_ONLY = ("training_split", "training_split_label_dir", "batch_size", "nu
                  "lr_scheduler", "num_workers", "use_activation_checkpoint", "project_name", "wandb_entity",
                  "wandb_logger_name", "resume_id", "resume_weight_only")
 TSP_KICK_SIZE, TSP_KICK_SPAN = 16, 30     # decode.TSP_KICK_SIZE / TSP_KICK_SPAN (this module parses without torch)
+TSP_KOPT_SAMPLES, TSP_KOPT_DEPTH = 1024, 10   # decode.TSP_KOPT_SAMPLES / TSP_KOPT_DEPTH
 EXTENSION_ARGS = [
     ("--seed", dict(type=int, default=0, help="base of the per-instance seeds (instance_seed)")),
     ("--instances_per_call", dict(type=int, default=None, help="chunk length (default: default_instances_per_call)")),
@@ -166,6 +171,11 @@ EXTENSION_ARGS = [
                                            help="TSP: where the first cut of a kick's draws falls: uniform (anywhere alike) or "
                                                 "heat (on a tour edge with a probability that rises as the sampled heat of the "
                                                 "edge falls; needs --tsp_local_search_kicks N > 0)")),
+    ("--tsp_kopt_rounds", dict(type=int, default=0,
+                               help="TSP: R > 0 runs up to R rounds of the heatmap-guided sampled k-opt search on every tour after "
+                                    "the local search, on each sample's own heatmap (0: off; records gain kopt_actions)")),
+    ("--tsp_kopt_samples", dict(type=int, default=TSP_KOPT_SAMPLES, help="TSP: simulations per round of the k-opt search (1 .. 4096)")),
+    ("--tsp_kopt_depth", dict(type=int, default=TSP_KOPT_DEPTH, help="TSP: new edges per simulated move of the k-opt search (1 .. 10)")),
     ("--tsp_local_search_window", dict(type=int, default=0,
                                         help="TSP: W > 0 runs the iterated search on windows of W tour positions (16 .. 1024), one "
                                              "GPU block per window, --tsp_local_search_kicks kicks (>= 0) per window and pass (needs "
@@ -257,6 +267,10 @@ def parse_args(argv=None):
                      "--tsp_local_search_kicks N > 0")
     if args.tsp_local_search_kick_bias == "heat" and args.task != "tsp":
         parser.error(f"--tsp_local_search_kick_bias heat biases the kicks of TSP tours: not with --task {args.task}")
+    if args.tsp_kopt_rounds < 0 or not 1 <= args.tsp_kopt_samples <= 4096 or not 1 <= args.tsp_kopt_depth <= 10:
+        parser.error("--tsp_kopt_rounds must be >= 0, --tsp_kopt_samples in 1 .. 4096 and --tsp_kopt_depth in 1 .. 10")
+    if args.tsp_kopt_rounds > 0 and args.task != "tsp":
+        parser.error(f"--tsp_kopt_rounds {args.tsp_kopt_rounds} refines TSP tours: not with --task {args.task}")
     W, R = args.tsp_local_search_window, args.tsp_local_search_passes
     if not (W == 0 or 16 <= W <= 1024) or R < 1:
         parser.error("--tsp_local_search_window must be 0 (off) or in 16 .. 1024 and --tsp_local_search_passes >= 1")
@@ -414,6 +428,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
         rec["kicks_improved"] = [int(v) for v in info["local_search_kicks_improved"]]
     if "local_search_closing_sweeps" in info:      # --tsp_local_search_descent focused
         rec["closing_sweeps"] = [int(v) for v in info["local_search_closing_sweeps"]]
+    if "kopt_actions" in info:                      # --tsp_kopt_rounds R > 0
+        rec["kopt_actions"] = [int(v) for v in info["kopt_actions"]]
     if "local_search_passes_kept" in info:         # --tsp_local_search_window W > 0
         rec["passes_kept"] = [int(v) for v in info["local_search_passes_kept"]]
     for k in ("local_search_full_sweeps", "local_search_full_rounds"):      # --local_search nbr2opt+oropt
@@ -462,7 +478,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 tsp_local_search_descent: str = "full", tsp_local_search_kick_bias: str = "uniform",
                 tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1,
                 two_opt_mode: str = "launches", tsp_local_search_candidates: int = 0,
-                tsp_local_search_closing: str = "full", tsp_local_search_mode: str = "launches") -> List[dict]:
+                tsp_local_search_closing: str = "full", tsp_local_search_mode: str = "launches", tsp_kopt_rounds: int = 0,
+                tsp_kopt_samples: int = TSP_KOPT_SAMPLES, tsp_kopt_depth: int = TSP_KOPT_DEPTH) -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -491,6 +508,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                      if tsp_local_search_window > 0 else {}),
                                   **(dict(local_search_descent="focused") if tsp_local_search_descent == "focused" else {}),
                                   **(dict(local_search_kick_bias="heat") if tsp_local_search_kick_bias == "heat" else {}),
+                                  **(dict(kopt_rounds=tsp_kopt_rounds, kopt_samples=tsp_kopt_samples, kopt_depth=tsp_kopt_depth)
+                                     if tsp_kopt_rounds > 0 else {}),
                                   **(dict(two_opt_mode="resident") if two_opt_mode == "resident" else {}),
                                   **(dict(local_search_mode="resident") if tsp_local_search_mode == "resident" else {}),
                                   **(dict(local_search_candidates=tsp_local_search_candidates,
@@ -516,6 +535,9 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                     records[-1].update(tsp_local_search_descent="focused")
                 if tsp_local_search_kick_bias == "heat":
                     records[-1].update(tsp_local_search_kick_bias="heat")
+                if tsp_kopt_rounds > 0:
+                    records[-1].update(tsp_kopt_rounds=tsp_kopt_rounds, tsp_kopt_samples=tsp_kopt_samples,
+                                       tsp_kopt_depth=tsp_kopt_depth)
                 if heats is not None:
                     save_numpy_heatmap(heats[k][-1], examples[i].points.astype(np.float32), heatmap_dir, i, split)
         else:
@@ -605,7 +627,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_passes=args.tsp_local_search_passes, two_opt_mode=args.two_opt_mode,
                                tsp_local_search_candidates=args.tsp_local_search_candidates,
                                tsp_local_search_closing=args.tsp_local_search_closing,
-                               tsp_local_search_mode=args.tsp_local_search_mode)
+                               tsp_local_search_mode=args.tsp_local_search_mode, tsp_kopt_rounds=args.tsp_kopt_rounds,
+                               tsp_kopt_samples=args.tsp_kopt_samples, tsp_kopt_depth=args.tsp_kopt_depth)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -650,6 +673,10 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                 line["tsp_local_search_descent"] = "focused"
             if args.tsp_local_search_kick_bias == "heat":
                 line["tsp_local_search_kick_bias"] = "heat"
+            if args.tsp_kopt_rounds > 0:
+                line["tsp_kopt_rounds"] = args.tsp_kopt_rounds
+                line["tsp_kopt_samples"] = args.tsp_kopt_samples
+                line["tsp_kopt_depth"] = args.tsp_kopt_depth
             if args.mis_local_search_kicks > 0:
                 line["mis_local_search_kicks"] = args.mis_local_search_kicks
                 line["mis_local_search_kick_size"] = args.mis_local_search_kick_size

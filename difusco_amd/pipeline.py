@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import decode
-from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, check_local_search, check_tsp_candidates, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
+from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, TSP_KOPT_DEPTH, TSP_KOPT_SAMPLES, check_local_search, check_tsp_kopt, check_tsp_candidates, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
                      check_tsp_kicks, check_tsp_local_search_mode, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours,
                      merge_tours_batch)
 from .graph import knn_edge_index_gpu
@@ -44,7 +44,8 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               local_search_kick_span: int = TSP_KICK_SPAN, local_search_descent: str = "full",
               local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1,
               two_opt_mode: str = "launches", local_search_candidates: int = 0, local_search_closing: bool = True,
-              local_search_mode: str = "launches"):
+              local_search_mode: str = "launches", kopt_rounds: int = 0, kopt_samples: int = TSP_KOPT_SAMPLES,
+              kopt_depth: int = TSP_KOPT_DEPTH):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -93,7 +94,14 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     ``local_search_closing``, ``local_search_full_sweeps`` and ``local_search_full_rounds``.  ``local_search_mode``: "launches"
     (default) or "resident" (only with ``local_search="2opt+oropt"``, else ``ValueError``): that search runs with one GPU block
     for the instance (``mode="resident"`` of ``decode.batched_local_search_torch``), same tours and info; the
-    ``parallel_sampling`` tours must fit its limit, there is no fallback."""
+    ``parallel_sampling`` tours must fit its limit, there is no fallback.  ``kopt_rounds`` = R > 0 (0, the default, changes
+    nothing: results and info are what they are without the option): after the chosen local search, and before the best tour is
+    picked, every tour runs up to R rounds of the heatmap-guided sampled k-opt search (``decode.batched_kopt_search_torch``) with
+    ``kopt_samples`` simulations per round and moves of up to ``kopt_depth`` new edges, on its own heatmap of its sequential
+    round (the tensor the merge received) - never a longer tour.  Copy p of sequential round r is keyed by the model's seed at
+    the Philox offset ``3 * 2^61 + (r P + p) 2^32``, which no kick offset of the same tour reaches.  info gains ``kopt_rounds``,
+    ``kopt_samples``, ``kopt_depth`` and, of the last round, one per copy, ``kopt_rounds_run`` and ``kopt_actions``."""
+    kopt = check_tsp_kopt(kopt_rounds, kopt_samples, kopt_depth)
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
     two_opt_mode = check_two_opt_mode(local_search, two_opt_mode)
@@ -126,7 +134,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
 
     stacked, merged_costs = [], []
     merge_iterations, ns = 0.0, 0
-    ls_stats, kick_stats = {}, {}
+    ls_stats, kick_stats, kopt_stats = {}, {}, {}
     for r in range(sequential_sampling):                                                    # :185
         t0 = time.perf_counter()
         heat = model.sample(pts_rep, ei_rep, generator=generator, graphed=graphed)          # :186-222, on the device
@@ -139,6 +147,9 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
         solved, ns, ls_stats = _local_search("torch", search, np_points64, np.asarray(tours, dtype=np.int64), two_opt_iterations, dev,
                                              [_kick_key(model.seed)] * parallel_sampling, _kick_offsets(r, parallel_sampling),
                                              heat, edge_index, kick_stats)
+        if kopt[0] > 0:
+            solved = _kopt_stage("torch", kopt, np_points64, solved, dev, [_kick_key(model.seed)] * parallel_sampling,
+                                 _kopt_offsets(r, parallel_sampling), heat, edge_index, kopt_stats)
         tick("two_opt", t0)
         stacked.append(solved)
         merged_costs += [tour_length(np_points64, t) for t in tours]
@@ -147,6 +158,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     best = int(np.argmin(costs))
     info = {"merge_iterations": merge_iterations, "two_opt_iterations": ns, "merged_costs": merged_costs}
     info.update(_local_search_info(search, ls_stats, kick_stats, 0, parallel_sampling, 0))
+    info.update(_kopt_info(kopt, kopt_stats, 0, parallel_sampling))
     return solved[best].tolist(), costs[best], costs, info
 
 
@@ -226,6 +238,35 @@ def _kick_offsets(r: int, P: int):
 def _kick_key(seed) -> int:
     """A sampling seed as the Philox key of a kick stream: the way ``sample_batch`` resolves it."""
     return int(seed) & (2 ** 63 - 1)
+
+
+TSP_KOPT_OFFSET = 3 << 61       # first Philox offset of the k-opt streams: 2^61 above the first kick offset (2^62)
+
+
+def _kopt_offsets(r: int, P: int):
+    """Philox offsets of the k-opt streams of the P copies of sequential round ``r``: copy p owns the 2^32 offsets from
+    ``3 * 2^61 + (r P + p) 2^32`` (round t of the search draws at + t).  The kick offsets of the same copy lie in
+    ``2^62 + (r P + p) 2^32 + [0, 2^32)`` (``_kick_offsets``), 2^61 below: the two cannot meet for fewer than 2^29 copies."""
+    return [TSP_KOPT_OFFSET + ((r * P + p) << 32) for p in range(P)]
+
+
+def _kopt_stage(form: str, kopt: tuple, points, tours, dev, seeds, offsets, heat, edge_index, kopt_stats):
+    """The sampled k-opt search of one round on the tours the local search returned, through the ``decode.batched_kopt_search_*``
+    wrapper of ``form``; ``kopt``: the checked (rounds, samples, depth), rounds > 0.  ``kopt_stats`` receives the per-tour
+    arrays."""
+    rounds, samples, depth = kopt
+    return getattr(decode, f"batched_kopt_search_{form}")(points, tours, heat=heat, edge_index=edge_index, samples=samples,
+                                                          depth=depth, rounds=rounds, seeds=seeds, offsets=offsets,
+                                                          stats=kopt_stats, device=dev)
+
+
+def _kopt_info(kopt: tuple, kopt_stats: dict, first: int, P: int) -> dict:
+    """What info gains from the k-opt stage of the last round (nothing when it is off)."""
+    if kopt[0] == 0:
+        return {}
+    cut = lambda k: [int(v) for v in kopt_stats[k][first:first + P]]
+    return dict(kopt_rounds=kopt[0], kopt_samples=kopt[1], kopt_depth=kopt[2], kopt_rounds_run=cut("rounds"),
+                kopt_actions=cut("actions"))
 
 
 def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, dev, seeds, offsets, heat, edge_index, kick_stats):
@@ -345,7 +386,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     local_search_kick_size: int = TSP_KICK_SIZE, local_search_kick_span: int = TSP_KICK_SPAN,
                     local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
                     local_search_passes: int = 1, two_opt_mode: str = "launches", local_search_candidates: int = 0,
-                    local_search_closing: bool = True, local_search_mode: str = "launches") -> List[tuple]:
+                    local_search_closing: bool = True, local_search_mode: str = "launches", kopt_rounds: int = 0,
+                    kopt_samples: int = TSP_KOPT_SAMPLES, kopt_depth: int = TSP_KOPT_DEPTH) -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -366,7 +408,10 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     ``local_search_passes``: as ``solve_tsp``; an instance gets what its solo call gets.  ``two_opt_mode``: as ``solve_tsp``,
     one GPU block per instance, for arrays and sequences of instances alike.  ``local_search_candidates``,
     ``local_search_closing``: as ``solve_tsp``, per instance, for arrays and sequences alike.  ``local_search_mode``: as
-    ``solve_tsp``, one GPU block per instance, for arrays and sequences of instances alike."""
+    ``solve_tsp``, one GPU block per instance, for arrays and sequences of instances alike.  ``kopt_rounds``,
+    ``kopt_samples``, ``kopt_depth``: as ``solve_tsp``; every copy of an instance is its own tour on its own heatmap, keyed by
+    the instance's seed, so an instance gets what its solo call gets."""
+    kopt = check_tsp_kopt(kopt_rounds, kopt_samples, kopt_depth)
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
     check_local_search(local_search, two_opt_method)
@@ -380,7 +425,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     search = (local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,
-                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search)
+                               seeds, generators, timings, instances_per_call, step_offset, heatmaps, merge_method, search, kopt)
     pts_all = np.ascontiguousarray(points, dtype=np.float64)
     if pts_all.ndim != 3 or pts_all.shape[2] != 2 or pts_all.shape[0] < 1:
         raise ValueError("points must be [B, N, 2] with B >= 1")
@@ -413,7 +458,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         ns = np.zeros(G, dtype=np.int64)
-        ls_stats, kick_stats = {}, {}
+        ls_stats, kick_stats, kopt_stats = {}, {}, {}
         # the Philox keys of the chunk's instances, resolved the way sample_batch resolves them
         keys = [_kick_key(v) for v in ([model.seed] * G if seeds is None else seeds_c)]
         for r in range(sequential_sampling):
@@ -441,6 +486,9 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             solved, ns, ls_stats = _local_search("grouped", search, np_points64, np.asarray(tours, dtype=np.int64).reshape(G * P, n + 1),
                                                  two_opt_iterations, dev, [k for k in keys for _ in range(P)], _kick_offsets(r, P) * G,
                                                  heats, eis if sparse else None, kick_stats)
+            if kopt[0] > 0:
+                solved = _kopt_stage("grouped", kopt, np_points64, solved, dev, [k for k in keys for _ in range(P)],
+                                     _kopt_offsets(r, P) * G, heats, eis if sparse else None, kopt_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g * P:(g + 1) * P])
@@ -451,6 +499,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
             best = int(np.argmin(costs))
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(ns[g]), "merged_costs": merged_costs[g]}
             info.update(_local_search_info(search, ls_stats, kick_stats, g * P, P, g))
+            info.update(_kopt_info(kopt, kopt_stats, g * P, P))
             results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)
@@ -458,9 +507,10 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
 
 
 def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_opt_iterations, seeds, generators, timings,
-                    instances_per_call, step_offset, heatmaps, merge_method, search) -> List[tuple]:
+                    instances_per_call, step_offset, heatmaps, merge_method, search, kopt=(0, 0, 0)) -> List[tuple]:
     """``solve_tsp_batch`` for a sequence of instances [n_b, 2] of any sizes; ``search``: its checked local-search settings, as
-    ``_local_search`` takes them.  Every argument is checked before any library call."""
+    ``_local_search`` takes them; ``kopt``: the checked (rounds, samples, depth) of the k-opt stage.  Every argument is checked
+    before any library call."""
     pts_list = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64)
                 for p in points]
     B = len(pts_list)
@@ -502,7 +552,7 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
         heat_out = [[] for _ in range(G)]
         merge_its = [0.0] * G
         its = np.zeros(G, dtype=np.int64)
-        ls_stats, kick_stats = {}, {}
+        ls_stats, kick_stats, kopt_stats = {}, {}, {}
         keys = [_kick_key(v) for v in ([model.seed] * G if seeds is None else seeds_c)]
         for r in range(sequential_sampling):
             t0 = time.perf_counter()
@@ -529,6 +579,9 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             solved, its, ls_stats = _local_search("ragged", search, np_points64, [np.asarray(t, dtype=np.int64) for t in tours],
                                                   two_opt_iterations, dev, [k for k in keys for _ in range(P)], _kick_offsets(r, P) * G,
                                                   heats, eis if sparse else None, kick_stats)
+            if kopt[0] > 0:
+                solved = _kopt_stage("ragged", kopt, np_points64, solved, dev, [k for k in keys for _ in range(P)],
+                                     _kopt_offsets(r, P) * G, heats, eis if sparse else None, kopt_stats)
             tick("two_opt", t0)
             for g in range(G):
                 stacked[g].append(solved[g])
@@ -539,6 +592,7 @@ def _solve_tsp_list(model, points, sparse_factor, P, sequential_sampling, two_op
             best = int(np.argmin(costs))
             info = {"merge_iterations": merge_its[g], "two_opt_iterations": int(its[g]), "merged_costs": merged_costs[g]}
             info.update(_local_search_info(search, ls_stats, kick_stats, g * P, P, g))
+            info.update(_kopt_info(kopt, kopt_stats, g * P, P))
             results.append((sol[best].tolist(), costs[best], costs, info))
         if heatmaps is not None:
             heatmaps.extend(heat_out)

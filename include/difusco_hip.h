@@ -996,6 +996,69 @@ int difusco_tsp_guided_search_ragged(int groups, const int32_t* group_n, const i
                                      double* first_length_out, double* final_length_out, int32_t* closing_sweeps_out,
                                      void* stream);
 
+/* Heatmap-guided sampled k-opt search (additive to ABI 13): a parallel, deterministic restatement of the sampling, selection and
+ * weight update of the reference's last TSP stage (tsp_mcts/code/TSP_MCTS.h), not a port of it.  Groups, points (float64), closed
+ * int32 tours [n+1], n >= 4, the per-group CSR candidate graph (group_edges HOST [groups], row_ptr, col DEVICE), one heat float32
+ * [E_g] per tour, tour_seeds / tour_offsets (DEVICE uint64 [T]) and the device-side graph check are those of
+ * difusco_tsp_guided_search_ragged.  New: samples S in 1 .. 4096, depth D in 1 .. 10, max_rounds R >= 0, patience H >= 1, beta
+ * (float64, finite, >= 0) and explore: HOST float64 [R], finite and >= 0 - an input, so that no logarithm has to agree between two
+ * math libraries (the Python layer fills it with alpha sqrt(log1p(r S))).  Every TOUR runs on its own; nothing it does depends
+ * on what shares the call.  All arithmetic is float64 + - x / sqrt without contraction, or integer.
+ *   State of a tour.  The incumbent I (positions 0 .. n-1, closed on I[0]).  Entry e of row u is a CANDIDATE of u iff col[e] != u
+ *     and no earlier entry of the row has the same column.  Per candidate entry the weight w[e] = 100.0 (double) clamp(heat_e, 0,
+ *     1) - the clamp fminf(fmaxf(h, 0), 1), so a NaN counts as 0 - and the count C[e] = 0 (int32).  Per city sw[u] = the sum of w
+ *     over the candidates of u in rising e, from 0.0.  len(I) in the association of step 4 of
+ *     difusco_tsp_iterated_search_ragged, computed when I changes.  stall = 0.
+ *   Round r = 0 .. R-1.  All S simulations of a round read I, w, sw and C as they stood at the start of the round.
+ *     Draws.  Simulation s uses the words of Philox4x32-10 with key seed and offset offset + r (mod 2^64); call j has index
+ *       (j << 32) | s; step i takes word i mod 4 of call i div 4; the begin position is step 0.
+ *     Start.  p = word % n, a1 = I[p], b_1 = I[(p+1) mod n]; path position x = 0 .. n-1 is I[(p+1+x) mod n].  Gain_0 =
+ *       d(a1, b_1), d(u, v) = the distance of two_opt's pairs: the coordinate differences, two products, one sum, one square root.
+ *     Step i = 1 .. D, head b_i at path position 0.  avg = sw[b_i] / (n-1); if avg is not > 0 the simulation ends.  Candidate e
+ *       of b_i with c = col[e] is PROMISING iff c != a1, c is not at current path position 1 and
+ *       pot(e) = w[e] / avg + explore[r] / sqrt((double)(C[e] + 1)) >= 1.0.  tot = the sum of pot over the promising entries in
+ *       rising e, from 0.0; none: the simulation ends.  Cumulative c_k = c_k-1 + (int)((1000.0 pot_k) / tot), the last promising
+ *       entry has c = 1000; the draw is word % 1000 and the first k with draw < c_k is chosen.  y = the current path position of
+ *       the chosen city c (2 <= y <= n-2), b_i+1 = the city at position y-1, Gain_i = Gain_i-1 - d(b_i, c) + d(c, b_i+1) (left
+ *       to right), Real_i = Gain_i - d(b_i+1, a1).  The path prefix [0, y) is reversed: b_i+1 is the new head.  The simulation
+ *       ends after this step if Real_i > 1e-6 or i == D.
+ *     Value of a simulation: the largest Real_i, at the lowest such i = i*; a simulation without a step has none.
+ *     Counts, after the round: for every step taken by every simulation C of the chosen entry grows by 1, and so does C of the
+ *       candidate entry (c, b_i) of row c where it exists.
+ *     Best of the round: the largest value, ties to the lowest s.  If it is > 1e-6: the new incumbent is the path after the first
+ *       i* reversals of that simulation - path position x becomes tour position x, then the tour is rotated so that the city at
+ *       input position 0 is at position 0 again.  x = value / len(I) (before the change), inc = beta (x + (0.5 x) x) in that
+ *       association.  For every added edge - (b_i, c_i) for i <= i* and (b_i*+1, a1) -, in step order, and for both of its
+ *       orientations (u, v), first as listed: w[entry(u, v)] += inc where that candidate entry exists, sw[u] += inc always.  len
+ *       is recomputed and stall = 0.  Otherwise stall += S, and the tour stops when stall >= H n (int64).
+ *   Output.  I, or the input tour if len(I) > len(input); reverted_out reports that case (expected: 0).  R = 0 returns the input.
+ * So: the output is a permutation closed on tour[0], never longer than the input; the same (seed, offset, heat) gives a tour the
+ * same result in a solo, a grouped and a ragged call.
+ * Deviations from TSP_MCTS.h.  (1) The simulations of a round run in parallel on frozen counts; the reference is sequential and
+ * breaks at the first improving action.  (2) The total simulation count enters through explore[r].  (3) Distances are float64,
+ * not integers magnified 10^4.  (4) The improvement threshold is 1e-6.  (5) exp(x) - 1 is replaced by x + x^2 / 2, because exp is
+ * not correctly rounded.  (6) Weights live on the sparse candidate entries, with dense row sums.  (7) There is no random restart
+ * and no built-in 2-opt stage: the caller's local search runs before it.  (8) Termination is by stall or round cap, not by clock.
+ * HOST outputs [T] per tour: rounds_out (int32; rounds run), actions_out (int32; actions applied), depth_sum_out (int64; the sum
+ * of their i*), reverted_out (int32), first_length_out and final_length_out (float64; len of the input and of the output).
+ * DIFUSCO_EINVAL before any GPU work on the group conditions of difusco_tsp_guided_search_ragged, a null array, samples, depth,
+ * max_rounds, patience, beta or an explore entry out of range, group_edges[g] < 0 and a workspace that is too small; a bad CSR
+ * is refused by the device check with the setup synchronisation.  A refused call leaves `tours` untouched.  _workspace_bytes
+ * takes samples and depth: the workspace holds, per tour, two tours, the inverse, sw, w and C and per simulation its value, i*,
+ * step count, begin position and D x (entry, mirror entry, cut).  Launches: per round one thread per simulation over a grid of
+ * (tours x ceil(S / 256)) blocks - a single large tour still fills the chip - and one block per tour for the end of the round;
+ * no block waits on another.  The host enqueues rounds without synchronising and polls the count of stopped tours every 8.
+ * Blocks until every tour is done.  difusco_tsp_search_host_syncs also reports this call. */
+int difusco_tsp_kopt_search_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                   const int32_t* group_edges, int32_t samples, int32_t depth, size_t* bytes);
+int difusco_tsp_kopt_search_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const double* points,
+                                   int32_t* tours, const int32_t* group_edges, const int32_t* row_ptr, const int32_t* col,
+                                   const float* heat, const uint64_t* tour_seeds, const uint64_t* tour_offsets, int32_t samples,
+                                   int32_t depth, int32_t max_rounds, int32_t patience, double beta, const double* explore,
+                                   void* workspace, size_t workspace_bytes, int32_t* rounds_out, int32_t* actions_out,
+                                   int64_t* depth_sum_out, int32_t* reverted_out, double* first_length_out,
+                                   double* final_length_out, void* stream);
+
 /* WINDOWED iterated multi-move local search: one block per tour window (additive to ABI 13; not in the reference): the arrays,
  * conventions and limits of difusco_tsp_iterated_search_ragged, plus window = W in 16 .. 1024, passes = R >= 1 and kicks = K in
  * 0 .. 1024 per window and pass.  Every TOUR runs on its own; its result never depends on what shares the call.
