@@ -199,7 +199,7 @@ def mcts_heatmap_rows_gpu(heat, edge_index, points, num_nodes: int, expected_val
     ``edge_index`` [2,E], ``points`` [N,2]: torch tensors (any device) or numpy arrays.  Yields float32 numpy rows."""
     import ctypes
     import torch
-    from . import _lib
+    from . import _lib, graph
     n = int(num_nodes)
     if device is not None:
         dev = torch.device(device)
@@ -218,7 +218,7 @@ def mcts_heatmap_rows_gpu(heat, edge_index, points, num_nodes: int, expected_val
     L = _lib.lib()
     nbytes = ctypes.c_size_t()
     _lib.check(L.difusco_mcts_heatmap_workspace_bytes(n, E, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    ws = graph._workspace(nbytes.value, dev)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     with torch.cuda.device(dev):
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)

@@ -18,6 +18,11 @@ import torch
 from . import _lib
 
 
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """The scratch buffer of one library call of this module or of ``formats``: ``nbytes`` uninitialised bytes on ``device``."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
 @dataclass
 class CsrGraph:
     n_nodes: int
@@ -127,7 +132,7 @@ def _build_csr_device(edge_index, n_nodes: int, device, points=None) -> CsrGraph
     order = torch.empty(n_nodes, dtype=torch.int64, device=device) if pts is not None else None
     nbytes = ctypes.c_size_t()
     _lib.check(L.difusco_graph_build_workspace_bytes(n_nodes, E, int(pts is not None), ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+    ws = _workspace(nbytes.value, device)
     flags = (ctypes.c_uint32 * 2)()
     ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None      # noqa: E731
     _lib.check(L.difusco_graph_build(n_nodes, E, ptr(ei), ptr(pts), int(pts is not None and pts.dtype == torch.float64),
@@ -354,7 +359,7 @@ def knn_edge_index_gpu(points, k: int, device="cuda:0", graphs: int = 1, sizes=N
     for n in sorted(set(sizes)):                                  # one workspace, large enough for every size of the call
         _lib.check(L.difusco_knn_graph_workspace_bytes(n, k, ctypes.byref(nbytes)))
         need = max(need, nbytes.value)
-    ws = torch.empty(need, dtype=torch.uint8, device=device)
+    ws = _workspace(need, device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
     node, col = 0, 0
     for n in sizes:
