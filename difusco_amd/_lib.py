@@ -170,6 +170,8 @@ def lib():
                                                                  ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_tsp_kopt_search_ragged.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32,
                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_double, vp, vp, ctypes.c_size_t] + [vp] * 7
+    L.difusco_tsp_heat_candidates_ragged_workspace_bytes.argtypes = [i32, vp, vp, vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_size_t)]
+    L.difusco_tsp_heat_candidates_ragged.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, vp, ctypes.c_size_t, vp, vp, vp]
     L.difusco_tsp_search_host_syncs.argtypes = []
     L.difusco_knn_graph_workspace_bytes.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_size_t)]
     L.difusco_knn_graph.argtypes = [i32, i32, vp, i64, vp, vp, vp, ctypes.c_size_t, vp]

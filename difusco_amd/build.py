@@ -18,7 +18,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip.so")
 PROF_LIB_PATH = os.path.join(LIB_DIR, "libdifusco_hip_prof.so")
-SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "or_opt.hip", "tsp_resident.hip", "two_opt_multi.hip", "or_opt_multi.hip", "tsp_window_search.hip", "tsp_kopt_search.hip", "knn.hip", "mis_decode.hip", "mis_local_search.hip", "mis_resident_search.hip", "formats.hip", "graph_build.hip", "api.hip"]
+SOURCES = ["linear.hip", "linear_split.hip", "node_linear.hip", "edge_embed.hip", "edge_layer.hip", "edge_layer_bf16.hip", "edge_layer_fp16x1.hip", "graph_kernels.hip", "decode.hip", "two_opt.hip", "or_opt.hip", "tsp_resident.hip", "two_opt_multi.hip", "or_opt_multi.hip", "tsp_window_search.hip", "tsp_kopt_search.hip", "tsp_heat_candidates.hip", "knn.hip", "mis_decode.hip", "mis_local_search.hip", "mis_resident_search.hip", "formats.hip", "graph_build.hip", "api.hip"]
 PROF_SOURCES = SOURCES + ["edge_layer_abl.hip", "stage_lab.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "edge_layer_common.h"), os.path.join(CSRC, "edge_layer_kernel.h"),
            os.path.join(CSRC, "two_opt_common.h"), os.path.join(CSRC, "or_opt_move.h"), os.path.join(CSRC, "multi_move_common.h"), os.path.join(CSRC, "or_opt_rows.h"), os.path.join(CSRC, "nbr_rows.h"), os.path.join(CSRC, "or_opt_nbr.h"), os.path.join(CSRC, "or_opt_focused.h"),
@@ -61,6 +61,8 @@ EXTRA_FLAGS["or_opt_multi.hip"] = ["-ffp-contract=off"]
 EXTRA_FLAGS["tsp_window_search.hip"] = ["-ffp-contract=off"]
 # tsp_kopt_search.hip likewise: tests/tsp_kopt_search_emulation.py
 EXTRA_FLAGS["tsp_kopt_search.hip"] = ["-ffp-contract=off"]
+# tsp_heat_candidates.hip likewise: tests/tsp_heat_candidates_emulation.py (d2 of its sort key)
+EXTRA_FLAGS["tsp_heat_candidates.hip"] = ["-ffp-contract=off"]
 
 TORCH_LIB_PATH = os.path.join(LIB_DIR, "libdifusco_torch.so")
 TORCH_SRC = os.path.join(CSRC, "torch_ops.cpp")

@@ -905,6 +905,90 @@ def _heat_graph(who, pts, trs, heat, edge_index, device):
             pad(torch.cat(hs).contiguous(), torch.float32))
 
 
+TSP_CANDIDATE_SOURCES = ("knn", "heat")
+TSP_HEAT_CANDIDATES_MAX = 128             # K of difusco_tsp_heat_candidates_ragged
+
+
+def check_tsp_candidate_source(source, candidates):
+    """``local_search_candidate_source`` of ``solve_tsp``, ``solve_tsp_batch`` and the runner: "knn" (default; the lists of
+    ``check_tsp_candidates`` as they are) or "heat" (``tsp_heat_candidate_lists`` on the round's heatmaps), which is a source of
+    neighbour lists and so needs ``local_search_candidates`` = K >= 1 (at most 128)."""
+    if source not in TSP_CANDIDATE_SOURCES:
+        raise ValueError(f"local_search_candidate_source = {source!r}: one of {TSP_CANDIDATE_SOURCES}")
+    if source == "heat" and not 1 <= candidates <= TSP_HEAT_CANDIDATES_MAX:
+        raise ValueError("local_search_candidate_source = 'heat' draws the neighbour lists from the heatmaps: it needs "
+                         f"local_search_candidates = K in 1 .. {TSP_HEAT_CANDIDATES_MAX}, not {candidates!r}")
+    return source
+
+
+class _Samples:
+    """What ``_heat_graph`` reads of a group's tours: how many there are."""
+
+    def __init__(self, count):
+        self.shape = (int(count),)
+
+
+def tsp_heat_candidate_lists(points, heat, edge_index=None, candidates=8, *, device="cuda:0", stats=None):
+    """Neighbour lists for ``batched_nbr_two_opt_*`` / ``batched_nbr_local_search_*`` (``neighbors=``) ranked by HEAT instead of
+    distance (the rule: ``difusco_tsp_heat_candidates_ragged``, include/difusco_hip.h; GPU only).  One instance: ``points``
+    [N, 2], ``heat`` [P, E] with ``edge_index`` [2, E], or ``heat`` [P, N, N] with ``edge_index=None`` (the complete graph) - the
+    P heatmaps of the instance's samples on its directed candidate graph, as ``batched_iterated_search_torch`` with
+    ``kick_bias="heat"`` takes them.  City a lists the cities its row names or whose row names it, first by the quantised heat
+    of both orientations summed over the P samples (descending), then by squared distance, then by index; the first
+    ``candidates`` = K (1 .. 128) are kept and a city with fewer gets -1 pads at the end.  Sequences of instances (lists of
+    ``points``, ``heat`` and - unless all are dense - ``edge_index``) run as one library call; an instance gets the lists of its
+    own call.  Returns one int32 device tensor [N, K] (a list of them for sequences); ``stats`` (a dict) receives ``listed`` -
+    the list entries with a score above 0 - and ``pads``, ints (int64 arrays [G] for sequences).  Every shape and value is checked
+    before any library call."""
+    who = "tsp_heat_candidate_lists"
+    single = isinstance(points, (np.ndarray, torch.Tensor))
+    if single:
+        points, heat, edge_index = [points], [heat], None if edge_index is None else [edge_index]
+    if isinstance(candidates, bool) or not isinstance(candidates, (int, np.integer)) or not 1 <= candidates <= TSP_HEAT_CANDIDATES_MAX:
+        raise ValueError(f"candidates = {candidates!r}: an integer in 1 .. {TSP_HEAT_CANDIDATES_MAX}")
+    K = int(candidates)
+    pts = [np.ascontiguousarray(p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else p, dtype=np.float64) for p in points]
+    heat = list(heat)
+    G = len(pts)
+    if G < 1:
+        raise ValueError(f"{who}: needs at least one instance")
+    if len(heat) != G or (edge_index is not None and len(edge_index) != G):
+        raise ValueError(f"{who}: {G} point arrays, {len(heat)} heat arrays" +
+                         ("" if edge_index is None else f", {len(edge_index)} edge_index arrays"))
+    samples = []
+    for g in range(G):
+        if pts[g].ndim != 2 or pts[g].shape[1] != 2 or pts[g].shape[0] < 1:
+            raise ValueError(f"{who}: points[{g}] must be [N, 2] with N >= 1, got {list(pts[g].shape)}")
+        shape = lambda x: tuple(x.shape) if hasattr(x, "shape") else tuple(np.shape(x))
+        n, hs = pts[g].shape[0], shape(heat[g])
+        if edge_index is None:
+            if len(hs) != 3 or hs[0] < 1 or hs[1:] != (n, n):
+                raise ValueError(f"{who}: heat[{g}] must be a dense [P, {n}, {n}] without edge_index, got {list(hs)}")
+        else:
+            es = shape(edge_index[g]) if edge_index[g] is not None else None
+            if es is None or len(es) != 2 or es[0] != 2:
+                raise ValueError(f"{who}: edge_index[{g}] must be [2, E], got {es and list(es)}")
+            if len(hs) != 2 or hs[0] < 1 or hs[1] != es[1]:
+                raise ValueError(f"{who}: heat[{g}] must be [P, {es[1]}] for the {es[1]} edges of edge_index[{g}], got {list(hs)}")
+        samples.append(_Samples(hs[0]))
+    device = _gpu_only(who, device)
+    group_edges, row_ptr, col, d_heat = _heat_graph(who, pts, samples, heat, edge_index, device)
+    group_n = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    group_tours = np.array([s.shape[0] for s in samples], dtype=np.int32)
+    d_pts = _dev(np.concatenate([p.reshape(-1) for p in pts]), torch.float64, device)
+    out = torch.empty(int(group_n.sum()) * K, dtype=torch.int32, device=device)
+    L = _lib.lib()
+    sizes = (G, group_n.ctypes.data, group_tours.ctypes.data, group_edges.ctypes.data)
+    ws, nbytes = _workspace(L.difusco_tsp_heat_candidates_ragged_workspace_bytes, *sizes, K, device=device)
+    listed, pads = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+    _lib.check(L.difusco_tsp_heat_candidates_ragged(*sizes, _ptr(d_pts), _ptr(row_ptr), _ptr(col), _ptr(d_heat), K, _ptr(out),
+                                                    _ptr(ws), nbytes, listed.ctypes.data, pads.ctypes.data, _stream(device)))
+    per = [t.reshape(int(n), K) for t, n in zip(torch.split(out, [int(n) * K for n in group_n]), group_n)]
+    if stats is not None:
+        stats.update(listed=int(listed[0]), pads=int(pads[0])) if single else stats.update(listed=listed, pads=pads)
+    return per[0] if single else per
+
+
 def _iterated_search(form, points, tours, max_iterations, device, max_rounds, select_rounds, kicks, kick_size, span, seeds, offsets,
                      stats, descent, compact_select_max, kick_bias, heat, edge_index):
     """``batched_iterated_search_<form>``: the checks (before any library call) and one ``difusco_tsp_iterated_search_ragged``

@@ -61,7 +61,9 @@ lists of K cities, ``decode.batched_nbr_two_opt_grouped``, closed by full sweeps
 ``two_opt_full_sweeps`` and with the header the two settings; without K every record is what it was; ``--local_search
 nbr2opt+oropt`` needs K >= 1: the 2-opt + Or-opt search on these lists, ``decode.batched_nbr_local_search_grouped`` - a name of its
 own because ``multi2opt+oropt`` with K > 0 stays refused -, the records of ``multi2opt+oropt`` plus, after every other field,
-``local_search_full_sweeps`` and ``local_search_full_rounds``), ``--tsp_kopt_rounds R`` / ``--tsp_kopt_samples S`` /
+``local_search_full_sweeps`` and ``local_search_full_rounds``), ``--tsp_local_search_candidate_source {knn,heat}`` (``heat``
+needs K in 1 .. 128: the neighbour lists come from the round's heatmaps, ``decode.tsp_heat_candidate_lists``; the records gain
+``heat_listed`` and with the header the setting; with ``knn`` every record is what it was), ``--tsp_kopt_rounds R`` / ``--tsp_kopt_samples S`` /
 ``--tsp_kopt_depth D`` (R > 0 only with ``--task tsp``: up to R rounds of the heatmap-guided sampled k-opt search,
 ``decode.batched_kopt_search_grouped``, on every tour after the local search and on each sample's own heatmap, keyed by its
 instance seed; the records gain ``kopt_actions``, one count per copy, and with the header the three settings; with R = 0 every
@@ -190,6 +192,11 @@ EXTENSION_ARGS = [
     ("--tsp_local_search_closing", dict(type=str, default="full", choices=("full", "none"),
                                          help="TSP: what follows the neighbour-list sweeps: full (full sweeps until one finds "
                                               "nothing: a 2-opt optimum) or none (needs --tsp_local_search_candidates K > 0)")),
+    ("--tsp_local_search_candidate_source", dict(type=str, default="knn", choices=("knn", "heat"),
+                                                  help="TSP: where the neighbour lists come from: knn (the K nearest cities) or "
+                                                       "heat (the K cities whose edges the sampled heatmaps rate highest, built on "
+                                                       "the GPU per round; needs --tsp_local_search_candidates K in 1 .. 128; "
+                                                       "records gain heat_listed)")),
     ("--mis_local_search", dict(type=str, default="none", choices=("none", "swap"),
                                  help="MIS refinement after the greedy decode: none (the reference's) or swap ((1,2)-swap local "
                                       "search; records gain decoded_costs)")),
@@ -302,6 +309,11 @@ def parse_args(argv=None):
     if K == 0 and args.tsp_local_search_closing != "full":
         parser.error(f"--tsp_local_search_closing {args.tsp_local_search_closing} closes the neighbour-list sweeps: pass "
                      "--tsp_local_search_candidates K > 0")
+    if args.tsp_local_search_candidate_source == "heat" and args.task != "tsp":
+        parser.error(f"--tsp_local_search_candidate_source heat lists the neighbours of TSP cities: not with --task {args.task}")
+    if args.tsp_local_search_candidate_source == "heat" and not 1 <= K <= 128:
+        parser.error("--tsp_local_search_candidate_source heat draws the neighbour lists from the heatmaps: pass "
+                     "--tsp_local_search_candidates K in 1 .. 128")
     if args.mis_local_search != "none" and args.task != "mis":
         parser.error(f"--mis_local_search {args.mis_local_search} refines MIS solutions: not with --task {args.task}")
     if args.mis_local_search_kicks < 0 or args.mis_local_search_kick_size < 1:
@@ -435,6 +447,8 @@ def tsp_record(split: str, index: int, ex, seed: int, result) -> dict:
     for k in ("local_search_full_sweeps", "local_search_full_rounds"):      # --local_search nbr2opt+oropt
         if k in info:
             rec[k] = int(info[k])
+    if "local_search_heat_listed" in info:         # --tsp_local_search_candidate_source heat
+        rec["heat_listed"] = float(info["local_search_heat_listed"])
     return rec
 
 
@@ -479,7 +493,8 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                 tsp_local_search_window: int = 0, tsp_local_search_passes: int = 1,
                 two_opt_mode: str = "launches", tsp_local_search_candidates: int = 0,
                 tsp_local_search_closing: str = "full", tsp_local_search_mode: str = "launches", tsp_kopt_rounds: int = 0,
-                tsp_kopt_samples: int = TSP_KOPT_SAMPLES, tsp_kopt_depth: int = TSP_KOPT_DEPTH) -> List[dict]:
+                tsp_kopt_samples: int = TSP_KOPT_SAMPLES, tsp_kopt_depth: int = TSP_KOPT_DEPTH,
+                tsp_local_search_candidate_source: str = "knn") -> List[dict]:
     """One ``solve_tsp_batch`` / ``solve_mis_batch`` call per chunk ``(lo, hi)`` of ``examples``, each starting its steps at
     offset 0, instance i with ``instance_seed(seed, split, i)`` and its generator.  Returns one record per instance
     (``tsp_record`` / ``mis_record``).  ``heatmap_dir`` (TSP): also writes the ``.npy`` pair ``test_step`` saves
@@ -514,12 +529,16 @@ def solve_split(model, task: str, examples, split: str, chunks, *, seed: int = 0
                                   **(dict(local_search_mode="resident") if tsp_local_search_mode == "resident" else {}),
                                   **(dict(local_search_candidates=tsp_local_search_candidates,
                                           local_search_closing=tsp_local_search_closing == "full")
-                                     if tsp_local_search_candidates > 0 else {}))
+                                     if tsp_local_search_candidates > 0 else {}),
+                                  **(dict(local_search_candidate_source="heat")
+                                     if tsp_local_search_candidate_source == "heat" else {}))
             for k, i in enumerate(idx):
                 records.append(tsp_record(split, i, examples[i], seeds[k], res[k]))
                 if tsp_local_search_candidates > 0:
                     records[-1].update(tsp_local_search_candidates=tsp_local_search_candidates,
                                        tsp_local_search_closing=tsp_local_search_closing)
+                if tsp_local_search_candidate_source == "heat":
+                    records[-1].update(tsp_local_search_candidate_source="heat")
                 if two_opt_mode == "resident":
                     records[-1].update(two_opt_mode="resident")
                 if tsp_local_search_mode == "resident":
@@ -628,7 +647,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
                                tsp_local_search_candidates=args.tsp_local_search_candidates,
                                tsp_local_search_closing=args.tsp_local_search_closing,
                                tsp_local_search_mode=args.tsp_local_search_mode, tsp_kopt_rounds=args.tsp_kopt_rounds,
-                               tsp_kopt_samples=args.tsp_kopt_samples, tsp_kopt_depth=args.tsp_kopt_depth)
+                               tsp_kopt_samples=args.tsp_kopt_samples, tsp_kopt_depth=args.tsp_kopt_depth,
+                               tsp_local_search_candidate_source=args.tsp_local_search_candidate_source)
             torch.cuda.synchronize(dev)
             gathered = [(recs, timings)]
             if world > 1:
@@ -669,6 +689,8 @@ def run(argv=None) -> Tuple[List[dict], List[dict]]:
             if args.tsp_local_search_candidates > 0:
                 line["tsp_local_search_candidates"] = args.tsp_local_search_candidates
                 line["tsp_local_search_closing"] = args.tsp_local_search_closing
+            if args.tsp_local_search_candidate_source == "heat":
+                line["tsp_local_search_candidate_source"] = "heat"
             if args.tsp_local_search_descent == "focused":
                 line["tsp_local_search_descent"] = "focused"
             if args.tsp_local_search_kick_bias == "heat":

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import decode
-from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, TSP_KOPT_DEPTH, TSP_KOPT_SAMPLES, check_local_search, check_tsp_kopt, check_tsp_candidates, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
+from .decode import (TSP_KICK_SIZE, TSP_KICK_SPAN, TSP_KOPT_DEPTH, TSP_KOPT_SAMPLES, check_local_search, check_tsp_kopt, check_tsp_candidates, check_tsp_candidate_source, check_merge_method, check_tsp_descent, check_tsp_kick_bias,
                      check_tsp_kicks, check_tsp_local_search_mode, check_tsp_window, check_two_opt_method, check_two_opt_mode, merge_tours,
                      merge_tours_batch)
 from .graph import knn_edge_index_gpu
@@ -45,7 +45,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
               local_search_kick_bias: str = "uniform", local_search_window: int = 0, local_search_passes: int = 1,
               two_opt_mode: str = "launches", local_search_candidates: int = 0, local_search_closing: bool = True,
               local_search_mode: str = "launches", kopt_rounds: int = 0, kopt_samples: int = TSP_KOPT_SAMPLES,
-              kopt_depth: int = TSP_KOPT_DEPTH):
+              kopt_depth: int = TSP_KOPT_DEPTH, local_search_candidate_source: str = "knn"):
     """points: float64/float32 [N,2] of ONE instance.  ``sparse_factor`` > 0: k-NN graph (the sparse models);
     <= 0: dense mode (``pl_tsp_model.py:158-160``, TSP-50/100).  Returns (best_tour list, best_cost, all_costs, info):
     ``all_costs`` has ``parallel_sampling * sequential_sampling`` entries in the reference's stacking order, info holds
@@ -100,7 +100,13 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     ``kopt_samples`` simulations per round and moves of up to ``kopt_depth`` new edges, on its own heatmap of its sequential
     round (the tensor the merge received) - never a longer tour.  Copy p of sequential round r is keyed by the model's seed at
     the Philox offset ``3 * 2^61 + (r P + p) 2^32``, which no kick offset of the same tour reaches.  info gains ``kopt_rounds``,
-    ``kopt_samples``, ``kopt_depth`` and, of the last round, one per copy, ``kopt_rounds_run`` and ``kopt_actions``."""
+    ``kopt_samples``, ``kopt_depth`` and, of the last round, one per copy, ``kopt_rounds_run`` and ``kopt_actions``.
+    ``local_search_candidate_source``: "knn" (default: every result and info is what it is without the option) or "heat" (needs
+    ``local_search_candidates`` = K >= 1, else ``ValueError``): the neighbour lists of "multi2opt" with K > 0 and of
+    "nbr2opt+oropt" are ranked by heat, not distance (``decode.tsp_heat_candidate_lists``), from the round's own heatmaps and
+    graph - the dense heatmaps in dense mode - so every sequential round builds its own lists; info gains
+    ``local_search_candidate_source`` ("heat") and ``local_search_heat_listed``, the share of the last round's list slots that
+    hold a city with a score above 0."""
     kopt = check_tsp_kopt(kopt_rounds, kopt_samples, kopt_depth)
     check_two_opt_method(two_opt_method)
     check_local_search(local_search, two_opt_method)
@@ -111,6 +117,7 @@ def solve_tsp(model, points: np.ndarray, sparse_factor: int, parallel_sampling: 
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
+    nbr += (check_tsp_candidate_source(local_search_candidate_source, nbr[0]),)
     search = (local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     dev = model.device
     pts64 = np.ascontiguousarray(points, dtype=np.float64)
@@ -278,19 +285,22 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
     local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr = search
     run = lambda stem, **kw: getattr(decode, f"batched_{stem}_{form}")(points, tours, max_iterations=two_opt_iterations, device=dev, **kw)
     ls_stats = {}
+    lists = lambda: _candidate_lists(form, points, edge_index, nbr[0], nbr[2], heat, dev)
     if local_search == "2opt":
         solved, iterations = run("two_opt", method=two_opt_method,                              # pl_tsp_model.py:233-236
                                  **(dict(mode="resident") if two_opt_mode == "resident" else {}))
     elif local_search == "multi2opt" and nbr[0] > 0:
-        solved, iterations = run("nbr_two_opt", candidates=nbr[0], closing=nbr[1], stats=ls_stats,
-                                 neighbors=_candidate_lists(form, points, edge_index, nbr[0]))
+        neighbors, heat_stats = lists()
+        solved, iterations = run("nbr_two_opt", candidates=nbr[0], closing=nbr[1], stats=ls_stats, neighbors=neighbors)
+        ls_stats.update(heat_stats)
     elif local_search == "multi2opt":
         solved, iterations = run("multi_two_opt", stats=ls_stats)
     elif local_search == "2opt+oropt":
         solved, iterations = run("local_search", stats=ls_stats, **(dict(mode="resident") if ls_mode == "resident" else {}))
     elif local_search == "nbr2opt+oropt":
-        solved, ls_stats = run("nbr_local_search", candidates=nbr[0], closing=nbr[1],
-                               neighbors=_candidate_lists(form, points, edge_index, nbr[0]))
+        neighbors, heat_stats = lists()
+        solved, ls_stats = run("nbr_local_search", candidates=nbr[0], closing=nbr[1], neighbors=neighbors)
+        ls_stats = dict(ls_stats, **heat_stats)
         iterations = ls_stats["two_opt_sweeps"]
     else:
         kicked = dict(kicks=kicks, kick_size=kick_size, span=kick_span, seeds=seeds, offsets=offsets, stats=kick_stats)
@@ -305,18 +315,32 @@ def _local_search(form: str, search: tuple, points, tours, two_opt_iterations, d
     return solved, iterations, ls_stats
 
 
-def _candidate_lists(form: str, points, edge_index, K: int):
-    """The neighbour lists of the K-candidate 2-opt from the instances' own k-NN graphs (``edge_index`` of the form: one
-    [2, n k] tensor, or one per instance with local node ids) where they hold K other cities per node; else None, and the
-    search builds the lists with a k-NN call of its own."""
+def _candidate_lists(form: str, points, edge_index, K: int, source: str = "knn", heat=None, dev=None):
+    """(the neighbour lists of the K-candidate searches, what the statistics of the search gain).  ``source="knn"``: from the
+    instances' own k-NN graphs (``edge_index`` of the form: one [2, n k] tensor, or one per instance with local node ids) where
+    they hold K other cities per node; else None, and the search builds the lists with a k-NN call of its own.
+    ``source="heat"``: ``decode.tsp_heat_candidate_lists`` on ``heat`` - the round's heatmaps, one [P, E] or dense [P, n, n] per
+    instance - and the same graphs, one library call; the statistics gain ``heat_listed``, per instance the share of its n K
+    list slots that hold a city with a score above 0."""
+    if source == "heat":
+        st = {}
+        # a sparse heatmap comes flat, the P samples of an instance one after the other: [P E] -> [P, E]
+        rows = lambda h, e: h if e is None else h.reshape(-1, e.shape[1])
+        if form == "torch":
+            lists = decode.tsp_heat_candidate_lists(np.asarray(points), rows(heat, edge_index), edge_index, K, device=dev, stats=st)
+            return lists, dict(heat_listed=np.array([st["listed"] / (len(points) * K)]))
+        eis = None if edge_index is None else list(edge_index)
+        heats = [rows(h, None if eis is None else eis[g]) for g, h in enumerate(heat)]
+        lists = decode.tsp_heat_candidate_lists([np.asarray(p) for p in points], heats, eis, K, device=dev, stats=st)
+        return lists, dict(heat_listed=st["listed"] / np.array([len(p) * K for p in points], dtype=np.float64))
     if edge_index is None:
-        return None
+        return None, {}
     eis = [edge_index] if form == "torch" else list(edge_index)
     sizes = [len(points)] if form == "torch" else [len(p) for p in points]
     if any(e.shape[1] // n - 1 < K for e, n in zip(eis, sizes)):
-        return None
+        return None, {}
     lists = decode.tsp_candidate_lists(eis, sizes, K)
-    return lists[0] if form == "torch" else lists
+    return (lists[0] if form == "torch" else lists), {}
 
 
 def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: int, P: int, g: int) -> dict:
@@ -327,9 +351,11 @@ def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: i
     cut = lambda k: [int(v) for v in kick_stats[k][first:first + P]]
     if local_search == "2opt":
         return {}
+    heat_lists = dict(local_search_candidate_source="heat", local_search_heat_listed=float(np.reshape(ls_stats["heat_listed"], -1)[g])) \
+        if nbr[2] == "heat" else {}
     if local_search == "multi2opt" and nbr[0] > 0:
         return dict(two_opt_moves=at("moves"), local_search_candidates=nbr[0], local_search_closing=nbr[1],
-                    two_opt_full_sweeps=at("full_sweeps"))
+                    two_opt_full_sweeps=at("full_sweeps"), **heat_lists)
     if local_search == "multi2opt":
         return dict(two_opt_moves=at("moves"))
     if local_search == "2opt+oropt":
@@ -338,7 +364,7 @@ def _local_search_info(search: tuple, ls_stats: dict, kick_stats: dict, first: i
                 local_search_rounds=at("rounds"))
     if local_search == "nbr2opt+oropt":
         info.update(local_search_candidates=nbr[0], local_search_closing=nbr[1], local_search_full_sweeps=at("full_sweeps"),
-                    local_search_full_rounds=at("full_rounds"))
+                    local_search_full_rounds=at("full_rounds"), **heat_lists)
     elif window > 0:
         info.update(local_search_window=window, local_search_passes=passes, local_search_kicks_improved=cut("kicks_improved"),
                     local_search_passes_kept=cut("passes_kept"), local_search_closing_sweeps=cut("closing_sweeps"))
@@ -387,7 +413,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
                     local_search_descent: str = "full", local_search_kick_bias: str = "uniform", local_search_window: int = 0,
                     local_search_passes: int = 1, two_opt_mode: str = "launches", local_search_candidates: int = 0,
                     local_search_closing: bool = True, local_search_mode: str = "launches", kopt_rounds: int = 0,
-                    kopt_samples: int = TSP_KOPT_SAMPLES, kopt_depth: int = TSP_KOPT_DEPTH) -> List[tuple]:
+                    kopt_samples: int = TSP_KOPT_SAMPLES, kopt_depth: int = TSP_KOPT_DEPTH,
+                    local_search_candidate_source: str = "knn") -> List[tuple]:
     """``solve_tsp`` of B instances: ``points`` [B, N, 2], or a sequence of B arrays [n_b, 2] of any sizes (one ragged k-NN
     sequence, one sampling loop, per-instance merges and one ragged 2-opt per chunk: ``_solve_tsp_list``).  Returns the list of what ``solve_tsp`` returns for
     every instance, run with ``seed = seeds[b]`` (default: the model's) and ``generator = generators[b]``.  Up to
@@ -410,7 +437,8 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     ``local_search_closing``: as ``solve_tsp``, per instance, for arrays and sequences alike.  ``local_search_mode``: as
     ``solve_tsp``, one GPU block per instance, for arrays and sequences of instances alike.  ``kopt_rounds``,
     ``kopt_samples``, ``kopt_depth``: as ``solve_tsp``; every copy of an instance is its own tour on its own heatmap, keyed by
-    the instance's seed, so an instance gets what its solo call gets."""
+    the instance's seed, so an instance gets what its solo call gets.  ``local_search_candidate_source``: as ``solve_tsp``, per
+    instance, from its own heatmaps and graph, one library call per chunk and round."""
     kopt = check_tsp_kopt(kopt_rounds, kopt_samples, kopt_depth)
     check_two_opt_method(two_opt_method)
     check_merge_method(merge_method)
@@ -422,6 +450,7 @@ def solve_tsp_batch(model, points, sparse_factor: int, parallel_sampling: int = 
     kick_bias = check_tsp_kick_bias(local_search_kick_bias, kicks)
     window, passes = check_tsp_window(local_search, local_search_window, local_search_passes, kicks, descent, kick_bias)
     nbr = (check_tsp_candidates(local_search, local_search_candidates, kicks, window, two_opt_mode), bool(local_search_closing))
+    nbr += (check_tsp_candidate_source(local_search_candidate_source, nbr[0]),)
     search = (local_search, (two_opt_method, two_opt_mode, ls_mode), window, passes, kicks, kick_size, kick_span, descent, kick_bias, nbr)
     if not isinstance(points, (np.ndarray, torch.Tensor)):      # a sequence of instances; one array keeps the equal-size path
         return _solve_tsp_list(model, points, sparse_factor, int(parallel_sampling), sequential_sampling, two_opt_iterations,

@@ -1059,6 +1059,45 @@ int difusco_tsp_kopt_search_ragged(int groups, const int32_t* group_n, const int
                                    int64_t* depth_sum_out, int32_t* reverted_out, double* first_length_out,
                                    double* final_length_out, void* stream);
 
+/* Candidate lists for the neighbour-list searches FROM THE HEATMAPS (additive to ABI 13; not in the reference - its search stage
+ * lists candidates by heat too, tsp_mcts/code/TSP_Basic_Functions.h:171-212; this is a parallel, deterministic rule of our own).
+ *   Inputs.  Those of difusco_tsp_guided_search_ragged: group g has n_g cities, P_g = group_tours[g] tours, points float64, the
+ *     directed candidate graph in CSR (row_ptr int32 [n_g + 1], col int32 [E_g], E_g = group_edges[g]; any degrees, 0 included;
+ *     duplicate entries and self edges allowed) and one heat float32 [E_g] per tour in that entry order; DEVICE arrays laid out as
+ *     there.  No tour is read, so n_g >= 1 suffices here (the searches need n_g >= 4).  New: K, 1 <= K <= 128.
+ *   Quantised heat.  q_t(u, v) for tour t of the group exactly as defined there: q(e) = (uint32) rint(clamp(heat_e, 0, 1) *
+ *     65535.0f), a NaN counts as 0, q_t(u, v) = the largest q(e) over the entries e of row u with col[e] == v, 0 if there is none.
+ *   Score.  S(a, b) = the sum over the group's tours t of (q_t(a, b) + q_t(b, a)), an integer held in 64 bits: symmetric, and
+ *     independent of the order of the tours and of the entries.
+ *   Candidate set.  C(a) = { b != a : b is a column of row a, or a is a column of row b }.
+ *   List of a.  The members of C(a) sorted by (S(a, b) descending, d2(a, b) ascending, b ascending), d2 = dx dx + dy dy in
+ *     float64 with every operation rounded on its own (dx, dy the coordinate differences).  The first K go to
+ *     neighbors_out[(cities before the group) K + a K + 0 .. K-1] (DEVICE int32), cities local to the group; if |C(a)| < K the
+ *     remaining slots hold -1, the pad convention of difusco_tsp_nbr_two_opt_ragged.
+ * So: every row holds distinct cities, never the city itself, and pads only at its end; a group's lists depend neither on what
+ * shares the call nor on how threads are scheduled; they do not change when the entries inside a row are permuted or the group's
+ * tours are reordered; with all-zero heat on a k-NN graph whose rows are in (d2, index) order and pairwise distinct distances
+ * per city they are the first K non-self neighbours of every row for K <= k - 1; with K = n - 1 on the complete graph every
+ * list names every other city, so the neighbour-list searches sweep what the full sweeps do.
+ * Outputs on the host, HOST int64 [groups]: listed_out (the list entries with S > 0, summed over the group's cities) and pads_out
+ * (the pad slots).
+ * DIFUSCO_EINVAL before any GPU work on null pointers, K outside 1 .. 128, groups < 1, n_g < 1 or above the limit of the
+ * searches, P_g < 1, more tours than a call of the searches takes, E_g < 0 and a workspace that is too small.  The graphs pass the
+ * device check of the guided search first; its flag comes back with the one synchronisation in front of the work, and a bad
+ * graph is DIFUSCO_EINVAL with neighbors_out untouched.  Behind it: the q table of the guided search; one thread per entry for
+ * the sums over the tours and the in-degrees (integer atomics); one block per group for the row pointers of the transpose; one
+ * thread per entry to scatter the transpose (arbitrary order inside a row - the list order is total); one wave per city for the
+ * selection - it gathers the out-row and the in-row, drops the city itself, repeated columns and incoming cities the out-row
+ * names, and takes K rounds of a wave-wide lexicographic maximum, so any degree works.  Launch boundaries are the only
+ * synchronisation.  _workspace_bytes: per group about 2 P_g E_g (the q table) + 32 E_g (the sums, the transpose and the 2 E_g
+ * selection slots of 12 bytes) + 8 n_g bytes.  Blocks until done. */
+int difusco_tsp_heat_candidates_ragged_workspace_bytes(int groups, const int32_t* group_n, const int32_t* group_tours,
+                                                       const int32_t* group_edges, int32_t K, size_t* bytes);
+int difusco_tsp_heat_candidates_ragged(int groups, const int32_t* group_n, const int32_t* group_tours, const int32_t* group_edges,
+                                       const double* points, const int32_t* row_ptr, const int32_t* col, const float* heat,
+                                       int32_t K, int32_t* neighbors_out, void* workspace, size_t workspace_bytes,
+                                       int64_t* listed_out, int64_t* pads_out, void* stream);
+
 /* WINDOWED iterated multi-move local search: one block per tour window (additive to ABI 13; not in the reference): the arrays,
  * conventions and limits of difusco_tsp_iterated_search_ragged, plus window = W in 16 .. 1024, passes = R >= 1 and kicks = K in
  * 0 .. 1024 per window and pass.  Every TOUR runs on its own; its result never depends on what shares the call.
